@@ -2,7 +2,7 @@
 """bench.py -- BASELINE.json's headline metric on MI355X:
     time-steps/sec + SpMV GB/s (% HBM roofline), 3D mono diffusion 512^3   (benchmark/Heat3D.jl shape)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--strong]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 512] [--strong] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path over the resident problem: one Crank-Nicolson time step of
@@ -21,9 +21,18 @@ overlapped with the interior rows).  No multi-GPU run of either kind has been me
 available to the author): the slab code is verified with virtual ranks on one GPU (tests/test_gpu_config4.py).
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = the SpMV launch,
-HIP-event timed on the library stream inside the timed region), `step_roofline` (the whole time step's algorithmic
-bytes over its wall time) and `cpu_baseline` (the oracle's C restatement of the same Krylov loop on the same matrix, on
-the host cores of this box; rank 0, N=1 only).
+HIP-event timed on the library stream inside the timed region) and `step_roofline` (the whole time step's algorithmic
+bytes over its wall time).  A plain run does only that: set-up, warm-up, the K timed steps, the line.
+
+--full adds what takes runs of its own: `cpu_baseline` (the oracle's C restatement of the same Krylov loop on the same
+matrix, on the host cores of this box; rank 0, N=1 only; --no-cpu-baseline leaves it out) and, on several ranks in the
+default weak-scaling run, the `strong_scaling` sub-record.
+
+--dump-outputs DIR: after the timed steps, what they computed -- the state x of the last step, the full unknown vector a
+caller of the path receives (pg_solver_get_state) -- goes to DIR as float64 .npy files: `state.npy` (the whole vector, or a
+fixed seeded sample of DUMP_SAMPLE entries of a larger one), `state_index.npy` (the positions of those entries in x) and
+`state_summary.npy` (length, sum, L2 norm, min, max of the whole vector).  The workload is synthetic and deterministic:
+the same arguments give the same inputs, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -45,6 +54,8 @@ if str(ROOT) not in sys.path:
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 HBM_ACHIEVABLE_GBS = 6300.0   # same guide: what a streaming kernel reaches on this part (the practical ceiling)
 PROFILE_SUMMARY = ROOT / "profiles" / "r03_spmv_profile.json"   # scripts/profile_round3.sh: rocprofv3 trace + PMC passes
+DUMP_SAMPLE = 3_000_000   # --dump-outputs: entries of x written at most (float64 values + positions: 48 MB)
+DUMP_SEED = 20261016
 
 
 def fail(msg: str) -> None:
@@ -64,6 +75,10 @@ def spawn_ranks(args) -> int:
         cmd.append("--strong")
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd += ["--full", "--cpu-steps", str(args.cpu_steps)]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", str(Path(args.dump_outputs).resolve())]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC: RCCL across processes needs it on this image
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -79,10 +94,18 @@ def main() -> None:
     ap.add_argument("--strong", action="store_true",
                     help="strong scaling (SURVEY 8d, config 4): the SAME n^3 problem slab-decomposed over the ranks "
                          "(default: weak scaling, one n^3 sphere problem per rank)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (1 GPU) and, on several ranks "
+                         "without --strong, the strong-scaling sub-run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--cpu-steps", type=int, default=4,
-                    help="time-steps the CPU baseline times per variant (4 single-thread plain solves ~ 10 s)")
+                    help="with --full: time-steps the CPU baseline times per variant (4 single-thread plain solves ~ 10 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state x after the last timed step to DIR as float64 .npy files (a fixed seeded sample of "
+                         f"{DUMP_SAMPLE} entries when x is longer)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -179,6 +202,9 @@ def main() -> None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    # before anything else runs on the solver: the --full CPU baseline advances the state
+    if args.dump_outputs:
+        dump_outputs(s, Path(args.dump_outputs), world, rank, dist, torch)
 
     sysinfo = s.system_info(3)                         # the run matrix as the SpMV streams it (preconditioned)
     n_rows, nnz = int(sysinfo.n_own), int(sysinfo.nnz)
@@ -391,8 +417,8 @@ def main() -> None:
     # SAME run therefore also times the strong-scaling shape of config 4 -- the one n^3 sphere problem cut into `world` slabs
     # balanced by active rows, every product exchanging one ghost chunk per unknown kind with each neighbour (ncclSend /
     # ncclRecv on the communication stream, overlapped with the interior rows) -- and reports it as a sub-record, so that the
-    # first run on a multi-GPU node exercises the halo path without a second invocation.  Same loop, same tolerances.
-    if world > 1 and not args.strong:
+    # first run on a multi-GPU node exercises the halo path without a second invocation.  Same loop, same tolerances.  --full only.
+    if args.full and world > 1 and not args.strong:
         try:
             out["strong_scaling"] = strong_record(pj, L, lib, dist, torch, args, world, rank, opts, CN, sync)
         except SystemExit:
@@ -400,7 +426,7 @@ def main() -> None:
         except Exception as e:
             out["strong_scaling"] = {"value": None, "error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             # the GPU loop's iteration count from a zero initial guess, for the comparison with the (cold-start) CPU figures
             cold = L.pg_krylov_opts(L.PG_METHOD["bicgstab"], 1e-12, 0.0, 0, 4, 0, 0, 0)
@@ -415,6 +441,47 @@ def main() -> None:
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(s, out_dir: Path, world: int, rank: int, dist, torch) -> None:
+    """--dump-outputs: the state x after the last timed step (module docstring).  With several ranks every rank writes only
+    its owned entries of the full vector (pg_solver_get_state): the sample and the summary are reduced over the ranks and
+    rank 0 writes them.  Unknowns no rank writes are eliminated ones, zeros in x as one rank returns it."""
+    from penguin.jl_amd import _lib as L
+
+    n = int(s._nunk)
+    x = np.full(n, np.nan)
+    L.check(L.lib().pg_solver_get_state(s._h, C.c_int64(-1), L.dptr(x), C.c_int64(n)))
+    unset = np.isnan(x)
+    written = n - int(unset.sum())
+    lo = float(np.nanmin(x)) if written else np.inf
+    hi = float(np.nanmax(x)) if written else -np.inf
+    x[unset] = 0.0
+    del unset
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    sample = x[idx]
+    total, sumsq = float(x.sum()), float(np.dot(x, x))
+    del x
+    if world > 1:
+        t = torch.from_numpy(sample).to("cuda")
+        dist.all_reduce(t)
+        sample = t.cpu().numpy()
+        sums = torch.tensor([total, sumsq, float(written)], dtype=torch.float64, device="cuda")
+        dist.all_reduce(sums)
+        total, sumsq, written = float(sums[0].item()), float(sums[1].item()), int(sums[2].item())
+        ext = torch.tensor([lo, -hi], dtype=torch.float64, device="cuda")
+        dist.all_reduce(ext, op=dist.ReduceOp.MIN)
+        lo, hi = float(ext[0].item()), -float(ext[1].item())
+    if written < n:
+        lo, hi = min(lo, 0.0), max(hi, 0.0)
+    if rank == 0:
+        out_dir.mkdir(parents=True, exist_ok=True)
+        np.save(out_dir / "state.npy", np.ascontiguousarray(sample, dtype=np.float64))
+        np.save(out_dir / "state_index.npy", idx.astype(np.float64))
+        np.save(out_dir / "state_summary.npy", np.array([float(n), total, np.sqrt(sumsq), lo, hi], dtype=np.float64))
 
 
 def strong_record(pj, L, lib, dist, torch, args, world, rank, opts, CN, sync) -> dict:
