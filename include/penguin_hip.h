@@ -234,6 +234,16 @@ int32_t pg_diffops_export_csc(const pg_diffops* o, int32_t which, int64_t* colpt
    with a velocity assembles the advection-diffusion blocks (advectiondiffusion.jl:29-44,180-213: conv_bulk = ΣC_d and
    conv_iface = ½ΣK_d on the bulk rows); pg_diffops_export_csc(PG_OP_C0 + d / PG_OP_K0 + d) returns C_d / K_d. */
 int32_t pg_diffops_set_velocity(pg_diffops* o, const double* const* u_omega, const double* u_gamma);
+/* ConvectionOps(capacity, uₒ, uᵧ) of a SPACE-TIME capacity (2-D+t), as A_/b_*_unstead_advdiff_moving read it
+   (prescribedmotionsolver/advectiondiffusion.jl:94-95,158-159: the blocks C[1][L1,L1], C[2][L2,L2], C[3][L1,L2] and the same
+   of K, of which only K[1] is used; L1 = first time layer, L2 = time padding).  u_omega: N+1 pointers to 2M doubles (x, y, t),
+   u_gamma: (N+1)*2M doubles (block d = component d).  Stored: C_x from the first layer (C[1]) and ½K_x (K[1] = diag(Σ_p[x] h),
+   h = Hᵀuᵧ on the first layer); C[2] is C_y on the time padding, where A_y = 0: zero whatever uₒy is (no bulk y-advection, as
+   in the reference).  Refused: a non-zero time component of uₒ or time block of uᵧ (C[3] / H_t, which needs B_t), N = 1 (the
+   reference's C[3] of a 2-tuple: BoundsError), N = 3, a static capacity.  pg_diffops_export_csc returns C_x / K_x of the
+   first layer (PG_OP_C0 / PG_OP_K0) and refuses the other directions.  The moving DIFFUSION constructors refuse such
+   operators; the moving advection-diffusion constructors below need them. */
+int32_t pg_diffops_set_velocity_spacetime(pg_diffops* o, const double* const* u_omega, const double* u_gamma);
 int32_t pg_diffops_grad(const pg_diffops* o, const double* p /*2M*/, double* out /*N*M*/);      /* ∇  :20-23 */
 int32_t pg_diffops_div(const pg_diffops* o, const double* qw /*N*M*/, const double* qg /*N*M*/,
                        double* out /*M*/);                                                     /* ∇₋ :30-34 */
@@ -286,6 +296,30 @@ int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const p
                                           const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                           const double* source_n, const double* source_np1, pg_solver* previous,
                                           int32_t scheme, pg_solver** out);
+/* One space-time step of solve_MovingAdvDiffusionUnsteadyMono! (prescribedmotionsolver/advectiondiffusion.jl:15-33
+   constructor, 64-129 A, 131-199 b, 201-242 loop): the arguments of pg_solver_create_moving_mono, o = the space-time
+   ConvectionOps of c (pg_diffops_set_velocity_spacetime).  A = the moving blocks with - (ΣC + ½K[1]) Ψc and - ½K[1] Ψc in the
+   bulk rows, Ψc = psip_conv.(Vn, Vn_1) (:35-47; 1 only where Vn = 0, Vn_1 ≠ 0); b subtracts the explicit convection of the
+   previous state: BE (:194) ½K[1] Ψm Tω + ½K[1] Tγ + ΣC Ψm Tω with Ψm = psim_conv.(Vn, Vn_1) (:49-61), CN (:192)
+   ½K[1] Ψn Tω + ½K[1] Tγ + ΣC Tω with Ψn = psim_cn -- on the device, from T_prev or from the previous solver. */
+int32_t pg_solver_create_moving_advdiff_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                                             const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
+                                             const double* source_n, const double* source_np1, const double* T_prev,
+                                             int32_t scheme, pg_solver** out);
+/* the same with the previous slab's solver as T_prev, device to device (as pg_solver_create_moving_mono_next) */
+int32_t pg_solver_create_moving_advdiff_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                                                  const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
+                                                  const double* source_n, const double* source_np1, pg_solver* previous,
+                                                  int32_t scheme, pg_solver** out);
+/* MovingAdvDiffusionUnsteadyDiph + A_/b_diph_unstead_advdiff_moving (prescribedmotionsolver/advectiondiffusion.jl:246-507): one
+   slab, the arguments of pg_solver_create_moving_diph with space-time ConvectionOps o1 / o2.  Differs from the moving
+   diffusion blocks beyond the convection terms (as mono per phase; CN: - ΣC Tω - ½K[1] Tω - ½K[1] Tγ, no Ψ): the flux row
+   has no -(Vn_1 - Vn) term (:362-365) and the CN γ term of b is -½ Id GᵀWꜝH Tγ without Ψ (:494-495). */
+int32_t pg_solver_create_moving_advdiff_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                             const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                             const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
+                                             const double* f2_n, const double* f2_np1, const double* T_prev,
+                                             pg_solver* previous, int32_t scheme, pg_solver** out);
 int32_t pg_solver_destroy(pg_solver* s);
 
 /* per-step data for time-dependent closures; the host evaluates them at the reference's points and

@@ -21,7 +21,9 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_AdvectionDiffusionSteadyDiph!, AdvectionDiffusionUnsteadyMono, solve_AdvectionDiffusionUnsteadyMono!,
        AdvectionDiffusionUnsteadyDiph, solve_AdvectionDiffusionUnsteadyDiph!,
        SpaceTimeMesh, MovingSphere, MovingHalfSpace, SpaceTimeCapacity, MovingDiffusionUnsteadyMono,
-       solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!, config_string, guess_info,
+       solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!,
+       MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
+       solve_MovingAdvDiffusionUnsteadyDiph!, config_string, guess_info,
        ∇, ∇₋, gmres, bicgstabl, cg
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
@@ -792,12 +794,33 @@ function Capacity(body::MovingBody, mesh::SpaceTimeMesh; method::String="VOFI", 
 end
 DiffusionOps(cap::SpaceTimeCapacity) = DiffusionOps(cap.layer)
 
+# ConvectionOps(capacity, uₒ, uᵧ) of a space-time capacity (2-D+t), as the moving advection-diffusion blocks slice it
+# (prescribedmotionsolver/advectiondiffusion.jl:94-95): C = (C[1][L1,L1], C[2][L2,L2], C[3][L1,L2]) = (C_x of the first layer,
+# 0, 0) and the same of K; uₒ = (uₒx, uₒy, uₒt) of 2M each, uᵧ of 3·2M.  A non-zero uₒt or time block of uᵧ, and 1-D+t (the
+# reference's BoundsError), are refused by pg_diffops_set_velocity_spacetime.
+function ConvectionOps(cap::SpaceTimeCapacity{N}, uₒ::NTuple{3, Vector{Float64}}, uᵧ::Vector{Float64}) where N
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pg_diffops_create, libpg), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}), cap.handle, h))
+    sz = cap.layer.mesh.dims .+ 1
+    M = prod(sz)
+    GC.@preserve uₒ uᵧ begin
+        ptrs = [pointer(u) for u in uₒ]
+        check(ccall((:pg_diffops_set_velocity_spacetime, libpg), Int32, (Ptr{Cvoid}, Ptr{Ptr{Float64}}, Ptr{Float64}), h[], ptrs, uᵧ))
+    end
+    Z = spzeros(M, M)
+    op = ConvectionOps{3}((_export_csc(h[], 3, M, M), Z, Z), (_export_csc(h[], 6, M, M), Z, Z), _export_csc(h[], 0, N * M, M),
+                          _export_csc(h[], 1, N * M, M), _export_csc(h[], 2, N * M, N * M), cap.V, (sz..., 2), h[])
+    finalizer(x -> ccall((:pg_diffops_destroy, libpg), Int32, (Ptr{Cvoid},), x.handle), op)
+    op
+end
+
 # closures see the space-time centroids padded to three coordinates (build_source / build_g_g on the (N+1)-D capacity)
 _st_coords(C, Ct) = [coords3((c..., Ct[i])) for (i, c) in enumerate(C)]
 function _moving_step!(s::Solver, phase::Phase, bc_b::BorderConditions, bc_i::AbstractBoundary, Δt::Float64, Tᵢ::Vector{Float64},
-                       mesh::Mesh, scheme::String, t::Float64)
+                       mesh::Mesh, scheme::String, t::Float64; advdiff::Bool=false)
     cap = phase.capacity
     cap isa SpaceTimeCapacity || error("the moving solver needs a space-time capacity: Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
+    advdiff && _need_st_conv(phase)
     Cω = _st_coords(cap.C_ω, cap.Ct_ω)
     g = bc_i.value isa Function ? Float64[Float64(bc_i.value(c...)) for c in _st_coords(cap.C_γ, cap.Ct_γ)] : Float64[]   # :172
     D = Float64[Float64(phase.Diffusion_coeff(c...)) for c in Cω]
@@ -809,10 +832,17 @@ function _moving_step!(s::Solver, phase::Phase, bc_b::BorderConditions, bc_i::Ab
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve g D fn fn1 Tᵢ borders begin
         desc = Ref(_interface_desc(bc_i, g))
-        check(ccall((:pg_solver_create_moving_mono, libpg), Int32,
-                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                     Ptr{Float64}, Int32, Ptr{Ptr{Cvoid}}),
-                    cap.handle, phase.operator.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, _scheme(scheme), h))
+        if advdiff          # A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:64-199)
+            check(ccall((:pg_solver_create_moving_advdiff_mono, libpg), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                         Ptr{Float64}, Int32, Ptr{Ptr{Cvoid}}),
+                        cap.handle, phase.operator.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, _scheme(scheme), h))
+        else
+            check(ccall((:pg_solver_create_moving_mono, libpg), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                         Ptr{Float64}, Int32, Ptr{Ptr{Cvoid}}),
+                        cap.handle, phase.operator.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, _scheme(scheme), h))
+        end
     end
     s.handle = h[]
     _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, t)
@@ -859,8 +889,9 @@ end
 # ---- two phases: MovingDiffusionUnsteadyDiph (:272-290), A_/b_diph_unstead_diff_moving (:292-498),
 # solve_MovingDiffusionUnsteadyDiph! (:501-535) -----------------------------------------------------------------------------------
 function _moving_step_diph!(s::Solver, phase1::Phase, phase2::Phase, bc_b::BorderConditions, ic::InterfaceConditions, Δt::Float64,
-                            Tᵢ::Vector{Float64}, mesh::Mesh, scheme::String, t::Float64)
+                            Tᵢ::Vector{Float64}, mesh::Mesh, scheme::String, t::Float64; advdiff::Bool=false)
     c1, c2 = phase1.capacity, phase2.capacity
+    advdiff && (_need_st_conv(phase1); _need_st_conv(phase2))
     (c1 isa SpaceTimeCapacity && c2 isa SpaceTimeCapacity) ||
         error("the moving solver needs space-time capacities: Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
     Cω1, Cω2 = _st_coords(c1.C_ω, c1.Ct_ω), _st_coords(c2.C_ω, c2.Ct_ω)
@@ -879,11 +910,19 @@ function _moving_step_diph!(s::Solver, phase1::Phase, phase2::Phase, bc_b::Borde
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve g hh D1 D2 f1n f2n f1n1 f2n1 Tᵢ borders begin
         desc = Ref(_jump_desc(ic, c1, c2, g, hh))
-        check(ccall((:pg_solver_create_moving_diph, libpg), Int32,
-                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
-                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
-                    c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
-                    f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
+        if advdiff          # A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:266-507)
+            check(ccall((:pg_solver_create_moving_advdiff_diph, libpg), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
+                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                        c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
+                        f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
+        else
+            check(ccall((:pg_solver_create_moving_diph, libpg), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
+                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                        c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
+                        f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
+        end
     end
     s.handle = h[]
     _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, nothing)   # BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
@@ -923,6 +962,87 @@ function solve_MovingDiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Ph
         ph1 = Phase(capacity1, DiffusionOps(capacity1), phase1.source, phase1.Diffusion_coeff)
         ph2 = Phase(capacity2, DiffusionOps(capacity2), phase2.source, phase2.Diffusion_coeff)
         _moving_step_diph!(s, ph1, ph2, bc_b, ic, Δt, Tᵢ, mesh, scheme, t)   # A, b, BC_border_diph!(A, b, bc_b, mesh)   :519-523
+        solve!()
+        Tᵢ = s.x
+    end
+    s
+end
+
+# ---- prescribed-motion advection-diffusion: MovingAdvDiffusionUnsteadyMono / Diph and their loops
+# (prescribedmotionsolver/advectiondiffusion.jl:15-33, 201-242, 246-264, 510-553); the operators are ConvectionOps of the
+# space-time capacities, rebuilt per slab from the same uₒ, uᵧ ----------------------------------------------------------------
+_need_st_conv(ph::Phase) = (ph.operator isa ConvectionOps && ph.capacity isa SpaceTimeCapacity) ||
+    error("the moving advection-diffusion solver needs phase.operator = ConvectionOps(capacity, uₒ, uᵧ) of a space-time capacity")
+
+function MovingAdvDiffusionUnsteadyMono(phase::Phase, bc_b::BorderConditions, bc_i::AbstractBoundary, Δt::Float64, Tᵢ::Vector{Float64},
+                                        mesh::AbstractMesh, scheme::String)
+    println("Solver Creation:"); println("- Moving problem"); println("- Monophasic problem"); println("- Unsteady problem"); println("- Advection-Diffusion problem")
+    s = _new_solver(:Unsteady, :Monophasic, :DiffusionAdvection, Ptr{Cvoid}(C_NULL), length(Tᵢ))
+    _moving_step!(s, phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme, 0.0; advdiff=true)   # t = 0.0 in b and in the border rows (:24-31)
+end
+
+function solve_MovingAdvDiffusionUnsteadyMono!(s::Solver, phase::Phase, body::Function, Δt::Float64, Tₛ::Float64, Tₑ::Float64,
+                                               bc_b::BorderConditions, bc::AbstractBoundary, mesh::AbstractMesh, scheme::String, uₒ, uᵧ;
+                                               method::Function=gmres, algorithm=nothing, kwargs...)
+    (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
+    kw = Dict{Symbol, Any}(kwargs)
+    log = get(kw, :log, false)
+    opts = Ref(_opts(method, kw))
+    info = pg_step_info()
+    function solve!()
+        check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
+        _record!(s, info, log)
+        println("Solver Extremum : ", maximum(abs.(s.x)))
+    end
+    t = Tₛ                                                                   # :213
+    println("Time : $(t)")
+    solve!()
+    Tᵢ = s.x
+    while t < Tₑ
+        t += Δt
+        println("Time : $(t)")
+        capacity = Capacity(body, SpaceTimeMesh(mesh, [t, t + Δt], tag=mesh.tag); compute_centroids=true)
+        ph = Phase(capacity, ConvectionOps(capacity, uₒ, uᵧ), phase.source, phase.Diffusion_coeff)      # :225-227
+        _moving_step!(s, ph, bc_b, bc, Δt, Tᵢ, mesh, scheme, t; advdiff=true)    # A, b, BC_border_mono!(...; t=t)   :229-232
+        solve!()
+        Tᵢ = s.x
+    end
+    s
+end
+
+function MovingAdvDiffusionUnsteadyDiph(phase1::Phase, phase2::Phase, bc_b::BorderConditions, ic::InterfaceConditions, Δt::Float64,
+                                        Tᵢ::Vector{Float64}, mesh::AbstractMesh, scheme::String)
+    println("Solver Creation:"); println("- Moving problem"); println("- Diphasic problem"); println("- Unsteady problem"); println("- Advection-Diffusion problem")
+    s = _new_solver(:Unsteady, :Diphasic, :DiffusionAdvection, Ptr{Cvoid}(C_NULL), length(Tᵢ))
+    _moving_step_diph!(s, phase1, phase2, bc_b, ic, Δt, Tᵢ, mesh, scheme, 0.0; advdiff=true)     # t = 0.0 in b (:255-262)
+end
+
+function solve_MovingAdvDiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Phase, body::Function, body_c::Function, Δt::Float64,
+                                               Tₛ::Float64, Tₑ::Float64, bc_b::BorderConditions, ic::InterfaceConditions,
+                                               mesh::AbstractMesh, scheme::String, uₒ, uᵧ; method::Function=gmres, algorithm=nothing,
+                                               kwargs...)
+    (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
+    kw = Dict{Symbol, Any}(kwargs)
+    log = get(kw, :log, false)
+    opts = Ref(_opts(method, kw))
+    info = pg_step_info()
+    function solve!()
+        check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
+        _record!(s, info, log)
+        println("Solver Extremum : ", maximum(abs.(s.x)))
+    end
+    t = Tₛ                                                                   # :522 (the diffusion twin starts at 0.0)
+    println("Time : $(t)")
+    solve!()
+    Tᵢ = s.x
+    while t < Tₑ
+        t += Δt
+        println("Time : $(t)")
+        STmesh = SpaceTimeMesh(mesh, [t, t + Δt], tag=mesh.tag)
+        capacity1, capacity2 = Capacity(body, STmesh), Capacity(body_c, STmesh)
+        ph1 = Phase(capacity1, ConvectionOps(capacity1, uₒ, uᵧ), phase1.source, phase1.Diffusion_coeff)   # :537-538
+        ph2 = Phase(capacity2, ConvectionOps(capacity2, uₒ, uᵧ), phase2.source, phase2.Diffusion_coeff)
+        _moving_step_diph!(s, ph1, ph2, bc_b, ic, Δt, Tᵢ, mesh, scheme, t; advdiff=true)   # BC_border_diph!(A, b, bc_b, mesh)  :543
         solve!()
         Tᵢ = s.x
     end

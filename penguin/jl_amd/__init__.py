@@ -23,6 +23,8 @@ from .utils import (  # noqa: F401,E402
 )
 from .vtk import write_vtk  # noqa: F401,E402
 from .moving import (  # noqa: F401,E402
-    MovingCircle, MovingDiffusionUnsteadyDiph, MovingDiffusionUnsteadyMono, MovingHalfSpace, MovingSphere, SpaceTimeCapacity,
-    SpaceTimeMesh, solve_MovingDiffusionUnsteadyDiph_b, solve_MovingDiffusionUnsteadyMono_b,
+    MovingAdvDiffusionUnsteadyDiph, MovingAdvDiffusionUnsteadyMono, MovingCircle, MovingDiffusionUnsteadyDiph,
+    MovingDiffusionUnsteadyMono, MovingHalfSpace, MovingSphere, SpaceTimeCapacity, SpaceTimeMesh,
+    solve_MovingAdvDiffusionUnsteadyDiph_b, solve_MovingAdvDiffusionUnsteadyMono_b, solve_MovingDiffusionUnsteadyDiph_b,
+    solve_MovingDiffusionUnsteadyMono_b,
 )

@@ -387,24 +387,49 @@ class DiffusionOps:
 
 class ConvectionOps(DiffusionOps):
     """ConvectionOps(capacity, uₒ, uᵧ) -- src/operators.jl:194-210: C_d = δ_p[d]·diag(Σ_m[d] A_d uₒ_d)·Σ_m[d],
-    K_d = diag(Σ_p[d] Hᵀuᵧ), plus G, H, Wꜝ, V, size as DiffusionOps.  uₒ: N arrays of length M, uᵧ: length N·M."""
+    K_d = diag(Σ_p[d] Hᵀuᵧ), plus G, H, Wꜝ, V, size as DiffusionOps.  uₒ: N arrays of length M, uᵧ: length N·M.
+
+    On a space-time capacity (Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt])), 2-D+t): uₒ = (uₒx, uₒy, uₒt), each of length
+    2M, uᵧ of length 3·2M, as the reference's moving advection-diffusion solvers take them; `C` / `K` are then the three
+    blocks those solvers slice (prescribedmotionsolver/advectiondiffusion.jl:94-95): C[1][L1,L1] = C_x of the first time
+    layer, C[2][L2,L2] = C_y on the time padding (zero: A_y = 0 there), C[3][L1,L2] (zero: uₒt = 0 is required), and the same
+    of K, where only K[1][L1,L1] = diag(Σ_p[x] Hᵀuᵧ) is used.  A non-zero uₒt or time block of uᵧ is refused."""
 
     def __init__(self, capacity: Capacity, uₒ, uᵧ):
         super().__init__(capacity)
         N, M = capacity.N, int(np.prod(capacity.mesh.ext))
         us = [np.ascontiguousarray(u, dtype=np.float64) for u in uₒ]
         ug = np.ascontiguousarray(uᵧ, dtype=np.float64)
+        self._st = getattr(capacity, "stmesh", None) is not None          # a SpaceTimeCapacity (moving.py)
+        if self._st:
+            n1, M2 = N + 1, 2 * M
+            if len(us) != n1 or any(u.shape != (M2,) for u in us) or ug.shape != (n1 * M2,):
+                raise ValueError(f"ConvectionOps(space-time capacity): uₒ must be {n1} vectors of length {M2} (space "
+                                 f"components, then time), uᵧ a vector of length {n1 * M2}")
+            ptrs = (C.POINTER(C.c_double) * n1)(*[L.dptr(u) for u in us])
+            L.check(L.lib().pg_diffops_set_velocity_spacetime(self._h, ptrs, L.dptr(ug)))
+            return
         if len(us) != N or any(u.shape != (M,) for u in us) or ug.shape != (N * M,):
             raise ValueError(f"ConvectionOps: uₒ must be {N} vectors of length {M}, uᵧ a vector of length {N * M}")
         ptrs = (C.POINTER(C.c_double) * N)(*[L.dptr(u) for u in us])
         L.check(L.lib().pg_diffops_set_velocity(self._h, ptrs, L.dptr(ug)))
 
+    def _st_blocks(self, first):
+        import scipy.sparse as sp
+
+        M = int(np.prod(self.capacity.mesh.ext))
+        return (self._export(first),) + tuple(sp.csc_matrix((M, M)) for _ in range(2))
+
     @property
     def C(self):
+        if self._st:
+            return self._st_blocks(L.PG_OP_C0)
         return tuple(self._export(L.PG_OP_C0 + d) for d in range(self.capacity.N))
 
     @property
     def K(self):
+        if self._st:
+            return self._st_blocks(L.PG_OP_K0)
         return tuple(self._export(L.PG_OP_K0 + d) for d in range(self.capacity.N))
 
 

@@ -30,6 +30,9 @@ struct pg_diffops {
   pg::DevBuf<double> conv_a[3];   // a_d = Σ_m[d] (A_d ∘ uω_d): C_d = δ_p[d] diag(a_d) Σ_m[d]
   pg::DevBuf<double> conv_h;      // Hᵀ uγ
   pg::DevBuf<double> conv_k;      // ½ Σ_d Σ_p[d] Hᵀuγ = the diagonal of 0.5 * sum(K)
+  // ConvectionOps of a SPACE-TIME capacity (pg_diffops_set_velocity_spacetime): what the moving advection-diffusion blocks
+  // read of it on the first time layer -- conv_a[0] of C_x only (C_y is taken on the time padding: zero), conv_k = ½K_x
+  bool st_velocity = false;
 };
 
 namespace pg {

@@ -75,13 +75,14 @@ __global__ void k_conv_h(CapView c, i64 Mloc, const double* __restrict__ ug /*N 
   }
 }
 
-// diagonal of 0.5 * sum_d K_d,  K_d = diag(Σ_p[d] h):  (Σ_p h)[k] = ½(h[k] + h[k+1]) for k < m, 0 in the last row
-__global__ void k_conv_kappa(CapView c, i64 Mloc, const double* __restrict__ h, double* __restrict__ kap) {
+// diagonal of 0.5 * sum_{d < nd} K_d,  K_d = diag(Σ_p[d] h):  (Σ_p h)[k] = ½(h[k] + h[k+1]) for k < m, 0 in the last row
+// (nd = N: ½ΣK of the static operators; nd = 1: ½K_x, the only K block the moving advection-diffusion solvers read)
+__global__ void k_conv_kappa(CapView c, i64 Mloc, int nd, const double* __restrict__ h, double* __restrict__ kap) {
   for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < Mloc; lc += (i64)gridDim.x * blockDim.x) {
     i64 idx[3];
     decode_cell(c.N, c.ext, c.plane, c.s0, lc, idx);
     double s = 0.0;
-    for (int d = 0; d < c.N; ++d) {
+    for (int d = 0; d < nd; ++d) {
       const i64 st = c.stride[d], m = c.ext[d] - 1;
       if (idx[d] < m && lc + st < Mloc) s += 0.5 * (h[lc] + h[lc + st]);
     }
@@ -116,10 +117,58 @@ int32_t pg_diffops_set_velocity(pg_diffops* o, const double* const* u_omega, con
   o->conv_h.alloc(Ml);
   o->conv_k.alloc(Ml);
   hipLaunchKernelGGL(k_conv_h, dim3(gr), dim3(256), 0, st, cv, Ml, ug.p, o->conv_h.p);
-  hipLaunchKernelGGL(k_conv_kappa, dim3(gr), dim3(256), 0, st, cv, Ml, o->conv_h.p, o->conv_k.p);
+  hipLaunchKernelGGL(k_conv_kappa, dim3(gr), dim3(256), 0, st, cv, Ml, c->N, o->conv_h.p, o->conv_k.p);
   PG_HIP(hipGetLastError());
   PG_HIP(hipStreamSynchronize(st));
   o->has_velocity = true;
+  o->st_velocity = false;
+  PG_API_END
+}
+
+// ConvectionOps(capacity, uₒ, uᵧ) of a space-time capacity, as A_/b_*_unstead_advdiff_moving read it
+// (prescribedmotionsolver/advectiondiffusion.jl:94-95, 158-159: C[1][L1,L1], C[2][L2,L2], C[3][L1,L2] and the same blocks
+// of K, of which only K[1] is used).  On the first layer L1: C_x from the space-time A_x and uₒx[L1]; C[2] is C_y on the
+// time padding, where A_y = 0 -- zero whatever uₒy is; C[3] and the H_t part of Hᵀuᵧ vanish with uₒt = 0 and uᵧt = 0, which
+// are required (H_t would need B_t, which the space-time capacity does not compute).  K[1][L1,L1] = diag(Σ_p[x] h),
+// h = Hᵀuᵧ on L1 summed over the space directions: ½K_x is stored in conv_k.
+int32_t pg_diffops_set_velocity_spacetime(pg_diffops* o, const double* const* u_omega, const double* u_gamma) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(o && u_omega && u_gamma, "pg_diffops_set_velocity_spacetime: NULL argument");
+  pg_capacity* c = o->cap;
+  PG_REQUIRE(c->spacetime, "pg_diffops_set_velocity_spacetime needs a space-time capacity (pg_capacity_create_spacetime)");
+  PG_REQUIRE(c->N != 1, "ConvectionOps on a 1-D+t space-time capacity is refused: the reference's moving advection-diffusion "
+             "blocks index C[3] of a 2-tuple there (BoundsError, prescribedmotionsolver/advectiondiffusion.jl:94,158)");
+  PG_REQUIRE(c->N == 2, "ConvectionOps on a space-time capacity: 2-D+t only (as the moving diffusion solvers)");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "space-time operators are single-rank");
+  const Slab& s = c->slab;
+  const int N = c->N;
+  const i64 M = s.M, Ml = s.Mloc();
+  for (int d = 0; d <= N; ++d) PG_REQUIRE(u_omega[d], "pg_diffops_set_velocity_spacetime: NULL velocity component");
+  for (i64 i = 0; i < 2 * M; ++i)
+    PG_REQUIRE(u_omega[N][i] == 0.0, "ConvectionOps(space-time capacity): the time component of uₒ must be zero (its block "
+               "C[3] needs the space-time A_t of both layers, which the moving advection-diffusion solvers do not support)");
+  for (i64 i = 0; i < 2 * M; ++i)
+    PG_REQUIRE(u_gamma[(i64)N * 2 * M + i] == 0.0, "ConvectionOps(space-time capacity): the time block of uᵧ must be zero "
+               "(Hᵀuᵧ would need H_t, i.e. B_t, which the space-time capacity does not compute)");
+  hipStream_t st = ctx().stream;
+  const CapView cv = cap_view(c);
+  const int gr = grid_for(Ml, 256, 256 * 16);
+  DevBuf<double> u(Ml), ug((i64)N * Ml);
+  u.upload(u_omega[0], Ml);                                   // uₒx on L1
+  o->conv_a[0].alloc(Ml);
+  for (int d = 1; d < 3; ++d) o->conv_a[d].release();       // no C_y (quirk: taken on the time padding)
+  hipLaunchKernelGGL(k_conv_a, dim3(gr), dim3(256), 0, st, cv, Ml, 0, u.p, o->conv_a[0].p);
+  PG_HIP(hipGetLastError());
+  for (int d = 0; d < N; ++d) ug.upload(u_gamma + (i64)d * 2 * M, Ml, (i64)d * Ml);   // uᵧ_d on L1
+  o->conv_h.alloc(Ml);
+  o->conv_k.alloc(Ml);
+  hipLaunchKernelGGL(k_conv_h, dim3(gr), dim3(256), 0, st, cv, Ml, ug.p, o->conv_h.p);
+  hipLaunchKernelGGL(k_conv_kappa, dim3(gr), dim3(256), 0, st, cv, Ml, 1, o->conv_h.p, o->conv_k.p);
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipStreamSynchronize(st));
+  o->has_velocity = true;
+  o->st_velocity = true;
   PG_API_END
 }
 
@@ -184,6 +233,7 @@ int32_t pg_diffops_export_csc(const pg_diffops* o, int32_t which, int64_t* colpt
     // C_d = δ_p diag(a_d) Σ_m  (M x M, tridiagonal along dimension d; rows k = m are empty)
     const int d = which - PG_OP_C0;
     PG_REQUIRE(o->has_velocity && d < N, "pg_diffops_export_csc: no velocity set (ConvectionOps) or bad dimension");
+    PG_REQUIRE(!o->st_velocity || d == 0, "pg_diffops_export_csc: a space-time ConvectionOps holds C_x of the first layer only");
     std::vector<double> a(M);
     o->conv_a[d].download(a.data(), M);
     const i64 m = s.ext[d] - 1, st = s.stride[d];
@@ -215,6 +265,7 @@ int32_t pg_diffops_export_csc(const pg_diffops* o, int32_t which, int64_t* colpt
     // K_d = diag(Σ_p[d] Hᵀuγ)
     const int d = which - PG_OP_K0;
     PG_REQUIRE(o->has_velocity && d < N, "pg_diffops_export_csc: no velocity set (ConvectionOps) or bad dimension");
+    PG_REQUIRE(!o->st_velocity || d == 0, "pg_diffops_export_csc: a space-time ConvectionOps holds K_x of the first layer only");
     *nnz = M;
     if (!nzval) return 0;
     std::vector<double> h(M);

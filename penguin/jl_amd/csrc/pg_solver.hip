@@ -101,6 +101,10 @@ struct pg_solver {
   // moving body (pg_solver_create_moving_mono): one space-time step; Ψn1 = psip.(Vn, Vn_1), Ψn = psim.(Vn, Vn_1)
   bool moving = false;
   DevBuf<double> psi_p[2], psi_m[2];   // per phase
+  // moving advection-diffusion (pg_solver_create_moving_advdiff_*): psip_conv.(Vn, Vn_1) / psim_conv.(Vn, Vn_1), per phase
+  // (prescribedmotionsolver/advectiondiffusion.jl:35-61); the convection data come from the ConvectionOps in ops[]
+  bool advdiff = false;
+  DevBuf<double> psi_cp[2], psi_cm[2];
   pg_solver* init_from = nullptr;   // constructor only: the previous slab's solver whose state is this one's initial state
 };
 
@@ -858,7 +862,8 @@ __global__ void k_rhs_first(RowSegs seg, i64 n, i64 Mloc, int scheme, const int*
     double v;
     if (fixed[r]) v = bconst[r];
     else if (moving && (k & 1)) v = bconst[r];                                        // b2 = Γ g
-    else if (moving && scheme == PG_SCHEME_CN) v = mass[r] * T - ypad[q] + bconst[r];   // (Vn - Id GᵀWꜝGΨn)Tω - ½Id GᵀWꜝH Tγ + ...
+    else if (moving && ypad) v = mass[r] * T - ypad[q] + bconst[r];   // CN: (Vn - Id GᵀWꜝGΨn)Tω - ½Id GᵀWꜝH Tγ + ...;
+                                                                     // advection-diffusion: - the explicit convection too
     else if (scheme == PG_SCHEME_CN) v = 2.0 * (mass[r] * T) - ypad[q] + bconst[r];
     else v = mass[r] * T + bconst[r];
     braw[r] = v;
@@ -867,8 +872,10 @@ __global__ void k_rhs_first(RowSegs seg, i64 n, i64 Mloc, int scheme, const int*
 }
 
 // Ψn1 = psip.(Vn, Vn_1), Ψn = psim.(Vn, Vn_1)      prescribedmotionsolver/diffusion.jl:55-98 (the live definitions)
+// and, for the advection-diffusion solvers (psicp != nullptr), psip_conv / psim_conv     advectiondiffusion.jl:35-61
 __global__ void k_psi(i64 Mloc, int scheme, const double* __restrict__ vn_1 /*lower face*/, const double* __restrict__ vn,
-                      double* __restrict__ psip, double* __restrict__ psim) {
+                      double* __restrict__ psip, double* __restrict__ psim, double* __restrict__ psicp,
+                      double* __restrict__ psicm) {
   for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < Mloc; i += (i64)gridDim.x * blockDim.x) {
     const bool z1 = vn[i] == 0.0, z2 = vn_1[i] == 0.0;   // args = (Vn, Vn_1)
     double pp, pm;
@@ -881,6 +888,10 @@ __global__ void k_psi(i64 Mloc, int scheme, const double* __restrict__ vn_1 /*lo
     }
     psip[i] = pp;
     psim[i] = pm;
+    if (psicp) {
+      psicp[i] = (z1 && !z2) ? 1.0 : 0.0;                                     // psip_conv: 1 only for (Vn = 0, Vn_1 ≠ 0)
+      psicm[i] = (!z1 && !z2) || (!z1 && z2) ? 1.0 : 0.0;                     // psim_conv: both live, or (Vn ≠ 0, Vn_1 = 0)
+    }
   }
 }
 
@@ -963,18 +974,41 @@ SysParams make_params(const pg_solver* s, int scheme) {
       P.mv_psi_g[q] = s->psi_p[q].p;
     }
     if (s->nphase == 1) { P.mv_v0[1] = P.mv_v0[0]; P.mv_v1[1] = P.mv_v1[0]; P.mv_psi_w[1] = P.mv_psi_w[0]; P.mv_psi_g[1] = P.mv_psi_g[0]; }
+    if (s->advdiff) {         // A: - (sum(C) + ½K[1]) Ψ_conv, - ½K[1] Ψ_conv   (advectiondiffusion.jl:123-124, 357-360)
+      P.mv_conv_sign = -1.0;
+      for (int q = 0; q < 2; ++q) {
+        const int src = q < s->nphase ? q : 0;
+        P.mv_psi_c[q] = P.mv_psi_k[q] = P.mv_psi_kg[q] = s->psi_cp[src].p;
+      }
+      P.mv_flux_no_dv = s->nphase == 2 ? 1 : 0;   // :362-365: no -(Vn_1 - Vn) in the flux row
+    }
   }
   return P;
 }
 
-// the explicit operator of the moving Crank-Nicolson right-hand side (diffusion.jl:214)
+// the explicit operator of the moving Crank-Nicolson right-hand side (diffusion.jl:214); advection-diffusion: the explicit
+// operator of either scheme, convection included (advectiondiffusion.jl:192-194, 494-498):
+//   BE        b1 = Vn Tω + V f - ½K Ψc Tω - ½K Tγ - ΣC Ψc Tω                      Ψc = psim_conv, no diffusion term
+//   CN mono   b1 = (Vn - Id GᵀWꜝG Ψn) Tω - ½Id GᵀWꜝH Tγ + .. - ½K Ψn Tω - ½K Tγ - ΣC Tω      Ψn = psim
+//   CN diph   b1 = (Vn - Id GᵀWꜝG Ψn) Tω - ½Id GᵀWꜝH Tγ + .. - ΣC Tω - ½K Tω - ½K Tγ    (no Ψ on the γ term either)
 SysParams make_params_moving_explicit(const pg_solver* s) {
   SysParams P = make_params(s, PG_SCHEME_CN);
+  const bool cn = s->scheme_ctor == PG_SCHEME_CN;
   for (int q = 0; q < 2; ++q) {
     const int src = q < s->nphase ? q : 0;
     P.mv_psi_w[q] = s->psi_m[src].p;
     // mono (:214): the γ term is -½ Id GᵀWꜝH Tγ; diph (:487-488): -Id GᵀWꜝH Ψn Tγ with the same Ψn = psim as the ω term
     P.mv_psi_g[q] = s->nphase == 2 ? s->psi_m[src].p : nullptr;
+    if (s->advdiff) {
+      P.mv_psi_g[q] = cn ? nullptr : s->psi_m[src].p;            // CN: the constant ½; BE: psim_be = 0, no diffusion term
+      P.mv_psi_c[q] = cn ? nullptr : s->psi_cm[src].p;
+      P.mv_psi_k[q] = cn ? (s->nphase == 1 ? s->psi_m[src].p : nullptr) : s->psi_cm[src].p;
+      P.mv_psi_kg[q] = nullptr;
+    }
+  }
+  if (s->advdiff) {
+    P.mv_conv_sign = 1.0;
+    P.mv_flux_no_dv = 0;   // (interface rows are empty in the explicit operator)
   }
   P.mv_gconst = 0.5;
   P.mv_explicit = 1;
@@ -1022,7 +1056,7 @@ void build_first_rhs(pg_solver* s) {
   const SysParams P = make_params(s, s->scheme_ctor);
   ensure_bconst(s, s->scheme_ctor);
   DevBuf<double> ypad;
-  if (s->scheme_ctor == PG_SCHEME_CN) {
+  if (s->scheme_ctor == PG_SCHEME_CN || s->advdiff) {
     ypad.alloc((i64)s->K * s->Mloc);
     ypad.zero();
     apply_rows_padded(s->moving ? make_params_moving_explicit(s) : P, s->slab, s->T0pad.p, ypad.p);
@@ -1606,7 +1640,7 @@ int32_t pg_solver_create_unsteady_mono(pg_capacity* c, pg_diffops* o, const pg_b
 
 static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
                              int32_t nborders, const double* Dcoef, const double* source_n, const double* source_np1,
-                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out);
+                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out, bool advdiff = false);
 
 int32_t pg_solver_create_moving_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                      const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
@@ -1626,9 +1660,29 @@ int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const p
   return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, nullptr, previous, scheme, out);
 }
 
+// MovingAdvDiffusionUnsteadyMono + A_/b_mono_unstead_advdiff_moving of one slab   prescribedmotionsolver/advectiondiffusion.jl:15-33,
+// 64-199: the moving blocks with the convection of the space-time ConvectionOps o (pg_diffops_set_velocity_spacetime)
+int32_t pg_solver_create_moving_advdiff_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                                             const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
+                                             const double* source_n, const double* source_np1, const double* T_prev,
+                                             int32_t scheme, pg_solver** out) {
+  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, T_prev, nullptr, scheme, out, true);
+}
+
+int32_t pg_solver_create_moving_advdiff_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                                                  const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
+                                                  const double* source_n, const double* source_np1, pg_solver* previous,
+                                                  int32_t scheme, pg_solver** out) {
+  if (!previous) {
+    pg::set_last_error("pg_solver_create_moving_advdiff_mono_next: NULL previous solver");
+    return 1;
+  }
+  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, nullptr, previous, scheme, out, true);
+}
+
 static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
                              int32_t nborders, const double* Dcoef, const double* source_n, const double* source_np1,
-                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out) {
+                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out, bool advdiff) {
   PG_API_BEGIN
   require_init();
   if (prev) PG_REQUIRE(prev->initial_done, "pg_solver_create_moving_mono_next: the previous slab has not been solved");
@@ -1637,7 +1691,11 @@ static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc
   PG_REQUIRE(c && o && bc_interface && out, "solver constructor: NULL argument");
   PG_REQUIRE(o->cap == c, "operators were built from a different capacity");
   PG_REQUIRE(c->spacetime, "pg_solver_create_moving_mono needs a space-time capacity (pg_capacity_create_spacetime)");
-  PG_REQUIRE(!o->has_velocity, "the moving diffusion solver takes no convection operators");
+  if (advdiff)
+    PG_REQUIRE(o->st_velocity, "the moving advection-diffusion solver needs the ConvectionOps of its space-time capacity "
+               "(pg_diffops_set_velocity_spacetime)");
+  else
+    PG_REQUIRE(!o->has_velocity, "the moving diffusion solver takes no convection operators");
   PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "space-time steps are single-rank");
   auto* s = new pg_solver();
   std::unique_ptr<pg_solver> guard(s);
@@ -1647,13 +1705,18 @@ static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc
   s->slab = c->slab;
   s->dt = 1.0;            // Δt is inside the space-time capacities
   s->moving = true;
+  s->advdiff = advdiff;
   s->scheme_ctor = scheme;
   s->bc_i = *bc_interface;
   const i64 Ml = s->slab.Mloc();
   s->psi_p[0].alloc(Ml);
   s->psi_m[0].alloc(Ml);
+  if (advdiff) {
+    s->psi_cp[0].alloc(Ml);
+    s->psi_cm[0].alloc(Ml);
+  }
   hipLaunchKernelGGL(k_psi, dim3(grid_for(Ml, BLOCK)), dim3(BLOCK), 0, ctx().stream, Ml, (int)scheme, c->Vt[0].p, c->Vt[1].p,
-                     s->psi_p[0].p, s->psi_m[0].p);
+                     s->psi_p[0].p, s->psi_m[0].p, s->psi_cp[0].p, s->psi_cm[0].p);
   PG_HIP(hipGetLastError());
   if (Dcoef) upload_local(s->Id[0], Dcoef, s->slab);
   if (source_np1) upload_local(s->f_np1[0], source_np1, s->slab);
@@ -1670,11 +1733,34 @@ static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc
   PG_API_END
 }
 
+static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
+                                  const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
+                                  const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
+                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff);
+
 // MovingDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving of one slab      prescribedmotionsolver/diffusion.jl:272-498
 int32_t pg_solver_create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
                                      const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
                                      const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
                                      const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out) {
+  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
+                            out, false);
+}
+
+// MovingAdvDiffusionUnsteadyDiph + A_/b_diph_unstead_advdiff_moving of one slab   prescribedmotionsolver/advectiondiffusion.jl:246-507
+int32_t pg_solver_create_moving_advdiff_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                             const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                             const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
+                                             const double* f2_n, const double* f2_np1, const double* T_prev,
+                                             pg_solver* previous, int32_t scheme, pg_solver** out) {
+  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
+                            out, true);
+}
+
+static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
+                                  const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
+                                  const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
+                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff) {
   PG_API_BEGIN
   require_init();
   if (previous) PG_REQUIRE(previous->initial_done, "pg_solver_create_moving_diph: the previous slab has not been solved");
@@ -1684,7 +1770,11 @@ int32_t pg_solver_create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacit
   PG_REQUIRE(o1->cap == c1 && o2->cap == c2, "operators were built from a different capacity");
   PG_REQUIRE(c1->spacetime && c2->spacetime, "pg_solver_create_moving_diph needs space-time capacities (pg_capacity_create_spacetime)");
   PG_REQUIRE(c1->mesh == c2->mesh, "Phase capacities must share the same mesh.");
-  PG_REQUIRE(!o1->has_velocity && !o2->has_velocity, "the moving diffusion solver takes no convection operators");
+  if (advdiff)
+    PG_REQUIRE(o1->st_velocity && o2->st_velocity, "the moving advection-diffusion solver needs the ConvectionOps of its "
+               "space-time capacities (pg_diffops_set_velocity_spacetime)");
+  else
+    PG_REQUIRE(!o1->has_velocity && !o2->has_velocity, "the moving diffusion solver takes no convection operators");
   PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "space-time steps are single-rank");
   auto* s = new pg_solver();
   std::unique_ptr<pg_solver> guard(s);
@@ -1694,14 +1784,19 @@ int32_t pg_solver_create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacit
   s->slab = c1->slab;
   s->dt = 1.0;            // Δt is inside the space-time capacities
   s->moving = true;
+  s->advdiff = advdiff;
   s->scheme_ctor = scheme;
   s->ic = *ic;
   const i64 Ml = s->slab.Mloc();
   for (int q = 0; q < 2; ++q) {
     s->psi_p[q].alloc(Ml);
     s->psi_m[q].alloc(Ml);
+    if (advdiff) {
+      s->psi_cp[q].alloc(Ml);
+      s->psi_cm[q].alloc(Ml);
+    }
     hipLaunchKernelGGL(k_psi, dim3(grid_for(Ml, BLOCK)), dim3(BLOCK), 0, ctx().stream, Ml, (int)scheme, s->cap[q]->Vt[0].p,
-                       s->cap[q]->Vt[1].p, s->psi_p[q].p, s->psi_m[q].p);
+                       s->cap[q]->Vt[1].p, s->psi_p[q].p, s->psi_m[q].p, s->psi_cp[q].p, s->psi_cm[q].p);
   }
   PG_HIP(hipGetLastError());
   if (D1) upload_local(s->Id[0], D1, s->slab);

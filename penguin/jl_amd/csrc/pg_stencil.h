@@ -45,6 +45,15 @@ struct SysParams {
   double mv_gconst;
   int mv_explicit;         // 1: the explicit Crank-Nicolson operator [Id GᵀWꜝG Ψn, ½ Id GᵀWꜝH] of :214 -- bulk rows only, no
                            // volume terms; interface rows are empty (b2 = Γ g carries no T term there)
+  // moving advection-diffusion (prescribedmotionsolver/advectiondiffusion.jl): conv_a[q][0] (C_x of the first time layer)
+  // and conv_k[q] (½K_x) enter the moving bulk rows as  mv_conv_sign · [ΣC Ψc + ½K Ψk ,  ½K Ψkg]  with per-column
+  // scalings (nullptr = 1):  A (:123-124, :357-360): sign -1, Ψc = Ψk = Ψkg = psip_conv;  the explicit operator subtracted
+  // in b (:192-194, :494-498): sign +1 with the scheme's scalings (make_params_moving_explicit)
+  double mv_conv_sign;
+  const double* mv_psi_c[2];
+  const double* mv_psi_k[2];
+  const double* mv_psi_kg[2];
+  int mv_flux_no_dv;       // diph advection-diffusion: the flux row has no -(Vn_1 - Vn) term (:362-365 vs diffusion.jl:379-381)
 };
 
 __host__ __device__ inline int nkinds(const SysParams& P) { return P.nphase == 1 ? 2 : 4; }
@@ -187,13 +196,16 @@ __device__ inline void eval_row(const SysParams& P, int kind, i64 lc, const i64*
             cm = -0.5 * a0;
             dC += 0.5 * (a1 - a0);
           }
-          if (mv) {       // column scaling Ψ (no convection in the moving solver)
+          if (mv) {       // column scaling Ψ; convection (advection-diffusion only) with its own scaling Ψc
+            const double* pc = P.mv_psi_c[q];
             if (L.has_p) {
-              emit(kw, lc + st, scale * (L.gl_p * L.w_p * L.gd_p) * P.mv_psi_w[q][lc + st]);
+              const double cv = ca ? P.mv_conv_sign * cp * (pc ? pc[lc + st] : 1.0) : 0.0;
+              emit(kw, lc + st, scale * (L.gl_p * L.w_p * L.gd_p) * P.mv_psi_w[q][lc + st] + cv);
               emit(kg, lc + st, scale * (L.gl_p * L.w_p * L.hd_p) * (P.mv_psi_g[q] ? P.mv_psi_g[q][lc + st] : P.mv_gconst));
             }
             if (L.has_m) {
-              emit(kw, lc - st, scale * (L.gd_j * L.w_j * L.gl_j) * P.mv_psi_w[q][lc - st]);
+              const double cv = ca ? P.mv_conv_sign * cm * (pc ? pc[lc - st] : 1.0) : 0.0;
+              emit(kw, lc - st, scale * (L.gd_j * L.w_j * L.gl_j) * P.mv_psi_w[q][lc - st] + cv);
               emit(kg, lc - st, scale * (L.gd_j * L.w_j * L.hl_j) * (P.mv_psi_g[q] ? P.mv_psi_g[q][lc - st] : P.mv_gconst));
             }
             continue;
@@ -236,8 +248,14 @@ __device__ inline void eval_row(const SysParams& P, int kind, i64 lc, const i64*
     if (bulk && mv) {
       const double pw = P.mv_psi_w[q][lc], pg = P.mv_psi_g[q] ? P.mv_psi_g[q][lc] : P.mv_gconst;
       const double v0 = P.mv_explicit ? 0.0 : P.mv_v0[q][lc], v1 = P.mv_explicit ? 0.0 : P.mv_v1[q][lc];
-      emit(kw, lc, v0 + scale * dW * pw);               // Vn_1 + (Id GᵀWꜝG Ψ)_jj
-      emit(kg, lc, -(v0 - v1) + scale * dG * pg);       // -(Vn_1 - Vn) + (Id GᵀWꜝH Ψ)_jj
+      double cw = 0.0, cg = 0.0;                        // advection-diffusion: ±(ΣC Ψc + ½K Ψk)_jj, ±(½K Ψkg)_jj
+      if (P.conv_k[q]) {
+        const double ck = P.conv_k[q][lc];
+        cw = P.mv_conv_sign * (dC * (P.mv_psi_c[q] ? P.mv_psi_c[q][lc] : 1.0) + ck * (P.mv_psi_k[q] ? P.mv_psi_k[q][lc] : 1.0));
+        cg = P.mv_conv_sign * ck * (P.mv_psi_kg[q] ? P.mv_psi_kg[q][lc] : 1.0);
+      }
+      emit(kw, lc, v0 + scale * dW * pw + cw);          // Vn_1 + (Id GᵀWꜝG Ψ)_jj
+      emit(kg, lc, -(v0 - v1) + scale * dG * pg + cg);  // -(Vn_1 - Vn) + (Id GᵀWꜝH Ψ)_jj
     } else if (bulk) {
       const double ck = P.conv_k[q] ? P.conv_k[q][lc] : 0.0;          // 0.5 sum(K): on both diagonals (A11 and A12)
       emit(kw, lc, P.mass * c.V[lc] + scale * dW + P.theta * (dC + ck));   // V + θ(Id·GᵀWꜝG + ΣC + ½ΣK)_jj  (steady: no V)
@@ -248,7 +266,7 @@ __device__ inline void eval_row(const SysParams& P, int kind, i64 lc, const i64*
     } else if (mv) {                    // moving flux row: β_q (HᵀWꜝG Ψ)_jj, β_q (HᵀWꜝH Ψ)_jj - (Vn_1 - Vn)   (:378-381)
       const double pw = P.mv_psi_w[q][lc];
       emit(kw, lc, scale * dW * pw);
-      emit(kg, lc, scale * dG * pw - (P.mv_v0[q][lc] - P.mv_v1[q][lc]));
+      emit(kg, lc, scale * dG * pw - (P.mv_flux_no_dv ? 0.0 : P.mv_v0[q][lc] - P.mv_v1[q][lc]));
     } else {
       emit(kw, lc, scale * dW);
       emit(kg, lc, scale * dG);

@@ -212,12 +212,22 @@ def _capacity_new(cls, body=None, mesh=None, *args, **kwargs):
 api.Capacity.__new__ = staticmethod(_capacity_new)
 
 
+def _require_st_convection(phase: api.Phase):
+    op = phase.operator
+    if not (isinstance(op, api.ConvectionOps) and op._st):
+        raise PenguinHipError("the moving advection-diffusion solver needs phase.operator = ConvectionOps(capacity, uâ‚’, uáµ§) of "
+                              "the phase's space-time capacity (got a " + type(op).__name__ + ")")
+
+
 def _create_step(s: api.Solver, phase: api.Phase, bc_b, bc_i, Î”t: float, Táµ¢: Optional[np.ndarray], mesh: api.Mesh, scheme: str,
-                 t: float, from_previous: bool = False):
-    """A_/b_mono_unstead_diff_moving + BC_border_mono!(A, b, bc_b, mesh; t) of one slab (diffusion.jl:29-33, 254-258)."""
+                 t: float, from_previous: bool = False, advdiff: bool = False):
+    """A_/b_mono_unstead_diff_moving + BC_border_mono!(A, b, bc_b, mesh; t) of one slab (diffusion.jl:29-33, 254-258);
+    advdiff: A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:24-31, 229-232), the same border rows."""
     cap = phase.capacity
     if not isinstance(cap, SpaceTimeCapacity):
         raise PenguinHipError("the moving solver needs a space-time capacity: Capacity(body, SpaceTimeMesh(mesh, [t, t+Î”t]))")
+    if advdiff:
+        _require_st_convection(phase)
     if cap.mesh is not mesh and tuple(cap.mesh.dims) != tuple(mesh.dims):
         raise ValueError("mesh does not match the capacity's space mesh")
     M = int(np.prod(mesh.ext))
@@ -232,11 +242,13 @@ def _create_step(s: api.Solver, phase: api.Phase, bc_b, bc_i, Î”t: float, Táµ¢: 
     old, new = s._h, C.c_void_p()
     common = (cap._h, phase.operator._h, C.byref(desc), borders, C.c_int32(nb), L.dptr(D_arr) if D_arr is not None else None,
               L.dptr(f0) if f0 is not None else None, L.dptr(f1) if f1 is not None else None)
+    lib = L.lib()
+    create = lib.pg_solver_create_moving_advdiff_mono if advdiff else lib.pg_solver_create_moving_mono
+    create_next = lib.pg_solver_create_moving_advdiff_mono_next if advdiff else lib.pg_solver_create_moving_mono_next
     if from_previous:      # the previous slab's state stays on the device (pg_solver_create_moving_mono_next)
-        L.check(L.lib().pg_solver_create_moving_mono_next(*common, old, C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
+        L.check(create_next(*common, old, C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
     else:
-        L.check(L.lib().pg_solver_create_moving_mono(*common, L.dptr(Táµ¢) if Táµ¢ is not None else None,
-                                                     C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
+        L.check(create(*common, L.dptr(Táµ¢) if Táµ¢ is not None else None, C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
     s._h = new
     if old:
         L.check(L.lib().pg_solver_destroy(old))
@@ -272,27 +284,35 @@ def solve_MovingDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Î
     t += Î”t, the capacity of the slab [t, t+Î”t], new blocks and border rows at t, solve, push.
     `save_states=False` (not in the reference): the state is handed from slab to slab on the device and only the last one is
     fetched (`s.x`, `s.states[-1]`); the reference's `push!(s.states, s.x)` costs a device-to-host copy of 2M doubles per slab."""
+    return _solve_mono(s, phase, body, Î”t, Tâ‚›, Tâ‚‘, bc_b, bc, mesh, scheme, api.DiffusionOps, False, method, geometry_method,
+                       verbose, max_steps, time_panels, time_order, save_states, kwargs)
+
+
+def _solve_current(s: api.Solver, opts, what: str, save_states: bool, verbose: bool):
+    info = L.pg_step_info()
+    L.check(L.lib().pg_solver_initial_solve(s._h, C.byref(opts), C.byref(info)))
+    api._step_info_check(s, info, what)
+    s._initial_done = True
+    s.ch.append(info)
+    if save_states:
+        s.x = s._fetch_state(-1)
+        s.states.append(s.x)
+    if verbose:
+        print("Solver Extremum : ", float(info.extremum))
+
+
+def _solve_mono(s, phase, body, Î”t, Tâ‚›, Tâ‚‘, bc_b, bc, mesh, scheme, make_ops, advdiff, method, geometry_method, verbose,
+                max_steps, time_panels, time_order, save_states, kwargs):
+    """The slab loop shared by the moving mono solvers (diffusion.jl:227-268, advectiondiffusion.jl:201-242): `make_ops(cap)`
+    builds the slab's operator (DiffusionOps, or ConvectionOps from the same uâ‚’, uáµ§ every slab)."""
     if s is None or not s._h:
         raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")
     opts = api._krylov_opts(method, kwargs)
     sch = "CN" if scheme == "CN" else "BE"
-
-    def solve_current(what):
-        info = L.pg_step_info()
-        L.check(L.lib().pg_solver_initial_solve(s._h, C.byref(opts), C.byref(info)))
-        api._step_info_check(s, info, what)
-        s._initial_done = True
-        s.ch.append(info)
-        if save_states:
-            s.x = s._fetch_state(-1)
-            s.states.append(s.x)
-        if verbose:
-            print("Solver Extremum : ", float(info.extremum))
-
     t = float(Tâ‚›)
     if verbose:
         print(f"Time : {t}")
-    solve_current("the first solve")
+    _solve_current(s, opts, "the first solve", save_states, verbose)
     Táµ¢ = s.x
     steps = 0
     while t < Tâ‚‘:
@@ -303,9 +323,9 @@ def solve_MovingDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Î
             print(f"Time : {t}")
         cap = api.Capacity(body, SpaceTimeMesh(mesh, [t, t + Î”t]), time_panels=time_panels, time_order=time_order,
                            compute_centroids=True, method=geometry_method)
-        ph = api.Phase(cap, api.DiffusionOps(cap), phase.source, phase.Diffusion_coeff)
-        _create_step(s, ph, bc_b, bc, float(Î”t), Táµ¢, mesh, sch, t, from_previous=not save_states)
-        solve_current(f"the solve of the slab starting at t = {t}")
+        ph = api.Phase(cap, make_ops(cap), phase.source, phase.Diffusion_coeff)
+        _create_step(s, ph, bc_b, bc, float(Î”t), Táµ¢, mesh, sch, t, from_previous=not save_states, advdiff=advdiff)
+        _solve_current(s, opts, f"the solve of the slab starting at t = {t}", save_states, verbose)
         Táµ¢ = s.x
         steps += 1
     if not save_states:
@@ -314,18 +334,55 @@ def solve_MovingDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Î
     return s
 
 
+def MovingAdvDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Î”t: float, Táµ¢: np.ndarray, mesh: api.Mesh, scheme: str,
+                                   verbose: bool = False) -> api.Solver:
+    """MovingAdvDiffusionUnsteadyMono(phase, bc_b, bc_i, Î”t, Táµ¢, mesh, scheme) -- prescribedmotionsolver/advectiondiffusion.jl:15-33.
+    phase.operator = ConvectionOps(capacity, uâ‚’, uáµ§) of the first slab's space-time capacity (2-D+t).  Convection enters A
+    only in the cells with Vn = 0, Vn_1 â‰  0 (psip_conv); elsewhere it is explicit, through the previous state in b.  The
+    reference's quirks are kept: no bulk y-advection, Â½K_x only (DESIGN.md "Moving advection-diffusion")."""
+    if verbose:
+        print("Solver Creation:\n- Moving problem\n- Monophasic problem\n- Unsteady problem\n- Advection-Diffusion problem")
+    _require_st_convection(phase)
+    s = api.Solver("Unsteady", "Monophasic", "DiffusionAdvection")
+    M = int(np.prod(mesh.ext))
+    s._nunk = 2 * M
+    if Táµ¢ is not None:
+        Táµ¢ = np.ascontiguousarray(Táµ¢, dtype=np.float64)
+        if Táµ¢.shape != (2 * M,):
+            raise ValueError(f"Táµ¢ must have length 2*prod(n+1) = {2 * M}")
+    s._ctx = dict(phase=phase, bc_i=bc_i, dt=float(Î”t), M=M)
+    _create_step(s, phase, bc_b, bc_i, float(Î”t), Táµ¢, mesh, scheme, 0.0, advdiff=True)    # t = 0.0 in b and the border rows
+    return s
+
+
+def solve_MovingAdvDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Î”t: float, Tâ‚›: float, Tâ‚‘: float, bc_b, bc,
+                                           mesh: api.Mesh, scheme: str, uâ‚’, uáµ§, method="gmres", algorithm=None,
+                                           geometry_method="VOFI", verbose: bool = False, max_steps: Optional[int] = None,
+                                           time_panels: int = 16, time_order: int = 4, save_states: bool = True, **kwargs):
+    """solve_MovingAdvDiffusionUnsteadyMono!(s, phase, body, Î”t, Tâ‚›, Tâ‚‘, bc_b, bc, mesh, scheme, uâ‚’, uáµ§; method, ...) --
+    prescribedmotionsolver/advectiondiffusion.jl:201-242: the loop of solve_MovingDiffusionUnsteadyMono_b with
+    ConvectionOps(capacity, uâ‚’, uáµ§) rebuilt on every slab from the same uâ‚’, uáµ§ (:225-227).  The explicit convection of b is
+    formed on the device from the previous state, also with `save_states=False` (state handed over device to device)."""
+    return _solve_mono(s, phase, body, Î”t, Tâ‚›, Tâ‚‘, bc_b, bc, mesh, scheme, lambda cap: api.ConvectionOps(cap, uâ‚’, uáµ§), True,
+                       method, geometry_method, verbose, max_steps, time_panels, time_order, save_states, kwargs)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # two phases                                                          prescribedmotionsolver/diffusion.jl:272-535
 # ---------------------------------------------------------------------------------------------------------------------
 def _create_step_diph(s: api.Solver, phase1: api.Phase, phase2: api.Phase, bc_b, ic, Î”t: float, Táµ¢: Optional[np.ndarray],
-                      mesh: api.Mesh, scheme: str, t: float, from_previous: bool = False):
-    """A_/b_diph_unstead_diff_moving + BC_border_diph!(A, b, bc_b, mesh) of one slab (diffusion.jl:281-288, 519-523)."""
+                      mesh: api.Mesh, scheme: str, t: float, from_previous: bool = False, advdiff: bool = False):
+    """A_/b_diph_unstead_diff_moving + BC_border_diph!(A, b, bc_b, mesh) of one slab (diffusion.jl:281-288, 519-523);
+    advdiff: A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:255-262, 540-543), the same border rows."""
     cap1, cap2 = phase1.capacity, phase2.capacity
     for cap in (cap1, cap2):
         if not isinstance(cap, SpaceTimeCapacity):
             raise PenguinHipError("the moving solver needs space-time capacities: Capacity(body, SpaceTimeMesh(mesh, [t, t+Î”t]))")
         if cap.mesh is not mesh and tuple(cap.mesh.dims) != tuple(mesh.dims):
             raise ValueError("mesh does not match the capacity's space mesh")
+    if advdiff:
+        _require_st_convection(phase1)
+        _require_st_convection(phase2)
     M = int(np.prod(mesh.ext))
     sch = "CN" if scheme == "CN" else "BE"
     jump, flux = ic.scalar, ic.flux
@@ -347,7 +404,8 @@ def _create_step_diph(s: api.Solver, phase1: api.Phase, phase2: api.Phase, bc_b,
         fs.append((f0, f1))
     borders, nb, bvals = api._border_descs(bc_b, mesh, None)       # BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
     old, new = s._h, C.c_void_p()
-    L.check(L.lib().pg_solver_create_moving_diph(
+    create = L.lib().pg_solver_create_moving_advdiff_diph if advdiff else L.lib().pg_solver_create_moving_diph
+    L.check(create(
         cap1._h, phase1.operator._h, cap2._h, phase2.operator._h, C.byref(desc), borders, C.c_int32(nb), p(D1), p(D2),
         p(fs[0][0]), p(fs[0][1]), p(fs[1][0]), p(fs[1][1]),
         None if from_previous else (L.dptr(Táµ¢) if Táµ¢ is not None else None), old if from_previous else None,
@@ -385,27 +443,21 @@ def solve_MovingDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, phase2
     """solve_MovingDiffusionUnsteadyDiph!(s, phase1, phase2, body, body_c, Î”t, Tâ‚‘, bc_b, ic, mesh, scheme; method, ...) --
     prescribedmotionsolver/diffusion.jl:501-535: the constructor's system first (states[1]); then from t = 0.0 `while t < Tâ‚‘`:
     t += Î”t, the two capacities of the slab [t, t+Î”t], new blocks and border rows, solve, push."""
+    return _solve_diph(s, phase1, phase2, body, body_c, Î”t, 0.0, Tâ‚‘, bc_b, ic, mesh, scheme, api.DiffusionOps, False, method,
+                       verbose, max_steps, time_panels, time_order, save_states, kwargs)   # t = 0.0 (:513)
+
+
+def _solve_diph(s, phase1, phase2, body, body_c, Î”t, Tâ‚›, Tâ‚‘, bc_b, ic, mesh, scheme, make_ops, advdiff, method, verbose,
+                max_steps, time_panels, time_order, save_states, kwargs):
+    """The slab loop shared by the moving diph solvers (diffusion.jl:501-535, advectiondiffusion.jl:510-553)."""
     if s is None or not s._h:
         raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")
     opts = api._krylov_opts(method, kwargs)
     sch = "CN" if scheme == "CN" else "BE"
-
-    def solve_current(what):
-        info = L.pg_step_info()
-        L.check(L.lib().pg_solver_initial_solve(s._h, C.byref(opts), C.byref(info)))
-        api._step_info_check(s, info, what)
-        s._initial_done = True
-        s.ch.append(info)
-        if save_states:
-            s.x = s._fetch_state(-1)
-            s.states.append(s.x)
-        if verbose:
-            print("Solver Extremum : ", float(info.extremum))
-
-    t = 0.0                                        # :513
+    t = float(Tâ‚›)
     if verbose:
         print(f"Time : {t}")
-    solve_current("the first solve")
+    _solve_current(s, opts, "the first solve", save_states, verbose)
     Táµ¢ = s.x
     steps = 0
     while t < Tâ‚‘:
@@ -416,13 +468,45 @@ def solve_MovingDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, phase2
             print(f"Time : {t}")
         caps = [api.Capacity(b, SpaceTimeMesh(mesh, [t, t + Î”t]), time_panels=time_panels, time_order=time_order,
                              compute_centroids=True) for b in (body, body_c)]
-        ph1 = api.Phase(caps[0], api.DiffusionOps(caps[0]), phase1.source, phase1.Diffusion_coeff)
-        ph2 = api.Phase(caps[1], api.DiffusionOps(caps[1]), phase2.source, phase2.Diffusion_coeff)
-        _create_step_diph(s, ph1, ph2, bc_b, ic, float(Î”t), Táµ¢, mesh, sch, t, from_previous=not save_states)
-        solve_current(f"the solve of the slab starting at t = {t}")
+        ph1 = api.Phase(caps[0], make_ops(caps[0]), phase1.source, phase1.Diffusion_coeff)
+        ph2 = api.Phase(caps[1], make_ops(caps[1]), phase2.source, phase2.Diffusion_coeff)
+        _create_step_diph(s, ph1, ph2, bc_b, ic, float(Î”t), Táµ¢, mesh, sch, t, from_previous=not save_states, advdiff=advdiff)
+        _solve_current(s, opts, f"the solve of the slab starting at t = {t}", save_states, verbose)
         Táµ¢ = s.x
         steps += 1
     if not save_states:
         s.x = s._fetch_state(-1)
         s.states.append(s.x)
     return s
+
+
+def MovingAdvDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b, ic, Î”t: float, Táµ¢: np.ndarray, mesh: api.Mesh,
+                                   scheme: str, verbose: bool = False) -> api.Solver:
+    """MovingAdvDiffusionUnsteadyDiph(phase1, phase2, bc_b, ic, Î”t, Táµ¢, mesh, scheme) --
+    prescribedmotionsolver/advectiondiffusion.jl:246-264; both operators are space-time ConvectionOps."""
+    if verbose:
+        print("Solver Creation:\n- Moving problem\n- Diphasic problem\n- Unsteady problem\n- Advection-Diffusion problem")
+    _require_st_convection(phase1)
+    _require_st_convection(phase2)
+    s = api.Solver("Unsteady", "Diphasic", "DiffusionAdvection")
+    M = int(np.prod(mesh.ext))
+    s._nunk = 4 * M
+    if Táµ¢ is not None:
+        Táµ¢ = np.ascontiguousarray(Táµ¢, dtype=np.float64)
+        if Táµ¢.shape != (4 * M,):
+            raise ValueError(f"Táµ¢ must have length 4*prod(n+1) = {4 * M}")
+    s._ctx = dict(dt=float(Î”t), M=M)
+    _create_step_diph(s, phase1, phase2, bc_b, ic, float(Î”t), Táµ¢, mesh, scheme, 0.0, advdiff=True)     # t = 0.0 in b
+    return s
+
+
+def solve_MovingAdvDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, phase2: api.Phase, body, body_c, Î”t: float, Tâ‚›: float,
+                                           Tâ‚‘: float, bc_b, ic, mesh: api.Mesh, scheme: str, uâ‚’, uáµ§, method="gmres",
+                                           algorithm=None, verbose: bool = False, max_steps: Optional[int] = None,
+                                           time_panels: int = 16, time_order: int = 4, save_states: bool = True, **kwargs):
+    """solve_MovingAdvDiffusionUnsteadyDiph!(s, phase1, phase2, body, body_c, Î”t, Tâ‚›, Tâ‚‘, bc_b, ic, mesh, scheme, uâ‚’, uáµ§; ...) --
+    prescribedmotionsolver/advectiondiffusion.jl:510-553: from t = Tâ‚› (the diffusion twin starts at 0.0), both phases'
+    ConvectionOps rebuilt per slab from the same uâ‚’, uáµ§ (:535-538), BC_border_diph! without t."""
+    return _solve_diph(s, phase1, phase2, body, body_c, Î”t, Tâ‚›, Tâ‚‘, bc_b, ic, mesh, scheme,
+                       lambda cap: api.ConvectionOps(cap, uâ‚’, uáµ§), True, method, verbose, max_steps, time_panels, time_order,
+                       save_states, kwargs)

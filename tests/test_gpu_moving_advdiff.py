@@ -1,0 +1,337 @@
+"""GPU parity of the prescribed-motion ADVECTION-diffusion solvers (prescribedmotionsolver/advectiondiffusion.jl):
+pg_diffops_set_velocity_spacetime + pg_solver_create_moving_advdiff_{mono,mono_next,diph} through penguin.jl_amd.moving
+against the literal restatement in tests/moving_advdiff_oracle.py, fed with the capacities the HIP path computed."""
+import math
+
+import numpy as np
+import pytest
+
+from oracle import penguin_oracle as po
+from oracle import spacetime as ost
+from tests import moving_advdiff_oracle as oad
+from tests.common import rel_l2
+from tests.test_gpu_moving import _oracle_cap
+
+pytestmark = pytest.mark.gpu
+TOL_T = 1e-10
+DISC_BARS = (0.14, 0.16, 0.17)   # translating-disc study: global L2 errors measured 0.1362, 0.1552, 0.1627
+
+
+def _disc(pj, complement=False):
+    """a disc translating at (2, 0) across the cell faces (h = 0.25, 0.1 per slab)"""
+    cen, dcen = (lambda t: (1.76 + 2.0 * t, 2.03)), (lambda t: (2.0, 0.0))
+    rad, drad = (lambda t: 0.93), (lambda t: 0.0)
+    return (pj.MovingSphere(cen, rad, complement, dcenter=dcen, dradius=drad),
+            ost.MovingBall(cen, rad, complement, dcenter=dcen, dradius=drad))
+
+
+def _mesh(pj):
+    return pj.Mesh((16, 16), (4.0, 4.0), (0.0, 0.0)), po.Mesh((16, 16), (4.0, 4.0), (0.0, 0.0))
+
+
+def _velocity(omesh, zero=False):
+    """uₒ = (uₒx, uₒy, 0), uᵧ = (uᵧx, uᵧy, 0) on the (2+1)-D grid, both space components varying and non-zero"""
+    M = int(np.prod(omesh.ext))
+    X, Y = np.meshgrid(np.append(omesh.centers[0], 4.0), np.append(omesh.centers[1], 4.0), indexing="ij")
+    x, y = X.ravel(order="F"), Y.ravel(order="F")
+    two = lambda a: np.concatenate([a, 1.3 * a])          # the time-padding layer gets other values (they must not matter)
+    uox, uoy = two(2.0 + 0.3 * np.sin(y)), two(-0.7 + 0.2 * x)
+    ugx, ugy = two(1.5 + 0.2 * y), two(0.4 - 0.1 * x * y)
+    if zero:
+        uox, uoy, ugx, ugy = (0.0 * a for a in (uox, uoy, ugx, ugy))
+    z = np.zeros(2 * M)
+    return (uox, uoy, z), np.concatenate([ugx, ugy, z])
+
+
+def _probe(so, sens, systems=None):
+    import scipy.sparse.linalg as spla
+    po.solve_system(so)
+    so.states.append(so.x)
+    A, b = so.last_A_reduced, so.last_b_reduced
+    Ap = A.copy()
+    Ap.data = Ap.data * (1.0 + 2.2e-16 * np.random.default_rng(1).standard_normal(len(Ap.data)))
+    sens.append(rel_l2(spla.spsolve(Ap.tocsc(), b), spla.spsolve(A.tocsc(), b)))
+
+
+@pytest.mark.parametrize("scheme,bc_kind", [("BE", "dirichlet"), ("CN", "dirichlet"), ("BE", "robin"), ("CN", "robin")])
+def test_moving_advdiff_mono_matches_oracle(pj, scheme, bc_kind):
+    """MovingAdvDiffusionUnsteadyMono + solve_MovingAdvDiffusionUnsteadyMono! (advectiondiffusion.jl:15-33, 64-242): 1 + 4
+    slabs of a translating disc, varying uₒ and uᵧ in both space directions (so the missing bulk y-advection and the ½K_x-only
+    interface term are pinned), source, variable D, time-dependent border data; cells with Ψ_conv^A = 1 occur."""
+    mesh, omesh = _mesh(pj)
+    body, obody = _disc(pj)
+    dt, M = 0.05, int(np.prod(omesh.ext))
+    uo, ug = _velocity(omesh)
+    f = lambda x, y, z, t: 0.3 + 0.2 * x + 0.5 * t
+    D = lambda x, y, z: 1.0 + 0.1 * x
+    if bc_kind == "robin":
+        g = lambda x, y, z=0.0: 0.5 + 0.1 * x
+        bc, obc = pj.Robin(0.7, 1.3, g), po.Robin(0.7, 1.3, g)
+    else:
+        g = lambda x, y, z=0.0: 1.0 + 0.2 * x + 0.3 * y
+        bc, obc = pj.Dirichlet(g), po.Dirichlet(g)
+    keys = ("left", "right", "top", "bottom")
+    bval = lambda *a: 0.2 + 0.1 * a[-1]
+    bcb = pj.BorderConditions({k: pj.Dirichlet(bval) for k in keys})
+    obcb = po.BorderConditions({k: po.Dirichlet(bval) for k in keys})
+    T0 = np.random.default_rng(7).random(2 * M)
+    cap0 = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [0.0, dt]))
+    ph = pj.Phase(cap0, pj.ConvectionOps(cap0, uo, ug), f, D)
+    s = pj.MovingAdvDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, scheme)
+    pj.solve_MovingAdvDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, 3.5 * dt, bcb, bc, mesh, scheme, uo, ug, method="bicgstab",
+                                              reltol=1e-14)
+    assert s.unconverged == 0 and len(s.states) == 5
+    ocap = _oracle_cap(cap0, omesh, 0.0, dt, obody)
+    so = oad.MovingAdvDiffusionUnsteadyMono(po.Phase(ocap, po.make_convection_ops(ocap, uo, ug), f, D), obcb, obc, dt, T0, omesh,
+                                            scheme)
+    sens, t, fresh = [], 0.0, 0
+    fresh += int(np.count_nonzero((cap0.Vn == 0) & (cap0.Vn_1 != 0)))
+    _probe(so, sens)
+    while t < 3.5 * dt:
+        t += dt
+        c = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [t, t + dt]))
+        fresh += int(np.count_nonzero((c.Vn == 0) & (c.Vn_1 != 0)))
+        k = _oracle_cap(c, omesh, t, t + dt, obody)
+        op = po.make_convection_ops(k, uo, ug)
+        so.A = oad.A_mono_unstead_advdiff_moving(op, k, D, obc, scheme)
+        so.b = oad.b_mono_unstead_advdiff_moving(op, k, D, f, obc, so.states[-1], dt, t, scheme)
+        so.A, so.b = po.BC_border_mono(so.A, so.b, obcb, omesh, t=t)
+        _probe(so, sens)
+    assert fresh > 0                      # psip_conv = 1 somewhere: convection entered A
+    nact = set()
+    for k, (x, xo) in enumerate(zip(s.states, so.states)):
+        assert np.array_equal(np.flatnonzero(x != 0.0), np.flatnonzero(xo != 0.0)), f"active set of state {k}"
+        tol = max(TOL_T, 50.0 * max(sens[: k + 1]))
+        assert rel_l2(x, xo) <= tol, f"state {k}: {rel_l2(x, xo):.2e} (bar {tol:.1e})"
+        nact.add(int(np.count_nonzero(xo)))
+    assert len(nact) > 1
+
+
+@pytest.mark.parametrize("scheme", ["BE", "CN"])
+def test_moving_advdiff_diph_matches_oracle(pj, scheme):
+    """MovingAdvDiffusionUnsteadyDiph + solve_MovingAdvDiffusionUnsteadyDiph! (advectiondiffusion.jl:246-553): the disc and its
+    complement, 1 + 4 slabs from Tₛ = 0, jump and flux data varying along the interface, border rows in both phases.  The
+    flux row without -(Vn_1 - Vn) and the CN γ term without Ψ are what separates these blocks from the diffusion ones."""
+    import scipy.sparse.linalg as spla  # noqa: F401
+
+    mesh, omesh = _mesh(pj)
+    (body, obody), (body_c, obody_c) = _disc(pj), _disc(pj, True)
+    dt, M = 0.05, int(np.prod(omesh.ext))
+    uo, ug = _velocity(omesh)
+    f1 = lambda x, y, z, t: 0.3 + 0.2 * x + 0.5 * t
+    f2 = lambda x, y, z, t: 0.1 - 0.1 * x + 0.2 * t
+    D1, D2 = (lambda x, y, z: 1.0 + 0.1 * x), (lambda x, y, z: 2.0)
+    gj = lambda x, y, z=0.0: 0.2 + 0.1 * x
+    hj = lambda x, y, z=0.0: 0.5 - 0.05 * x
+    ic = pj.InterfaceConditions(pj.ScalarJump(1.0, 0.5, gj), pj.FluxJump(1.0, 2.0, hj))
+    oic = po.InterfaceConditions(po.ScalarJump(1.0, 0.5, gj), po.FluxJump(1.0, 2.0, hj))
+    keys = ("left", "right", "top", "bottom")
+    bcb = pj.BorderConditions({k: pj.Dirichlet(0.3) for k in keys})
+    obcb = po.BorderConditions({k: po.Dirichlet(0.3) for k in keys})
+    T0 = np.random.default_rng(11).random(4 * M)
+    caps = lambda t0, t1: (pj.Capacity(body, pj.SpaceTimeMesh(mesh, [t0, t1])), pj.Capacity(body_c, pj.SpaceTimeMesh(mesh, [t0, t1])))
+    c1, c2 = caps(0.0, dt)
+    p1 = pj.Phase(c1, pj.ConvectionOps(c1, uo, ug), f1, D1)
+    p2 = pj.Phase(c2, pj.ConvectionOps(c2, uo, ug), f2, D2)
+    s = pj.MovingAdvDiffusionUnsteadyDiph(p1, p2, bcb, ic, dt, T0, mesh, scheme)
+    pj.solve_MovingAdvDiffusionUnsteadyDiph_b(s, p1, p2, body, body_c, dt, 0.0, 3.5 * dt, bcb, ic, mesh, scheme, uo, ug,
+                                              method="bicgstab", reltol=1e-14)
+    assert s.unconverged == 0 and len(s.states) == 5
+    k1, k2 = _oracle_cap(c1, omesh, 0.0, dt, obody), _oracle_cap(c2, omesh, 0.0, dt, obody_c)
+    q1 = po.Phase(k1, po.make_convection_ops(k1, uo, ug), f1, D1)
+    q2 = po.Phase(k2, po.make_convection_ops(k2, uo, ug), f2, D2)
+    so = oad.MovingAdvDiffusionUnsteadyDiph(q1, q2, obcb, oic, dt, T0, omesh, scheme)
+    sens, t = [], 0.0
+    _probe(so, sens)
+    while t < 3.5 * dt:
+        t += dt
+        h1, h2 = caps(t, t + dt)
+        k1, k2 = _oracle_cap(h1, omesh, t, t + dt, obody), _oracle_cap(h2, omesh, t, t + dt, obody_c)
+        o1, o2 = po.make_convection_ops(k1, uo, ug), po.make_convection_ops(k2, uo, ug)
+        so.A = oad.A_diph_unstead_advdiff_moving(o1, o2, k1, k2, D1, D2, oic, scheme)
+        # (previous state: the HIP one -- every slab is compared on identical inputs, as the moving diffusion test does)
+        so.b = oad.b_diph_unstead_advdiff_moving(o1, o2, k1, k2, D1, D2, f1, f2, oic, s.states[len(so.states) - 1], dt, t, scheme)
+        so.A, so.b = ost._border_diph(so.A, so.b, obcb, k1, k2, omesh, None)
+        _probe(so, sens)
+    nact = set()
+    for k, (x, xo) in enumerate(zip(s.states, so.states)):
+        assert np.array_equal(np.flatnonzero(x != 0.0), np.flatnonzero(xo != 0.0)), f"active set of state {k}"
+        tol = max(TOL_T, 50.0 * sens[k])
+        assert rel_l2(x, xo) <= tol, f"state {k}: {rel_l2(x, xo):.2e} (bar {tol:.1e}, sensitivity {sens[k]:.1e})"
+        nact.add(int(np.count_nonzero(xo)))
+    assert len(nact) > 1
+
+
+@pytest.mark.parametrize("scheme", ["BE", "CN"])
+def test_moving_advdiff_zero_velocity_is_moving_diffusion(pj, scheme):
+    """uₒ = uᵧ = 0: the advection-diffusion blocks are the moving diffusion blocks (mono), so are the states."""
+    mesh, omesh = _mesh(pj)
+    body, _ = _disc(pj)
+    dt, M = 0.05, int(np.prod(omesh.ext))
+    uo, ug = _velocity(omesh, zero=True)
+    f = lambda x, y, z, t: 0.3 + 0.2 * x + 0.5 * t
+    D = lambda x, y, z: 1.0 + 0.1 * x
+    bc = pj.Robin(0.7, 1.3, lambda x, y, z=0.0: 0.5 + 0.1 * x)
+    bcb = pj.BorderConditions({k: pj.Dirichlet(lambda *a: 0.2 + 0.1 * a[-1]) for k in ("left", "right", "top", "bottom")})
+    T0 = np.random.default_rng(3).random(2 * M)
+    out = []
+    for adv in (False, True):
+        cap0 = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [0.0, dt]))
+        if adv:
+            ph = pj.Phase(cap0, pj.ConvectionOps(cap0, uo, ug), f, D)
+            s = pj.MovingAdvDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, scheme)
+            pj.solve_MovingAdvDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, 3.5 * dt, bcb, bc, mesh, scheme, uo, ug,
+                                                      method="bicgstab", reltol=1e-14)
+        else:
+            ph = pj.Phase(cap0, pj.DiffusionOps(cap0), f, D)
+            s = pj.MovingDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, scheme)
+            pj.solve_MovingDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, 3.5 * dt, bcb, bc, mesh, scheme, method="bicgstab",
+                                                   reltol=1e-14)
+        assert s.unconverged == 0 and len(s.states) == 5
+        out.append(s.states)
+    for k, (a, b) in enumerate(zip(*out)):
+        assert rel_l2(b, a) <= 1e-13, f"state {k}: {rel_l2(b, a):.2e}"
+
+
+def _disc_series(r, t, R, D, alphas):
+    """benchmark/Heat_dir_mov.jl:258-279: T = 1 - 2 Σ exp(-α_m² D t) J0(α_m r/R) / (α_m J1(α_m)) inside the disc, 0 outside"""
+    from scipy.special import j0, j1
+    out = np.zeros_like(r)
+    inside = r < R
+    rr = r[inside]
+    s = np.zeros_like(rr)
+    for a in alphas:
+        s += math.exp(-a * a * D * t) * j0(a * rr / R) / (a * j1(a))
+    out[inside] = 1.0 - 2.0 * s
+    return out
+
+
+def _translating_disc(pj, n, advdiff, alphas):
+    """benchmark/Heat_dir_mov.jl:282-294: r = 0.75, centre (2.01, 2.01), u = (2, 0), D = 1, BE, Δt = ½h², Tₑ = 0.1, T0ω = 0,
+    T0γ = 1, Dirichlet 1 on the disc, 0 on the borders -> (global, cut-cell) L2 errors against the series of :258-279"""
+    R, xc, yc, vx, D, Tend = 0.75, 2.01, 2.01, 2.0, 1.0, 0.1
+    mesh = pj.Mesh((n, n), (4.0, 4.0), (0.0, 0.0))
+    body = pj.MovingSphere(lambda t: (xc + vx * t, yc), lambda t: R, dcenter=lambda t: (vx, 0.0), dradius=lambda t: 0.0)
+    dt = 0.5 * (4.0 / n) ** 2
+    M = (n + 1) ** 2
+    uo = (np.full(2 * M, vx), np.zeros(2 * M), np.zeros(2 * M))
+    ug = np.concatenate([np.full(2 * M, vx), np.zeros(2 * M), np.zeros(2 * M)])
+    cap = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [0.0, dt]))
+    bcb = pj.BorderConditions({k: pj.Dirichlet(0.0) for k in ("left", "right", "top", "bottom")})
+    T0 = np.concatenate([np.zeros(M), np.ones(M)])
+    src, Dc, bc = (lambda x, y, z, t: 0.0), (lambda x, y, z: D), pj.Dirichlet(1.0)
+    if advdiff:
+        ph = pj.Phase(cap, pj.ConvectionOps(cap, uo, ug), src, Dc)
+        s = pj.MovingAdvDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, "BE")
+        pj.solve_MovingAdvDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, Tend, bcb, bc, mesh, "BE", uo, ug, method="bicgstab",
+                                                  reltol=1e-12, save_states=False)
+    else:
+        ph = pj.Phase(cap, pj.DiffusionOps(cap), src, Dc)
+        s = pj.MovingDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, "BE")
+        pj.solve_MovingDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, Tend, bcb, bc, mesh, "BE", method="bicgstab", reltol=1e-12,
+                                               save_states=False)
+    assert s.unconverged == 0
+    t = 0.0
+    while t < Tend:               # the loop's clock: the last slab is [t, t + Δt]
+        t += dt
+    tau = t + dt
+    ctau = pj.Capacity(pj.Sphere((xc + vx * tau, yc), R), mesh)
+    ua = lambda x, y: _disc_series(np.hypot(np.atleast_1d(x) - (xc + vx * tau), np.atleast_1d(y) - yc), tau, R, D, alphas)
+    r = pj.check_convergence(ua, s, ctau, 2)
+    return float(r[2]), float(r[4])
+
+
+def test_moving_advdiff_translating_disc(pj):
+    """The reference's convergence study benchmark/Heat_dir_mov.jl:282-294 at nx = 32, 64, 128, with Tₛ = 0 and the series
+    evaluated at the time the last slab ends, τ = (number of slabs)·Δt, centred where the body is then.  (The benchmark starts
+    its loop at Tₛ = 0.01 after the constructor's slab [0, Δt]: the body jumps ahead by u·0.01 with no time step, and it
+    compares at Tₑ although the loop stops past it.  Measured that way: L2 errors 0.139, 0.135, 0.134.)
+
+    The reference's scheme, reproduced here literally, does NOT converge to the series on this problem; the reference sets no
+    bar for it.  Measured on MI355X (global L2 / cut-cell L2):
+        advection-diffusion   nx=32 0.1362 / 0.0072   nx=64 0.1552 / 0.0034   nx=128 0.1627 / 0.0011
+        moving diffusion      nx=32 0.1794 / 0.0150   nx=64 0.1871 / 0.0063   nx=128 0.1885 / 0.0023
+    (the full cells stay too warm: mean 0.69 against 0.56 of the series at nx = 32; the opposite velocity gives 0.242).  What
+    is asserted is what holds: the advection moves the state towards the series at every resolution, the cut-cell error falls,
+    and the global error stays within a bar just above the measured one (DESIGN.md "Moving advection-diffusion")."""
+    from scipy.special import jn_zeros
+    alphas = jn_zeros(0, 100)
+    adv = [_translating_disc(pj, n, True, alphas) for n in (32, 64, 128)]
+    dif = [_translating_disc(pj, n, False, alphas) for n in (32, 64, 128)]
+    print(f"translating disc: advection-diffusion {adv}, moving diffusion {dif}")
+    for (ea, _), (ed, _) in zip(adv, dif):
+        assert ea < 0.9 * ed, (adv, dif)
+    cut = [c for _, c in adv]
+    assert cut[0] > cut[1] > cut[2], cut
+    for (e, _), bar in zip(adv, DISC_BARS):
+        assert e <= bar, (adv, DISC_BARS)
+
+
+def test_moving_advdiff_states_handed_over_on_the_device(pj):
+    """save_states=False: pg_solver_create_moving_advdiff_mono_next takes the previous state on the device and forms the explicit
+    convection of b from it there; the last state equals the host-state loop's bit for bit."""
+    mesh, omesh = _mesh(pj)
+    body, _ = _disc(pj)
+    dt, M = 0.05, int(np.prod(omesh.ext))
+    uo, ug = _velocity(omesh)
+    f = lambda x, y, z, t: 0.3 + 0.2 * x + 0.5 * t
+    bc = pj.Dirichlet(lambda x, y, z=0.0: 1.0 + 0.2 * x)
+    bcb = pj.BorderConditions({k: pj.Dirichlet(0.2) for k in ("left", "right", "top", "bottom")})
+    T0 = np.random.default_rng(9).random(2 * M)
+    for scheme in ("BE", "CN"):
+        out = []
+        for keep in (True, False):
+            cap0 = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [0.0, dt]))
+            ph = pj.Phase(cap0, pj.ConvectionOps(cap0, uo, ug), f, 1.0)
+            s = pj.MovingAdvDiffusionUnsteadyMono(ph, bcb, bc, dt, T0, mesh, scheme)
+            pj.solve_MovingAdvDiffusionUnsteadyMono_b(s, ph, body, dt, 0.0, 3.5 * dt, bcb, bc, mesh, scheme, uo, ug,
+                                                      method="bicgstab", save_states=keep)
+            assert s.unconverged == 0 and len(s.states) == (5 if keep else 1)
+            out.append(s.states[-1])
+        assert np.array_equal(out[0], out[1]), scheme
+
+
+def test_moving_advdiff_refusals(pj):
+    mesh, omesh = _mesh(pj)
+    body, _ = _disc(pj)
+    dt, M = 0.05, int(np.prod(omesh.ext))
+    cap = pj.Capacity(body, pj.SpaceTimeMesh(mesh, [0.0, dt]))
+    uo, ug = _velocity(omesh)
+    f, bc, bcb = (lambda x, y, z, t: 0.0), pj.Dirichlet(1.0), pj.BorderConditions({})
+    # non-zero time components
+    with pytest.raises(pj.PenguinHipError, match="time component of uₒ"):
+        pj.ConvectionOps(cap, (uo[0], uo[1], np.full(2 * M, 0.1)), ug)
+    ugt = ug.copy()
+    ugt[4 * M + 3] = 1.0
+    with pytest.raises(pj.PenguinHipError, match="time block of uᵧ"):
+        pj.ConvectionOps(cap, uo, ugt)
+    # wrong lengths
+    with pytest.raises(ValueError, match="space-time capacity"):
+        pj.ConvectionOps(cap, uo[:2], ug)
+    with pytest.raises(ValueError, match="space-time capacity"):
+        pj.ConvectionOps(cap, tuple(u[:M] for u in uo), ug[: 3 * M])
+    # N = 1: the reference indexes C[3] of a 2-tuple
+    m1 = pj.Mesh((20,), (1.0,), (0.0,))
+    c1 = pj.Capacity(pj.MovingHalfSpace(0, lambda t: 0.3 + t, 1.0), pj.SpaceTimeMesh(m1, [0.0, 0.01]))
+    with pytest.raises(pj.PenguinHipError, match="BoundsError"):
+        pj.ConvectionOps(c1, (np.ones(42), np.zeros(42)), np.zeros(84))
+    # a plain DiffusionOps phase
+    ph_d = pj.Phase(cap, pj.DiffusionOps(cap), f, 1.0)
+    with pytest.raises(pj.PenguinHipError, match="ConvectionOps"):
+        pj.MovingAdvDiffusionUnsteadyMono(ph_d, bcb, bc, dt, np.zeros(2 * M), mesh, "BE")
+    with pytest.raises(pj.PenguinHipError, match="ConvectionOps"):
+        pj.MovingAdvDiffusionUnsteadyDiph(ph_d, ph_d, bcb, pj.InterfaceConditions(pj.ScalarJump(1.0, 1.0, 0.0),
+                                                                                  pj.FluxJump(1.0, 1.0, 0.0)),
+                                          dt, np.zeros(4 * M), mesh, "BE")
+    # the moving DIFFUSION constructors still refuse a convection operator
+    ph_c = pj.Phase(cap, pj.ConvectionOps(cap, uo, ug), f, 1.0)
+    with pytest.raises(pj.PenguinHipError, match="takes no convection operators"):
+        pj.MovingDiffusionUnsteadyMono(ph_c, bcb, bc, dt, np.zeros(2 * M), mesh, "BE")
+    ic = pj.InterfaceConditions(pj.ScalarJump(1.0, 1.0, 0.0), pj.FluxJump(1.0, 1.0, 0.0))
+    with pytest.raises(pj.PenguinHipError, match="takes no convection operators"):
+        pj.MovingDiffusionUnsteadyDiph(ph_c, ph_c, bcb, ic, dt, np.zeros(4 * M), mesh, "BE")
+    # a static ConvectionOps (static capacity) is no space-time operator
+    static = pj.Capacity(pj.Sphere((2.0, 2.0), 0.9), mesh)
+    ph_s = pj.Phase(static, pj.ConvectionOps(static, (np.ones(M), np.ones(M)), np.zeros(2 * M)), f, 1.0)
+    with pytest.raises(pj.PenguinHipError):
+        pj.MovingAdvDiffusionUnsteadyMono(ph_s, bcb, bc, dt, np.zeros(2 * M), mesh, "BE")
