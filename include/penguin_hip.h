@@ -320,6 +320,23 @@ int32_t pg_solver_create_moving_advdiff_diph(pg_capacity* c1, pg_diffops* o1, pg
                                              const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
                                              const double* f2_n, const double* f2_np1, const double* T_prev,
                                              pg_solver* previous, int32_t scheme, pg_solver** out);
+/* MovingLiquidDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving_stef (liquidmotionsolver/diffusion.jl:445-673): one slab
+   of the two-phase Stefan problem, the arguments of pg_solver_create_moving_diph (`previous`: device hand-over).  Differs
+   from the moving diphasic blocks in row block 4 = [0 0 0 Iα₂] (:542; the flux blocks 5-8 are built there but not used),
+   b₂ = b₄ = gᵧ (:646-647) and, under CN, b₁ / b₃ = (Vn - Id GᵀWꜝG Ψn) Tω - ½ Id GᵀWꜝH Tγ + ½ V (fₙ + fₙ₊₁) with no Ψ on
+   the γ term (:637-642).  BE: Vn Tω + V fₙ₊₁. */
+int32_t pg_solver_create_moving_stefan_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                            const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                            const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
+                                            const double* f2_n, const double* f2_np1, const double* T_prev,
+                                            pg_solver* previous, int32_t scheme, pg_solver** out);
+/* The Stefan terms of a 1-D slab of a moving diffusion solver (mono, diph or Stefan diph), computed on the device from its
+   space-time capacities, operators, D and current state: its solution, or before the first solve the state it was built
+   from (liquidmotionsolver/diffusion.jl:240-255, 318-330; height_tracking.jl:23-31).  out: 4 doubles per phase, {Σ A_t(t0), Σ A_t(t1), Σᵢ qᵢ, maxᵢ |qᵢ|} with
+   q = Id Hᵀ Wꜝ (G Tω + H Tγ) on the first time layer.  Σ A_t(t0) is the capacity's Vn_1 summed: the reference's "Hₙ₊₁";
+   Σ A_t(t1) (Vn) is its "Hₙ".  Fixed-order reduction: the same state gives bitwise the same out.  Refuses a solver that is
+   not a space-time diffusion slab, several ranks and N ≠ 1. */
+int32_t pg_solver_stefan_terms(const pg_solver* s, double* out);
 int32_t pg_solver_destroy(pg_solver* s);
 
 /* per-step data for time-dependent closures; the host evaluates them at the reference's points and

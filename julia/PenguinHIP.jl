@@ -23,7 +23,8 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        SpaceTimeMesh, MovingSphere, MovingHalfSpace, SpaceTimeCapacity, MovingDiffusionUnsteadyMono,
        solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!,
        MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
-       solve_MovingAdvDiffusionUnsteadyDiph!, config_string, guess_info,
+       solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
+       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info,
        ∇, ∇₋, gmres, bicgstabl, cg
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
@@ -1047,6 +1048,180 @@ function solve_MovingAdvDiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2:
         Tᵢ = s.x
     end
     s
+end
+
+# ---- liquid motion, 1-D (liquidmotionsolver/diffusion.jl): MovingLiquidDiffusionUnsteadyMono (:152-171) and its loop
+# (:173-442), MovingLiquidDiffusionUnsteadyDiph (:653-673) with A_/b_diph_unstead_diff_moving_stef (:445-651) and its loop
+# (:675-946).  Every Newton iteration solves one slab and reads its Stefan terms on the device (pg_solver_stefan_terms:
+# Σ A_t(t0) = Hₙ₊₁, Σ A_t(t1) = Hₙ, Σq, max|q| per phase).  The learning rate here is the fixed one (α); the Python package
+# carries all six strategies, adapt_timestep and the border rows at tₙ₊₁ of the Newton rebuilds (penguin/jl_amd/liquid.py);
+# here the border rows take b's time.
+function _stefan_terms(s::Solver, nphase::Int)
+    out = zeros(Float64, 4 * nphase)
+    check(ccall((:pg_solver_stefan_terms, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}), s.handle, out))
+    out
+end
+
+function _liquid_1d(mesh)
+    length(mesh.nodes) == 1 || error("the liquid-motion solvers are 1-D only: the reference's N ≥ 2 call feeds y into the body's time argument")
+end
+
+_front_body(xf, new_xf, tn, tn1, Δt; complement::Bool=false) =
+    MovingHalfSpace(1, tt -> xf * (tn1 - tt) / Δt + new_xf * (tt - tn) / Δt; complement=complement)
+
+function _stefan_step_diph!(s::Solver, phase1::Phase, phase2::Phase, bc_b::BorderConditions, ic::InterfaceConditions, Δt::Float64,
+                            Tᵢ::Vector{Float64}, mesh::Mesh, scheme::String, t::Float64)
+    c1, c2 = phase1.capacity, phase2.capacity
+    Cω1, Cω2 = _st_coords(c1.C_ω, c1.Ct_ω), _st_coords(c2.C_ω, c2.Ct_ω)
+    g = ic.scalar.value isa Function ? Float64[Float64(ic.scalar.value(c...)) for c in _st_coords(c1.C_γ, c1.Ct_γ)] : Float64[]
+    hh = Float64[]
+    D1 = Float64[Float64(phase1.Diffusion_coeff(c...)) for c in Cω1]
+    D2 = Float64[Float64(phase2.Diffusion_coeff(c...)) for c in Cω2]
+    f1n1 = Float64[Float64(phase1.source(c..., t + Δt)) for c in Cω1]
+    f2n1 = Float64[Float64(phase2.source(c..., t + Δt)) for c in Cω2]
+    f1n = Float64[Float64(phase1.source(c..., t)) for c in Cω1]
+    f2n = Float64[Float64(phase2.source(c..., t)) for c in Cω2]
+    borders = _border_descs(bc_b)
+    s.handle != C_NULL && ccall((:pg_solver_destroy, libpg), Int32, (Ptr{Cvoid},), s.handle)
+    s.handle = C_NULL
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve g hh D1 D2 f1n f2n f1n1 f2n1 Tᵢ borders begin
+        desc = Ref(_jump_desc(ic, c1, c2, g, hh))
+        check(ccall((:pg_solver_create_moving_stefan_diph, libpg), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
+                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                    c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
+                    f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
+    end
+    s.handle = h[]
+    _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, nothing)
+    s.A = (c1, c2, phase1.operator, phase2.operator)
+    s
+end
+
+function MovingLiquidDiffusionUnsteadyMono(phase::Phase, bc_b::BorderConditions, bc_i::AbstractBoundary, Δt::Float64,
+                                           Tᵢ::Vector{Float64}, mesh::AbstractMesh, scheme::String)
+    _liquid_1d(mesh)
+    println("Solver Creation:"); println("- Moving problem"); println("- Non prescibed motion"); println("- Monophasic problem")
+    println("- Unsteady problem"); println("- Diffusion problem")
+    s = _new_solver(:Unsteady, :Monophasic, :Diffusion, Ptr{Cvoid}(C_NULL), length(Tᵢ))
+    _moving_step!(s, phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme, 0.0)            # BC_border_mono!(...; t=0.0)   :165-169
+end
+
+function solve_MovingLiquidDiffusionUnsteadyMono!(s::Solver, phase::Phase, xf, Δt::Float64, Tₛ::Float64, Tₑ::Float64,
+                                                  bc_b::BorderConditions, bc::AbstractBoundary, ic::InterfaceConditions,
+                                                  mesh::AbstractMesh, scheme::String; Newton_params=(1000, 1e-10, 1e-10, 1.0),
+                                                  method::Function=gmres, algorithm=nothing, kwargs...)
+    (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
+    _liquid_1d(mesh)
+    kw = Dict{Symbol, Any}(kwargs)
+    opts = Ref(_opts(method, kw))
+    info = pg_step_info()
+    ρL = ic.flux.value
+    max_iter, tol, reltol, α = Newton_params
+    residuals = Dict{Int, Vector{Float64}}()
+    xf_log = Float64[]
+    timestep_history = Tuple{Float64, Float64}[(Tₛ, Δt)]
+    t = Tₛ
+    new_xf = Float64(xf)
+    k = 1
+    while true
+        err = Inf; iter = 0; current_xf = new_xf; xf0 = current_xf
+        while (iter < max_iter) && (err > tol) && (err > reltol * abs(current_xf))
+            iter += 1
+            check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
+            _record!(s, info, false)
+            Tᵢ = s.x
+            r = _stefan_terms(s, 1)
+            res = r[1] - r[2] - 1 / ρL * r[3]                                # Hₙ₊₁ - Hₙ - Interface_term
+            step = α * res
+            new_xf = current_xf + step
+            err = k == 1 ? abs(res) : abs(step)
+            push!(get!(residuals, k, Float64[]), err)
+            if (err <= tol) || (err <= reltol * abs(current_xf)) || (iter == max_iter)
+                push!(xf_log, new_xf)
+                break
+            end
+            tn1, tn = t + Δt, t
+            capacity = Capacity(_front_body(xf0, new_xf, tn, tn1, Δt), SpaceTimeMesh(mesh, [tn, tn1], tag=mesh.tag))
+            ph = Phase(capacity, DiffusionOps(capacity), phase.source, phase.Diffusion_coeff)
+            _moving_step!(s, ph, bc_b, bc, Δt, Tᵢ, mesh, scheme, t)
+            current_xf = new_xf
+        end
+        t < Tₑ || break
+        t += Δt
+        capacity = Capacity(MovingHalfSpace(1, tt -> new_xf), SpaceTimeMesh(mesh, [Δt, 2Δt], tag=mesh.tag))
+        ph = Phase(capacity, DiffusionOps(capacity), phase.source, phase.Diffusion_coeff)
+        _moving_step!(s, ph, bc_b, bc, Δt, s.x, mesh, scheme, 0.0)
+        k += 1
+    end
+    return s, residuals, xf_log, timestep_history
+end
+
+function MovingLiquidDiffusionUnsteadyDiph(phase1::Phase, phase2::Phase, bc_b::BorderConditions, ic::InterfaceConditions, Δt::Float64,
+                                           Tᵢ::Vector{Float64}, mesh::AbstractMesh, scheme::String)
+    _liquid_1d(mesh)
+    println("Solver Creation:"); println("- Moving problem"); println("- Non prescibed motion"); println("- Diphasic problem")
+    println("- Unsteady problem"); println("- Diffusion problem")
+    s = _new_solver(:Unsteady, :Diphasic, :Diffusion, Ptr{Cvoid}(C_NULL), length(Tᵢ))
+    _stefan_step_diph!(s, phase1, phase2, bc_b, ic, Δt, Tᵢ, mesh, scheme, 0.0)
+end
+
+function solve_MovingLiquidDiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Phase, xf, Δt::Float64, Tₛ::Float64, Tₑ::Float64,
+                                                  bc_b::BorderConditions, ic::InterfaceConditions, mesh::AbstractMesh, scheme::String;
+                                                  Newton_params=(1000, 1e-10, 1e-10, 1.0), method::Function=gmres,
+                                                  algorithm=nothing, kwargs...)
+    (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
+    _liquid_1d(mesh)
+    kw = Dict{Symbol, Any}(kwargs)
+    opts = Ref(_opts(method, kw))
+    info = pg_step_info()
+    ρL = ic.flux.value
+    max_iter, tol, reltol, α = Newton_params
+    residuals = Dict{Int, Vector{Float64}}()
+    xf_log = Float64[]
+    t = Tₛ
+    new_xf = Float64(xf)
+    Tᵢ = Float64[]
+    k = 1
+    while true
+        err = Inf; iter = 0; current_xf = new_xf; xf0 = current_xf
+        while (iter < max_iter) && (err > tol) && (err > reltol * abs(current_xf))
+            iter += 1
+            check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
+            _record!(s, info, false)
+            Tᵢ = s.x
+            r = _stefan_terms(s, 2)
+            res = r[1] - r[2] - (1 / ρL * r[3] + 1 / ρL * r[7])              # Hₙ, Hₙ₊₁ of phase 1 only
+            step = α * res
+            new_xf = current_xf + step
+            err = k == 1 ? abs(res) : abs(step)
+            push!(get!(residuals, k, Float64[]), err)
+            if (err <= tol) || (err <= reltol * abs(current_xf))
+                push!(xf_log, new_xf)
+                break
+            end
+            tn1, tn = t + Δt, t
+            current_xf = new_xf
+            ((iter < max_iter) && (err > tol) && (err > reltol * abs(current_xf))) || break   # the rebuilt slab is never solved
+            STmesh = SpaceTimeMesh(mesh, [tn, tn1], tag=mesh.tag)
+            c1 = Capacity(_front_body(xf0, new_xf, tn, tn1, Δt), STmesh)
+            c2 = Capacity(_front_body(xf0, new_xf, tn, tn1, Δt; complement=true), STmesh)
+            ph1 = Phase(c1, DiffusionOps(c1), phase1.source, phase1.Diffusion_coeff)
+            ph2 = Phase(c2, DiffusionOps(c2), phase2.source, phase2.Diffusion_coeff)
+            _stefan_step_diph!(s, ph1, ph2, bc_b, ic, Δt, Tᵢ, mesh, scheme, t)
+        end
+        t < Tₑ || break
+        t += Δt
+        STmesh = SpaceTimeMesh(mesh, [Δt, 2Δt], tag=mesh.tag)
+        c1 = Capacity(MovingHalfSpace(1, tt -> new_xf), STmesh)
+        c2 = Capacity(MovingHalfSpace(1, tt -> new_xf; complement=true), STmesh)
+        ph1 = Phase(c1, DiffusionOps(c1), phase1.source, phase1.Diffusion_coeff)
+        ph2 = Phase(c2, DiffusionOps(c2), phase2.source, phase2.Diffusion_coeff)
+        _stefan_step_diph!(s, ph1, ph2, bc_b, ic, Δt, Tᵢ, mesh, scheme, 0.0)
+        k += 1
+    end
+    return s, residuals, xf_log
 end
 
 "Every PG_* tuning / variant selector the library runs with (`pg_config_string`)."

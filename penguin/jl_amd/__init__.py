@@ -28,3 +28,8 @@ from .moving import (  # noqa: F401,E402
     solve_MovingAdvDiffusionUnsteadyDiph_b, solve_MovingAdvDiffusionUnsteadyMono_b, solve_MovingDiffusionUnsteadyDiph_b,
     solve_MovingDiffusionUnsteadyMono_b,
 )
+from .liquid import (  # noqa: F401,E402
+    LearningRateState, MovingLiquidDiffusionUnsteadyDiph, MovingLiquidDiffusionUnsteadyMono, adapt_timestep,
+    apply_learning_rate_step_b, extract_height_profiles, init_learning_rate_state, normalize_lr_options, normalize_lr_strategy,
+    solve_MovingLiquidDiffusionUnsteadyDiph_b, solve_MovingLiquidDiffusionUnsteadyMono_b, stefan_terms,
+)

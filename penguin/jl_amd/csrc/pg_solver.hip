@@ -105,6 +105,8 @@ struct pg_solver {
   // (prescribedmotionsolver/advectiondiffusion.jl:35-61); the convection data come from the ConvectionOps in ops[]
   bool advdiff = false;
   DevBuf<double> psi_cp[2], psi_cm[2];
+  // the Stefan diphasic blocks (pg_solver_create_moving_stefan_diph, liquidmotionsolver/diffusion.jl:445-651)
+  bool stefan = false;
   pg_solver* init_from = nullptr;   // constructor only: the previous slab's solver whose state is this one's initial state
 };
 
@@ -210,8 +212,8 @@ __global__ void k_bconst(SysParams P, RowSegs seg, i64 n_own, const int* row_cel
       } else {
         v = G * g1;
       }
-    } else if (k == 1) {
-      v = s.g_n ? s.g_n[lc] : s.g_const;                          // b2 = gᵧ
+    } else if (k == 1 || P.mv_stefan) {
+      v = s.g_n ? s.g_n[lc] : s.g_const;                          // b2 = gᵧ  (Stefan: b4 = gᵧ too, :646-647)
     } else {
       v = P.cap[1].G[lc] * (s.g_np1 ? s.g_np1[lc] : s.h_const);   // b4 = Γ₂ hᵧ
     }
@@ -919,6 +921,82 @@ __global__ void k_maxabs(i64 n, const double* x, const double* ds /*NULL: x is u
   if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
 }
 
+// The Stefan terms of a solved 1-D space-time slab, per phase    liquidmotionsolver/diffusion.jl:240-255, height_tracking.jl:23-31
+//   Σ A_t(t0) ("Hₙ₊₁", Vn_1), Σ A_t(t1) ("Hₙ", Vn), Σᵢ qᵢ, maxᵢ |qᵢ|,   q = Id Hᵀ Wꜝ (G Tω + H Tγ)
+// q_i is row i of the monophasic interface rows [HᵀWꜝG, HᵀWꜝH] (eval_row, Iᵦ = 1, Iₐ = 0, no Ψ) applied to the padded state and
+// scaled by Id_i.  Fixed-order reduction (no atomics): wave64 shuffles, the block's waves in order, then k_stefan_final over the
+// blocks in order -- the same state gives bitwise the same numbers (the Newton loop branches on them).
+constexpr int STEFAN_OUT = 8;        // 4 per phase
+constexpr int STEFAN_BLOCKS = 64;    // most partial rows (grid depends on Mloc only)
+struct StefanArgs {
+  SysParams P[2];                    // mono interface-row parameters of each phase's capacity
+  const double* v0[2];
+  const double* v1[2];
+  const double* Id[2];               // D(C_ω), or nullptr (= 1)
+  const int* red;                    // K*Mloc: reduced index of (kind, cell), -1 = eliminated (T = 0 there)
+  const double* x;                   // reduced state: unscaled x (ds == nullptr) or z with x = S z
+  const double* ds;
+  const double* Tpad;                // != nullptr: an unsolved slab, T = the padded state it was built from (K*Mloc)
+  i64 Mloc;
+  int nphase;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_stefan_partials(StefanArgs a, double* __restrict__ partials) {
+  double acc[STEFAN_OUT];
+#pragma unroll
+  for (int j = 0; j < STEFAN_OUT; ++j) acc[j] = 0.0;
+  const CapView& c = a.P[0].cap[0];
+  for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < a.Mloc; lc += (i64)gridDim.x * blockDim.x) {
+    i64 idx[3];
+    decode_cell(c.N, c.ext, c.plane, c.s0, lc, idx);
+    for (int ph = 0; ph < a.nphase; ++ph) {
+      const int* red = a.red + (i64)(2 * ph) * a.Mloc;
+      double row = 0.0;
+      eval_row(a.P[ph], 1, lc, idx, [&](int k, i64 col, double v) {
+        const i64 q = (i64)k * a.Mloc + col;
+        if (a.Tpad) {
+          row += v * a.Tpad[(i64)(2 * ph) * a.Mloc + q];
+        } else {
+          const int r = red[q];
+          if (r >= 0) row += v * (a.ds ? a.ds[r] * a.x[r] : a.x[r]);
+        }
+      });
+      const double q = (a.Id[ph] ? a.Id[ph][lc] : 1.0) * row;
+      acc[4 * ph + 0] += a.v0[ph][lc];
+      acc[4 * ph + 1] += a.v1[ph][lc];
+      acc[4 * ph + 2] += q;
+      acc[4 * ph + 3] = fmax(acc[4 * ph + 3], fabs(q));
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < STEFAN_OUT; ++j)
+    for (int off = 32; off > 0; off >>= 1) {
+      const double o = __shfl_down(acc[j], off, 64);
+      acc[j] = (j & 3) == 3 ? fmax(acc[j], o) : acc[j] + o;
+    }
+  __shared__ double sh[BLOCK / 64][STEFAN_OUT];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0)
+#pragma unroll
+    for (int j = 0; j < STEFAN_OUT; ++j) sh[wave][j] = acc[j];
+  __syncthreads();
+  if (threadIdx.x < STEFAN_OUT) {
+    const int j = threadIdx.x;
+    double v = sh[0][j];
+    for (int w = 1; w < BLOCK / 64; ++w) v = (j & 3) == 3 ? fmax(v, sh[w][j]) : v + sh[w][j];
+    partials[(i64)blockIdx.x * STEFAN_OUT + j] = v;
+  }
+}
+
+__global__ void k_stefan_final(const double* __restrict__ partials, int nblk, double* __restrict__ out) {
+  if (threadIdx.x < STEFAN_OUT) {
+    const int j = threadIdx.x;
+    double v = partials[j];
+    for (int b = 1; b < nblk; ++b) v = (j & 3) == 3 ? fmax(v, partials[(i64)b * STEFAN_OUT + j]) : v + partials[(i64)b * STEFAN_OUT + j];
+    out[j] = v;
+  }
+}
+
 __global__ void k_set_border_values(i64 nb, const i64* cells_global, const double* values, i64 first_cell, i64 Mloc,
                                     int nbulk, const int* red, i64 n_own, double* bcv) {
   for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < nb; q += (i64)gridDim.x * blockDim.x) {
@@ -982,6 +1060,7 @@ SysParams make_params(const pg_solver* s, int scheme) {
       }
       P.mv_flux_no_dv = s->nphase == 2 ? 1 : 0;   // :362-365: no -(Vn_1 - Vn) in the flux row
     }
+    P.mv_stefan = s->stefan ? 1 : 0;
   }
   return P;
 }
@@ -999,6 +1078,7 @@ SysParams make_params_moving_explicit(const pg_solver* s) {
     P.mv_psi_w[q] = s->psi_m[src].p;
     // mono (:214): the γ term is -½ Id GᵀWꜝH Tγ; diph (:487-488): -Id GᵀWꜝH Ψn Tγ with the same Ψn = psim as the ω term
     P.mv_psi_g[q] = s->nphase == 2 ? s->psi_m[src].p : nullptr;
+    if (s->stefan) P.mv_psi_g[q] = nullptr;                      // Stefan CN (:637-638): -½ Id GᵀWꜝH Tγ, no Ψ
     if (s->advdiff) {
       P.mv_psi_g[q] = cn ? nullptr : s->psi_m[src].p;            // CN: the constant ½; BE: psim_be = 0, no diffusion term
       P.mv_psi_c[q] = cn ? nullptr : s->psi_cm[src].p;
@@ -1736,7 +1816,8 @@ static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc
 static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
                                   const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
                                   const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
-                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff);
+                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff,
+                                  bool stefan = false);
 
 // MovingDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving of one slab      prescribedmotionsolver/diffusion.jl:272-498
 int32_t pg_solver_create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
@@ -1757,10 +1838,22 @@ int32_t pg_solver_create_moving_advdiff_diph(pg_capacity* c1, pg_diffops* o1, pg
                             out, true);
 }
 
+// MovingLiquidDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving_stef of one slab   liquidmotionsolver/diffusion.jl:445-673:
+// the moving diphasic blocks with row block 4 = [0 0 0 Iα₂], b₂ = b₄ = gᵧ and, under CN, -½ Id GᵀWꜝH Tγ without Ψ in b₁ / b₃
+int32_t pg_solver_create_moving_stefan_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                            const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                            const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
+                                            const double* f2_n, const double* f2_np1, const double* T_prev,
+                                            pg_solver* previous, int32_t scheme, pg_solver** out) {
+  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
+                            out, false, true);
+}
+
 static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
                                   const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
                                   const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
-                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff) {
+                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff,
+                                  bool stefan) {
   PG_API_BEGIN
   require_init();
   if (previous) PG_REQUIRE(previous->initial_done, "pg_solver_create_moving_diph: the previous slab has not been solved");
@@ -1785,6 +1878,7 @@ static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* 
   s->dt = 1.0;            // Δt is inside the space-time capacities
   s->moving = true;
   s->advdiff = advdiff;
+  s->stefan = stefan;
   s->scheme_ctor = scheme;
   s->ic = *ic;
   const i64 Ml = s->slab.Mloc();
@@ -2153,6 +2247,48 @@ int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* row
       idx[r] = (i64)k * s->M + s->slab.first_cell() + h[r];
     }
   }
+  PG_API_END
+}
+
+// Hₙ₊₁, Hₙ, Σq, max|q| of each phase of a 1-D space-time slab (k_stefan_partials); out: 4 * nphase doubles.  T is the
+// slab's solution once it is solved, the state it was built from before
+int32_t pg_solver_stefan_terms(const pg_solver* s, double* out) {
+  PG_API_BEGIN
+  PG_REQUIRE(s && out, "pg_solver_stefan_terms: NULL argument");
+  PG_REQUIRE(s->moving && !s->advdiff && s->cap[0]->spacetime && (s->nphase == 1 || s->cap[1]->spacetime),
+             "pg_solver_stefan_terms needs a moving diffusion solver on space-time capacities");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "pg_solver_stefan_terms: space-time steps are single-rank");
+  PG_REQUIRE(s->slab.N == 1, "pg_solver_stefan_terms: 1-D liquid motion only (N = 1)");
+  hipStream_t st = ctx().stream;
+  StefanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  for (int q = 0; q < s->nphase; ++q) {
+    SysParams& P = a.P[q];
+    P.nphase = 1;
+    P.cap[0] = P.cap[1] = cap_view(s->cap[q]);
+    P.ct[0] = P.ct[1] = s->cap[q]->ct.p;
+    P.Ib = 1.0;
+    P.gscale = 1.0;
+    a.v0[q] = s->cap[q]->Vt[0].p;
+    a.v1[q] = s->cap[q]->Vt[1].p;
+    a.Id[q] = s->Id[q].p;
+  }
+  a.red = s->nb.red.p;
+  if (s->initial_done) {
+    a.x = s->x_valid ? s->x.p : s->z.p;
+    a.ds = s->x_valid ? nullptr : s->z_matrix->ds.p;
+  } else {
+    a.Tpad = s->T0pad.p;   // not solved yet: the state the slab was built from (T_prev or the previous solver's)
+  }
+  a.Mloc = s->Mloc;
+  a.nphase = s->nphase;
+  const int g = grid_for(s->Mloc, BLOCK, STEFAN_BLOCKS);
+  double* partials = s->red_scratch.p;                    // (2048 doubles: g * 8 partials, then the 8 results)
+  double* res = s->red_scratch.p + STEFAN_BLOCKS * STEFAN_OUT;
+  hipLaunchKernelGGL(k_stefan_partials, dim3(g), dim3(BLOCK), 0, st, a, partials);
+  hipLaunchKernelGGL(k_stefan_final, dim3(1), dim3(64), 0, st, (const double*)partials, g, res);
+  PG_HIP(hipGetLastError());
+  s->red_scratch.download(out, 4 * s->nphase, STEFAN_BLOCKS * STEFAN_OUT);
   PG_API_END
 }
 

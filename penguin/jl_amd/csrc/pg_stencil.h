@@ -54,6 +54,7 @@ struct SysParams {
   const double* mv_psi_k[2];
   const double* mv_psi_kg[2];
   int mv_flux_no_dv;       // diph advection-diffusion: the flux row has no -(Vn_1 - Vn) term (:362-365 vs diffusion.jl:379-381)
+  int mv_stefan;           // diph Stefan blocks (liquidmotionsolver/diffusion.jl:445-548): row block 4 is [0 0 0 Iα₂] (:542)
 };
 
 __host__ __device__ inline int nkinds(const SysParams& P) { return P.nphase == 1 ? 2 : 4; }
@@ -161,6 +162,10 @@ __device__ inline void eval_row(const SysParams& P, int kind, i64 lc, const i64*
   if (P.nphase == 2 && kind == 1) {   // scalar jump row: α₁Tγ¹ − α₂Tγ² = g   diffusion.jl:374-376
     emit(1, lc, P.a1);
     emit(3, lc, -P.a2);
+    return;
+  }
+  if (P.nphase == 2 && kind == 3 && P.mv_stefan) {   // Stefan: α₂Tγ² = g, the flux blocks 5-8 are built but not used
+    emit(3, lc, P.a2);
     return;
   }
 

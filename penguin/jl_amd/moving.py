@@ -220,9 +220,10 @@ def _require_st_convection(phase: api.Phase):
 
 
 def _create_step(s: api.Solver, phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: Optional[np.ndarray], mesh: api.Mesh, scheme: str,
-                 t: float, from_previous: bool = False, advdiff: bool = False):
+                 t: float, from_previous: bool = False, advdiff: bool = False, t_border: Optional[float] = None):
     """A_/b_mono_unstead_diff_moving + BC_border_mono!(A, b, bc_b, mesh; t) of one slab (diffusion.jl:29-33, 254-258);
-    advdiff: A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:24-31, 229-232), the same border rows."""
+    advdiff: A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:24-31, 229-232), the same border rows.
+    t_border: the time of the border rows when it is not b's t (the liquid-motion Newton rebuilds: BC_border_mono!(...; t=tn1))."""
     cap = phase.capacity
     if not isinstance(cap, SpaceTimeCapacity):
         raise PenguinHipError("the moving solver needs a space-time capacity: Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
@@ -238,7 +239,7 @@ def _create_step(s: api.Solver, phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: 
     f0 = api._padded_field(api._eval(phase.source, cap._cw, float(t), 3), M) if sch == "CN" else None
     if sch == "CN" and f1 is not None and f0 is None:
         f0 = np.zeros(M)
-    borders, nb, bvals = api._border_descs(bc_b, mesh, float(t))
+    borders, nb, bvals = api._border_descs(bc_b, mesh, float(t if t_border is None else t_border))
     old, new = s._h, C.c_void_p()
     common = (cap._h, phase.operator._h, C.byref(desc), borders, C.c_int32(nb), L.dptr(D_arr) if D_arr is not None else None,
               L.dptr(f0) if f0 is not None else None, L.dptr(f1) if f1 is not None else None)
@@ -371,9 +372,11 @@ def solve_MovingAdvDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body
 # two phases                                                          prescribedmotionsolver/diffusion.jl:272-535
 # ---------------------------------------------------------------------------------------------------------------------
 def _create_step_diph(s: api.Solver, phase1: api.Phase, phase2: api.Phase, bc_b, ic, Δt: float, Tᵢ: Optional[np.ndarray],
-                      mesh: api.Mesh, scheme: str, t: float, from_previous: bool = False, advdiff: bool = False):
+                      mesh: api.Mesh, scheme: str, t: float, from_previous: bool = False, advdiff: bool = False,
+                      stefan: bool = False):
     """A_/b_diph_unstead_diff_moving + BC_border_diph!(A, b, bc_b, mesh) of one slab (diffusion.jl:281-288, 519-523);
-    advdiff: A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:255-262, 540-543), the same border rows."""
+    advdiff: A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:255-262, 540-543), the same border rows;
+    stefan: A_/b_diph_unstead_diff_moving_stef (liquidmotionsolver/diffusion.jl:445-651), the same border rows."""
     cap1, cap2 = phase1.capacity, phase2.capacity
     for cap in (cap1, cap2):
         if not isinstance(cap, SpaceTimeCapacity):
@@ -404,7 +407,8 @@ def _create_step_diph(s: api.Solver, phase1: api.Phase, phase2: api.Phase, bc_b,
         fs.append((f0, f1))
     borders, nb, bvals = api._border_descs(bc_b, mesh, None)       # BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
     old, new = s._h, C.c_void_p()
-    create = L.lib().pg_solver_create_moving_advdiff_diph if advdiff else L.lib().pg_solver_create_moving_diph
+    create = (L.lib().pg_solver_create_moving_advdiff_diph if advdiff else
+              L.lib().pg_solver_create_moving_stefan_diph if stefan else L.lib().pg_solver_create_moving_diph)
     L.check(create(
         cap1._h, phase1.operator._h, cap2._h, phase2.operator._h, C.byref(desc), borders, C.c_int32(nb), p(D1), p(D2),
         p(fs[0][0]), p(fs[0][1]), p(fs[1][0]), p(fs[1][1]),
