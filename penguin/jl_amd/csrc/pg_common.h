@@ -73,18 +73,12 @@ struct Config {
   bool poly = true;               // PG_POLY: polynomial right preconditioner where admissible
   int poly_degree = 6;            // PG_POLY_DEGREE: degree of the first solve on a matrix / of every solve when adaptation is off
   bool poly_adapt = true;         // PG_POLY_ADAPT (default: on unless PG_POLY_DEGREE is given)
-  bool poly_xspace = true;        // PG_POLY_XSPACE
-  int half_test = -1;             // PG_HALF_TEST: -1 automatic (degree >= 3), 0 off, 1 on
-  bool half_batch = true;         // PG_HALF_BATCH
-  bool krylov_nt = true;          // PG_KRYLOV_NT: stream hints on the dead vectors of the vector kernels
-  bool fuse_half_update = true;   // PG_FUSE_HALF: x-space loop: x += α M⁻¹p inside the s kernel (k_bicg_s_x) instead of k_bicg_half
   double poly_margin = 1.0;       // PG_POLY_MARGIN
-  double poly_slack = -1.0;       // PG_POLY_SLACK (< 0: 0.3 products in the x-space form, 0 otherwise)
+  double poly_slack = -1.0;       // PG_POLY_SLACK (< 0: 0.3 products)
   int poly_hist = 3;              // PG_POLY_HIST
   bool poly_trend = true;         // PG_POLY_TREND: the degree estimate follows the trend of the last estimates
-  int poly_maxdeg = 0;            // PG_POLY_MAXDEG (0: 32 x-space / 10 y-space)
+  int poly_maxdeg = 0;            // PG_POLY_MAXDEG (0: 32)
   int poly_mindeg = 4;            // PG_POLY_MINDEG: the smallest degree the per-solve choice takes (2 .. 8)
-  bool recovery_horner = true;    // PG_RECOVERY_HORNER (y-space form)
   int profile_sample = 3;         // PG_PROFILE_SAMPLE
   bool gamma_elim = true;         // PG_GAMMA_ELIM
   bool diag_elim = true;          // PG_DIAG_ELIM
@@ -104,10 +98,8 @@ struct Config {
   // the start of a quiet time step extrapolated from older states (pg_solver.hip, GuessArgs / k_guess_fit):
   int guess_n = 4;                // PG_GUESS_STATES: older states read at most (0: off, <= 4)
   int guess_depth = 7;            // PG_GUESS_DEPTH: older states kept to choose from (<= 7)
-  bool guess_defer = true;        // PG_GUESS_DEFER: compact x-space loop: the extrapolated state is formed by the solve's first update of x
+  bool guess_defer = true;        // PG_GUESS_DEFER: compact loop: the extrapolated state is formed by the solve's first update of x
   bool guess_always = false;      // PG_GUESS_ALWAYS=1: also where the fit's launch is not expected to pay (small, easy systems)
-  bool guess_async = false;       // PG_GUESS_ASYNC=1: one rank: the fit runs on a stream of its own beside the solve (measured: the
-                                  // Horner launches beside it slow down by more than the 21 us it takes off the stream: 586 vs 592 steps/s)
   int guess_monitor = 256;        // PG_GUESS_MONITOR: the fit samples every n-th chunk of 256 rows
   double guess_pass_cost = 0.34;  // PG_GUESS_PASS_COST: one more vector read of k_rhs_init_c, in products of the loop
   double guess_gain = 0.8;        // PG_GUESS_GAIN: products saved per product the fit predicts (what is left after the

@@ -33,7 +33,7 @@ struct KrylovWork {
   double fail_L = 0.0;
   int fail_wait = 0, fail_backoff = 1;  // solves left before that degree may be tried again; doubles when it falls short again
   // set by the caller around one krylov_solve: the system is a compact image of the caller's (pg_reduce.hip, DiagElim) and
-  // x is the caller's FULL vector -- the solution update x += q(Â)y lands at x[scatter[i]].  Needs the polynomial path.
+  // x is the caller's FULL vector -- the updates x += α M⁻¹p, x += ω M⁻¹s land at x[scatter[i]].  Needs the polynomial path.
   const int* scatter = nullptr;
   // set by the caller of a compact solve whose start was extrapolated from older states (pg_solver.hip, GuessArgs) and who left
   // the extrapolated state unformed: the FIRST update of x then writes  x[map] = z_g[map] + α M⁻¹p,  z_g = zbase + Σ c_j (zr[o_j] -
@@ -46,10 +46,9 @@ struct KrylovWork {
   // set by the caller whose start kernel has already reset the scalars, summed the start sums and derived PH_INIT
   // (k_rhs_init_c with a ticket): krylov_solve launches no start kernel.  Reset by krylov_solve.
   bool start_folded = false;
-  // polynomial right preconditioner (pg_krylov.hip), n_vec each, on first use: the accumulated solution of the
-  // preconditioned system (x = x0 + q(Â) ya) and the two work vectors the chain of products alternates between
-  DevBuf<double> ya, wa, wb;
-  DevBuf<double> yb;        // x-space form: ya = M⁻¹p, yb = M⁻¹s of the running iteration
+  // polynomial right preconditioner (pg_krylov.hip), n_vec each, on first use: ya = M⁻¹p, yb = M⁻¹s of the running
+  // iteration (the updates of x read them) and the two work vectors the Horner chain alternates between
+  DevBuf<double> ya, yb, wa, wb;
   // GMRES(m) only, allocated on first use (pg_gmres.hip): m+1 basis vectors, H / rotations / g, per-block partial sums
   DevBuf<double> gm_basis, gm, gm_partials;
   int gm_m = -1;
@@ -73,7 +72,7 @@ struct SolveStats {
   i64 spmv_launches = 0, spmv_lean_launches = 0;
   int poly_degree = 0;      // products with Â per application of the preconditioned operator (0: plain iteration)
   int half_exit = 0;        // 1: the solve ended at the half step of its last iteration (counted as an iteration)
-  int poly_xspace = 0;      // 1: x-space form of the preconditioned loop (Horner chains, no recovery), pg_krylov.hip
+  int poly_xspace = 0;      // 1: the polynomial preconditioner ran (kept for the ABI field pg_run_info.poly_xspace)
   i64 products = 0;         // products with Â inside the solve (the caller's start product not counted)
   int polls = 0;            // host waits of the solve (1: it ended inside the first batch of queued launches)
 };
@@ -97,7 +96,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
                   KrylovWork& w, const pg_krylov_opts& opts, SolveStats& stats, const double* x0 = nullptr,
                   const double* Ax0 = nullptr, bool preinit = false);
 
-// will krylov_solve(A, ..., opts) run BiCGStab right-preconditioned with the polynomial (the y-space iteration)?
+// will krylov_solve(A, ..., opts) run BiCGStab right-preconditioned with the polynomial?  (Only that loop can solve a
+// compact system: it updates x through KrylovWork::scatter.)
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts);
 
 // restarted GMRES (pg_gmres.hip): zero initial guess, x (n_vec, overwritten) = A^{-1} b

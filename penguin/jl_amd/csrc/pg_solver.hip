@@ -76,19 +76,6 @@ struct pg_solver {
   // the extrapolated start of a quiet step (GuessArgs).  hist_cnt of them are valid, all for the matrix of hist_de.
   DevBuf<double> zh[8], yh[8], guess_coef, guess_partials;
   DevBuf<unsigned> guess_ticket;
-  // k_guess_fit runs beside the solve on a stream of its own (one rank): it reads what the step's first kernel left (b̂, r̂,
-  // the products) and writes the coefficients the NEXT step's first kernel reads; fit_join() orders that kernel behind it
-  struct FitAsync {
-    hipStream_t st = nullptr;
-    hipEvent_t ev_rhs = nullptr, ev_fit = nullptr;
-    bool pending = false;
-    ~FitAsync() {
-      if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
-      if (ev_rhs) (void)hipEventDestroy(ev_rhs);
-      if (ev_fit) (void)hipEventDestroy(ev_fit);
-    }
-  } fit;
-  ~pg_solver() { if (fit.st) (void)hipStreamSynchronize(fit.st); }   // (before any buffer it reads goes back to the cache)
   int hist_cnt = 0, hist_k = 0;     // (hist_k: the ring's depth the count refers to)
   bool plain_guess_on[2] = {false, false};          // the plain warm path's switch and last solve's products, per matrix
   double plain_last_products[2] = {0.0, 0.0};       // (ctor / run; the compact path keeps its own in DiagElim)
@@ -113,14 +100,6 @@ struct pg_solver {
 namespace {
 
 using pg::BLOCK;   // 256 (pg_spmv.h)
-
-// the compute stream waits for a fit that may still be running beside it (host = true: the host does)
-void fit_join(pg_solver* s, bool host = false) {
-  if (!s->fit.pending) return;
-  if (host) PG_HIP(hipStreamSynchronize(s->fit.st));
-  else PG_HIP(hipStreamWaitEvent(ctx().stream, s->fit.ev_fit, 0));
-  s->fit.pending = false;
-}
 
 struct RowSegs {
   int K;
@@ -1316,7 +1295,6 @@ pg_krylov_opts default_opts() {
 
 void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
-  fit_join(s);
   // solve_system!(s) with the constructor's A and b (diffusion.jl:275)
   const i64 n = s->nb.n_own;
   if (s->moving && o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
@@ -1408,23 +1386,8 @@ void guess_after_rhs(pg_solver* s, const GuessPlan& gp, i64 n, const int* cmap, 
     gf.pass_cost = cfg.guess_pass_cost;
     gf.gain = cfg.guess_gain;
     gf.sums = single ? nullptr : s->guess_coef.p + 16;
-    hipStream_t fst = stream;
-    if (single && cfg.guess_async) {
-      if (!s->fit.st) {
-        PG_HIP(hipStreamCreateWithFlags(&s->fit.st, hipStreamNonBlocking));
-        PG_HIP(hipEventCreateWithFlags(&s->fit.ev_rhs, hipEventDisableTiming));
-        PG_HIP(hipEventCreateWithFlags(&s->fit.ev_fit, hipEventDisableTiming));
-      }
-      PG_HIP(hipEventRecord(s->fit.ev_rhs, stream));
-      PG_HIP(hipStreamWaitEvent(s->fit.st, s->fit.ev_rhs, 0));
-      fst = s->fit.st;
-    }
-    hipLaunchKernelGGL(k_guess_fit, dim3(std::max(gfit, 1)), dim3(BLOCK), 0, fst, n, cmap, ds, (const double*)s->b.p,
+    hipLaunchKernelGGL(k_guess_fit, dim3(std::max(gfit, 1)), dim3(BLOCK), 0, stream, n, cmap, ds, (const double*)s->b.p,
                        (const double*)s->y.p, rhat, gf);
-    if (fst != stream) {
-      PG_HIP(hipEventRecord(s->fit.ev_fit, fst));
-      s->fit.pending = true;
-    }
     if (!single) {
       comm_allreduce_sum_f64(gf.sums, GUESS_NS, stream);
       hipLaunchKernelGGL(k_guess_decide, dim3(1), dim3(BLOCK), 0, stream, gf);
@@ -1447,7 +1410,6 @@ void guess_commit(pg_solver* s, const GuessPlan& gp, const void* owner) {
   if (gp.KH == 0) return;
   if (config().debug) {
     double hc[16];
-    fit_join(s, true);
     s->guess_coef.download(hc, 16);
     fprintf(stderr, "[pg_solver] extrapolated start: %d older states kept; sampled (r,r)_W plain %.3e, taken %.3e; next step: %d states",
             gp.hist_had, hc[9], hc[10], (int)hc[4]);
@@ -1465,7 +1427,6 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   PG_REQUIRE(s->initial_done, "Solver is not initialized. Call pg_solver_initial_solve first.");
   const pg_krylov_opts o = opts ? *opts : default_opts();
   hipStream_t stream = ctx().stream;
-  fit_join(s);
   ensure_run_matrix(s, scheme);
   const CsrMatrix& A = run_matrix(s);
   const i64 n = s->nb.n_own;
@@ -1535,7 +1496,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       const Config& cfg = config();
       // (not after a solve that met the tolerance at its start: the next one probably will too, no update of x runs then, and
       //  writing the state from the first s kernel's early exit costs more than writing it here -- 64^3 BE near steady state)
-      const bool defer = KH > 0 && cfg.guess_defer && cfg.poly_xspace && cfg.fuse_half_update && DE.last_products > 0.0;
+      const bool defer = KH > 0 && cfg.guess_defer && DE.last_products > 0.0;
       gp.ga.defer = defer ? 1 : 0;
       const GuessArgs& ga = gp.ga;
       const double* zprev = s->z.p;      // z^n (the buffers trade places below)
@@ -2058,7 +2019,7 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
   const double wait0 = pg::g_host_wait_us;
   PG_HIP(hipEventRecord(ev.e0, stream));
   double used0 = 0.0;               // older states read by the extrapolated starts so far (device counter, GuessArgs)
-  if (s->guess_coef.n >= 16) { fit_join(s, true); s->guess_coef.download(&used0, 1, 13); }
+  if (s->guess_coef.n >= 16) s->guess_coef.download(&used0, 1, 13);
   SolveStats tot;
   i64 steps = 0, iters = 0, unconverged = 0;
   double worst = 0.0;
@@ -2117,7 +2078,6 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
     info->guess_states_read = 0;
     if (s->guess_coef.n >= 16) {
       double hc[16];
-      fit_join(s, true);
       s->guess_coef.download(hc, 16);
       info->guess_states_read = (int64_t)(hc[13] - used0);
     }
@@ -2370,7 +2330,6 @@ int32_t pg_solver_guess_info(pg_solver* s, int32_t* kept, int32_t* nstates, int3
   for (int j = 0; j < 4; ++j) { offsets[j] = 0; coef[j] = 0.0; }
   if (s->guess_coef.n >= 16 && s->hist_cnt > 0) {
     double hc[16];
-    fit_join(s, true);
     s->guess_coef.download(hc, 16);
     *nstates = (int32_t)hc[4];
     for (int j = 0; j < *nstates && j < 4; ++j) { offsets[j] = (int32_t)hc[5 + j] + 1; coef[j] = hc[j]; }
@@ -2384,10 +2343,10 @@ int32_t pg_solver_time_spmv(pg_solver* s, int32_t which, int32_t reps, double* a
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(s && avg_ms && reps > 0, "pg_solver_time_spmv: bad arguments");
-  // bits 4-6: mode of the launch (0 plain, 1, 2, 3 fused dots, 4: 2x - Ax); bit 11: the Horner step of the x-space loop
+  // bits 4-6: mode of the launch (0 plain, 1, 2, 3 fused dots); bit 11: the Horner step of the preconditioned loop
   // (mode 8: out = pc2 base + pc0 x + pc1 A x, three vector streams)
   const int sel = which & 1, mode = (which & 2048) ? 8 : ((which >> 4) & 7);
-  PG_REQUIRE(mode <= 4 || mode == 8, "pg_solver_time_spmv: unknown launch mode");
+  PG_REQUIRE(mode <= 3 || mode == 8, "pg_solver_time_spmv: unknown launch mode");
   if (sel == 1) PG_REQUIRE(s->have_run, "run matrix not assembled yet");
   const CsrMatrix& Afull = sel == 0 ? s->A_ctor : run_matrix(s);
   // bit 9: the matrix the warm loop iterates on (without the Dirichlet interface rows, pg_reduce.hip), built here if need be

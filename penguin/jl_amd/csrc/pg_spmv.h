@@ -117,11 +117,10 @@ __device__ inline void derive(int phase, double* sc) {
       if (sc[S_PENDING3] != 0.0) end_of_iteration(sc);
       break;
     case PH_BICG_S:
-      // half step: s = r - αv already meets the tolerance (S_RED4 = (s,s)_W): x += αp and stop (k_bicg_half) -- with a
-      // polynomial of degree m in every application of the operator a whole iteration is 2m products, worth testing in
-      // the middle
-      // (S_HALF = the number of the iteration that ended this way: k_bicg_half applies x += αp in that iteration only --
-      // iterations queued past it find S_DONE set and must not repeat the update)
+      // half step: s = r - αv already meets the tolerance (S_RED4 = (s,s)_W): stop -- x += αp went in with s (k_bicg_s_x)
+      // -- with a polynomial of degree m in every application of the operator a whole iteration is 2m products, worth
+      // testing in the middle
+      // (S_HALF = the number of the iteration that ended this way; iterations queued past it find S_DONE set)
       if (sc[S_DONE] == 0.0 && sc[S_RED4] <= sc[S_TOL2]) {
         sc[S_RR] = sc[S_RED4];
         sc[S_ITERS] += 1.0;
@@ -189,9 +188,8 @@ struct FinArgs {
   int nslots;         // partial slots [0, nslots) to sum into S_RED0..
   int do_derive;      // 0: sums only (several ranks: an all-reduce follows)
   const double* dotx; // operand of the (y, .) dot of modes 2 / 3; nullptr: the input vector x itself
-  double pc0 = 2.0, pc1 = -1.0;   // modes 4..7: pc0 x + pc1 A x  (default: the Neumann product 2x - Âx)
-  const double* base = nullptr;   // mode 5: y = base - (pc0 x + pc1 A x);  mode 8: y = pc2 base + pc0 x + pc1 A x
-  double* accv = nullptr;         // mode 7: accv += pc2 x
+  double pc0 = 0.0, pc1 = 0.0;    // mode 8: y = pc2 base + (pc0 x + pc1 A x)
+  const double* base = nullptr;
   double pc2 = 0.0;
 };
 
@@ -211,8 +209,9 @@ __device__ inline void fold_scalar_phase(const FinArgs& fin, const double* __res
 
 // y = A x on rows [0, A.n).  mode 0: plain; 1: partials[0..grid) = aux . y; 2: partials[0..grid) = y . x and
 // partials[grid..2grid) = y . y; 3: mode 2 plus partials[4grid..5grid) = aux . y (the operand of the (y, .) dot of modes
-// 2 / 3 is fin->dotx when set); 4 (slice kernel only): y = 2x - A x, i.e. u = M⁻¹x for the Neumann preconditioner
-// M⁻¹ = 2I - Â of the BiCGStab driver, no dots.  `sc` (may be NULL): kernels return immediately when sc[S_DONE] != 0.
+// 2 / 3 is fin->dotx when set); 8 (slice kernel only): y = pc2 base + pc0 x + pc1 A x, a Horner step of the polynomial
+// preconditioner M⁻¹ = q(Â) of the BiCGStab driver (FinArgs), no dots.  `sc` (may be NULL): kernels return immediately
+// when sc[S_DONE] != 0.
 // `grid` must be the value used to size `partials` (KrylovWork::grid) for modes 1/2.
 // `fin` (optional): scalar phase evaluated by the last block of the launch; returns true when the launched kernel
 // does that (the stencil-slice kernel), false when the caller still has to launch the scalar kernel itself.
@@ -228,6 +227,6 @@ bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Sla
 // plain y = A x with an explicit kernel variant (PG_SPMV_VARIANT numbering): kernel-vs-kernel parity checks
 void launch_spmv_variant(int variant, const CsrMatrix& A, const double* x, double* y, hipStream_t st);
 int spmv_default_grid(i64 n);
-bool spmv_supports_preconditioner_product();   // mode 4 and FinArgs::dotx exist in the slice kernel only (PG_SPMV_VARIANT)
+bool spmv_supports_preconditioner_product();   // mode 8 and FinArgs::dotx exist in the slice kernel only (PG_SPMV_VARIANT)
 
 }  // namespace pg

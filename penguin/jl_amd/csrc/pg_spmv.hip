@@ -20,7 +20,8 @@
 //
 // The dots that follow an SpMV in BiCGStab / CG are fused into the epilogue (one partial per block, summed in a fixed
 // order: deterministic); the slice kernel's last-arriving block can also evaluate the scalar phase (pg_spmv.h).  The slice
-// kernel has one more epilogue, y = 2x - A x: the product with the Neumann preconditioner 2I - A of pg_krylov.hip.
+// kernel has one more epilogue, y = pc2 base + pc0 x + pc1 A x: a Horner step of the polynomial preconditioner of
+// pg_krylov.hip (launch mode 8).
 #include <algorithm>
 #include <cstdlib>
 #include <thread>
@@ -276,40 +277,29 @@ __device__ inline d2_t load_pair(const double* p) {
   return r;
 }
 
-// epilogue of mode 4: y = pc0 x + pc1 (A x) -- one factor I - τÂ (pc0 = 1, pc1 = -τ) of the polynomial preconditioner's
-// residual polynomial, or 2x - Âx (pg_krylov.hip); the ONE expression every path of the kernel uses
-__device__ inline double mode4_out(double xown, double ax, double pc0, double pc1) { return pc0 * xown + pc1 * ax; }
-
 // Launch modes of the slice kernel (MODE): what the epilogue does with s = (A x)_row.  A, B = operand vectors read at the
 // row (pa, pb below); own = x_row.
 //   0  y = s
 //   1  y = s;                         acc0 += A y                                   A = aux
 //   2  y = s;                         acc0 += A y, acc1 += y y                      A = dotx (or x)
 //   3  y = s;                         acc0 += A y, acc1 += y y, acc2 += B y         A = dotx (or x), B = aux
-//   4  y = pc0 own + pc1 s                                                          (one factor of the polynomial)
-//   5  y = B - (pc0 own + pc1 s);     acc0 += A y                                   A = aux, B = base
-//   6  y = A - (pc0 own + pc1 s);     acc0 += A y, acc1 += y y, acc2 += B y         A = dotx, B = aux
-//   7  y = pc0 own + pc1 s;           A_row += pc2 own  (A = accv, read and written)
-//   8  y = B + (pc0 own + pc1 s)                                                     B = base  (Horner step of x = x0 + q(Â)y)
-// 5 / 6 close a chain of mode-4 launches: v = p - R(Â)p with (r̂,v), t = s - R(Â)s with (t,s), (t,t), (r̂,t); 7 is a step of
-// the same chain that also accumulates q(Â)y = Σ τ_k w_(k-1) (pg_krylov.hip).
+//   8  y = pc2 B + (pc0 own + pc1 s)                                                B = base
+// 8 is a step of the Horner chain that applies the polynomial preconditioner M⁻¹ = q(Â) (pg_krylov.hip); 1 / 3 close an
+// application of the operator with its dots.
 template <int MODE>
 struct ModeInfo {
-  static constexpr bool OWN = MODE >= 4;
-  static constexpr bool HAS_A = MODE == 1 || MODE == 2 || MODE == 3 || MODE == 5 || MODE == 6 || MODE == 7;
-  static constexpr bool HAS_B = MODE == 3 || MODE == 5 || MODE == 6 || MODE == 8;
-  static constexpr bool DOT0 = MODE == 1 || MODE == 2 || MODE == 3 || MODE == 5 || MODE == 6;
-  static constexpr bool DOT1 = MODE == 2 || MODE == 3 || MODE == 6;
-  static constexpr bool DOT2 = MODE == 3 || MODE == 6;
+  static constexpr bool OWN = MODE == 8;
+  static constexpr bool HAS_A = MODE == 1 || MODE == 2 || MODE == 3;
+  static constexpr bool HAS_B = MODE == 3 || MODE == 8;
+  static constexpr bool DOT0 = MODE == 1 || MODE == 2 || MODE == 3;
+  static constexpr bool DOT1 = MODE == 2 || MODE == 3;
+  static constexpr bool DOT2 = MODE == 3;
 };
 
-// y of one row from its product s; a, b = the operands A, B at the row
+// y of one row from its product s; b = the operand B at the row.  The ONE expression every path of the kernel uses.
 template <int MODE>
-__device__ __forceinline__ double mode_out(double s, double own, double a, double b, double pc0, double pc1, double pc2) {
-  if (MODE == 4 || MODE == 7) return mode4_out(own, s, pc0, pc1);
-  if (MODE == 5) return b - mode4_out(own, s, pc0, pc1);
-  if (MODE == 6) return a - mode4_out(own, s, pc0, pc1);
-  if (MODE == 8) return pc2 * b + mode4_out(own, s, pc0, pc1);   // Horner step: pc2 base + pc0 x + pc1 A x
+__device__ __forceinline__ double mode_out(double s, double own, double b, double pc0, double pc1, double pc2) {
+  if (MODE == 8) return pc2 * b + (pc0 * own + pc1 * s);
   return s;
 }
 
@@ -373,11 +363,10 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
   }
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
-    sum[b].x = mode_out<MODE>(sum[b].x, own[b].x, ax[b].x, ax2[b].x, pc0, pc1, pc2);
-    sum[b].y = mode_out<MODE>(sum[b].y, own[b].y, ax[b].y, ax2[b].y, pc0, pc1, pc2);
+    sum[b].x = mode_out<MODE>(sum[b].x, own[b].x, ax2[b].x, pc0, pc1, pc2);
+    sum[b].y = mode_out<MODE>(sum[b].y, own[b].y, ax2[b].y, pc0, pc1, pc2);
     const bool st = !(dbg & 8) || sum[b].x == 1.2345e-300;
     double* yp = y + d.r0 + l0[b];
-    double* ap = const_cast<double*>(pa) + d.r0 + l0[b];   // mode 7: the accumulated vector
     if (live1[b]) {
       if (st) {
         d2u_t out;
@@ -385,17 +374,11 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
         if (!(dbg & 2048)) __builtin_nontemporal_store(out, reinterpret_cast<d2u_t*>(yp));
         else *reinterpret_cast<d2u_t*>(yp) = out;
       }
-      if (MODE == 7) {
-        d2u_t out;
-        out.x = ax[b].x + pc2 * own[b].x; out.y = ax[b].y + pc2 * own[b].y;
-        *reinterpret_cast<d2u_t*>(ap) = out;
-      }
       if (MI::DOT0) acc0 += ax[b].x * sum[b].x + ax[b].y * sum[b].y;
       if (MI::DOT1) acc1 += sum[b].x * sum[b].x + sum[b].y * sum[b].y;
       if (MI::DOT2) acc2 += ax2[b].x * sum[b].x + ax2[b].y * sum[b].y;
     } else if (live0[b]) {
       if (st) *yp = sum[b].x;
-      if (MODE == 7) *ap = ax[b].x + pc2 * own[b].x;
       if (MI::DOT0) acc0 += ax[b].x * sum[b].x;
       if (MI::DOT1) acc1 += sum[b].x * sum[b].x;
       if (MI::DOT2) acc2 += ax2[b].x * sum[b].x;
@@ -474,8 +457,7 @@ struct MarchSide {   // per-plane operands besides the chain's own lines: latera
 template <int CNT, int MODE>
 __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, int l2, double* __restrict__ yrow, const d2_t& xm,
                                               double xm_n, const d2_t& xc, const d2_t& xp, const MarchSide& sd, double pc0,
-                                              double pc1, double pc2, double* __restrict__ arow, double& acc0, double& acc1,
-                                              double& acc2, int dbg) {
+                                              double pc1, double pc2, double& acc0, double& acc1, double& acc2, int dbg) {
   using MI = ModeInfo<MODE>;
   constexpr bool Y = CNT == 7;
   const double xc_nx = lane_up(xc.x), xc_ny = lane_up(xc.y), xp_n = lane_up(xp.x);
@@ -492,8 +474,8 @@ __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, i
   s1 += c[j] * xm.y;  s2 += c[j] * xm_n;  ++j;
   s1 += c[j] * xc.y;  s2 += c[j] * xc_nx;
   // (the row's own x: elements 2l+1, 2l+2 of the centre line)
-  s1 = mode_out<MODE>(s1, xc.y, sd.ax.x, sd.ax2.x, pc0, pc1, pc2);
-  s2 = mode_out<MODE>(s2, xc_nx, sd.ax.y, sd.ax2.y, pc0, pc1, pc2);
+  s1 = mode_out<MODE>(s1, xc.y, sd.ax2.x, pc0, pc1, pc2);
+  s2 = mode_out<MODE>(s2, xc_nx, sd.ax2.y, pc0, pc1, pc2);
   const int lo = rng & 255, hi = rng >> 8;
   const bool nost = (dbg & 32) && s1 != 1.2345e-300;   // diagnostics: no stores
   const bool allst = (dbg & 512) != 0;                  // diagnostics: every lane stores its pair (whole windows)
@@ -510,18 +492,6 @@ __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, i
     yrow[0] = s1;
   } else if (v2) {
     yrow[1] = s2;
-  }
-  if (MODE == 7) {   // the accumulated vector of the chain: A_row += pc2 own
-    const double a1 = sd.ax.x + pc2 * xc.y, a2 = sd.ax.y + pc2 * xc_nx;
-    if (v1 && v2) {
-      d2u_t out;
-      out.x = a1; out.y = a2;
-      *reinterpret_cast<d2u_t*>(arow) = out;
-    } else if (v1) {
-      arow[0] = a1;
-    } else if (v2) {
-      arow[1] = a2;
-    }
   }
   if (MI::DOT0) {
     const double w1 = v1 ? s1 : 0.0, w2 = v2 ? s2 : 0.0;
@@ -586,7 +556,7 @@ __device__ __forceinline__ void march_unit(int rec, int lane, const double* __re
 #pragma unroll
   for (int q = 0; q < KK; ++q)
     xm_n = march_plane<CNT, MODE>(c, rlane(rec, 21 + 4 * (Q0 + q)), l2, y + rb[q] + l2 + one, ln[q], xm_n, ln[q + 1], ln[q + 2], sd[q], pc0,
-                                  pc1, pc2, const_cast<double*>(pa) + rb[q] + l2 + one, acc0, acc1, acc2, dbg);
+                                  pc1, pc2, acc0, acc1, acc2, dbg);
 }
 
 template <int CNT, int MODE>
@@ -594,10 +564,9 @@ __device__ __forceinline__ void march_dispatch(int rec, int lane, const double* 
                                       const double* __restrict__ pa, const double* __restrict__ pb, double pc0, double pc1,
                                       double pc2, double& acc0, double& acc1, double& acc2, int dbg) {
   // The launches with fused dots and one or two more operand vectors per plane (modes 1, 3: the closing launch of an
-  // application of the operator; 5, 6: the same in the y-space form of the preconditioned loop) do not fit a unit of MARCH_K
-  // planes into the 128 VGPRs of four waves per SIMD (10 / 14 VGPRs went to scratch in modes 5 / 6): they take it in two
-  // halves -- two more line loads per unit, which hit L1
-  constexpr bool SPLIT = (MODE == 1 || MODE == 3 || MODE == 5 || MODE == 6) && MARCH_K == 2 * MARCH_KS && PG_MARCH_SPLIT;
+  // application of the operator) do not fit a unit of MARCH_K planes into the 128 VGPRs of four waves per SIMD: they take it
+  // in two halves -- two more line loads per unit, which hit L1
+  constexpr bool SPLIT = (MODE == 1 || MODE == 3) && MARCH_K == 2 * MARCH_KS && PG_MARCH_SPLIT;
   if ((rlane(rec, 0) & 255) == MARCH_K) {
     if (SPLIT) {
       march_unit<CNT, MODE, MARCH_KS, 0, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg);
@@ -628,10 +597,10 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
   if (sc && sc[S_DONE] != 0.0) return;
   using MI = ModeInfo<MODE>;
   constexpr bool DOTS = MI::DOT0;
-  const double* __restrict__ dx = fin.dotx ? fin.dotx : x;   // operand of the (y, .) dot of modes 2 / 3 / 6
+  const double* __restrict__ dx = fin.dotx ? fin.dotx : x;   // operand of the (y, .) dot of modes 2 / 3
   // operand vectors A and B of the epilogue (ModeInfo)
-  const double* __restrict__ pa = (MODE == 1 || MODE == 5) ? aux : ((MODE == 2 || MODE == 3 || MODE == 6) ? dx : (MODE == 7 ? fin.accv : nullptr));
-  const double* __restrict__ pb = (MODE == 3 || MODE == 6) ? aux : ((MODE == 5 || MODE == 8) ? fin.base : nullptr);
+  const double* __restrict__ pa = MODE == 1 ? aux : ((MODE == 2 || MODE == 3) ? dx : nullptr);
+  const double* __restrict__ pb = MODE == 3 ? aux : (MODE == 8 ? fin.base : nullptr);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double* __restrict__ sv = s_val[wave];
@@ -772,9 +741,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
       }
       __builtin_amdgcn_wave_barrier();
       if (live) {
-        sum = mode_out<MODE>(sum, xown, opa, opb, fin.pc0, fin.pc1, fin.pc2);
+        sum = mode_out<MODE>(sum, xown, opb, fin.pc0, fin.pc1, fin.pc2);
         y[rid] = sum;
-        if (MODE == 7) const_cast<double*>(pa)[rid] = opa + fin.pc2 * xown;
         if (MI::DOT0) acc0 += opa * sum;
         if (MI::DOT1) acc1 += sum * sum;
         if (MI::DOT2) acc2 += opb * sum;
@@ -918,7 +886,7 @@ template <int MODE>
 bool launch_mode(int v, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
                  const double* sc, int grid, hipStream_t st, const FinArgs* fin) {
   if (v & 64) return launch_slices<MODE>(v, A, 0, A.nslices, x, y, aux, partials, sc, grid, grid, 0, st, fin);
-  PG_REQUIRE(MODE < 4 && !(fin && fin->dotx), "the preconditioner products and separate dot operands need the slice kernel");
+  PG_REQUIRE(MODE != 8 && !(fin && fin->dotx), "the preconditioner products and separate dot operands need the slice kernel");
   if (v != 1) ensure_csr_chunks(A);
   if (v == 1) {
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv<MODE>), dim3(grid), dim3(BLOCK), 0, st, A.n, A.rowptr.p, A.col.p, A.val.p, x, y,
@@ -1456,10 +1424,6 @@ bool launch_spmv(int mode, const CsrMatrix& A, const double* x, double* y, const
   if (mode == 0) return launch_mode<0>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 1) return launch_mode<1>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 2) return launch_mode<2>(v, A, x, y, aux, partials, sc, grid, st, fin);
-  if (mode == 4) return launch_mode<4>(v, A, x, y, aux, partials, sc, grid, st, fin);
-  if (mode == 5) return launch_mode<5>(v, A, x, y, aux, partials, sc, grid, st, fin);
-  if (mode == 6) return launch_mode<6>(v, A, x, y, aux, partials, sc, grid, st, fin);
-  if (mode == 7) return launch_mode<7>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 8) return launch_mode<8>(v, A, x, y, aux, partials, sc, grid, st, fin);
   PG_REQUIRE(mode == 3, "unknown SpMV launch mode");
   return launch_mode<3>(v, A, x, y, aux, partials, sc, grid, st, fin);
@@ -1484,7 +1448,7 @@ bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Sla
   halo_begin(nb, slab, x, st);                      // x's owned part is final on `st`; ghosts arrive on the comm stream
   bool folded;
   FinArgs fin_nofold{nullptr, nullptr, PH_NONE, 0, 0, fin ? fin->dotx : nullptr};   // first launch: dot operand, no scalar phase
-  if (fin) { fin_nofold.pc0 = fin->pc0; fin_nofold.pc1 = fin->pc1; fin_nofold.pc2 = fin->pc2; fin_nofold.base = fin->base; fin_nofold.accv = fin->accv; }
+  if (fin) { fin_nofold.pc0 = fin->pc0; fin_nofold.pc1 = fin->pc1; fin_nofold.pc2 = fin->pc2; fin_nofold.base = fin->base; }
 #define PG_SPLIT(MODE_)                                                                                              \
   launch_slices<MODE_>(v, A, 0, ni, x, y, aux, partials, sc, grid, grid, 0, st, fin ? &fin_nofold : nullptr);      \
   halo_end(st);                                                                                                      \
@@ -1492,12 +1456,8 @@ bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Sla
   if (mode == 0) { PG_SPLIT(0); }
   else if (mode == 1) { PG_SPLIT(1); }
   else if (mode == 2) { PG_SPLIT(2); }
-  else if (mode == 4) { PG_SPLIT(4); }
-  else if (mode == 5) { PG_SPLIT(5); }
-  else if (mode == 6) { PG_SPLIT(6); }
-  else if (mode == 7) { PG_SPLIT(7); }
   else if (mode == 8) { PG_SPLIT(8); }
-  else { PG_SPLIT(3); }
+  else { PG_REQUIRE(mode == 3, "unknown SpMV launch mode"); PG_SPLIT(3); }
 #undef PG_SPLIT
   return folded;
 }

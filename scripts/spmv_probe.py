@@ -1,7 +1,7 @@
 """Back-to-back timing of the SpMV launch modes on the run matrix of the n^3 heat problem (developer probe).
 
     python scripts/spmv_probe.py [n=512] [reps=50]
-Modes: 0 plain, 1 (+ r-hat dot), 3 (three dots), 4 (y = 2x - Ax).  Kernel variants via the PG_SPMV_* environment.
+Modes: 0 plain, 1 (+ r-hat dot), 3 (three dots).  Kernel variants via the PG_SPMV_* environment.
 """
 import ctypes as C
 import os
@@ -15,8 +15,8 @@ from penguin.jl_amd import _lib as L
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
 reps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-modes = [int(c) for c in sys.argv[3]] if len(sys.argv) > 3 else [0, 1, 3, 4]
-modes = [m for m in modes if m <= 4]
+modes = [int(c) for c in sys.argv[3]] if len(sys.argv) > 3 else [0, 1, 3]
+modes = [m for m in modes if m <= 3]
 pj.init(0)
 mesh = pj.Mesh((n, n, n), (4.0, 4.0, 4.0))
 cap = pj.Capacity(pj.Sphere((2.01, 2.01, 2.01), 1.0), mesh)
@@ -42,15 +42,11 @@ ms = C.c_double()
 print(out[0], file=sys.stderr, flush=True)
 for mode in modes:
     print(f"mode {mode} ...", file=sys.stderr, flush=True)
-    extra = {0: 0, 1: 8, 3: 16, 4: 0}[mode] * info.n_own
+    extra = {0: 0, 1: 8, 3: 16}[mode] * info.n_own
     L.check(lib.pg_solver_time_spmv(s._h, sel | (mode << 4), reps, C.byref(ms)))
     warm = ms.value
     L.check(lib.pg_solver_time_spmv(s._h, sel | (mode << 4) | 256, reps, C.byref(ms)))
     out.append(f"m{mode} warm {warm * 1e3:5.1f} cold {ms.value * 1e3:5.1f} us ({(info.spmv_bytes + extra) / ms.value / 1e6:5.0f} GB/s)")
-    if mode == 4:      # the loop's own matrix (Dirichlet interface rows left out), launches chained as in a polynomial chain
-        L.check(lib.pg_solver_time_spmv(s._h, sel | (mode << 4) | 512 | 1024, reps, C.byref(ms)))
-        li = s.system_info(6 + sel)
-        out.append(f"loop-matrix chained {ms.value * 1e3:5.1f} us ({li.spmv_bytes / 1e6:.1f} MB)")
 if not broken:
     L.check(lib.pg_set_profiling(1))
     L.check(lib.pg_solver_run(s._h, C.c_double(1e9), C.c_int32(1), C.byref(opts), 0, C.c_int64(10), 0, C.byref(run)))

@@ -902,14 +902,14 @@ def test_spmv_work_item_orders_bitwise_equal_csr_kernels(env):
     assert r.returncode == 0 and "orders ok" in r.stdout, (env, r.stdout[-2000:], r.stderr[-4000:])
 
 
-@pytest.mark.parametrize("env", [{"PG_POLY_XSPACE": "0"}, {"PG_POLY_MAXDEG": "7"}, {"PG_POLY_XSPACE": "0", "PG_DIAG_ELIM": "0"},
+@pytest.mark.parametrize("env", [{"PG_POLY_MAXDEG": "7"}, {"PG_DIAG_ELIM": "0"},
                                  {"PG_DIAG_ELIM": "0", "PG_GAMMA_ELIM": "0"}, {"PG_GUESS_STATES": "0"},
                                  {"PG_GUESS_STATES": "2", "PG_GUESS_DEPTH": "3", "PG_POLY_TREND": "0"}])
 def test_forms_of_the_preconditioned_loop_match_the_oracle(env):
-    """The loop's variants -- y-space form (lean chains + recovery), low degree cap (several applications per solve), the
-    Dirichlet-interface reduction without the compact system, the full system, the start of the quiet steps without / with a
-    shallower extrapolation -- are selected by environment variables read once per process: parity tests against the oracle's
-    direct solve in a child process per setting."""
+    """The loop's variants -- low degree cap (several applications per solve), the Dirichlet-interface reduction without the
+    compact system, the full system, the start of the quiet steps without / with a shallower extrapolation -- are selected by
+    environment variables read once per process: parity tests against the oracle's direct solve in a child process per
+    setting."""
     import subprocess
     root = pathlib.Path(__file__).resolve().parents[1]
     code = ("import sys; sys.path.insert(0, '.'); import penguin.jl_amd as pj; pj.init(0); import tests.test_gpu_parity as t\n"
@@ -954,7 +954,7 @@ def test_extrapolated_start_of_quiet_steps_keeps_the_solution(pj, scheme, source
     cfg = dict(kv.split("=", 1) for kv in pj.config_string().split() if "=" in kv)
     states, depth = int(cfg["guess_states"]), int(cfg["guess_depth"])
     if not s.system_info(1).loop_is_compact:
-        return      # (PG_DIAG_ELIM=0 / y-space form: the plain warm path decides for itself; parity is what is checked there)
+        return      # (PG_DIAG_ELIM=0: the plain warm path decides for itself; parity is what is checked there)
     if states == 0 or (g["kept"] == 0 and scheme == "BE"):
         # switched off (PG_GUESS_STATES=0), or never switched on: the backward-Euler solves of this small problem use too few
         # products for the fit's launch to pay (pg_solver.hip; PG_GUESS_ALWAYS=1 forces it): nothing kept, nothing read
