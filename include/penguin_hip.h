@@ -285,17 +285,14 @@ int32_t pg_solver_create_steady_diph(pg_capacity* c1, pg_diffops* o1, pg_capacit
    249-258): A = [Vn_1 + Id GᵀWꜝG Ψ, -(Vn_1 - Vn) + Id GᵀWꜝH Ψ; Iᵦ HᵀWꜝG, Iᵦ HᵀWꜝH + Iₐ Γ] on the space-time capacity c
    (Δt is inside it), b from T_prev (2M, or NULL for zeros), border rows as BC_border_mono!.  source_n / source_np1 =
    f(C_ω.., t) and f(C_ω.., t+Δt) (M doubles or NULL = 0; the first is read by "CN" only).  pg_solver_initial_solve solves
-   it; pg_solver_get_state(-1) is the new state, the T_prev of the next slab's solver.  pg_solver_step refuses. */
+   it; pg_solver_get_state(-1) is the new state, the T_prev of the next slab's solver.  pg_solver_step refuses.
+   `previous` (or NULL): the previous slab's solver (solved, same mesh), whose state is taken as T_prev -- device to device:
+   the time loop then moves no state over PCIe unless the caller asks for one (pg_solver_get_state).  With both given, the
+   active unknowns of `previous` overwrite T_prev's; the same holds for every moving constructor. */
 int32_t pg_solver_create_moving_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                      const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                      const double* source_n, const double* source_np1, const double* T_prev,
-                                     int32_t scheme, pg_solver** out);
-/* the same, with the state of the previous slab's solver (solved, same mesh) as T_prev -- device to device: the time loop
-   then moves no state over PCIe unless the caller asks for one (pg_solver_get_state) */
-int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
-                                          const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
-                                          const double* source_n, const double* source_np1, pg_solver* previous,
-                                          int32_t scheme, pg_solver** out);
+                                     pg_solver* previous, int32_t scheme, pg_solver** out);
 /* One space-time step of solve_MovingAdvDiffusionUnsteadyMono! (prescribedmotionsolver/advectiondiffusion.jl:15-33
    constructor, 64-129 A, 131-199 b, 201-242 loop): the arguments of pg_solver_create_moving_mono, o = the space-time
    ConvectionOps of c (pg_diffops_set_velocity_spacetime).  A = the moving blocks with - (ΣC + ½K[1]) Ψc and - ½K[1] Ψc in the
@@ -305,12 +302,7 @@ int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const p
 int32_t pg_solver_create_moving_advdiff_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                              const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                              const double* source_n, const double* source_np1, const double* T_prev,
-                                             int32_t scheme, pg_solver** out);
-/* the same with the previous slab's solver as T_prev, device to device (as pg_solver_create_moving_mono_next) */
-int32_t pg_solver_create_moving_advdiff_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
-                                                  const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
-                                                  const double* source_n, const double* source_np1, pg_solver* previous,
-                                                  int32_t scheme, pg_solver** out);
+                                             pg_solver* previous, int32_t scheme, pg_solver** out);
 /* MovingAdvDiffusionUnsteadyDiph + A_/b_diph_unstead_advdiff_moving (prescribedmotionsolver/advectiondiffusion.jl:246-507): one
    slab, the arguments of pg_solver_create_moving_diph with space-time ConvectionOps o1 / o2.  Differs from the moving
    diffusion blocks beyond the convection terms (as mono per phase; CN: - ΣC Tω - ½K[1] Tω - ½K[1] Tγ, no Ψ): the flux row

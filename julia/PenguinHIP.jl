@@ -11,7 +11,7 @@
 # the GPU path cannot take (arbitrary level-set closures) raise instead of being replaced by something else.
 module PenguinHIP
 
-using SparseArrays, StaticArrays, LinearAlgebra
+using SparseArrays, StaticArrays, LinearAlgebra, Libdl
 
 export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace, Ellipsoid, DiffusionOps, Phase,
        Dirichlet, Neumann, Robin, Periodic, ScalarJump, FluxJump, BorderConditions, InterfaceConditions, Solver,
@@ -815,6 +815,20 @@ function ConvectionOps(cap::SpaceTimeCapacity{N}, uₒ::NTuple{3, Vector{Float64
     op
 end
 
+# The moving constructors of the library, one argument list per arity; `sym` names the variant (a computed name cannot stand
+# in ccall's (name, library) tuple, so it is looked up with dlsym).  T_prev comes from the host, `previous` is not used here.
+_create_moving_mono(sym::Symbol, cap, op, desc, borders, D, fn, fn1, Tᵢ, scheme, h) =
+    check(ccall(Libdl.dlsym(Libdl.dlopen(libpg), sym), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                cap.handle, op.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, C_NULL, _scheme(scheme), h))
+_create_moving_diph(sym::Symbol, c1, o1, c2, o2, desc, borders, D1, D2, f1n, f1n1, f2n, f2n1, Tᵢ, scheme, h) =
+    check(ccall(Libdl.dlsym(Libdl.dlopen(libpg), sym), Int32,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                c1.handle, o1.handle, c2.handle, o2.handle, desc, borders, length(borders), D1, D2, f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL,
+                _scheme(scheme), h))
+
 # closures see the space-time centroids padded to three coordinates (build_source / build_g_g on the (N+1)-D capacity)
 _st_coords(C, Ct) = [coords3((c..., Ct[i])) for (i, c) in enumerate(C)]
 function _moving_step!(s::Solver, phase::Phase, bc_b::BorderConditions, bc_i::AbstractBoundary, Δt::Float64, Tᵢ::Vector{Float64},
@@ -833,17 +847,9 @@ function _moving_step!(s::Solver, phase::Phase, bc_b::BorderConditions, bc_i::Ab
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve g D fn fn1 Tᵢ borders begin
         desc = Ref(_interface_desc(bc_i, g))
-        if advdiff          # A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:64-199)
-            check(ccall((:pg_solver_create_moving_advdiff_mono, libpg), Int32,
-                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                         Ptr{Float64}, Int32, Ptr{Ptr{Cvoid}}),
-                        cap.handle, phase.operator.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, _scheme(scheme), h))
-        else
-            check(ccall((:pg_solver_create_moving_mono, libpg), Int32,
-                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                         Ptr{Float64}, Int32, Ptr{Ptr{Cvoid}}),
-                        cap.handle, phase.operator.handle, desc, borders, length(borders), D, fn, fn1, Tᵢ, _scheme(scheme), h))
-        end
+        # advdiff: A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:64-199)
+        _create_moving_mono(advdiff ? :pg_solver_create_moving_advdiff_mono : :pg_solver_create_moving_mono, cap, phase.operator,
+                            desc, borders, D, fn, fn1, Tᵢ, scheme, h)
     end
     s.handle = h[]
     _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, t)
@@ -911,19 +917,9 @@ function _moving_step_diph!(s::Solver, phase1::Phase, phase2::Phase, bc_b::Borde
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve g hh D1 D2 f1n f2n f1n1 f2n1 Tᵢ borders begin
         desc = Ref(_jump_desc(ic, c1, c2, g, hh))
-        if advdiff          # A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:266-507)
-            check(ccall((:pg_solver_create_moving_advdiff_diph, libpg), Int32,
-                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
-                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
-                        c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
-                        f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
-        else
-            check(ccall((:pg_solver_create_moving_diph, libpg), Int32,
-                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
-                         Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
-                        c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
-                        f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
-        end
+        # advdiff: A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:266-507)
+        _create_moving_diph(advdiff ? :pg_solver_create_moving_advdiff_diph : :pg_solver_create_moving_diph, c1, phase1.operator, c2,
+                            phase2.operator, desc, borders, D1, D2, f1n, f1n1, f2n, f2n1, Tᵢ, scheme, h)
     end
     s.handle = h[]
     _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, nothing)   # BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
@@ -1087,11 +1083,8 @@ function _stefan_step_diph!(s::Solver, phase1::Phase, phase2::Phase, bc_b::Borde
     h = Ref{Ptr{Cvoid}}(C_NULL)
     GC.@preserve g hh D1 D2 f1n f2n f1n1 f2n1 Tᵢ borders begin
         desc = Ref(_jump_desc(ic, c1, c2, g, hh))
-        check(ccall((:pg_solver_create_moving_stefan_diph, libpg), Int32,
-                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{pg_jump_desc}, Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64},
-                     Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
-                    c1.handle, phase1.operator.handle, c2.handle, phase2.operator.handle, desc, borders, length(borders), D1, D2,
-                    f1n, f1n1, f2n, f2n1, Tᵢ, C_NULL, _scheme(scheme), h))
+        _create_moving_diph(:pg_solver_create_moving_stefan_diph, c1, phase1.operator, c2, phase2.operator, desc, borders, D1, D2,
+                            f1n, f1n1, f2n, f2n1, Tᵢ, scheme, h)
     end
     s.handle = h[]
     _has_border_functions(bc_b) && _set_border_values!(s, bc_b, mesh, nothing)

@@ -759,39 +759,11 @@ def DiffusionUnsteadyMono(phase: Phase, bc_b: BorderConditions, bc_i, Δt: float
         print("Solver creation:\n- Monophasic problem\n- Unsteady problem\n- Diffusion problem")
     s = Solver("Unsteady", "Monophasic", "Diffusion")
     cap, mesh = phase.capacity, phase.capacity.mesh
-    M = int(np.prod(mesh.ext))
-    s._nunk = 2 * M
-    if Tᵢ is not None:     # None = zeros(2M) without materialising it on the host (multi-GPU sizes)
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (2 * M,):
-            raise ValueError(f"Tᵢ must have length 2*prod(n+1) = {2 * M}")
+    Tᵢ = _unsteady_prelude(s, 2, mesh, Tᵢ, phase=phase, bc_i=bc_i, dt=float(Δt))
+    M = s._ctx["M"]
     sch = "CN" if scheme == "CN" else "BE"   # diffusion.jl:200-206: anything but "CN" is BE
-    # interface condition
-    if isinstance(bc_i, Dirichlet):
-        kind, a, b = L.PG_BC_DIRICHLET, 0.0, 0.0
-    elif isinstance(bc_i, Neumann):
-        kind, a, b = L.PG_BC_NEUMANN, 0.0, 0.0
-    elif isinstance(bc_i, Robin):
-        kind, a, b = L.PG_BC_ROBIN, float(bc_i.α), float(bc_i.β)
-    else:
-        raise TypeError(f"unsupported interface condition {bc_i!r}")
-    s._ctx = dict(phase=phase, bc_i=bc_i, dt=float(Δt), M=M)
-    g_arr = None
-    gval = 0.0
-    if callable(bc_i.value):
-        g = _eval(bc_i.value, cap._cg, float(Δt), 3)      # b(t=0) uses g(0+Δt)  diffusion.jl:249
-        if isinstance(g, float):
-            gval = g
-        else:
-            g_arr = g
-    else:
-        gval = float(bc_i.value)
-    desc = L.pg_bc_desc(kind, a, b, gval, L.dptr(g_arr) if g_arr is not None else None)
-    D = _eval(phase.Diffusion_coeff, cap._cw, None, 3) if callable(phase.Diffusion_coeff) else float(phase.Diffusion_coeff)
-    if isinstance(D, float):
-        D_arr = None if D == 1.0 else np.full(M, D)
-    else:
-        D_arr = D
+    desc, g_keep = _interface_desc(bc_i, cap._cg, float(Δt))      # b(t=0) uses g(0+Δt)  diffusion.jl:249
+    D_arr = _dcoef(phase, M)
     f1 = _eval(phase.source, cap._cw, float(Δt), 3)        # f(0+Δt)
     f_arr = _padded_field(f1, M)
     borders, nb, bvals = _border_descs(bc_b, mesh, 0.0)    # ctor applies borders with t = 0  (:207)
@@ -937,28 +909,11 @@ def DiffusionUnsteadyDiph(phase1: Phase, phase2: Phase, bc_b: BorderConditions, 
         print("Solver creation:\n- Diphasic problem\n- Unsteady problem\n- Diffusion problem")
     s = Solver("Unsteady", "Diphasic", "Diffusion")
     mesh = phase1.capacity.mesh
-    M = int(np.prod(mesh.ext))
-    s._nunk = 4 * M
-    Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-    if Tᵢ.shape != (4 * M,):
-        raise ValueError(f"Tᵢ must have length 4*prod(n+1) = {4 * M}")
-    jump, flux = ic.scalar, ic.flux
-    # g, h are built WITHOUT t (diffusion.jl:397)
-    g = _eval(jump.value, phase1.capacity._cg, None, 3) if callable(jump.value) else float(jump.value)
-    h = _eval(flux.value, phase2.capacity._cg, None, 3) if callable(flux.value) else float(flux.value)
-    g_arr = None if isinstance(g, float) else g
-    h_arr = None if isinstance(h, float) else h
-    desc = L.pg_jump_desc(float(jump.α1), float(jump.α2), g if isinstance(g, float) else 0.0, float(flux.β1),
-                          float(flux.β2), h if isinstance(h, float) else 0.0,
-                          L.dptr(g_arr) if g_arr is not None else None, L.dptr(h_arr) if h_arr is not None else None)
-
-    def dcoef(ph):
-        D = _eval(ph.Diffusion_coeff, ph.capacity._cw, None, 3) if callable(ph.Diffusion_coeff) else float(ph.Diffusion_coeff)
-        if isinstance(D, float):
-            return None if D == 1.0 else np.full(M, D)
-        return D
-
-    D1, D2 = dcoef(phase1), dcoef(phase2)
+    # (Tᵢ = None is not taken here: as an array it fails the length check)
+    Tᵢ = _unsteady_prelude(s, 4, mesh, np.asarray(Tᵢ, dtype=np.float64), dt=float(Δt))
+    M = s._ctx["M"]
+    desc, jump_keep = _jump_desc(ic, phase1, phase2)
+    D1, D2 = _dcoef(phase1, M), _dcoef(phase2, M)
     f1 = _padded_field(_eval(phase1.source, phase1.capacity._cw, float(Δt), 3), M)
     f2 = _padded_field(_eval(phase2.source, phase2.capacity._cw, float(Δt), 3), M)
     borders, nb, bvals = _border_descs(bc_b, mesh, None)   # BC_border_diph! is called without t (:330)
@@ -974,7 +929,6 @@ def DiffusionUnsteadyDiph(phase1: Phase, phase2: Phase, bc_b: BorderConditions, 
                 L.check(L.lib().pg_solver_set_source(s._h, q, L.dptr(f0), None))
     if bvals is not None:
         L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(bvals)))
-    s._ctx = dict(M=M, dt=float(Δt))
     s._ctor_scheme = sch
     return s
 
@@ -1056,6 +1010,35 @@ def _interface_desc(bc_i, cg, t):
     return L.pg_bc_desc(kind, a, b, gval, L.dptr(g_arr) if g_arr is not None else None), g_arr
 
 
+def _jump_desc(ic: InterfaceConditions, phase1: Phase, phase2: Phase):
+    """pg_jump_desc of a diphasic problem: g at C_γ of phase 1, h at C_γ of phase 2, both built WITHOUT t (diffusion.jl:397;
+    the moving solvers: build_g_g(operator, jump, capacity), prescribedmotionsolver/diffusion.jl:423-424).  Returns the
+    evaluated arrays too: the descriptor holds their addresses.  (What _eval returns is a contiguous float64 array already.)"""
+    jump, flux = ic.scalar, ic.flux
+    g = _eval(jump.value, phase1.capacity._cg, None, 3) if callable(jump.value) else float(jump.value)
+    h = _eval(flux.value, phase2.capacity._cg, None, 3) if callable(flux.value) else float(flux.value)
+    g_arr = None if isinstance(g, float) else g
+    h_arr = None if isinstance(h, float) else h
+    desc = L.pg_jump_desc(float(jump.α1), float(jump.α2), g if isinstance(g, float) else 0.0, float(flux.β1),
+                          float(flux.β2), h if isinstance(h, float) else 0.0,
+                          L.dptr(g_arr) if g_arr is not None else None, L.dptr(h_arr) if h_arr is not None else None)
+    return desc, (g_arr, h_arr)
+
+
+def _unsteady_prelude(s: Solver, K: int, mesh: Mesh, Tᵢ: Optional[np.ndarray], **ctx) -> Optional[np.ndarray]:
+    """What every unsteady constructor does first: M = prod(n+1), the unknown count K*M (K = 2 mono, 4 diph), Tᵢ as a
+    contiguous float64 vector of that length (None = zeros(K*M) without materialising it on the host, multi-GPU sizes) and
+    s._ctx (M and what the caller adds)."""
+    M = int(np.prod(mesh.ext))
+    s._nunk = K * M
+    if Tᵢ is not None:
+        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
+        if Tᵢ.shape != (K * M,):
+            raise ValueError(f"Tᵢ must have length {K}*prod(n+1) = {K * M}")
+    s._ctx = dict(M=M, **ctx)
+    return Tᵢ
+
+
 def _dcoef(ph: Phase, M: int):
     D = _eval(ph.Diffusion_coeff, ph.capacity._cw, None, 3) if callable(ph.Diffusion_coeff) else float(ph.Diffusion_coeff)
     if isinstance(D, float):
@@ -1120,14 +1103,8 @@ def DiffusionSteadyDiph(phase1: Phase, phase2: Phase, bc_b: BorderConditions, ic
     mesh = phase1.capacity.mesh
     M = int(np.prod(mesh.ext))
     s._nunk = 4 * M
-    jump, flux = ic.scalar, ic.flux
-    g = _eval(jump.value, phase1.capacity._cg, None, 3) if callable(jump.value) else float(jump.value)
-    h = _eval(flux.value, phase2.capacity._cg, None, 3) if callable(flux.value) else float(flux.value)
-    g_arr = None if isinstance(g, float) else g
-    h_arr = None if isinstance(h, float) else h
+    desc, jump_keep = _jump_desc(ic, phase1, phase2)
     p = lambda a: L.dptr(a) if a is not None else None
-    desc = L.pg_jump_desc(float(jump.α1), float(jump.α2), g if isinstance(g, float) else 0.0, float(flux.β1),
-                          float(flux.β2), h if isinstance(h, float) else 0.0, p(g_arr), p(h_arr))
     D1, D2 = _dcoef(phase1, M), _dcoef(phase2, M)
     f1 = _padded_field(_eval(phase1.source, phase1.capacity._cw, None, 3), M)
     f2 = _padded_field(_eval(phase2.source, phase2.capacity._cw, None, 3), M)

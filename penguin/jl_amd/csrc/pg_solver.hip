@@ -1642,63 +1642,162 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
 
 extern "C" {
 
-static void create_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
-                        int32_t nborders, const double* Dcoef, const double* source, double dt, const double* T0,
-                        int32_t scheme, pg_solver** out) {
-  PG_REQUIRE(c && o && bc_interface && out, "solver constructor: NULL argument");
-  PG_REQUIRE(o->cap == c, "operators were built from a different capacity");
-  PG_REQUIRE(dt > 0.0, "dt must be positive");
+// What a solver constructor is asked to build.  Every pg_solver_create_* below fills one of these, and create_solver is the
+// one place that checks it, fills the pg_solver and assembles.
+struct SolverSpec {
+  const char* entry;                          // the entry point that was called (error texts)
+  int nphase = 1;
+  pg_capacity* cap[2] = {nullptr, nullptr};   // per phase
+  pg_diffops* ops[2] = {nullptr, nullptr};
+  const double* D[2] = {nullptr, nullptr};
+  const double* f_n[2] = {nullptr, nullptr};
+  const double* f_np1[2] = {nullptr, nullptr};
+  const pg_bc_desc* bc_interface = nullptr;   // one phase
+  const pg_jump_desc* ic = nullptr;           // two phases
+  const pg_border_desc* borders = nullptr;
+  int32_t nborders = 0;
+  double dt = 1.0;
+  const double* T0 = nullptr;                 // the initial state on the host (NULL = zeros) ...
+  pg_solver* previous = nullptr;              // ... and / or a solved solver whose state is taken on the device
+  int32_t scheme = PG_SCHEME_BE;              // the caller's BE / CN; not read when ...
+  bool steady = false;                        // ... the steady blocks are asked for
+  bool moving = false, advdiff = false, stefan = false;
+  pg_solver** out = nullptr;
+};
+
+static int32_t create_solver(const SolverSpec& d) {
+  PG_API_BEGIN
+  require_init();
+  const std::string who = std::string(d.entry) + ": ";
+  const bool mono = d.nphase == 1;
+  // one solver per time slab: the stream-ordered allocator, freed blocks are reused without synchronisation (pg_common.h)
+  std::unique_ptr<AsyncAllocScope> pool(d.moving ? new AsyncAllocScope() : nullptr);
+  PG_REQUIRE(d.steady || d.scheme == PG_SCHEME_BE || d.scheme == PG_SCHEME_CN, who + "scheme must be BE or CN");
+  PG_REQUIRE(d.out && (mono ? d.bc_interface != nullptr : d.ic != nullptr), who + "NULL argument");
+  for (int q = 0; q < d.nphase; ++q) {
+    PG_REQUIRE(d.cap[q] && d.ops[q], who + "NULL argument");
+    PG_REQUIRE(d.ops[q]->cap == d.cap[q], who + "operators were built from a different capacity");
+  }
+  if (!mono) {
+    PG_REQUIRE(d.cap[0]->mesh == d.cap[1]->mesh, "Phase capacities must share the same mesh.");
+    PG_REQUIRE(d.cap[0]->slab.p0 == d.cap[1]->slab.p0 && d.cap[0]->slab.p1 == d.cap[1]->slab.p1,
+               who + "phase capacities must share the slab partition");
+  }
+  if (d.moving) {
+    for (int q = 0; q < d.nphase; ++q) {
+      PG_REQUIRE(d.cap[q]->spacetime, who + "every phase needs a space-time capacity (pg_capacity_create_spacetime)");
+      if (d.advdiff)
+        PG_REQUIRE(d.ops[q]->st_velocity, who + "the moving advection-diffusion solver needs the ConvectionOps of its "
+                   "space-time capacity (pg_diffops_set_velocity_spacetime)");
+      else
+        PG_REQUIRE(!d.ops[q]->has_velocity, who + "the moving diffusion solver takes no convection operators");
+    }
+    PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, who + "space-time steps are single-rank");
+    PG_REQUIRE(!d.previous || d.previous->initial_done, who + "the previous slab has not been solved");
+  } else {
+    PG_REQUIRE(d.dt > 0.0, who + "dt must be positive");
+  }
   auto* s = new pg_solver();
   std::unique_ptr<pg_solver> guard(s);
-  s->nphase = 1;
-  s->cap[0] = c;
-  s->ops[0] = o;
-  s->slab = c->slab;
-  s->dt = dt;
-  s->scheme_ctor = scheme;
-  s->bc_i = *bc_interface;
-  if (Dcoef) upload_local(s->Id[0], Dcoef, s->slab);
-  if (source) upload_local(s->f_np1[0], source, s->slab);
-  if (bc_interface->value_array) {
-    upload_local(s->g_np1, bc_interface->value_array, s->slab);
-    upload_local(s->g_n, bc_interface->value_array, s->slab);
+  s->nphase = d.nphase;
+  s->slab = d.cap[0]->slab;
+  s->dt = d.moving ? 1.0 : d.dt;            // moving: Δt is inside the space-time capacities
+  s->moving = d.moving;
+  s->advdiff = d.advdiff;
+  s->stefan = d.stefan;
+  s->scheme_ctor = d.steady ? PG_SCHEME_STEADY : d.scheme;
+  const i64 Ml = s->slab.Mloc();
+  for (int q = 0; q < d.nphase; ++q) {
+    s->cap[q] = d.cap[q];
+    s->ops[q] = d.ops[q];
+    if (d.moving) {
+      s->psi_p[q].alloc(Ml);
+      s->psi_m[q].alloc(Ml);
+      if (d.advdiff) {
+        s->psi_cp[q].alloc(Ml);
+        s->psi_cm[q].alloc(Ml);
+      }
+      hipLaunchKernelGGL(k_psi, dim3(grid_for(Ml, BLOCK)), dim3(BLOCK), 0, ctx().stream, Ml, (int)d.scheme, d.cap[q]->Vt[0].p,
+                         d.cap[q]->Vt[1].p, s->psi_p[q].p, s->psi_m[q].p, s->psi_cp[q].p, s->psi_cm[q].p);
+      PG_HIP(hipGetLastError());
+    }
+    if (d.D[q]) upload_local(s->Id[q], d.D[q], s->slab);
+    if (d.f_np1[q]) upload_local(s->f_np1[q], d.f_np1[q], s->slab);
+    if (d.f_n[q]) upload_local(s->f_n[q], d.f_n[q], s->slab);
   }
-  s->bc_i.value_array = nullptr;
-  setup_common(s, borders, nborders, T0);
-  *out = guard.release();
+  // the descriptor is copied, its arrays go to the device: their host memory dies with the call
+  if (mono) {
+    s->bc_i = *d.bc_interface;
+    if (d.bc_interface->value_array) {
+      upload_local(s->g_np1, d.bc_interface->value_array, s->slab);
+      upload_local(s->g_n, d.bc_interface->value_array, s->slab);
+    }
+    s->bc_i.value_array = nullptr;
+  } else {
+    s->ic = *d.ic;
+    if (d.ic->g_array) upload_local(s->g_arr, d.ic->g_array, s->slab);
+    if (d.ic->h_array) upload_local(s->h_arr, d.ic->h_array, s->slab);
+    s->ic.g_array = s->ic.h_array = nullptr;
+  }
+  s->init_from = d.previous;                // consumed by setup_common after T0: its active unknowns overwrite T0's
+  s->A_ctor.want_units = !d.moving;
+  setup_common(s, d.borders, d.nborders, d.T0);
+  *d.out = guard.release();
+  PG_API_END
+}
+
+static SolverSpec spec_mono(const char* entry, pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                            const pg_border_desc* borders, int32_t nborders, const double* Dcoef, const double* f_n,
+                            const double* f_np1, pg_solver** out) {
+  SolverSpec d;
+  d.entry = entry;
+  d.cap[0] = c; d.ops[0] = o; d.D[0] = Dcoef; d.f_n[0] = f_n; d.f_np1[0] = f_np1;
+  d.bc_interface = bc_interface;
+  d.borders = borders; d.nborders = nborders;
+  d.out = out;
+  return d;
+}
+
+static SolverSpec spec_diph(const char* entry, pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                            const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders, const double* D1,
+                            const double* D2, const double* f1_n, const double* f1_np1, const double* f2_n,
+                            const double* f2_np1, pg_solver** out) {
+  SolverSpec d;
+  d.entry = entry;
+  d.nphase = 2;
+  d.cap[0] = c1; d.ops[0] = o1; d.D[0] = D1; d.f_n[0] = f1_n; d.f_np1[0] = f1_np1;
+  d.cap[1] = c2; d.ops[1] = o2; d.D[1] = D2; d.f_n[1] = f2_n; d.f_np1[1] = f2_np1;
+  d.ic = ic;
+  d.borders = borders; d.nborders = nborders;
+  d.out = out;
+  return d;
 }
 
 int32_t pg_solver_create_unsteady_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                        const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                        const double* source, double dt, const double* T0, int32_t scheme,
                                        pg_solver** out) {
-  PG_API_BEGIN
-  require_init();
-  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
-  create_mono(c, o, bc_interface, borders, nborders, Dcoef, source, dt, T0, scheme, out);
-  PG_API_END
+  SolverSpec d = spec_mono("pg_solver_create_unsteady_mono", c, o, bc_interface, borders, nborders, Dcoef, nullptr, source, out);
+  d.dt = dt; d.T0 = T0; d.scheme = scheme;
+  return create_solver(d);
 }
 
-static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
-                             int32_t nborders, const double* Dcoef, const double* source_n, const double* source_np1,
-                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out, bool advdiff = false);
+int32_t pg_solver_create_steady_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
+                                     const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
+                                     const double* source, pg_solver** out) {
+  SolverSpec d = spec_mono("pg_solver_create_steady_mono", c, o, bc_interface, borders, nborders, Dcoef, nullptr, source, out);
+  d.steady = true;
+  return create_solver(d);
+}
 
 int32_t pg_solver_create_moving_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                      const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                      const double* source_n, const double* source_np1, const double* T_prev,
-                                     int32_t scheme, pg_solver** out) {
-  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, T_prev, nullptr, scheme, out);
-}
-
-int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
-                                          const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
-                                          const double* source_n, const double* source_np1, pg_solver* previous,
-                                          int32_t scheme, pg_solver** out) {
-  if (!previous) {
-    pg::set_last_error("pg_solver_create_moving_mono_next: NULL previous solver");
-    return 1;
-  }
-  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, nullptr, previous, scheme, out);
+                                     pg_solver* previous, int32_t scheme, pg_solver** out) {
+  SolverSpec d = spec_mono("pg_solver_create_moving_mono", c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, out);
+  d.moving = true;
+  d.T0 = T_prev; d.previous = previous; d.scheme = scheme;
+  return create_solver(d);
 }
 
 // MovingAdvDiffusionUnsteadyMono + A_/b_mono_unstead_advdiff_moving of one slab   prescribedmotionsolver/advectiondiffusion.jl:15-33,
@@ -1706,87 +1805,44 @@ int32_t pg_solver_create_moving_mono_next(pg_capacity* c, pg_diffops* o, const p
 int32_t pg_solver_create_moving_advdiff_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
                                              const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
                                              const double* source_n, const double* source_np1, const double* T_prev,
-                                             int32_t scheme, pg_solver** out) {
-  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, T_prev, nullptr, scheme, out, true);
+                                             pg_solver* previous, int32_t scheme, pg_solver** out) {
+  SolverSpec d = spec_mono("pg_solver_create_moving_advdiff_mono", c, o, bc_interface, borders, nborders, Dcoef, source_n,
+                           source_np1, out);
+  d.moving = d.advdiff = true;
+  d.T0 = T_prev; d.previous = previous; d.scheme = scheme;
+  return create_solver(d);
 }
 
-int32_t pg_solver_create_moving_advdiff_mono_next(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
-                                                  const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
-                                                  const double* source_n, const double* source_np1, pg_solver* previous,
-                                                  int32_t scheme, pg_solver** out) {
-  if (!previous) {
-    pg::set_last_error("pg_solver_create_moving_advdiff_mono_next: NULL previous solver");
-    return 1;
-  }
-  return create_moving(c, o, bc_interface, borders, nborders, Dcoef, source_n, source_np1, nullptr, previous, scheme, out, true);
+int32_t pg_solver_create_unsteady_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                       const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                       const double* D1, const double* D2, const double* f1, const double* f2, double dt,
+                                       const double* T0, int32_t scheme, pg_solver** out) {
+  SolverSpec d = spec_diph("pg_solver_create_unsteady_diph", c1, o1, c2, o2, ic, borders, nborders, D1, D2, nullptr, f1, nullptr,
+                           f2, out);
+  d.dt = dt; d.T0 = T0; d.scheme = scheme;
+  return create_solver(d);
 }
 
-static int32_t create_moving(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
-                             int32_t nborders, const double* Dcoef, const double* source_n, const double* source_np1,
-                             const double* T_prev, pg_solver* prev, int32_t scheme, pg_solver** out, bool advdiff) {
-  PG_API_BEGIN
-  require_init();
-  if (prev) PG_REQUIRE(prev->initial_done, "pg_solver_create_moving_mono_next: the previous slab has not been solved");
-  AsyncAllocScope pool;   // one solver per time slab: the stream-ordered allocator (pg_common.h)
-  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
-  PG_REQUIRE(c && o && bc_interface && out, "solver constructor: NULL argument");
-  PG_REQUIRE(o->cap == c, "operators were built from a different capacity");
-  PG_REQUIRE(c->spacetime, "pg_solver_create_moving_mono needs a space-time capacity (pg_capacity_create_spacetime)");
-  if (advdiff)
-    PG_REQUIRE(o->st_velocity, "the moving advection-diffusion solver needs the ConvectionOps of its space-time capacity "
-               "(pg_diffops_set_velocity_spacetime)");
-  else
-    PG_REQUIRE(!o->has_velocity, "the moving diffusion solver takes no convection operators");
-  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "space-time steps are single-rank");
-  auto* s = new pg_solver();
-  std::unique_ptr<pg_solver> guard(s);
-  s->nphase = 1;
-  s->cap[0] = c;
-  s->ops[0] = o;
-  s->slab = c->slab;
-  s->dt = 1.0;            // Δt is inside the space-time capacities
-  s->moving = true;
-  s->advdiff = advdiff;
-  s->scheme_ctor = scheme;
-  s->bc_i = *bc_interface;
-  const i64 Ml = s->slab.Mloc();
-  s->psi_p[0].alloc(Ml);
-  s->psi_m[0].alloc(Ml);
-  if (advdiff) {
-    s->psi_cp[0].alloc(Ml);
-    s->psi_cm[0].alloc(Ml);
-  }
-  hipLaunchKernelGGL(k_psi, dim3(grid_for(Ml, BLOCK)), dim3(BLOCK), 0, ctx().stream, Ml, (int)scheme, c->Vt[0].p, c->Vt[1].p,
-                     s->psi_p[0].p, s->psi_m[0].p, s->psi_cp[0].p, s->psi_cm[0].p);
-  PG_HIP(hipGetLastError());
-  if (Dcoef) upload_local(s->Id[0], Dcoef, s->slab);
-  if (source_np1) upload_local(s->f_np1[0], source_np1, s->slab);
-  if (source_n) upload_local(s->f_n[0], source_n, s->slab);
-  if (bc_interface->value_array) {
-    upload_local(s->g_np1, bc_interface->value_array, s->slab);
-    upload_local(s->g_n, bc_interface->value_array, s->slab);
-  }
-  s->bc_i.value_array = nullptr;
-  s->init_from = prev;
-  s->A_ctor.want_units = false;
-  setup_common(s, borders, nborders, T_prev);
-  *out = guard.release();
-  PG_API_END
+int32_t pg_solver_create_steady_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
+                                     const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
+                                     const double* D1, const double* D2, const double* f1, const double* f2,
+                                     pg_solver** out) {
+  SolverSpec d = spec_diph("pg_solver_create_steady_diph", c1, o1, c2, o2, ic, borders, nborders, D1, D2, nullptr, f1, nullptr, f2,
+                           out);
+  d.steady = true;
+  return create_solver(d);
 }
-
-static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
-                                  const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
-                                  const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
-                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff,
-                                  bool stefan = false);
 
 // MovingDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving of one slab      prescribedmotionsolver/diffusion.jl:272-498
 int32_t pg_solver_create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
                                      const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
                                      const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
                                      const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out) {
-  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
-                            out, false);
+  SolverSpec d = spec_diph("pg_solver_create_moving_diph", c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n,
+                           f2_np1, out);
+  d.moving = true;
+  d.T0 = T_prev; d.previous = previous; d.scheme = scheme;
+  return create_solver(d);
 }
 
 // MovingAdvDiffusionUnsteadyDiph + A_/b_diph_unstead_advdiff_moving of one slab   prescribedmotionsolver/advectiondiffusion.jl:246-507
@@ -1795,8 +1851,11 @@ int32_t pg_solver_create_moving_advdiff_diph(pg_capacity* c1, pg_diffops* o1, pg
                                              const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
                                              const double* f2_n, const double* f2_np1, const double* T_prev,
                                              pg_solver* previous, int32_t scheme, pg_solver** out) {
-  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
-                            out, true);
+  SolverSpec d = spec_diph("pg_solver_create_moving_advdiff_diph", c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1,
+                           f2_n, f2_np1, out);
+  d.moving = d.advdiff = true;
+  d.T0 = T_prev; d.previous = previous; d.scheme = scheme;
+  return create_solver(d);
 }
 
 // MovingLiquidDiffusionUnsteadyDiph + A_/b_diph_unstead_diff_moving_stef of one slab   liquidmotionsolver/diffusion.jl:445-673:
@@ -1806,127 +1865,11 @@ int32_t pg_solver_create_moving_stefan_diph(pg_capacity* c1, pg_diffops* o1, pg_
                                             const double* D1, const double* D2, const double* f1_n, const double* f1_np1,
                                             const double* f2_n, const double* f2_np1, const double* T_prev,
                                             pg_solver* previous, int32_t scheme, pg_solver** out) {
-  return create_moving_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1, f2_n, f2_np1, T_prev, previous, scheme,
-                            out, false, true);
-}
-
-static int32_t create_moving_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
-                                  const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
-                                  const double* f1_n, const double* f1_np1, const double* f2_n, const double* f2_np1,
-                                  const double* T_prev, pg_solver* previous, int32_t scheme, pg_solver** out, bool advdiff,
-                                  bool stefan) {
-  PG_API_BEGIN
-  require_init();
-  if (previous) PG_REQUIRE(previous->initial_done, "pg_solver_create_moving_diph: the previous slab has not been solved");
-  AsyncAllocScope pool;   // one solver per time slab: freed blocks are reused without synchronisation (pg_context.hip)
-  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
-  PG_REQUIRE(c1 && c2 && o1 && o2 && ic && out, "solver constructor: NULL argument");
-  PG_REQUIRE(o1->cap == c1 && o2->cap == c2, "operators were built from a different capacity");
-  PG_REQUIRE(c1->spacetime && c2->spacetime, "pg_solver_create_moving_diph needs space-time capacities (pg_capacity_create_spacetime)");
-  PG_REQUIRE(c1->mesh == c2->mesh, "Phase capacities must share the same mesh.");
-  if (advdiff)
-    PG_REQUIRE(o1->st_velocity && o2->st_velocity, "the moving advection-diffusion solver needs the ConvectionOps of its "
-               "space-time capacities (pg_diffops_set_velocity_spacetime)");
-  else
-    PG_REQUIRE(!o1->has_velocity && !o2->has_velocity, "the moving diffusion solver takes no convection operators");
-  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "space-time steps are single-rank");
-  auto* s = new pg_solver();
-  std::unique_ptr<pg_solver> guard(s);
-  s->nphase = 2;
-  s->cap[0] = c1; s->ops[0] = o1;
-  s->cap[1] = c2; s->ops[1] = o2;
-  s->slab = c1->slab;
-  s->dt = 1.0;            // Δt is inside the space-time capacities
-  s->moving = true;
-  s->advdiff = advdiff;
-  s->stefan = stefan;
-  s->scheme_ctor = scheme;
-  s->ic = *ic;
-  const i64 Ml = s->slab.Mloc();
-  for (int q = 0; q < 2; ++q) {
-    s->psi_p[q].alloc(Ml);
-    s->psi_m[q].alloc(Ml);
-    if (advdiff) {
-      s->psi_cp[q].alloc(Ml);
-      s->psi_cm[q].alloc(Ml);
-    }
-    hipLaunchKernelGGL(k_psi, dim3(grid_for(Ml, BLOCK)), dim3(BLOCK), 0, ctx().stream, Ml, (int)scheme, s->cap[q]->Vt[0].p,
-                       s->cap[q]->Vt[1].p, s->psi_p[q].p, s->psi_m[q].p, s->psi_cp[q].p, s->psi_cm[q].p);
-  }
-  PG_HIP(hipGetLastError());
-  if (D1) upload_local(s->Id[0], D1, s->slab);
-  if (D2) upload_local(s->Id[1], D2, s->slab);
-  if (f1_np1) upload_local(s->f_np1[0], f1_np1, s->slab);
-  if (f2_np1) upload_local(s->f_np1[1], f2_np1, s->slab);
-  if (f1_n) upload_local(s->f_n[0], f1_n, s->slab);
-  if (f2_n) upload_local(s->f_n[1], f2_n, s->slab);
-  if (ic->g_array) upload_local(s->g_arr, ic->g_array, s->slab);
-  if (ic->h_array) upload_local(s->h_arr, ic->h_array, s->slab);
-  s->ic.g_array = s->ic.h_array = nullptr;
-  s->init_from = previous;
-  s->A_ctor.want_units = false;
-  setup_common(s, borders, nborders, T_prev);
-  *out = guard.release();
-  PG_API_END
-}
-
-int32_t pg_solver_create_steady_mono(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface,
-                                     const pg_border_desc* borders, int32_t nborders, const double* Dcoef,
-                                     const double* source, pg_solver** out) {
-  PG_API_BEGIN
-  require_init();
-  create_mono(c, o, bc_interface, borders, nborders, Dcoef, source, 1.0, nullptr, PG_SCHEME_STEADY, out);
-  PG_API_END
-}
-
-static void create_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2, const pg_jump_desc* ic,
-                        const pg_border_desc* borders, int32_t nborders, const double* D1, const double* D2,
-                        const double* f1, const double* f2, double dt, const double* T0, int32_t scheme, pg_solver** out) {
-  PG_REQUIRE(c1 && c2 && o1 && o2 && ic && out, "solver constructor: NULL argument");
-  PG_REQUIRE(c1->mesh == c2->mesh, "Phase capacities must share the same mesh.");
-  PG_REQUIRE(c1->slab.p0 == c2->slab.p0 && c1->slab.p1 == c2->slab.p1, "phase capacities must share the slab partition");
-  PG_REQUIRE(dt > 0.0, "dt must be positive");
-  auto* s = new pg_solver();
-  std::unique_ptr<pg_solver> guard(s);
-  s->nphase = 2;
-  s->cap[0] = c1;
-  s->ops[0] = o1;
-  s->cap[1] = c2;
-  s->ops[1] = o2;
-  s->slab = c1->slab;
-  s->dt = dt;
-  s->scheme_ctor = scheme;
-  s->ic = *ic;
-  if (D1) upload_local(s->Id[0], D1, s->slab);
-  if (D2) upload_local(s->Id[1], D2, s->slab);
-  if (f1) upload_local(s->f_np1[0], f1, s->slab);
-  if (f2) upload_local(s->f_np1[1], f2, s->slab);
-  if (ic->g_array) upload_local(s->g_arr, ic->g_array, s->slab);
-  if (ic->h_array) upload_local(s->h_arr, ic->h_array, s->slab);
-  s->ic.g_array = s->ic.h_array = nullptr;
-  setup_common(s, borders, nborders, T0);
-  *out = guard.release();
-}
-
-int32_t pg_solver_create_unsteady_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
-                                       const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
-                                       const double* D1, const double* D2, const double* f1, const double* f2, double dt,
-                                       const double* T0, int32_t scheme, pg_solver** out) {
-  PG_API_BEGIN
-  require_init();
-  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
-  create_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1, f2, dt, T0, scheme, out);
-  PG_API_END
-}
-
-int32_t pg_solver_create_steady_diph(pg_capacity* c1, pg_diffops* o1, pg_capacity* c2, pg_diffops* o2,
-                                     const pg_jump_desc* ic, const pg_border_desc* borders, int32_t nborders,
-                                     const double* D1, const double* D2, const double* f1, const double* f2,
-                                     pg_solver** out) {
-  PG_API_BEGIN
-  require_init();
-  create_diph(c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1, f2, 1.0, nullptr, PG_SCHEME_STEADY, out);
-  PG_API_END
+  SolverSpec d = spec_diph("pg_solver_create_moving_stefan_diph", c1, o1, c2, o2, ic, borders, nborders, D1, D2, f1_n, f1_np1,
+                           f2_n, f2_np1, out);
+  d.moving = d.stefan = true;
+  d.T0 = T_prev; d.previous = previous; d.scheme = scheme;
+  return create_solver(d);
 }
 
 int32_t pg_solver_destroy(pg_solver* s) {

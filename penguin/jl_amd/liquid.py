@@ -18,7 +18,6 @@ quirks are kept as written; DESIGN.md §11 lists them.  1-D only: the reference'
 argument, so an N ≥ 2 mesh is refused."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
@@ -211,15 +210,6 @@ def _capacity(body, mesh, t0, t1, time_panels, time_order):
                         compute_centroids=True)
 
 
-def _solve(s: api.Solver, opts, what: str, verbose: bool):
-    info = L.pg_step_info()
-    L.check(L.lib().pg_solver_initial_solve(s._h, C.byref(opts), C.byref(info)))
-    api._step_info_check(s, info, what)
-    s._initial_done = True
-    s.ch.append(info)
-    s._newton_solves = getattr(s, "_newton_solves", 0) + 1
-
-
 def _push_state(s: api.Solver, save_states: bool, verbose: bool):
     if save_states:
         s.x = s._fetch_state(-1)
@@ -240,14 +230,8 @@ def MovingLiquidDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Δt: float, 
         print("Solver Creation:\n- Moving problem\n- Non prescibed motion\n- Monophasic problem\n- Unsteady problem\n"
               "- Diffusion problem")
     s = api.Solver("Unsteady", "Monophasic", "Diffusion")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 2 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (2 * M,):
-            raise ValueError(f"Tᵢ must have length 2*prod(n+1) = {2 * M}")
-    s._ctx = dict(phase=phase, bc_i=bc_i, dt=float(Δt), M=M)
-    moving._create_step(s, phase, bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0)
+    Tᵢ = api._unsteady_prelude(s, 2, mesh, Tᵢ, phase=phase, bc_i=bc_i, dt=float(Δt))
+    moving._create_step(s, [phase], bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0, 0.0)
     return s
 
 
@@ -260,7 +244,7 @@ def _newton_mono(s, ph, bc_b, bc, mesh, sch, opts, ρL, max_iter, tol, reltol, l
     terms = None
     while it < max_iter and err > tol and err > reltol * abs(current_xf):
         it += 1
-        _solve(s, opts, f"Newton iteration {it} of the step at t = {t}", verbose)
+        moving._solve_current(s, opts, f"Newton iteration {it} of the step at t = {t}", False, False)
         terms = stefan_terms(s)[0]
         Hn, Hn1 = terms[1], terms[0]
         interface_term = 1 / ρL * terms[2]
@@ -278,14 +262,14 @@ def _newton_mono(s, ph, bc_b, bc, mesh, sch, opts, ρL, max_iter, tol, reltol, l
         cap = _capacity(_front(xf, new_xf, tn, tn1, Δt), mesh, tn, tn1, time_panels, time_order)
         ph = api.Phase(cap, api.DiffusionOps(cap), ph.source, ph.Diffusion_coeff)
         if it < max_iter and err > tol and err > reltol * abs(new_xf):
-            moving._create_step(s, ph, bc_b, bc, float(Δt), None, mesh, sch, t, from_previous=True, t_border=tn1)
+            moving._create_step(s, [ph], bc_b, bc, float(Δt), None, mesh, sch, t, tn1, from_previous=True)
         else:
             # the while test (reltol |new_xf|) ends the loop on a slab that is never solved: s keeps the solved state, and
             # the next step's velocity reads that state through the unsolved slab's operator (:318-330) -- a side solver
             # built from the state, whose terms read the state it was built from
             side = api.Solver("Unsteady", "Monophasic", "Diffusion")
             side._nunk, side._ctx = s._nunk, s._ctx
-            moving._create_step(side, ph, bc_b, bc, float(Δt), s._fetch_state(-1), mesh, sch, t, t_border=tn1)
+            moving._create_step(side, [ph], bc_b, bc, float(Δt), s._fetch_state(-1), mesh, sch, t, tn1)
             terms = stefan_terms(side)[0]
         current_xf = new_xf
     if verbose:
@@ -342,7 +326,7 @@ def solve_MovingLiquidDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, x
             print(f"Time : {t}")
         cap = _capacity(_static(new_xf), mesh, Δt, 2 * Δt, time_panels, time_order)      # SpaceTimeMesh(mesh, [Δt, 2Δt])
         ph = api.Phase(cap, api.DiffusionOps(cap), ph.source, ph.Diffusion_coeff)
-        moving._create_step(s, ph, bc_b, bc, Δt, None, mesh, sch, 0.0, from_previous=True, t_border=t)
+        moving._create_step(s, [ph], bc_b, bc, Δt, None, mesh, sch, 0.0, t, from_previous=True)
         lr_state = init_learning_rate_state(learning_rate_strategy, α, **lr_opts)
         ph, new_xf, terms = _newton_mono(s, ph, bc_b, bc, mesh, sch, opts, ρL, max_iter, tol, reltol, lr_state, t, Δt,
                                          new_xf, False, residuals, k, xf_log, time_panels, time_order, verbose)
@@ -366,14 +350,8 @@ def MovingLiquidDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b
         print("Solver Creation:\n- Moving problem\n- Non prescibed motion\n- Diphasic problem\n- Unsteady problem\n"
               "- Diffusion problem")
     s = api.Solver("Unsteady", "Diphasic", "Diffusion")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 4 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (4 * M,):
-            raise ValueError(f"Tᵢ must have length 4*prod(n+1) = {4 * M}")
-    s._ctx = dict(dt=float(Δt), M=M)
-    moving._create_step_diph(s, phase1, phase2, bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0, stefan=True)
+    Tᵢ = api._unsteady_prelude(s, 4, mesh, Tᵢ, dt=float(Δt))
+    moving._create_step(s, [phase1, phase2], bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0, None, stefan=True)
     return s
 
 
@@ -385,7 +363,7 @@ def _newton_diph(s, ph1, ph2, bc_b, ic, mesh, sch, opts, ρL, max_iter, tol, rel
     current_xf = new_xf = xf
     while it < max_iter and err > tol and err > reltol * abs(current_xf):
         it += 1
-        _solve(s, opts, f"Newton iteration {it} of the step at t = {t}", verbose)
+        moving._solve_current(s, opts, f"Newton iteration {it} of the step at t = {t}", False, False)
         terms = stefan_terms(s)
         Hn, Hn1 = terms[0, 1], terms[0, 0]
         interface_term = 1 / ρL * terms[0, 2] + 1 / ρL * terms[1, 2]
@@ -407,7 +385,7 @@ def _newton_diph(s, ph1, ph2, bc_b, ic, mesh, sch, opts, ρL, max_iter, tol, rel
         c2 = _capacity(_front(xf, new_xf, tn, tn1, Δt, complement=True), mesh, tn, tn1, time_panels, time_order)
         ph1 = api.Phase(c1, api.DiffusionOps(c1), ph1.source, ph1.Diffusion_coeff)
         ph2 = api.Phase(c2, api.DiffusionOps(c2), ph2.source, ph2.Diffusion_coeff)
-        moving._create_step_diph(s, ph1, ph2, bc_b, ic, float(Δt), None, mesh, sch, t, from_previous=True, stefan=True)
+        moving._create_step(s, [ph1, ph2], bc_b, ic, float(Δt), None, mesh, sch, t, None, from_previous=True, stefan=True)
     if verbose:
         conv = err <= tol or err <= reltol * abs(current_xf)
         print(f"{'Converged after' if conv else 'Reached max_iter = ' + str(max_iter) + ' after'} {it} iterations with "
@@ -450,7 +428,7 @@ def solve_MovingLiquidDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, 
         c2 = _capacity(_static(new_xf, complement=True), mesh, Δt, 2 * Δt, time_panels, time_order)
         ph1 = api.Phase(c1, api.DiffusionOps(c1), ph1.source, ph1.Diffusion_coeff)
         ph2 = api.Phase(c2, api.DiffusionOps(c2), ph2.source, ph2.Diffusion_coeff)
-        moving._create_step_diph(s, ph1, ph2, bc_b, ic, Δt, None, mesh, sch, 0.0, from_previous=True, stefan=True)
+        moving._create_step(s, [ph1, ph2], bc_b, ic, Δt, None, mesh, sch, 0.0, None, from_previous=True, stefan=True)
         lr_state = init_learning_rate_state(learning_rate_strategy, α, **lr_opts)
         ph1, ph2, new_xf = _newton_diph(s, ph1, ph2, bc_b, ic, mesh, sch, opts, ρL, max_iter, tol, reltol, lr_state, t, Δt,
                                         new_xf, False, residuals, k, xf_log, time_panels, time_order, verbose)

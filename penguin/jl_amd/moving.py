@@ -219,74 +219,58 @@ def _require_st_convection(phase: api.Phase):
                               "the phase's space-time capacity (got a " + type(op).__name__ + ")")
 
 
-def _create_step(s: api.Solver, phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: Optional[np.ndarray], mesh: api.Mesh, scheme: str,
-                 t: float, from_previous: bool = False, advdiff: bool = False, t_border: Optional[float] = None):
-    """A_/b_mono_unstead_diff_moving + BC_border_mono!(A, b, bc_b, mesh; t) of one slab (diffusion.jl:29-33, 254-258);
-    advdiff: A_/b_mono_unstead_advdiff_moving (advectiondiffusion.jl:24-31, 229-232), the same border rows.
-    t_border: the time of the border rows when it is not b's t (the liquid-motion Newton rebuilds: BC_border_mono!(...; t=tn1))."""
-    cap = phase.capacity
-    if not isinstance(cap, SpaceTimeCapacity):
-        raise PenguinHipError("the moving solver needs a space-time capacity: Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
-    if advdiff:
-        _require_st_convection(phase)
-    if cap.mesh is not mesh and tuple(cap.mesh.dims) != tuple(mesh.dims):
-        raise ValueError("mesh does not match the capacity's space mesh")
+def _create_step(s: api.Solver, phases: Sequence[api.Phase], bc_b, interface, Δt: float, Tᵢ: Optional[np.ndarray], mesh: api.Mesh,
+                 scheme: str, t: float, t_border: Optional[float], from_previous: bool = False, advdiff: bool = False,
+                 stefan: bool = False):
+    """The system of one slab, one phase or two.  One phase, interface = bc_i: A_/b_mono_unstead_diff_moving +
+    BC_border_mono!(A, b, bc_b, mesh; t) (diffusion.jl:29-33, 254-258); advdiff: A_/b_mono_unstead_advdiff_moving
+    (advectiondiffusion.jl:24-31, 229-232), the same border rows.  Two phases, interface = ic: A_/b_diph_unstead_diff_moving +
+    BC_border_diph!(A, b, bc_b, mesh) (diffusion.jl:281-288, 519-523); advdiff: A_/b_diph_unstead_advdiff_moving
+    (advectiondiffusion.jl:255-262, 540-543); stefan: A_/b_diph_unstead_diff_moving_stef (liquidmotionsolver/diffusion.jl:
+    445-651), the same border rows.  t_border: the time of the border rows -- b's t, or tₙ₊₁ in
+    the liquid-motion Newton rebuilds (BC_border_mono!(...; t=tn1)); None: evaluated without t, as BC_border_diph! is called.
+    from_previous: the state of s's present slab stays on the device (`previous`), Tᵢ is not read."""
+    for ph in phases:
+        cap = ph.capacity
+        if not isinstance(cap, SpaceTimeCapacity):
+            raise PenguinHipError("the moving solver needs a space-time capacity in every phase: "
+                                  "Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
+        if cap.mesh is not mesh and tuple(cap.mesh.dims) != tuple(mesh.dims):
+            raise ValueError("mesh does not match the capacity's space mesh")
+        if advdiff:
+            _require_st_convection(ph)
     M = int(np.prod(mesh.ext))
     sch = "CN" if scheme == "CN" else "BE"
-    desc, g_arr = api._interface_desc(bc_i, cap._cg, None)          # build_g_g(operator, bc, capacity): value(C_γ...)  :172
-    D_arr = api._dcoef(phase, M)
-    f1 = api._padded_field(api._eval(phase.source, cap._cw, float(t + Δt), 3), M)    # f(C_ω..., t+Δt)   :171
-    f0 = api._padded_field(api._eval(phase.source, cap._cw, float(t), 3), M) if sch == "CN" else None
-    if sch == "CN" and f1 is not None and f0 is None:
-        f0 = np.zeros(M)
-    borders, nb, bvals = api._border_descs(bc_b, mesh, float(t if t_border is None else t_border))
-    old, new = s._h, C.c_void_p()
-    common = (cap._h, phase.operator._h, C.byref(desc), borders, C.c_int32(nb), L.dptr(D_arr) if D_arr is not None else None,
-              L.dptr(f0) if f0 is not None else None, L.dptr(f1) if f1 is not None else None)
-    lib = L.lib()
-    create = lib.pg_solver_create_moving_advdiff_mono if advdiff else lib.pg_solver_create_moving_mono
-    create_next = lib.pg_solver_create_moving_advdiff_mono_next if advdiff else lib.pg_solver_create_moving_mono_next
-    if from_previous:      # the previous slab's state stays on the device (pg_solver_create_moving_mono_next)
-        L.check(create_next(*common, old, C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
+    # build_g_g(operator, bc / jump, capacity): value(C_γ...) at the space-time interface centroids, no time argument (:172,
+    # :423-424)
+    if len(phases) == 1:
+        desc, keep = api._interface_desc(interface, phases[0].capacity._cg, None)
     else:
-        L.check(create(*common, L.dptr(Tᵢ) if Tᵢ is not None else None, C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
+        desc, keep = api._jump_desc(interface, *phases)
+    Ds, fs = [], []
+    for ph in phases:
+        Ds.append(api._dcoef(ph, M))
+        f1 = api._padded_field(api._eval(ph.source, ph.capacity._cw, float(t + Δt), 3), M)      # f(C_ω..., t+Δt)   :171, :416,418
+        f0 = api._padded_field(api._eval(ph.source, ph.capacity._cw, float(t), 3), M) if sch == "CN" else None
+        if sch == "CN" and f1 is not None and f0 is None:
+            f0 = np.zeros(M)
+        fs += [f0, f1]
+    borders, nb, bvals = api._border_descs(bc_b, mesh, t_border)
+    p = lambda a: L.dptr(a) if a is not None else None
+    kind = "_advdiff" if advdiff else "_stefan" if stefan else ""
+    create = getattr(L.lib(), "pg_solver_create_moving" + kind + ("_mono" if len(phases) == 1 else "_diph"))
+    old, new = s._h, C.c_void_p()
+    L.check(create(*[h for ph in phases for h in (ph.capacity._h, ph.operator._h)], C.byref(desc), borders, C.c_int32(nb),
+                   *map(p, Ds), *map(p, fs), None if from_previous else p(Tᵢ), old if from_previous else None,
+                   C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
     s._h = new
     if old:
         L.check(L.lib().pg_solver_destroy(old))
     if bvals is not None:
         L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(bvals)))
-    s._keep = (cap, phase.operator)      # the device solver reads the capacity: keep it alive as long as the handle
+    # the device solver reads the capacities and operators: keep them alive as long as the handle
+    s._keep = tuple(ph.capacity for ph in phases) + tuple(ph.operator for ph in phases)
     s._initial_done = False
-
-
-def MovingDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh, scheme: str,
-                                verbose: bool = False) -> api.Solver:
-    """MovingDiffusionUnsteadyMono(phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/diffusion.jl:16-35."""
-    if verbose:
-        print("Solver Creation:\n- Moving problem\n- Monophasic problem\n- Unsteady problem\n- Diffusion problem")
-    s = api.Solver("Unsteady", "Monophasic", "Diffusion")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 2 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (2 * M,):
-            raise ValueError(f"Tᵢ must have length 2*prod(n+1) = {2 * M}")
-    s._ctx = dict(phase=phase, bc_i=bc_i, dt=float(Δt), M=M)
-    _create_step(s, phase, bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0)     # t = 0.0 in b and the border rows (:27-33)
-    return s
-
-
-def solve_MovingDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Δt: float, Tₛ: float, Tₑ: float, bc_b, bc,
-                                        mesh: api.Mesh, scheme: str, method="gmres", algorithm=None, geometry_method="VOFI",
-                                        verbose: bool = False, max_steps: Optional[int] = None, time_panels: int = 16,
-                                        time_order: int = 4, save_states: bool = True, **kwargs):
-    """solve_MovingDiffusionUnsteadyMono!(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme; method, ...) --
-    prescribedmotionsolver/diffusion.jl:227-268: the constructor's system first (states[1]); then `while t < Tₑ`:
-    t += Δt, the capacity of the slab [t, t+Δt], new blocks and border rows at t, solve, push.
-    `save_states=False` (not in the reference): the state is handed from slab to slab on the device and only the last one is
-    fetched (`s.x`, `s.states[-1]`); the reference's `push!(s.states, s.x)` costs a device-to-host copy of 2M doubles per slab."""
-    return _solve_mono(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, api.DiffusionOps, False, method, geometry_method,
-                       verbose, max_steps, time_panels, time_order, save_states, kwargs)
 
 
 def _solve_current(s: api.Solver, opts, what: str, save_states: bool, verbose: bool):
@@ -302,158 +286,11 @@ def _solve_current(s: api.Solver, opts, what: str, save_states: bool, verbose: b
         print("Solver Extremum : ", float(info.extremum))
 
 
-def _solve_mono(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, make_ops, advdiff, method, geometry_method, verbose,
-                max_steps, time_panels, time_order, save_states, kwargs):
-    """The slab loop shared by the moving mono solvers (diffusion.jl:227-268, advectiondiffusion.jl:201-242): `make_ops(cap)`
-    builds the slab's operator (DiffusionOps, or ConvectionOps from the same uₒ, uᵧ every slab)."""
-    if s is None or not s._h:
-        raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")
-    opts = api._krylov_opts(method, kwargs)
-    sch = "CN" if scheme == "CN" else "BE"
-    t = float(Tₛ)
-    if verbose:
-        print(f"Time : {t}")
-    _solve_current(s, opts, "the first solve", save_states, verbose)
-    Tᵢ = s.x
-    steps = 0
-    while t < Tₑ:
-        if max_steps is not None and steps >= max_steps:
-            break
-        t += Δt
-        if verbose:
-            print(f"Time : {t}")
-        cap = api.Capacity(body, SpaceTimeMesh(mesh, [t, t + Δt]), time_panels=time_panels, time_order=time_order,
-                           compute_centroids=True, method=geometry_method)
-        ph = api.Phase(cap, make_ops(cap), phase.source, phase.Diffusion_coeff)
-        _create_step(s, ph, bc_b, bc, float(Δt), Tᵢ, mesh, sch, t, from_previous=not save_states, advdiff=advdiff)
-        _solve_current(s, opts, f"the solve of the slab starting at t = {t}", save_states, verbose)
-        Tᵢ = s.x
-        steps += 1
-    if not save_states:
-        s.x = s._fetch_state(-1)
-        s.states.append(s.x)
-    return s
-
-
-def MovingAdvDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh, scheme: str,
-                                   verbose: bool = False) -> api.Solver:
-    """MovingAdvDiffusionUnsteadyMono(phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/advectiondiffusion.jl:15-33.
-    phase.operator = ConvectionOps(capacity, uₒ, uᵧ) of the first slab's space-time capacity (2-D+t).  Convection enters A
-    only in the cells with Vn = 0, Vn_1 ≠ 0 (psip_conv); elsewhere it is explicit, through the previous state in b.  The
-    reference's quirks are kept: no bulk y-advection, ½K_x only (DESIGN.md "Moving advection-diffusion")."""
-    if verbose:
-        print("Solver Creation:\n- Moving problem\n- Monophasic problem\n- Unsteady problem\n- Advection-Diffusion problem")
-    _require_st_convection(phase)
-    s = api.Solver("Unsteady", "Monophasic", "DiffusionAdvection")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 2 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (2 * M,):
-            raise ValueError(f"Tᵢ must have length 2*prod(n+1) = {2 * M}")
-    s._ctx = dict(phase=phase, bc_i=bc_i, dt=float(Δt), M=M)
-    _create_step(s, phase, bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0, advdiff=True)    # t = 0.0 in b and the border rows
-    return s
-
-
-def solve_MovingAdvDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Δt: float, Tₛ: float, Tₑ: float, bc_b, bc,
-                                           mesh: api.Mesh, scheme: str, uₒ, uᵧ, method="gmres", algorithm=None,
-                                           geometry_method="VOFI", verbose: bool = False, max_steps: Optional[int] = None,
-                                           time_panels: int = 16, time_order: int = 4, save_states: bool = True, **kwargs):
-    """solve_MovingAdvDiffusionUnsteadyMono!(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, uₒ, uᵧ; method, ...) --
-    prescribedmotionsolver/advectiondiffusion.jl:201-242: the loop of solve_MovingDiffusionUnsteadyMono_b with
-    ConvectionOps(capacity, uₒ, uᵧ) rebuilt on every slab from the same uₒ, uᵧ (:225-227).  The explicit convection of b is
-    formed on the device from the previous state, also with `save_states=False` (state handed over device to device)."""
-    return _solve_mono(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, lambda cap: api.ConvectionOps(cap, uₒ, uᵧ), True,
-                       method, geometry_method, verbose, max_steps, time_panels, time_order, save_states, kwargs)
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# two phases                                                          prescribedmotionsolver/diffusion.jl:272-535
-# ---------------------------------------------------------------------------------------------------------------------
-def _create_step_diph(s: api.Solver, phase1: api.Phase, phase2: api.Phase, bc_b, ic, Δt: float, Tᵢ: Optional[np.ndarray],
-                      mesh: api.Mesh, scheme: str, t: float, from_previous: bool = False, advdiff: bool = False,
-                      stefan: bool = False):
-    """A_/b_diph_unstead_diff_moving + BC_border_diph!(A, b, bc_b, mesh) of one slab (diffusion.jl:281-288, 519-523);
-    advdiff: A_/b_diph_unstead_advdiff_moving (advectiondiffusion.jl:255-262, 540-543), the same border rows;
-    stefan: A_/b_diph_unstead_diff_moving_stef (liquidmotionsolver/diffusion.jl:445-651), the same border rows."""
-    cap1, cap2 = phase1.capacity, phase2.capacity
-    for cap in (cap1, cap2):
-        if not isinstance(cap, SpaceTimeCapacity):
-            raise PenguinHipError("the moving solver needs space-time capacities: Capacity(body, SpaceTimeMesh(mesh, [t, t+Δt]))")
-        if cap.mesh is not mesh and tuple(cap.mesh.dims) != tuple(mesh.dims):
-            raise ValueError("mesh does not match the capacity's space mesh")
-    if advdiff:
-        _require_st_convection(phase1)
-        _require_st_convection(phase2)
-    M = int(np.prod(mesh.ext))
-    sch = "CN" if scheme == "CN" else "BE"
-    jump, flux = ic.scalar, ic.flux
-    # build_g_g(operator, jump, capacity): value(C_γ...) at the space-time interface centroids, no time argument (:423-424)
-    g = api._eval(jump.value, cap1._cg, None, 3) if callable(jump.value) else float(jump.value)
-    h = api._eval(flux.value, cap2._cg, None, 3) if callable(flux.value) else float(flux.value)
-    g_arr = None if isinstance(g, float) else api._padded_field(g, M)
-    h_arr = None if isinstance(h, float) else api._padded_field(h, M)
-    p = lambda a: L.dptr(a) if a is not None else None
-    desc = L.pg_jump_desc(float(jump.α1), float(jump.α2), g if isinstance(g, float) else 0.0, float(flux.β1), float(flux.β2),
-                          h if isinstance(h, float) else 0.0, p(g_arr), p(h_arr))
-    D1, D2 = api._dcoef(phase1, M), api._dcoef(phase2, M)
-    fs = []
-    for ph in (phase1, phase2):
-        f1 = api._padded_field(api._eval(ph.source, ph.capacity._cw, float(t + Δt), 3), M)       # f(C_ω..., t+Δt)   :416,418
-        f0 = api._padded_field(api._eval(ph.source, ph.capacity._cw, float(t), 3), M) if sch == "CN" else None
-        if sch == "CN" and f1 is not None and f0 is None:
-            f0 = np.zeros(M)
-        fs.append((f0, f1))
-    borders, nb, bvals = api._border_descs(bc_b, mesh, None)       # BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
-    old, new = s._h, C.c_void_p()
-    create = (L.lib().pg_solver_create_moving_advdiff_diph if advdiff else
-              L.lib().pg_solver_create_moving_stefan_diph if stefan else L.lib().pg_solver_create_moving_diph)
-    L.check(create(
-        cap1._h, phase1.operator._h, cap2._h, phase2.operator._h, C.byref(desc), borders, C.c_int32(nb), p(D1), p(D2),
-        p(fs[0][0]), p(fs[0][1]), p(fs[1][0]), p(fs[1][1]),
-        None if from_previous else (L.dptr(Tᵢ) if Tᵢ is not None else None), old if from_previous else None,
-        C.c_int32(L.PG_SCHEME[sch]), C.byref(new)))
-    s._h = new
-    if old:
-        L.check(L.lib().pg_solver_destroy(old))
-    if bvals is not None:
-        L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(bvals)))
-    s._keep = (cap1, cap2, phase1.operator, phase2.operator)
-    s._initial_done = False
-
-
-def MovingDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b, ic, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh,
-                                scheme: str, verbose: bool = False) -> api.Solver:
-    """MovingDiffusionUnsteadyDiph(phase1, phase2, bc_b, ic, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/diffusion.jl:272-290."""
-    if verbose:
-        print("Solver Creation:\n- Moving problem\n- Diphasic problem\n- Unsteady problem\n- Diffusion problem")
-    s = api.Solver("Unsteady", "Diphasic", "Diffusion")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 4 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (4 * M,):
-            raise ValueError(f"Tᵢ must have length 4*prod(n+1) = {4 * M}")
-    s._ctx = dict(dt=float(Δt), M=M)
-    _create_step_diph(s, phase1, phase2, bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0)      # t = 0.0 in b (:282, :285)
-    return s
-
-
-def solve_MovingDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, phase2: api.Phase, body, body_c, Δt: float, Tₑ: float,
-                                        bc_b, ic, mesh: api.Mesh, scheme: str, method="gmres", algorithm=None, verbose: bool = False,
-                                        max_steps: Optional[int] = None, time_panels: int = 16, time_order: int = 4,
-                                        save_states: bool = True, **kwargs):
-    """solve_MovingDiffusionUnsteadyDiph!(s, phase1, phase2, body, body_c, Δt, Tₑ, bc_b, ic, mesh, scheme; method, ...) --
-    prescribedmotionsolver/diffusion.jl:501-535: the constructor's system first (states[1]); then from t = 0.0 `while t < Tₑ`:
-    t += Δt, the two capacities of the slab [t, t+Δt], new blocks and border rows, solve, push."""
-    return _solve_diph(s, phase1, phase2, body, body_c, Δt, 0.0, Tₑ, bc_b, ic, mesh, scheme, api.DiffusionOps, False, method,
-                       verbose, max_steps, time_panels, time_order, save_states, kwargs)   # t = 0.0 (:513)
-
-
-def _solve_diph(s, phase1, phase2, body, body_c, Δt, Tₛ, Tₑ, bc_b, ic, mesh, scheme, make_ops, advdiff, method, verbose,
-                max_steps, time_panels, time_order, save_states, kwargs):
-    """The slab loop shared by the moving diph solvers (diffusion.jl:501-535, advectiondiffusion.jl:510-553)."""
+def _solve_slabs(s, phases, bodies, Δt, Tₛ, Tₑ, bc_b, interface, mesh, scheme, make_ops, advdiff, border_has_t, method,
+                 geometry_method, verbose, max_steps, time_panels, time_order, save_states, kwargs):
+    """The slab loop of the four prescribed-motion solvers (diffusion.jl:227-268, 501-535, advectiondiffusion.jl:201-242,
+    510-553): phases[q] lives in bodies[q]; `make_ops(cap)` builds a slab's operator (DiffusionOps, or ConvectionOps from the
+    same uₒ, uᵧ every slab); border_has_t: BC_border_mono!(...; t) against BC_border_diph!(...) without t."""
     if s is None or not s._h:
         raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")
     opts = api._krylov_opts(method, kwargs)
@@ -471,10 +308,10 @@ def _solve_diph(s, phase1, phase2, body, body_c, Δt, Tₛ, Tₑ, bc_b, ic, mesh
         if verbose:
             print(f"Time : {t}")
         caps = [api.Capacity(b, SpaceTimeMesh(mesh, [t, t + Δt]), time_panels=time_panels, time_order=time_order,
-                             compute_centroids=True) for b in (body, body_c)]
-        ph1 = api.Phase(caps[0], make_ops(caps[0]), phase1.source, phase1.Diffusion_coeff)
-        ph2 = api.Phase(caps[1], make_ops(caps[1]), phase2.source, phase2.Diffusion_coeff)
-        _create_step_diph(s, ph1, ph2, bc_b, ic, float(Δt), Tᵢ, mesh, sch, t, from_previous=not save_states, advdiff=advdiff)
+                             compute_centroids=True, method=geometry_method) for b in bodies]
+        phs = [api.Phase(cap, make_ops(cap), ph.source, ph.Diffusion_coeff) for cap, ph in zip(caps, phases)]
+        _create_step(s, phs, bc_b, interface, float(Δt), Tᵢ, mesh, sch, t, t if border_has_t else None,
+                     from_previous=not save_states, advdiff=advdiff)
         _solve_current(s, opts, f"the solve of the slab starting at t = {t}", save_states, verbose)
         Tᵢ = s.x
         steps += 1
@@ -482,6 +319,84 @@ def _solve_diph(s, phase1, phase2, body, body_c, Δt, Tₛ, Tₑ, bc_b, ic, mesh
         s.x = s._fetch_state(-1)
         s.states.append(s.x)
     return s
+
+
+def MovingDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh, scheme: str,
+                                verbose: bool = False) -> api.Solver:
+    """MovingDiffusionUnsteadyMono(phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/diffusion.jl:16-35."""
+    if verbose:
+        print("Solver Creation:\n- Moving problem\n- Monophasic problem\n- Unsteady problem\n- Diffusion problem")
+    s = api.Solver("Unsteady", "Monophasic", "Diffusion")
+    Tᵢ = api._unsteady_prelude(s, 2, mesh, Tᵢ, phase=phase, bc_i=bc_i, dt=float(Δt))
+    _create_step(s, [phase], bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0, 0.0)     # t = 0.0 in b and the border rows (:27-33)
+    return s
+
+
+def solve_MovingDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Δt: float, Tₛ: float, Tₑ: float, bc_b, bc,
+                                        mesh: api.Mesh, scheme: str, method="gmres", algorithm=None, geometry_method="VOFI",
+                                        verbose: bool = False, max_steps: Optional[int] = None, time_panels: int = 16,
+                                        time_order: int = 4, save_states: bool = True, **kwargs):
+    """solve_MovingDiffusionUnsteadyMono!(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme; method, ...) --
+    prescribedmotionsolver/diffusion.jl:227-268: the constructor's system first (states[1]); then `while t < Tₑ`:
+    t += Δt, the capacity of the slab [t, t+Δt], new blocks and border rows at t, solve, push.
+    `save_states=False` (not in the reference): the state is handed from slab to slab on the device and only the last one is
+    fetched (`s.x`, `s.states[-1]`); the reference's `push!(s.states, s.x)` costs a device-to-host copy of 2M doubles per slab."""
+    return _solve_slabs(s, [phase], [body], Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, api.DiffusionOps, False, True, method,
+                        geometry_method, verbose, max_steps, time_panels, time_order, save_states, kwargs)
+
+
+def MovingAdvDiffusionUnsteadyMono(phase: api.Phase, bc_b, bc_i, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh, scheme: str,
+                                   verbose: bool = False) -> api.Solver:
+    """MovingAdvDiffusionUnsteadyMono(phase, bc_b, bc_i, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/advectiondiffusion.jl:15-33.
+    phase.operator = ConvectionOps(capacity, uₒ, uᵧ) of the first slab's space-time capacity (2-D+t).  Convection enters A
+    only in the cells with Vn = 0, Vn_1 ≠ 0 (psip_conv); elsewhere it is explicit, through the previous state in b.  The
+    reference's quirks are kept: no bulk y-advection, ½K_x only (DESIGN.md "Moving advection-diffusion")."""
+    if verbose:
+        print("Solver Creation:\n- Moving problem\n- Monophasic problem\n- Unsteady problem\n- Advection-Diffusion problem")
+    _require_st_convection(phase)
+    s = api.Solver("Unsteady", "Monophasic", "DiffusionAdvection")
+    Tᵢ = api._unsteady_prelude(s, 2, mesh, Tᵢ, phase=phase, bc_i=bc_i, dt=float(Δt))
+    _create_step(s, [phase], bc_b, bc_i, float(Δt), Tᵢ, mesh, scheme, 0.0, 0.0, advdiff=True)    # t = 0.0 in b and the border rows
+    return s
+
+
+def solve_MovingAdvDiffusionUnsteadyMono_b(s: api.Solver, phase: api.Phase, body, Δt: float, Tₛ: float, Tₑ: float, bc_b, bc,
+                                           mesh: api.Mesh, scheme: str, uₒ, uᵧ, method="gmres", algorithm=None,
+                                           geometry_method="VOFI", verbose: bool = False, max_steps: Optional[int] = None,
+                                           time_panels: int = 16, time_order: int = 4, save_states: bool = True, **kwargs):
+    """solve_MovingAdvDiffusionUnsteadyMono!(s, phase, body, Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, uₒ, uᵧ; method, ...) --
+    prescribedmotionsolver/advectiondiffusion.jl:201-242: the loop of solve_MovingDiffusionUnsteadyMono_b with
+    ConvectionOps(capacity, uₒ, uᵧ) rebuilt on every slab from the same uₒ, uᵧ (:225-227).  The explicit convection of b is
+    formed on the device from the previous state, also with `save_states=False` (state handed over device to device)."""
+    return _solve_slabs(s, [phase], [body], Δt, Tₛ, Tₑ, bc_b, bc, mesh, scheme, lambda cap: api.ConvectionOps(cap, uₒ, uᵧ), True,
+                        True, method, geometry_method, verbose, max_steps, time_panels, time_order, save_states, kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# two phases                                                          prescribedmotionsolver/diffusion.jl:272-535
+# ---------------------------------------------------------------------------------------------------------------------
+def MovingDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b, ic, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh,
+                                scheme: str, verbose: bool = False) -> api.Solver:
+    """MovingDiffusionUnsteadyDiph(phase1, phase2, bc_b, ic, Δt, Tᵢ, mesh, scheme) -- prescribedmotionsolver/diffusion.jl:272-290."""
+    if verbose:
+        print("Solver Creation:\n- Moving problem\n- Diphasic problem\n- Unsteady problem\n- Diffusion problem")
+    s = api.Solver("Unsteady", "Diphasic", "Diffusion")
+    Tᵢ = api._unsteady_prelude(s, 4, mesh, Tᵢ, dt=float(Δt))
+    # t = 0.0 in b (:282, :285); BC_border_diph!(s.A, s.b, bc_b, mesh): no t (:288, :523)
+    _create_step(s, [phase1, phase2], bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0, None)
+    return s
+
+
+def solve_MovingDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, phase2: api.Phase, body, body_c, Δt: float, Tₑ: float,
+                                        bc_b, ic, mesh: api.Mesh, scheme: str, method="gmres", algorithm=None, verbose: bool = False,
+                                        max_steps: Optional[int] = None, time_panels: int = 16, time_order: int = 4,
+                                        save_states: bool = True, **kwargs):
+    """solve_MovingDiffusionUnsteadyDiph!(s, phase1, phase2, body, body_c, Δt, Tₑ, bc_b, ic, mesh, scheme; method, ...) --
+    prescribedmotionsolver/diffusion.jl:501-535: the constructor's system first (states[1]); then from t = 0.0 `while t < Tₑ`:
+    t += Δt, the two capacities of the slab [t, t+Δt], new blocks and border rows, solve, push."""
+    # t = 0.0 (:513); no geometry_method in the diphasic loops: the capacities' default
+    return _solve_slabs(s, [phase1, phase2], [body, body_c], Δt, 0.0, Tₑ, bc_b, ic, mesh, scheme, api.DiffusionOps, False, False,
+                        method, "VOFI", verbose, max_steps, time_panels, time_order, save_states, kwargs)
 
 
 def MovingAdvDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b, ic, Δt: float, Tᵢ: np.ndarray, mesh: api.Mesh,
@@ -493,14 +408,8 @@ def MovingAdvDiffusionUnsteadyDiph(phase1: api.Phase, phase2: api.Phase, bc_b, i
     _require_st_convection(phase1)
     _require_st_convection(phase2)
     s = api.Solver("Unsteady", "Diphasic", "DiffusionAdvection")
-    M = int(np.prod(mesh.ext))
-    s._nunk = 4 * M
-    if Tᵢ is not None:
-        Tᵢ = np.ascontiguousarray(Tᵢ, dtype=np.float64)
-        if Tᵢ.shape != (4 * M,):
-            raise ValueError(f"Tᵢ must have length 4*prod(n+1) = {4 * M}")
-    s._ctx = dict(dt=float(Δt), M=M)
-    _create_step_diph(s, phase1, phase2, bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0, advdiff=True)     # t = 0.0 in b
+    Tᵢ = api._unsteady_prelude(s, 4, mesh, Tᵢ, dt=float(Δt))
+    _create_step(s, [phase1, phase2], bc_b, ic, float(Δt), Tᵢ, mesh, scheme, 0.0, None, advdiff=True)     # t = 0.0 in b
     return s
 
 
@@ -511,6 +420,6 @@ def solve_MovingAdvDiffusionUnsteadyDiph_b(s: api.Solver, phase1: api.Phase, pha
     """solve_MovingAdvDiffusionUnsteadyDiph!(s, phase1, phase2, body, body_c, Δt, Tₛ, Tₑ, bc_b, ic, mesh, scheme, uₒ, uᵧ; ...) --
     prescribedmotionsolver/advectiondiffusion.jl:510-553: from t = Tₛ (the diffusion twin starts at 0.0), both phases'
     ConvectionOps rebuilt per slab from the same uₒ, uᵧ (:535-538), BC_border_diph! without t."""
-    return _solve_diph(s, phase1, phase2, body, body_c, Δt, Tₛ, Tₑ, bc_b, ic, mesh, scheme,
-                       lambda cap: api.ConvectionOps(cap, uₒ, uᵧ), True, method, verbose, max_steps, time_panels, time_order,
-                       save_states, kwargs)
+    return _solve_slabs(s, [phase1, phase2], [body, body_c], Δt, Tₛ, Tₑ, bc_b, ic, mesh, scheme,
+                        lambda cap: api.ConvectionOps(cap, uₒ, uᵧ), True, False, method, "VOFI", verbose, max_steps, time_panels,
+                        time_order, save_states, kwargs)

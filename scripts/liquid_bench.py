@@ -62,7 +62,7 @@ def run(nx, nsteps):
 def timed_split(nx, nsteps):
     """The same run with every part of a Newton iteration timed on the host behind a device synchronisation."""
     parts = {"capacity": 0.0, "assembly": 0.0, "solve": 0.0, "terms": 0.0}
-    orig = (liquid._capacity, moving._create_step, liquid._solve, liquid.stefan_terms)
+    orig = (liquid._capacity, moving._create_step, moving._solve_current, liquid.stefan_terms)
 
     def timed(name, fn):
         def wrap(*a, **k):
@@ -76,12 +76,12 @@ def timed_split(nx, nsteps):
 
     liquid._capacity = timed("capacity", orig[0])
     moving._create_step = timed("assembly", orig[1])
-    liquid._solve = timed("solve", orig[2])
+    moving._solve_current = timed("solve", orig[2])
     liquid.stefan_terms = timed("terms", orig[3])
     try:
         _, nst, iters, _, _ = run(nx, nsteps)
     finally:
-        liquid._capacity, moving._create_step, liquid._solve, liquid.stefan_terms = orig
+        liquid._capacity, moving._create_step, moving._solve_current, liquid.stefan_terms = orig
     return {k: v * 1e3 / iters for k, v in parts.items()}, iters
 
 

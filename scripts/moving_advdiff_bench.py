@@ -50,11 +50,11 @@ def run(advdiff: bool):
             s = (pj.MovingAdvDiffusionUnsteadyMono if advdiff else pj.MovingDiffusionUnsteadyMono)(ph, bcb, bc, dt, Ti, mesh, scheme)
         elif DEVICE_STATE:
             s = prev[0]
-            mv._create_step(s, ph, bcb, bc, dt, None, mesh, scheme, t, from_previous=True, advdiff=advdiff)
+            mv._create_step(s, [ph], bcb, bc, dt, None, mesh, scheme, t, t, from_previous=True, advdiff=advdiff)
         else:
             s = pj.Solver("Unsteady", "Monophasic", "DiffusionAdvection" if advdiff else "Diffusion")
             s._nunk = 2 * M
-            mv._create_step(s, ph, bcb, bc, dt, Ti, mesh, scheme, t, advdiff=advdiff)
+            mv._create_step(s, [ph], bcb, bc, dt, Ti, mesh, scheme, t, t, advdiff=advdiff)
         L.check(L.lib().pg_device_synchronize())
         t2 = time.perf_counter()
         info = L.pg_step_info()

@@ -46,11 +46,11 @@ def slab(t, Ti, first=False):
     if not first:
         if DEVICE_STATE:
             s = prev
-            mv._create_step(s, ph, bcb, bc, dt, None, mesh, scheme, t, from_previous=True)
+            mv._create_step(s, [ph], bcb, bc, dt, None, mesh, scheme, t, t, from_previous=True)
         else:
             s = pj.Solver("Unsteady", "Monophasic", "Diffusion")
             s._nunk = 2 * M
-            mv._create_step(s, ph, bcb, bc, dt, Ti, mesh, scheme, t)
+            mv._create_step(s, [ph], bcb, bc, dt, Ti, mesh, scheme, t, t)
     L.check(L.lib().pg_device_synchronize())
     t2 = time.perf_counter()
     info = L.pg_step_info()

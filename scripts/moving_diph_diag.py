@@ -33,7 +33,7 @@ for k in range(4):
     if s is None:
         s = pj.MovingDiffusionUnsteadyDiph(p1, p2, bcb, ic, dt, T, mesh, scheme)
     else:
-        mv._create_step_diph(s, p1, p2, bcb, ic, dt, T, mesh, scheme, t)
+        mv._create_step(s, [p1, p2], bcb, ic, dt, T, mesh, scheme, t, None)
     A, b, idx = s.system(0)
     k1, k2 = _oracle_cap(c1, omesh, t, t + dt, obody), _oracle_cap(c2, omesh, t, t + dt, obody_c)
     o1, o2 = po.make_diffusion_ops(k1), po.make_diffusion_ops(k2)

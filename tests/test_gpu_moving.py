@@ -218,7 +218,7 @@ def test_moving_interface_similarity_solution(pj, scheme):
 
 
 def test_moving_states_handed_over_on_the_device(pj):
-    """save_states=False: pg_solver_create_moving_mono_next takes the previous slab's state on the device; the last state is the
+    """save_states=False: pg_solver_create_moving_mono takes the previous slab's state on the device (`previous`); the last state is the
     one the host-state loop ends with, bit for bit (same systems, same start vectors)."""
     mesh, omesh, (body, obody), dt = _cases(pj)["2d"]
     M = int(np.prod(omesh.ext))

@@ -1,5 +1,5 @@
 """GPU parity of the prescribed-motion ADVECTION-diffusion solvers (prescribedmotionsolver/advectiondiffusion.jl):
-pg_diffops_set_velocity_spacetime + pg_solver_create_moving_advdiff_{mono,mono_next,diph} through penguin.jl_amd.moving
+pg_diffops_set_velocity_spacetime + pg_solver_create_moving_advdiff_{mono,diph} through penguin.jl_amd.moving
 against the literal restatement in tests/moving_advdiff_oracle.py, fed with the capacities the HIP path computed."""
 import math
 
@@ -268,7 +268,7 @@ def test_moving_advdiff_translating_disc(pj):
 
 
 def test_moving_advdiff_states_handed_over_on_the_device(pj):
-    """save_states=False: pg_solver_create_moving_advdiff_mono_next takes the previous state on the device and forms the explicit
+    """save_states=False: pg_solver_create_moving_advdiff_mono takes the previous state on the device (`previous`) and forms the explicit
     convection of b from it there; the last state equals the host-state loop's bit for bit."""
     mesh, omesh = _mesh(pj)
     body, _ = _disc(pj)
