@@ -13,7 +13,7 @@ module PenguinHIP
 
 using SparseArrays, StaticArrays, LinearAlgebra, Libdl
 
-export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace, Ellipsoid, DiffusionOps, Phase,
+export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace, Ellipsoid, Plane, plane_through, DiffusionOps, Phase,
        Dirichlet, Neumann, Robin, Periodic, ScalarJump, FluxJump, BorderConditions, InterfaceConditions, Solver,
        DiffusionUnsteadyMono, solve_DiffusionUnsteadyMono!, DiffusionUnsteadyDiph, solve_DiffusionUnsteadyDiph!,
        DiffusionSteadyMono, solve_DiffusionSteadyMono!, DiffusionSteadyDiph, solve_DiffusionSteadyDiph!,
@@ -181,6 +181,22 @@ function (s::Ellipsoid{N})(x...) where N
     s.complement ? -f : f
 end
 _abi(s::Ellipsoid{N}, ::Val{N}) where N = (Int32(4), Float64[s.center..., s.semi_axes...], s.complement)
+"f(x) = normal . x - offset, an oblique half space (PG_BODY_PLANE); the normal is used as given, never normalised; complement: -f"
+struct Plane{N} <: TaggedBody
+    normal::NTuple{N, Float64}
+    offset::Float64
+    complement::Bool
+end
+Plane(normal::NTuple{N, Float64}, offset::Float64; complement::Bool=false) where N = Plane{N}(normal, offset, complement)
+"the plane through `point` with the given normal: offset = normal . point"
+plane_through(point::NTuple{N, Float64}, normal::NTuple{N, Float64}; complement::Bool=false) where N =
+    Plane{N}(normal, sum(normal[d] * point[d] for d in 1:N), complement)
+function (s::Plane{N})(x...) where N
+    f = sum(s.normal[d] * x[d] for d in 1:N) - s.offset
+    s.complement ? -f : f
+end
+_abi(s::Plane{N}, ::Val{N}) where N = (Int32(5), Float64[s.normal..., s.offset], s.complement)
+_abi(s::Plane{K}, ::Val{N}) where {K, N} = error("PG_BODY_PLANE: a normal of $(K) components on a $(N)-D mesh")
 
 # ---------------------------------------------------------------------------------- Capacity (src/capacity.jl:25-36)
 abstract type AbstractCapacity end
@@ -235,7 +251,7 @@ end
 # (`Penguin.Capacity(body, penguin_mesh)`, the libvofi path) and hand its arrays over with capacity_from_arrays.
 function Capacity(body::Function, mesh::Mesh{N}; kwargs...) where N
     error("PenguinHIP.Capacity: arbitrary level-set closures cannot run on the GPU; pass a Sphere / MultiSphere / " *
-          "HalfSpace, or build the capacity with Penguin.Capacity and call PenguinHIP.capacity_from_arrays(cap, mesh)")
+          "Ellipsoid / HalfSpace / Plane, or build the capacity with Penguin.Capacity and call PenguinHIP.capacity_from_arrays(cap, mesh)")
 end
 """
     capacity_from_arrays(cap, mesh::Mesh{N})

@@ -165,6 +165,34 @@ class HalfSpace:
                 (L.PG_FLAG_COMPLEMENT if self.complement else 0))
 
 
+class Plane:
+    """Tagged level set f(x) = normal . x - offset (fluid where f < 0), evaluated in-kernel: an oblique half space -- a tilted
+    wall, an inclined two-phase interface -- in 1-D, 2-D and 3-D.  The normal is used as given (it need not have unit
+    length, and is never normalised: f is the function the caller wrote); `complement=True` gives -f.  Every capacity of
+    a cut cell is closed form."""
+
+    def __init__(self, normal: Sequence[float], offset: float, complement: bool = False):
+        self.normal = tuple(float(v) for v in normal)
+        self.offset = float(offset)
+        self.complement = bool(complement)
+
+    @classmethod
+    def through(cls, point: Sequence[float], normal: Sequence[float], complement: bool = False) -> "Plane":
+        """the plane through `point` with the given normal: offset = normal . point"""
+        if len(point) != len(normal):
+            raise ValueError("Plane.through: point and normal must have the same dimension")
+        return cls(normal, sum(float(n) * float(x) for n, x in zip(normal, point)), complement)
+
+    def __call__(self, *x):
+        f = sum(self.normal[d] * np.asarray(x[d]) for d in range(len(self.normal))) - self.offset
+        return -f if self.complement else f
+
+    def _abi(self, N: int):
+        if len(self.normal) != N:
+            raise PenguinHipError(f"PG_BODY_PLANE: a normal of {len(self.normal)} components on a {N}-D mesh")
+        return (L.PG_BODY_PLANE, np.array(list(self.normal) + [self.offset]), (L.PG_FLAG_COMPLEMENT if self.complement else 0))
+
+
 # =============================================================================== Capacity
 
 
@@ -198,8 +226,8 @@ class Capacity:
 
     Fields A, B, W (N-tuples), V, Γ are the DIAGONALS of the reference's diagonal matrices (length
     M = prod(n_d+1)); C_ω, C_γ are (M,N) arrays; cell_types is the Float64 vector.  They are fetched
-    from the GPU on first access.  `body` must be a tagged body (Sphere / MultiSphere); an arbitrary
-    callable needs precomputed arrays: Capacity.from_arrays(...)."""
+    from the GPU on first access.  `body` must be a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace /
+    Plane); an arbitrary callable needs precomputed arrays: Capacity.from_arrays(...)."""
 
     def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True):
         if method not in ("VOFI", "ImplicitIntegration"):
@@ -207,7 +235,7 @@ class Capacity:
         if not hasattr(body, "_abi"):
             raise PenguinHipError(
                 "Capacity: arbitrary level-set callables cannot be evaluated on the GPU; pass a tagged body "
-                "(Sphere, MultiSphere) or use Capacity.from_arrays with precomputed capacities")
+                "(Sphere, MultiSphere, Ellipsoid, HalfSpace, Plane) or use Capacity.from_arrays with precomputed capacities")
         L.init()
         self.mesh = mesh
         self.body = body

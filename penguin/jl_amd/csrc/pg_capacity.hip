@@ -14,6 +14,7 @@
 #include "pg_capacity.h"
 
 #include <algorithm>
+#include <cmath>
 #include <memory>
 
 using namespace pg;
@@ -99,30 +100,38 @@ __global__ void k_classify(GeoView g, BallSet bs, i64 Mloc, double* V, double* G
 // leaves ~3 waves per SIMD walking long serial chains (20 + 43 ms at 512^3).  CUT_LANES lanes share a box instead: each
 // takes one Gauss-Legendre node of every z piece and the partial moments are summed with shuffles.
 constexpr int CUT_LANES = 16;   // = NGL
+// BODY_PLANE has no quadrature to share (closed form): by default it keeps the convention of the other closed-form kind --
+// lane 0 of the group returns the whole result -- and so the launch shape every body uses.  -DPG_PLANE_CUT_LANES=1 launches
+// its two work lists with one lane per item instead; which is faster at 256^3 is not measured yet
+#ifndef PG_PLANE_CUT_LANES
+#define PG_PLANE_CUT_LANES CUT_LANES
+#endif
 
+template <int LANES>
 struct LaneGroup {
   __device__ void operator()(pggeom::Mom& m) const {
 #pragma unroll
-    for (int off = CUT_LANES / 2; off > 0; off >>= 1) {
-      m.vol += __shfl_xor(m.vol, off, CUT_LANES);
-      m.gamma += __shfl_xor(m.gamma, off, CUT_LANES);
+    for (int off = LANES / 2; off > 0; off >>= 1) {
+      m.vol += __shfl_xor(m.vol, off, LANES);
+      m.gamma += __shfl_xor(m.gamma, off, LANES);
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
-        m.m[d] += __shfl_xor(m.m[d], off, CUT_LANES);
-        m.gm[d] += __shfl_xor(m.gm[d], off, CUT_LANES);
+        m.m[d] += __shfl_xor(m.m[d], off, LANES);
+        m.gm[d] += __shfl_xor(m.gm[d], off, LANES);
       }
     }
   }
 };
 
-// K1/K5 (expensive part): CUT_LANES lanes per cut cell of the compacted list.
+// K1/K5 (expensive part): LANES lanes per cut cell of the compacted list.
+template <int LANES>
 __global__ void k_cut_cells(GeoView g, BallSet bs, const int* cut_list, int ncut, double* V, double* G,
                             double* Cw0, double* Cw1, double* Cw2, double* Cg0, double* Cg1, double* Cg2) {
   double* Cw[3] = {Cw0, Cw1, Cw2};
   double* Cg[3] = {Cg0, Cg1, Cg2};
   const i64 gt = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-  const int ql = (int)(gt % CUT_LANES);
-  i64 k = gt / CUT_LANES;
+  const int ql = (int)(gt % LANES);
+  i64 k = gt / LANES;
   const bool live = k < ncut;
   if (!live) k = ncut - 1;          // whole groups stay in the shuffles
   const i64 lc = cut_list[k];
@@ -130,7 +139,7 @@ __global__ void k_cut_cells(GeoView g, BallSet bs, const int* cut_list, int ncut
   decode_cell(g.N, g.ext, g.plane, g.s0, lc, idx);
   double lo[3], hi[3];
   cell_box(g, idx, lo, hi);
-  const BoxMeasure m = box_measure(bs, lo, hi, true, c_gl, ql, CUT_LANES, LaneGroup());
+  const BoxMeasure m = box_measure(bs, lo, hi, true, c_gl, ql, LANES, LaneGroup<LANES>());
   if (!live || ql != 0) return;
   V[lc] = m.vol;
   G[lc] = m.gamma;
@@ -245,13 +254,14 @@ __global__ void k_stagger(GeoView g, BallSet bs, i64 Mloc, const double* ct, con
   }
 }
 
+template <int LANES>
 __global__ void k_stagger_cut(GeoView g, BallSet bs, const int* wlist, int nw, const double* Cw0,
                               const double* Cw1, const double* Cw2, double* W0, double* W1, double* W2) {
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* W[3] = {W0, W1, W2};
   const i64 gt = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-  const int ql = (int)(gt % CUT_LANES);
-  i64 k = gt / CUT_LANES;
+  const int ql = (int)(gt % LANES);
+  i64 k = gt / LANES;
   const bool live = k < nw;
   if (!live) k = nw - 1;
   const i64 lc = wlist[2 * k];
@@ -270,7 +280,7 @@ __global__ void k_stagger_cut(GeoView g, BallSet bs, const int* wlist, int nw, c
   }
   lo[d] = Cw[d][lp];
   hi[d] = Cw[d][ln];
-  const double w = box_measure(bs, lo, hi, false, c_gl, ql, CUT_LANES, LaneGroup()).vol;
+  const double w = box_measure(bs, lo, hi, false, c_gl, ql, LANES, LaneGroup<LANES>()).vol;
   if (live && ql == 0) W[d][lc] = w;
 }
 
@@ -714,6 +724,20 @@ int32_t pg_capacity_create_levelset(pg_mesh* m, int32_t body_kind, const double*
     }
     if (N == 1) bs.r = bs.ax[0];                 // an interval: the 1-D ball
     else bs.kind = BODY_ELLIPSOID;
+  } else if (body_kind == PG_BODY_PLANE) {
+    PG_REQUIRE(nparams == N + 1, "PG_BODY_PLANE expects params = {n_1..n_N, offset}");
+    bs.kind = BODY_PLANE;
+    bs.nballs = 1;
+    bs.r = 1.0;
+    double nn = 0.0;
+    for (int d = 0; d < N; ++d) {
+      PG_REQUIRE(std::isfinite(params[d]), "PG_BODY_PLANE: the normal must be finite");
+      bs.c[0][d] = params[d];                    // as passed: the classification never normalises
+      nn = std::max(nn, std::fabs(params[d]));
+    }
+    PG_REQUIRE(nn > 0.0, "PG_BODY_PLANE: the normal must not be zero");
+    PG_REQUIRE(std::isfinite(params[N]), "PG_BODY_PLANE: the offset must be finite");
+    bs.pos = params[N];
   } else {
     throw Error("pg_capacity_create_levelset: unknown body kind (arbitrary bodies: use pg_capacity_create_from_arrays)");
   }
@@ -761,6 +785,8 @@ int32_t pg_capacity_create_levelset(pg_mesh* m, int32_t body_kind, const double*
   PG_HIP(hipEventCreate(&e1));
   PG_HIP(hipEventRecord(e0, st));
   const int gr = grid_for(Ml, 256, 256 * 16);
+  const bool plane_lanes = bs.kind == BODY_PLANE;
+  const int lanes = plane_lanes ? PG_PLANE_CUT_LANES : CUT_LANES;
   hipLaunchKernelGGL(k_classify, dim3(gr), dim3(256), 0, st, g, bs, Ml, c->V.p, c->G.p, c->ct.p, c->Cw[0].p,
                      c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p, cut_list.p, counters.p);
   PG_HIP(hipGetLastError());
@@ -769,7 +795,8 @@ int32_t pg_capacity_create_levelset(pg_mesh* m, int32_t body_kind, const double*
   const int ncut = hc[0];
   c->n_cut_local = ncut;
   if (ncut > 0) {
-    hipLaunchKernelGGL(k_cut_cells, dim3((unsigned)(((i64)ncut * CUT_LANES + 255) / 256)), dim3(256), 0, st, g, bs, cut_list.p, ncut, c->V.p, c->G.p,
+    auto* const kern = plane_lanes ? k_cut_cells<PG_PLANE_CUT_LANES> : k_cut_cells<CUT_LANES>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((i64)ncut * lanes + 255) / 256)), dim3(256), 0, st, g, bs, cut_list.p, ncut, c->V.p, c->G.p,
                        c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p);
     PG_HIP(hipGetLastError());
   }
@@ -786,7 +813,8 @@ int32_t pg_capacity_create_levelset(pg_mesh* m, int32_t body_kind, const double*
   const int nw = hc[1];
   PG_REQUIRE(nw <= wcap, "internal: staggered-volume work list overflow");
   if (nw > 0) {
-    hipLaunchKernelGGL(k_stagger_cut, dim3((unsigned)(((i64)nw * CUT_LANES + 255) / 256)), dim3(256), 0, st, g, bs, wlist.p, nw, c->Cw[0].p, c->Cw[1].p,
+    auto* const kern = plane_lanes ? k_stagger_cut<PG_PLANE_CUT_LANES> : k_stagger_cut<CUT_LANES>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((i64)nw * lanes + 255) / 256)), dim3(256), 0, st, g, bs, wlist.p, nw, c->Cw[0].p, c->Cw[1].p,
                        c->Cw[2].p, c->W[0].p, c->W[1].p, c->W[2].p);
     PG_HIP(hipGetLastError());
   }

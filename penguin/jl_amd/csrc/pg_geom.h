@@ -12,6 +12,7 @@
 //          the kinks of rho(z) (circle meets a corner / an edge line of the rectangle), with the
 //          substitution z = zm + zh*(3t - t^3)/2 that removes the half-integer endpoint
 //          singularities (libvofi integrates heights between kinks with plain Gauss-Legendre).
+//   oblique half space: closed form in 1/2/3-D, Simpson's rule over exact sections along the dominant axis (see below).
 // Classification (full / empty / cut) uses only +,-,*,compare in a fixed order so that the host
 // oracle reproduces it bit for bit (compile with -ffp-contract=off).
 #pragma once
@@ -34,7 +35,7 @@ struct GLTable {
   double w[NGL];
 };
 
-constexpr int BODY_BALLS = 0, BODY_HALFSPACE = 1, BODY_ELLIPSOID = 2;
+constexpr int BODY_BALLS = 0, BODY_HALFSPACE = 1, BODY_ELLIPSOID = 2, BODY_PLANE = 3;
 
 struct BallSet {
   int N;          // spatial dimension 1..3
@@ -52,6 +53,8 @@ struct BallSet {
   // products of the semi-axes; the interface measure does not (it is not affine invariant) and carries the weight
   // |F^-T n| det F = sqrt(sum_d (n_d prod_(k != d) ax_k)^2) of the unit normal n along the arcs (ellipse_weight)
   double ax[3];
+  // oblique half space (kind == BODY_PLANE): f(x) = n.x - offset, fluid where f < 0, with the normal n in c[0] and the offset in
+  // pos (no field of its own: a BallSet is a by-value kernel argument).  n is used as given, never normalised
 };
 
 struct BoxMeasure {
@@ -355,8 +358,198 @@ PG_HD int hs_interval(const BallSet& bs, double lo, double hi, double& flo, doub
   return PG_CUT;
 }
 
+// ---- oblique half space ------------------------------------------------------------------------------------------
+// Classification: far / near = the largest / smallest value of n.x over the box, accumulated corner term by corner term in
+// dimension order (compare, + and * only: the host reproduces it bit for bit).  FULL if far <= offset, EMPTY if
+// near >= offset.
+PG_HD int plane_box_type(const double* n, double off, const double* lo, const double* hi, int N, double& near, double& far) {
+  far = 0.0; near = 0.0;
+  for (int d = 0; d < N; ++d) {
+    const double a = n[d] * lo[d], b = n[d] * hi[d];
+    far = far + (n[d] > 0.0 ? b : a);
+    near = near + (n[d] > 0.0 ? a : b);
+  }
+  if (far <= off) return PG_FULL;
+  if (near >= off) return PG_EMPTY;
+  return PG_CUT;
+}
+
+// Measures of a CUT box, closed form.  Formulation (deliberately different from the clipping / convex-hull oracle of the
+// tests): the box is described from the corner where n.x is smallest, with the axes turned so that every component of the
+// normal is m_d = |n_d| >= 0: the fluid is the corner piece {y in [0,e]: m.y <= beta}, beta = offset - near > 0.  Its
+// measure and first moments are integrated along the DOMINANT axis a (largest m_a) over the exact sections one dimension
+// down: between the kinks t = (beta - corner sum) / m_a, where the section's plane passes a corner of the section box, the
+// section measure is a polynomial of degree N-1 in t and its moments of degree N <= 3 -- Simpson's rule is exact on every
+// piece.  The only divisions are by m_a >= |n| / sqrt(N) and, in 1-D, by a component whose crossing lies inside the
+// interval: a zero or tiny component only makes a kink fall outside [0, e_a].  When the plane is nearer the opposite
+// corner (far - offset < beta) the SOLID corner piece is measured from there and subtracted from the box, so that the piece
+// that is integrated is never more than half the box (no cancellation in thin cells, and Γ > 0 for every CUT box).
+// The interface projects along a onto the difference of the sections at t = 0 and t = e_a: Γ = |m| / m_a times that
+// measure, C_γ its centroid lifted back onto the plane.
+struct PlanePM {
+  double v, m[3];
+};
+
+// {y in [0, e]: m y <= c}, a closed set: c = 0 keeps the point y = 0 (m > 0) or everything (m = 0)
+PG_HD PlanePM plane_corner1(double m, double e, double c) {
+  PlanePM o;
+  o.v = o.m[0] = o.m[1] = o.m[2] = 0.0;
+  if (!(c >= 0.0)) return o;
+  double x = e;
+  if (m * e > c) x = dmin(c / m, e);    // the crossing lies inside [0, e)
+  o.v = x;
+  o.m[0] = 0.5 * x * x;
+  return o;
+}
+
+// The integration variable is the LEVEL c = beta - m_a t the section's plane is left with, running down from beta (t = 0) to
+// max(beta - m_a e_a, 0): the kinks are then the corner sums themselves, and a section AT a kink is evaluated at that exact
+// level -- a level recomputed as beta - m_a t would be off by an ulp of beta, which a tiny component m_b turns into a
+// relative error ulp / m_b of the section there.
+PG_HD PlanePM plane_corner2(double m0, double m1, double e0, double e1, double beta) {
+  PlanePM o;
+  o.v = o.m[0] = o.m[1] = o.m[2] = 0.0;
+  if (!(beta >= 0.0)) return o;
+  const bool sw = m1 > m0;                      // integrate along a, sections along b
+  const double ma = sw ? m1 : m0, ea = sw ? e1 : e0, mb = sw ? m0 : m1, eb = sw ? e0 : e1;
+  double v = 0.0, pa = 0.0, pb = 0.0;
+  if (!(ma > 0.0)) {                            // no normal left in this section: all of it is fluid
+    v = ea * eb; pa = 0.5 * ea * v; pb = 0.5 * eb * v;
+  } else {
+    const double clo = dmax(beta - ma * ea, 0.0), inv = 1.0 / ma;
+    const double kinks[2] = {mb * eb, clo};
+    double c0 = beta;
+    PlanePM s0 = plane_corner1(mb, eb, c0);
+    for (int k = 0; k < 2; ++k) {
+      const double c2 = dmin(dmax(kinks[k], clo), c0);
+      if (!(c0 > c2)) continue;
+      const double c1 = 0.5 * (c0 + c2), w = (c0 - c2) * inv * (1.0 / 6.0);
+      const double t0 = (beta - c0) * inv, t1 = (beta - c1) * inv, t2 = (beta - c2) * inv;
+      const PlanePM s1 = plane_corner1(mb, eb, c1), s2 = plane_corner1(mb, eb, c2);
+      v += w * (s0.v + 4.0 * s1.v + s2.v);
+      pa += w * (t0 * s0.v + 4.0 * (t1 * s1.v) + t2 * s2.v);
+      pb += w * (s0.m[0] + 4.0 * s1.m[0] + s2.m[0]);
+      c0 = c2; s0 = s2;
+    }
+  }
+  o.v = v;
+  o.m[0] = sw ? pb : pa;
+  o.m[1] = sw ? pa : pb;
+  return o;
+}
+
+PG_HD PlanePM plane_corner3(const double* m, const double* e, double beta) {
+  PlanePM o;
+  o.v = o.m[0] = o.m[1] = o.m[2] = 0.0;
+  if (!(beta >= 0.0)) return o;
+  const int a = (m[1] > m[0]) ? (m[2] > m[1] ? 2 : 1) : (m[2] > m[0] ? 2 : 0);
+  const int b = a == 0 ? 1 : 0, c = a == 2 ? 1 : 2;
+  const double ma = m[a], ea = e[a], mb = m[b], eb = e[b], mc = m[c], ec = e[c];
+  double v = 0.0, pa = 0.0, pb = 0.0, pc = 0.0;
+  if (!(ma > 0.0)) {
+    v = ea * eb * ec; pa = 0.5 * ea * v; pb = 0.5 * eb * v; pc = 0.5 * ec * v;
+  } else {
+    const double sb = mb * eb, sc = mc * ec;
+    const double clo = dmax(beta - ma * ea, 0.0), inv = 1.0 / ma;
+    const double kinks[4] = {sb + sc, dmax(sb, sc), dmin(sb, sc), clo};     // descending
+    double c0 = beta;
+    PlanePM s0 = plane_corner2(mb, mc, eb, ec, c0);
+    for (int k = 0; k < 4; ++k) {
+      const double c2 = dmin(dmax(kinks[k], clo), c0);
+      if (!(c0 > c2)) continue;
+      const double c1 = 0.5 * (c0 + c2), w = (c0 - c2) * inv * (1.0 / 6.0);
+      const double t0 = (beta - c0) * inv, t1 = (beta - c1) * inv, t2 = (beta - c2) * inv;
+      const PlanePM s1 = plane_corner2(mb, mc, eb, ec, c1), s2 = plane_corner2(mb, mc, eb, ec, c2);
+      v += w * (s0.v + 4.0 * s1.v + s2.v);
+      pa += w * (t0 * s0.v + 4.0 * (t1 * s1.v) + t2 * s2.v);
+      pb += w * (s0.m[0] + 4.0 * s1.m[0] + s2.m[0]);
+      pc += w * (s0.m[1] + 4.0 * s1.m[1] + s2.m[1]);
+      c0 = c2; s0 = s2;
+    }
+  }
+  o.v = v;
+  o.m[a] = pa; o.m[b] = pb; o.m[c] = pc;
+  return o;
+}
+
+PG_HD PlanePM plane_corner(const double* m, const double* e, double beta, int N) {
+  if (N == 1) return plane_corner1(m[0], e[0], beta);
+  if (N == 2) return plane_corner2(m[0], m[1], e[0], e[1], beta);
+  return plane_corner3(m, e, beta);
+}
+
+// interface of the corner piece: measure and centroid (corner coordinates)
+PG_HD void plane_corner_interface(const double* m, const double* e, double beta, int N, double& gamma, double* cg) {
+  gamma = 0.0;
+  cg[0] = cg[1] = cg[2] = 0.0;
+  if (N == 1) {
+    gamma = 1.0;
+    cg[0] = dmin(beta / m[0], e[0]);
+    return;
+  }
+  int a = 0;
+  for (int d = 1; d < N; ++d)
+    if (m[d] > m[a]) a = d;
+  double mr[2] = {0.0, 0.0}, er[2] = {1.0, 1.0};
+  int map[2] = {0, 0}, q = 0;
+  double nn = 0.0;
+  for (int d = 0; d < N; ++d) {
+    nn += m[d] * m[d];
+    if (d != a) { mr[q] = m[d]; er[q] = e[d]; map[q] = d; ++q; }
+  }
+  const PlanePM s0 = plane_corner(mr, er, beta, N - 1), s1 = plane_corner(mr, er, beta - m[a] * e[a], N - 1);
+  const double dv = s0.v - s1.v;
+  gamma = sqrt(nn) / m[a] * dv;
+  if (!(dv > 0.0)) { gamma = 0.0; return; }
+  double rest = beta;
+  for (int k = 0; k < N - 1; ++k) {
+    const double ck = (s0.m[k] - s1.m[k]) / dv;
+    cg[map[k]] = ck;
+    rest -= mr[k] * ck;
+  }
+  cg[a] = dmin(dmax(rest / m[a], 0.0), e[a]);
+}
+
+// the normal and offset the measures use: the complement is n -> -n, offset -> -offset
+PG_HD void plane_of(const BallSet& bs, double* n, double& off) {
+  for (int d = 0; d < 3; ++d) n[d] = bs.complement ? -bs.c[0][d] : bs.c[0][d];
+  off = bs.complement ? -bs.pos : bs.pos;
+}
+
+// fluid part of a box that plane_box_type found CUT (near < off < far): measure, and where asked centroid / interface
+PG_HD void plane_cut_measure(const double* n, double off, double near, double far, const double* lo, const double* hi, int N,
+                             double full, bool want_moments, bool want_surface, BoxMeasure& o) {
+  double m[3] = {0.0, 0.0, 0.0}, e[3] = {1.0, 1.0, 1.0};
+  const double beta_near = off - near, beta_far = far - off;
+  const bool from_far = beta_far < beta_near;       // measure the solid corner piece and subtract it from the box
+  const double beta = from_far ? beta_far : beta_near;
+  for (int d = 0; d < N; ++d) { m[d] = fabs(n[d]); e[d] = hi[d] - lo[d]; }
+  const PlanePM p = plane_corner(m, e, beta, N);
+  o.vol = from_far ? full - p.v : p.v;
+  if (want_moments && o.vol > 0.0)
+    for (int d = 0; d < N; ++d) {
+      // corner coordinate y_d runs from lo (n_d > 0) or from hi (n_d <= 0) for the near corner, the other way round for the far one
+      const bool up = (n[d] > 0.0) != from_far;
+      const double mom = from_far ? 0.5 * e[d] * full - p.m[d] : p.m[d];
+      o.cen[d] = up ? lo[d] + mom / o.vol : hi[d] - mom / o.vol;
+    }
+  if (want_surface) {
+    double cg[3];
+    plane_corner_interface(m, e, beta, N, o.gamma, cg);
+    for (int d = 0; d < N; ++d) {
+      const bool up = (n[d] > 0.0) != from_far;
+      o.cg[d] = up ? lo[d] + cg[d] : hi[d] - cg[d];
+    }
+  }
+}
+
 // pick the ball a box can meet (balls are pairwise disjoint): first non-EMPTY, else the last one
 PG_HD int pick_ball(const BallSet& bs, const double* lo, const double* hi, int& type) {
+  if (bs.kind == BODY_PLANE) {
+    double near, far;
+    type = plane_box_type(bs.c[0], bs.pos, lo, hi, bs.N, near, far);
+    return 0;
+  }
   if (bs.kind == BODY_HALFSPACE) {
     double flo, fhi;
     type = hs_interval(bs, lo[bs.axis], hi[bs.axis], flo, fhi, false);
@@ -394,6 +587,18 @@ PG_HD BoxMeasure box_measure(const BallSet& bs, const double* lo, const double* 
   for (int d = 0; d < N; ++d) {
     o.cen[d] = 0.5 * (lo[d] + hi[d]);
     if (!(hi[d] - lo[d] > 0.0)) degenerate = true;
+  }
+  if (bs.kind == BODY_PLANE) {
+    double n[3], off, near, far;
+    plane_of(bs, n, off);
+    o.type = plane_box_type(n, off, lo, hi, N, near, far);
+    if (degenerate || o.type != PG_CUT) {
+      o.vol = (!degenerate && o.type == PG_FULL) ? prod_ext(lo, hi, N, -1) : 0.0;
+      return o;
+    }
+    // closed form: lane 0 of a cooperating group holds all of it (its callers store from lane 0 only), the others nothing
+    if (qlane == 0) plane_cut_measure(n, off, near, far, lo, hi, N, prod_ext(lo, hi, N, -1), true, want_surface, o);
+    return o;
   }
   int t;
   const int s = pick_ball(bs, lo, hi, t);
@@ -470,6 +675,27 @@ PG_HD double section_measure(const BallSet& bs, int d, double s, const double* l
   double plo[3], phi[3];
   for (int k = 0; k < N; ++k) { plo[k] = lo[k]; phi[k] = hi[k]; }
   plo[d] = s; phi[d] = s;
+  if (bs.kind == BODY_PLANE) {
+    // a point (N = 1: fluid iff f <= 0), or the box of the other N - 1 dimensions cut by the plane
+    // sum_(k != d) n_k x_k <= offset - n_d s: the same corner-piece primitive one dimension down.  The type comes from the
+    // N-D rule on the flattened box, so that the faces of a FULL (EMPTY) cell are full (empty) by the test that classified it
+    double n[3], off, near, far;
+    plane_of(bs, n, off);
+    const int t = plane_box_type(n, off, plo, phi, N, near, far);
+    if (N == 1) return t == PG_FULL ? 1.0 : 0.0;
+    const double full = full_measure >= 0.0 ? full_measure : prod_ext(lo, hi, N, d);
+    if (t != PG_CUT) return t == PG_FULL ? full : 0.0;
+    double nr[2] = {0.0, 0.0}, rlo[2] = {0.0, 0.0}, rhi[2] = {1.0, 1.0};
+    int q = 0;
+    for (int k = 0; k < N; ++k)
+      if (k != d) { nr[q] = n[k]; rlo[q] = lo[k]; rhi[q] = hi[k]; ++q; }
+    const double offr = off - n[d] * s;
+    const int tr = plane_box_type(nr, offr, rlo, rhi, N - 1, near, far);
+    if (tr != PG_CUT) return tr == PG_FULL ? full : 0.0;      // (rounding of offset - n_d s: the section is full / empty to 1 ulp)
+    BoxMeasure o;
+    plane_cut_measure(nr, offr, near, far, rlo, rhi, N - 1, full, false, false, o);
+    return o.vol;
+  }
   int t;
   const int sb = pick_ball(bs, plo, phi, t);
   if (bs.kind == BODY_HALFSPACE) {
