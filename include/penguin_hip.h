@@ -34,6 +34,7 @@ typedef struct pg_mesh pg_mesh;         /* Penguin.Mesh{N}            src/mesh.j
 typedef struct pg_capacity pg_capacity; /* Penguin.Capacity{N}        src/capacity.jl:25-36    */
 typedef struct pg_diffops pg_diffops;   /* Penguin.DiffusionOps{N}    src/operators.jl:49-55   */
 typedef struct pg_solver pg_solver;     /* Penguin.Solver             src/solver.jl:33-42      */
+typedef struct pg_streamvort pg_streamvort; /* Penguin.StreamVorticity{2} src/solver/streamfunction_vorticity.jl:37-54 */
 
 /* ---- enums --------------------------------------------------------------------------- */
 enum { PG_BODY_BALL = 1, PG_BODY_MULTIBALL = 2, PG_BODY_HALFSPACE = 3, PG_BODY_ELLIPSOID = 4, PG_BODY_PLANE = 5 }; /* closed-form level sets evaluated in-kernel */
@@ -52,6 +53,7 @@ enum { PG_KEY_LEFT = 0 /* dim2 = 1 */, PG_KEY_RIGHT = 1 /* dim2 = n2 */, PG_KEY_
        PG_KEY_TOP = 3 /* dim1 = n1 */, PG_KEY_BACKWARD = 4 /* dim3 = 1 */, PG_KEY_FORWARD = 5 /* dim3 = n3 */ };
 enum { PG_SCHEME_BE = 0, PG_SCHEME_CN = 1,                   /* "BE" / "CN" strings of the reference */
        PG_SCHEME_STEADY = 2 };                                /* internal: the steady constructors */
+enum { PG_SV_PSI = 0, PG_SV_OMEGA = 1, PG_SV_U = 2, PG_SV_V = 3 };   /* fields / systems of a pg_streamvort */
 enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2 };   /* IterativeSolvers methods kept:
    bicgstab (also serves `\` and bicgstabl), cg, gmres (solve_system!'s default, src/solver.jl:158) */
 
@@ -152,6 +154,22 @@ typedef struct {
   int64_t loop_is_compact;/* 1: the warm loop of this system iterates on the compact system (rows alone on their diagonal
                              solved in the right-hand-side pass, pg_reduce.hip) -- on several ranks with halos too     */
 } pg_system_info;
+
+typedef struct {
+  int64_t steps;            /* steps executed by this call                                                  */
+  int64_t psi_iters;        /* Krylov iterations of the stream-function (Poisson) solves                    */
+  int64_t omega_iters;      /* ... of the vorticity solves                                                  */
+  int64_t psi_products;     /* products with the system matrix inside the Poisson solves                    */
+  int64_t omega_products;   /* ... inside the vorticity solves                                              */
+  int64_t unconverged;      /* solves (of either system) that ended without meeting the tolerance           */
+  double worst_relres;      /* max over the call's solves of ||r|| / ||b|| at exit                          */
+  double t_final;
+  double total_ms;          /* wall time of the call, and its split (the device is waited for at each boundary): */
+  double psi_ms;            /* right-hand side from ω and the Poisson solve                                 */
+  double velocity_ms;       /* u, v from ψ and the convection operators                                     */
+  double build_ms;          /* construction of the step's vorticity solver (numbering, assembly, b)         */
+  double omega_ms;          /* the vorticity solve, the hand-over of its state, the saved state             */
+} pg_streamvort_run_info;
 
 /* ---- library / device -------------------------------------------------------------------- */
 int32_t pg_last_error(char* buf, size_t n);
@@ -333,6 +351,49 @@ int32_t pg_solver_create_moving_stefan_diph(pg_capacity* c1, pg_diffops* o1, pg_
    not a space-time diffusion slab, several ranks and N ≠ 1. */
 int32_t pg_solver_stefan_terms(const pg_solver* s, double* out);
 int32_t pg_solver_destroy(pg_solver* s);
+
+/* ---- StreamVorticity                replaces src/solver/streamfunction_vorticity.jl (2-D incompressible flow: ∇²ψ = -ω,
+   u = ∂ψ/∂y, v = -∂ψ/∂x, ω advected and diffused with (u, v)).  One rank, N = 2.  Both states, the velocity and the convection
+   operators stay on the device from step to step; the host sees them when it asks (pg_streamvort_get). */
+/* StreamVorticity(capacity, ν, Δt; bc_stream, bc_vorticity, bc_stream_border, bc_vorticity_border, ψ0, ω0), :73-98 with
+   assemble_laplacian :105-117 (the steady diffusion blocks, D = 1): o = DiffusionOps(c) WITHOUT a velocity; nu: M values
+   ν(C_ω); psi0 / omega0: 2M doubles or NULL (zeros).  states[0] = (0, ψ0, ω0).  Refuses N ≠ 2 and several ranks. */
+int32_t pg_streamvort_create(pg_capacity* c, pg_diffops* o, const double* nu, double dt, const pg_bc_desc* bc_stream,
+                             const pg_bc_desc* bc_vorticity, const pg_border_desc* borders_stream, int32_t nborders_stream,
+                             const pg_border_desc* borders_vorticity, int32_t nborders_vorticity, const double* psi0,
+                             const double* omega0, pg_streamvort** out);
+int32_t pg_streamvort_destroy(pg_streamvort* sv);
+/* `solver.ω = ...` after construction (test/solver/stream_vorticity_test.jl:30): 2M doubles; the next step starts from it */
+int32_t pg_streamvort_set_omega(pg_streamvort* sv, const double* omega);
+/* data of time-dependent closures, evaluated by the host at the reference's points: the vorticity source at t and t + Δt
+   (:228-229; NULL keeps what is there), interface values of ψ (which = PG_SV_PSI: g(C_γ, t), :134, only g_np1 is read) or of
+   ω (PG_SV_OMEGA: g at t and t + Δt), border values of either system (mesh border order; BC_border_mono! is called without
+   t, :198, :231) */
+int32_t pg_streamvort_set_source(pg_streamvort* sv, const double* f_n /*M*/, const double* f_np1 /*M*/);
+int32_t pg_streamvort_set_interface_values(pg_streamvort* sv, int32_t which, const double* g_n /*M*/, const double* g_np1 /*M*/);
+int32_t pg_streamvort_set_border_values(pg_streamvort* sv, int32_t which, const double* values /*nb*/);
+/* solve_StreamVorticity! (:273-275) = _solve_streamfunction! (:191-206): b = [-V ωω; Γ g], border rows, ψ = Aψ⁻¹ b (from
+   the second solve on started from the previous ψ), then update_velocity! (:146-159): u = (∇ψ)_y, v = -(∇ψ)_x */
+int32_t pg_streamvort_solve_stream(pg_streamvort* sv, const pg_krylov_opts* opts, pg_step_info* info);
+/* step_StreamVorticity! (:282-284) = _step! (:216-242): the above, ConvectionOps(capacity, (u, v), [u; v]) (:167-182), the
+   unsteady advection-diffusion system of ω with D = ν (the D that the call at :228 leaves out: read by "CN" only), its
+   solve, time += Δt, push!(states, (time, ψ, ω)) */
+int32_t pg_streamvort_step(pg_streamvort* sv, int32_t scheme, const pg_krylov_opts* opts, pg_step_info* info_psi,
+                           pg_step_info* info_omega);
+/* run_StreamVorticity! (:291-293) with constant-in-time data: `steps` steps; every save_every-th state of the call is kept
+   (save_every <= 0: none) */
+int32_t pg_streamvort_run(pg_streamvort* sv, int64_t steps, int32_t scheme, const pg_krylov_opts* opts, int32_t save_every,
+                          pg_streamvort_run_info* info);
+/* field = PG_SV_PSI / PG_SV_OMEGA: len = 2M, state_index < 0: the current s.ψ / s.ω, else states[state_index];
+   PG_SV_U / PG_SV_V: len = M, the current s.velocity (state_index < 0 only) */
+int32_t pg_streamvort_get(const pg_streamvort* sv, int32_t field, int64_t state_index, double* out, int64_t len);
+int32_t pg_streamvort_num_states(const pg_streamvort* sv, int64_t* out);
+/* s.time (state_index < 0) or states[state_index].time */
+int32_t pg_streamvort_time(const pg_streamvort* sv, int64_t state_index, double* out);
+/* the solver of the last Poisson solve (PG_SV_PSI) or of the last vorticity step (PG_SV_OMEGA; NULL before the first step),
+   BORROWED: for pg_solver_get_system_csr / pg_solver_system_info / pg_solver_get_state; never destroy it, and do not keep
+   it across a step (the vorticity solver is replaced by every step) */
+int32_t pg_streamvort_solver(pg_streamvort* sv, int32_t which, pg_solver** borrowed);
 
 /* per-step data for time-dependent closures; the host evaluates them at the reference's points and
    times (C_omega / C_gamma / mesh.centers; t+Δt -- diffusion.jl:248-249) and passes arrays.

@@ -25,6 +25,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
        MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info,
+       StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
        ∇, ∇₋, gmres, bicgstabl, cg
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
@@ -78,6 +79,12 @@ mutable struct pg_run_info
     spmv_lean_ms_total::Float64; spmv_lean_launches::Int64; poly_degree::Int64; half_exits::Int64; poly_xspace::Int64
     products::Int64; guess_states_read::Int64
     pg_run_info() = new(0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0, 0.0, 0, 0, 0, 0, 0, 0)
+end
+mutable struct pg_streamvort_run_info
+    steps::Int64; psi_iters::Int64; omega_iters::Int64; psi_products::Int64; omega_products::Int64; unconverged::Int64
+    worst_relres::Float64; t_final::Float64; total_ms::Float64; psi_ms::Float64; velocity_ms::Float64; build_ms::Float64
+    omega_ms::Float64
+    pg_streamvort_run_info() = new(0, 0, 0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
 end
 # kwargs... of solve_system! (src/solver.jl:158-188) -> the options of the device Krylov solve.  reltol defaults to 1e-12,
 # not IterativeSolvers' sqrt(eps): the parity target is the direct-solve path; warm_start and precond are not in the
@@ -1231,6 +1238,183 @@ function solve_MovingLiquidDiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phas
         k += 1
     end
     return s, residuals, xf_log
+end
+
+# ---------------------------------------------------------------------------------- StreamVorticity
+# src/solver/streamfunction_vorticity.jl: ∇²ψ = -ω, u = ∂ψ/∂y, v = -∂ψ/∂x, ω advected and diffused with (u, v).  ψ, ω, the
+# velocity and the convection operators stay on the device between steps (pg_streamvort); the fields below are refreshed
+# after every call.  Kept as the reference has them: the ψ of a state is solved from the ω of the state before (:222, :239);
+# uᵧ = [u; v] (:176-179); border values without a time (:198, :231).  The reference's call at :228 leaves the D of
+# b_mono_unstead_advdiff out (a MethodError); D = ν runs here -- never read under "BE", the explicit diffusion under "CN".
+mutable struct StreamVorticity{N}
+    capacity::Capacity{N}
+    operator::DiffusionOps{N}
+    ν::Union{Float64, Function}
+    Δt::Float64
+    bc_stream::AbstractBoundary
+    bc_vorticity::AbstractBoundary
+    bc_stream_border::BorderConditions
+    bc_vorticity_border::BorderConditions
+    ψ::Vector{Float64}
+    ω::Vector{Float64}
+    velocity::NTuple{N, Vector{Float64}}
+    source::Function
+    time::Float64
+    states::Vector{NamedTuple}
+    Aψ::Union{Nothing, SparseMatrixCSC{Float64, Int}}     # (not exported from the device: the Poisson system is pg_streamvort_solver(0))
+    last_convection::Union{Nothing, ConvectionOps{N}}
+    handle::Ptr{Cvoid}
+    ω_device::Vector{Float64}                              # the ω the library holds (s.ω may be assigned or broadcast into)
+    nstates_device::Int
+    sent::Dict{Any,Any}
+end
+
+function StreamVorticity(capacity::Capacity{2}, ν, Δt;
+                         bc_stream::AbstractBoundary = Dirichlet(0.0),
+                         bc_vorticity::AbstractBoundary = Dirichlet(0.0),
+                         bc_stream_border::BorderConditions = BorderConditions(Dict{Symbol,AbstractBoundary}()),
+                         bc_vorticity_border::BorderConditions = BorderConditions(Dict{Symbol,AbstractBoundary}()),
+                         ψ0::Union{Nothing,Vector{Float64}} = nothing,
+                         ω0::Union{Nothing,Vector{Float64}} = nothing,
+                         source::Function = (args...)->0.0)
+    operator = DiffusionOps(capacity)
+    n = prod(operator.size)
+    ψ_init = isnothing(ψ0) ? zeros(2n) : copy(ψ0)
+    ω_init = isnothing(ω0) ? zeros(2n) : copy(ω0)
+    nu = ν isa Function ? evalf0(ν, capacity.C_ω) : fill(Float64(ν), n)                     # build_I_D
+    gs = bc_stream.value isa Function ? evalf(bc_stream.value, capacity.C_γ, 0.0) : Float64[]
+    gw = bc_vorticity.value isa Function ? evalf(bc_vorticity.value, capacity.C_γ, Float64(Δt)) : Float64[]
+    bs, bw = _border_descs(bc_stream_border), _border_descs(bc_vorticity_border)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve nu gs gw bs bw ψ_init ω_init begin
+        ds, dw = Ref(_interface_desc(bc_stream, gs)), Ref(_interface_desc(bc_vorticity, gw))
+        check(ccall((:pg_streamvort_create, libpg), Int32,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}, Float64, Ptr{pg_bc_desc}, Ptr{pg_bc_desc}, Ptr{pg_border_desc}, Int32,
+                     Ptr{pg_border_desc}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                    capacity.handle, operator.handle, nu, Float64(Δt), ds, dw, bs, length(bs), bw, length(bw), ψ_init, ω_init, h))
+    end
+    s = StreamVorticity{2}(capacity, operator, ν, Float64(Δt), bc_stream, bc_vorticity, bc_stream_border, bc_vorticity_border,
+                           ψ_init, ω_init, (zeros(n), zeros(n)), source, 0.0,
+                           NamedTuple[(time = 0.0, ψ = copy(ψ_init), ω = copy(ω_init))], nothing, nothing, h[], copy(ω_init), 1,
+                           Dict{Any,Any}())
+    finalizer(x -> ccall((:pg_streamvort_destroy, libpg), Int32, (Ptr{Cvoid},), x.handle), s)
+    _has_border_functions(bc_stream_border) &&
+        check(ccall((:pg_streamvort_set_border_values, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, 0,
+                    _border_values(bc_stream_border, capacity.mesh, nothing)))
+    _has_border_functions(bc_vorticity_border) &&
+        check(ccall((:pg_streamvort_set_border_values, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), s.handle, 1,
+                    _border_values(bc_vorticity_border, capacity.mesh, nothing)))
+    s
+end
+
+function _sv_get(s::StreamVorticity, field::Integer, index::Integer, len::Integer)
+    out = zeros(len)
+    check(ccall((:pg_streamvort_get, libpg), Int32, (Ptr{Cvoid}, Int32, Int64, Ptr{Float64}, Int64), s.handle, field, index, out, len))
+    out
+end
+# what the library needs before a solve: the ω the caller may have assigned, and the data of the closures at s.time
+function _sv_push!(s::StreamVorticity)
+    n = prod(s.operator.size)
+    if s.ω != s.ω_device
+        check(ccall((:pg_streamvort_set_omega, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}), s.handle, s.ω))
+        s.ω_device = copy(s.ω)
+    end
+    t, cap = s.time, s.capacity
+    fn, fn1 = evalf(s.source, cap.C_ω, t), evalf(s.source, cap.C_ω, t + s.Δt)
+    if _changed!(s.sent, :f, fn, fn1) && (haskey(s.sent, :f_sent) || any(!iszero, fn) || any(!iszero, fn1))
+        check(ccall((:pg_streamvort_set_source, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, fn, fn1))
+        s.sent[:f_sent] = (true,)
+    end
+    if s.bc_stream.value isa Function
+        g = evalf(s.bc_stream.value, cap.C_γ, t)
+        _changed!(s.sent, :gs, g) &&
+            check(ccall((:pg_streamvort_set_interface_values, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}),
+                        s.handle, 0, Ptr{Float64}(C_NULL), g))
+    end
+    if s.bc_vorticity.value isa Function
+        g0, g1 = evalf(s.bc_vorticity.value, cap.C_γ, t), evalf(s.bc_vorticity.value, cap.C_γ, t + s.Δt)
+        _changed!(s.sent, :gw, g0, g1) &&
+            check(ccall((:pg_streamvort_set_interface_values, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}),
+                        s.handle, 1, g0, g1))
+    end
+    nothing
+end
+# the fields after a call: ψ, ω, velocity, time and the states the library has added
+function _sv_pull!(s::StreamVorticity)
+    n = prod(s.operator.size)
+    s.ψ, s.ω = _sv_get(s, 0, -1, 2n), _sv_get(s, 1, -1, 2n)
+    s.ω_device = copy(s.ω)
+    s.velocity = (_sv_get(s, 2, -1, n), _sv_get(s, 3, -1, n))
+    s.last_convection = nothing
+    t = Ref{Float64}(0.0)
+    check(ccall((:pg_streamvort_time, libpg), Int32, (Ptr{Cvoid}, Int64, Ref{Float64}), s.handle, -1, t))
+    s.time = t[]
+    ns = Ref{Int64}(0)
+    check(ccall((:pg_streamvort_num_states, libpg), Int32, (Ptr{Cvoid}, Ref{Int64}), s.handle, ns))
+    for k in s.nstates_device:(ns[] - 1)
+        check(ccall((:pg_streamvort_time, libpg), Int32, (Ptr{Cvoid}, Int64, Ref{Float64}), s.handle, k, t))
+        push!(s.states, (time = t[], ψ = _sv_get(s, 0, k, 2n), ω = _sv_get(s, 1, k, 2n)))
+    end
+    s.nstates_device = Int(ns[])
+    nothing
+end
+_sv_scheme(scheme::String) = scheme == "BE" ? Int32(0) : scheme == "CN" ? Int32(1) : error("Unknown scheme.")
+
+"ConvectionOps(capacity, (u, v), [u; v]) of the current velocity (build_convection, :167-182), cached until the next ψ solve."
+function build_convection(s::StreamVorticity{2})
+    s.last_convection !== nothing && return s.last_convection
+    u, v = s.velocity
+    s.last_convection = ConvectionOps(s.capacity, (u, v), vcat(u, v))
+end
+
+function solve_StreamVorticity!(s::StreamVorticity; method = bicgstabl, algorithm = nothing, kwargs...)
+    opts = Ref(_opts(method, kwargs))
+    info = pg_step_info()
+    _sv_push!(s)
+    check(ccall((:pg_streamvort_solve_stream, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
+    info.converged == 0 && @warn "PenguinHIP: the stream-function solve did not converge" iters = info.iters
+    _sv_pull!(s)
+    s.ψ
+end
+
+function step_StreamVorticity!(s::StreamVorticity; scheme::String = "BE", method = bicgstabl, algorithm = nothing, kwargs...)
+    opts = Ref(_opts(method, kwargs))
+    ip, iw = pg_step_info(), pg_step_info()
+    _sv_push!(s)
+    check(ccall((:pg_streamvort_step, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{pg_krylov_opts}, Ref{pg_step_info}, Ref{pg_step_info}),
+                s.handle, _sv_scheme(scheme), opts, ip, iw))
+    (ip.converged == 0 || iw.converged == 0) && @warn "PenguinHIP: a solve of the step did not converge" psi = ip.iters omega = iw.iters
+    _sv_pull!(s)
+    s.ω
+end
+
+# constant-in-time data (no closure among source and interface values takes part): the loop runs inside the library
+_sv_constant(s::StreamVorticity) = !(s.bc_stream.value isa Function) && !(s.bc_vorticity.value isa Function) &&
+                                   all(iszero, evalf(s.source, s.capacity.C_ω, s.time)) && !haskey(s.sent, :f_sent)
+
+function run_StreamVorticity!(s::StreamVorticity, steps::Integer; scheme::String = "BE", method = bicgstabl, algorithm = nothing,
+                              constant_data::Bool = _sv_constant(s), kwargs...)
+    if !constant_data
+        for _ in 1:steps
+            step_StreamVorticity!(s; scheme = scheme, method = method, algorithm = algorithm, kwargs...)
+        end
+        return s
+    end
+    opts = Ref(_opts(method, kwargs))
+    run = pg_streamvort_run_info()
+    _sv_push!(s)
+    check(ccall((:pg_streamvort_run, libpg), Int32, (Ptr{Cvoid}, Int64, Int32, Ptr{pg_krylov_opts}, Int32, Ptr{Cvoid}),
+                s.handle, steps, _sv_scheme(scheme), opts, 1, pointer_from_objref(run)))
+    run.unconverged > 0 && @warn "PenguinHIP: solves of the run did not converge" count = run.unconverged worst = run.worst_relres
+    _sv_pull!(s)
+    s
+end
+
+function run_until_StreamVorticity!(s::StreamVorticity, t_end::Float64; kwargs...)
+    while s.time < t_end - 1e-12
+        step_StreamVorticity!(s; kwargs...)
+    end
+    s
 end
 
 "Every PG_* tuning / variant selector the library runs with (`pg_config_string`)."

@@ -33,3 +33,6 @@ from .liquid import (  # noqa: F401,E402
     apply_learning_rate_step_b, extract_height_profiles, init_learning_rate_state, normalize_lr_options, normalize_lr_strategy,
     solve_MovingLiquidDiffusionUnsteadyDiph_b, solve_MovingLiquidDiffusionUnsteadyMono_b, stefan_terms,
 )
+from .streamvorticity import (  # noqa: F401,E402
+    StreamVorticity, run_StreamVorticity_b, run_until_StreamVorticity_b, solve_StreamVorticity_b, step_StreamVorticity_b,
+)

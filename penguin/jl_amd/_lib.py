@@ -32,6 +32,7 @@ PG_BC_NONE, PG_BC_DIRICHLET, PG_BC_NEUMANN, PG_BC_ROBIN, PG_BC_PERIODIC = 0, 1, 
 PG_KEY = {"left": 0, "right": 1, "bottom": 2, "top": 3, "backward": 4, "forward": 5}
 PG_SCHEME = {"BE": 0, "CN": 1, "STEADY": 2}
 PG_METHOD = {"bicgstab": 0, "cg": 1, "gmres": 2}
+PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a pg_streamvort
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -83,6 +84,13 @@ class pg_system_info(C.Structure):
                 ("neumann_ok", C.c_int64), ("gershgorin", C.c_double), ("spmv_units", C.c_int64),
                 ("rows_marched", C.c_int64), ("rows_matrix", C.c_int64), ("n_ghost_loop", C.c_int64),
                 ("loop_is_compact", C.c_int64)]
+
+
+class pg_streamvort_run_info(C.Structure):
+    _fields_ = [("steps", C.c_int64), ("psi_iters", C.c_int64), ("omega_iters", C.c_int64), ("psi_products", C.c_int64),
+                ("omega_products", C.c_int64), ("unconverged", C.c_int64), ("worst_relres", C.c_double), ("t_final", C.c_double),
+                ("total_ms", C.c_double), ("psi_ms", C.c_double), ("velocity_ms", C.c_double), ("build_ms", C.c_double),
+                ("omega_ms", C.c_double)]
 
 
 def declared_symbols() -> list[str]:

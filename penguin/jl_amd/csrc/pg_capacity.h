@@ -48,6 +48,8 @@ struct CapView {
   const double* W[3];
 };
 CapView cap_view(const pg_capacity* c);
+// ConvectionOps from device-resident velocities (pg_diffops.hip): u N x Mloc, ug N*Mloc; queued on st, not waited for
+void diffops_convection_from_device(pg_diffops* o, const double* const* u, const double* ug, hipStream_t st);
 
 // local cell -> 0-based Cartesian index (slowest dim from the plane number)
 __host__ __device__ inline void decode_cell(int N, const i64* ext, i64 plane, i64 s0, i64 lc, i64* idx) {

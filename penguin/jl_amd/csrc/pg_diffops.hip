@@ -92,6 +92,32 @@ __global__ void k_conv_kappa(CapView c, i64 Mloc, int nd, const double* __restri
 
 }  // namespace
 
+namespace pg {
+
+// ConvectionOps(capacity, uₒ, uᵧ) from velocities that are on the device: a_d of every C_d, h = Hᵀuᵧ and the diagonal of ½ΣK
+// (operators.jl:194-210).  u: N pointers to Mloc doubles, ug: N*Mloc doubles (block d = component d), local layout.  The
+// launches are queued on `st`; nothing is waited for.  Shared by pg_diffops_set_velocity (velocities uploaded by the caller)
+// and the stream function - vorticity handle (velocities computed on the device, pg_streamvort.hip).
+void diffops_convection_from_device(pg_diffops* o, const double* const* u, const double* ug, hipStream_t st) {
+  pg_capacity* c = o->cap;
+  const i64 Ml = c->slab.Mloc();
+  const CapView cv = cap_view(c);
+  const int gr = grid_for(Ml, 256, 256 * 16);
+  for (int d = 0; d < c->N; ++d) {
+    if (o->conv_a[d].n != Ml) o->conv_a[d].alloc(Ml);
+    hipLaunchKernelGGL(k_conv_a, dim3(gr), dim3(256), 0, st, cv, Ml, d, u[d], o->conv_a[d].p);
+  }
+  if (o->conv_h.n != Ml) o->conv_h.alloc(Ml);
+  if (o->conv_k.n != Ml) o->conv_k.alloc(Ml);
+  hipLaunchKernelGGL(k_conv_h, dim3(gr), dim3(256), 0, st, cv, Ml, ug, o->conv_h.p);
+  hipLaunchKernelGGL(k_conv_kappa, dim3(gr), dim3(256), 0, st, cv, Ml, c->N, o->conv_h.p, o->conv_k.p);
+  PG_HIP(hipGetLastError());
+  o->has_velocity = true;
+  o->st_velocity = false;
+}
+
+}  // namespace pg
+
 extern "C" {
 
 int32_t pg_diffops_set_velocity(pg_diffops* o, const double* const* u_omega, const double* u_gamma) {
@@ -102,26 +128,16 @@ int32_t pg_diffops_set_velocity(pg_diffops* o, const double* const* u_omega, con
   const Slab& s = c->slab;
   const i64 Ml = s.Mloc(), M = s.M;
   hipStream_t st = ctx().stream;
-  const CapView cv = cap_view(c);
-  const int gr = grid_for(Ml, 256, 256 * 16);
-  DevBuf<double> u(Ml), ug((i64)c->N * Ml);
+  DevBuf<double> u((i64)c->N * Ml), ug((i64)c->N * Ml);
+  const double* up[3] = {nullptr, nullptr, nullptr};
   for (int d = 0; d < c->N; ++d) {
     PG_REQUIRE(u_omega[d], "pg_diffops_set_velocity: NULL velocity component");
-    u.upload(u_omega[d] + s.first_cell(), Ml);
-    o->conv_a[d].alloc(Ml);
-    hipLaunchKernelGGL(k_conv_a, dim3(gr), dim3(256), 0, st, cv, Ml, d, u.p, o->conv_a[d].p);
-    PG_HIP(hipGetLastError());
-    PG_HIP(hipStreamSynchronize(st));
+    u.upload(u_omega[d] + s.first_cell(), Ml, (i64)d * Ml);
     ug.upload(u_gamma + (i64)d * M + s.first_cell(), Ml, (i64)d * Ml);
+    up[d] = u.p + (i64)d * Ml;
   }
-  o->conv_h.alloc(Ml);
-  o->conv_k.alloc(Ml);
-  hipLaunchKernelGGL(k_conv_h, dim3(gr), dim3(256), 0, st, cv, Ml, ug.p, o->conv_h.p);
-  hipLaunchKernelGGL(k_conv_kappa, dim3(gr), dim3(256), 0, st, cv, Ml, c->N, o->conv_h.p, o->conv_k.p);
-  PG_HIP(hipGetLastError());
+  diffops_convection_from_device(o, up, ug.p, st);
   PG_HIP(hipStreamSynchronize(st));
-  o->has_velocity = true;
-  o->st_velocity = false;
   PG_API_END
 }
 

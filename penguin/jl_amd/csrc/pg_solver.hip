@@ -15,6 +15,7 @@
 
 #include "pg_krylov.h"
 #include "pg_reduce.h"
+#include "pg_solver_internal.h"
 #include "pg_spmv.h"
 
 using namespace pg;
@@ -1662,6 +1663,10 @@ struct SolverSpec {
   int32_t scheme = PG_SCHEME_BE;              // the caller's BE / CN; not read when ...
   bool steady = false;                        // ... the steady blocks are asked for
   bool moving = false, advdiff = false, stefan = false;
+  // one phase, set by a composite handle that keeps its data on the device (pg_streamvort.hip): D, sources and interface values
+  // as Mloc doubles each in the local layout, copied device to device; they take the place of the host arrays above
+  const pg::SolverDeviceData* dev = nullptr;
+  bool solved_once = false;                   // the system is solved once and replaced (as a slab of the moving solvers)
   pg_solver** out = nullptr;
 };
 
@@ -1696,6 +1701,11 @@ static int32_t create_solver(const SolverSpec& d) {
     PG_REQUIRE(!d.previous || d.previous->initial_done, who + "the previous slab has not been solved");
   } else {
     PG_REQUIRE(d.dt > 0.0, who + "dt must be positive");
+    if (d.previous) {           // a time step built as a new solver: the state of the step before, handed over on the device
+      PG_REQUIRE(!d.steady, who + "a steady solver has no previous state");
+      PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, who + "a state is handed from solver to solver on one rank only");
+      PG_REQUIRE(d.previous->initial_done, who + "the previous solver has not been solved");
+    }
   }
   auto* s = new pg_solver();
   std::unique_ptr<pg_solver> guard(s);
@@ -1725,6 +1735,17 @@ static int32_t create_solver(const SolverSpec& d) {
     if (d.f_np1[q]) upload_local(s->f_np1[q], d.f_np1[q], s->slab);
     if (d.f_n[q]) upload_local(s->f_n[q], d.f_n[q], s->slab);
   }
+  if (d.dev) {
+    PG_REQUIRE(mono, who + "device-resident data: one phase only");
+    auto take = [&](DevBuf<double>& dst, const double* src) {
+      if (!src) return;
+      dst.alloc(Ml);
+      PG_HIP(hipMemcpyAsync(dst.p, src, sizeof(double) * (size_t)Ml, hipMemcpyDeviceToDevice, ctx().stream));
+    };
+    take(s->Id[0], d.dev->D);
+    take(s->f_n[0], d.dev->f_n);
+    take(s->f_np1[0], d.dev->f_np1);
+  }
   // the descriptor is copied, its arrays go to the device: their host memory dies with the call
   if (mono) {
     s->bc_i = *d.bc_interface;
@@ -1733,6 +1754,13 @@ static int32_t create_solver(const SolverSpec& d) {
       upload_local(s->g_n, d.bc_interface->value_array, s->slab);
     }
     s->bc_i.value_array = nullptr;
+    if (d.dev && d.dev->g_np1) {
+      s->g_np1.alloc(Ml);
+      s->g_n.alloc(Ml);
+      PG_HIP(hipMemcpyAsync(s->g_np1.p, d.dev->g_np1, sizeof(double) * (size_t)Ml, hipMemcpyDeviceToDevice, ctx().stream));
+      PG_HIP(hipMemcpyAsync(s->g_n.p, d.dev->g_n ? d.dev->g_n : d.dev->g_np1, sizeof(double) * (size_t)Ml, hipMemcpyDeviceToDevice,
+                            ctx().stream));
+    }
   } else {
     s->ic = *d.ic;
     if (d.ic->g_array) upload_local(s->g_arr, d.ic->g_array, s->slab);
@@ -1740,7 +1768,7 @@ static int32_t create_solver(const SolverSpec& d) {
     s->ic.g_array = s->ic.h_array = nullptr;
   }
   s->init_from = d.previous;                // consumed by setup_common after T0: its active unknowns overwrite T0's
-  s->A_ctor.want_units = !d.moving;
+  s->A_ctor.want_units = !d.moving && !d.solved_once;
   setup_common(s, d.borders, d.nborders, d.T0);
   *d.out = guard.release();
   PG_API_END
@@ -2346,3 +2374,137 @@ int32_t pg_solver_time_spmv(pg_solver* s, int32_t which, int32_t reps, double* a
 }
 
 }  // extern "C"
+
+// ---- what a composite handle needs of a solver (pg_solver_internal.h) ----------------------------------------------------
+namespace pg {
+
+int32_t solver_create_unsteady_mono_dev(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
+                                        int32_t nborders, const SolverDeviceData& dev, double dt, const double* T0,
+                                        pg_solver* previous, int32_t scheme, pg_solver** out) {
+  SolverSpec d = spec_mono("pg_streamvort_step", c, o, bc_interface, borders, nborders, nullptr, nullptr, nullptr, out);
+  d.dt = dt; d.T0 = T0; d.previous = previous; d.scheme = scheme;
+  d.dev = &dev;
+  d.solved_once = true;
+  return create_solver(d);
+}
+
+i64 solver_mloc(const pg_solver* s) { return s->Mloc; }
+
+double* solver_source_dev(pg_solver* s) {
+  if (s->f_np1[0].n != s->Mloc) { s->f_np1[0].alloc(s->Mloc); s->f_np1[0].zero(); }
+  return s->f_np1[0].p;
+}
+
+void solver_data_changed(pg_solver* s) { s->bconst_dirty = true; }
+
+// A steady system solved again with a new right-hand side: the matrix, its numbering and its preconditioner stand; b = the
+// time-data part alone (no mass term: b₁ = V f, b₂ = Γ g, border rows their values -- diffusion.jl:45-58); BiCGStab starts
+// from the previous solution unless the caller asks for a cold start.  The first call is the initial solve.
+void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
+  PG_REQUIRE(s->scheme_ctor == PG_SCHEME_STEADY && !s->moving, "solve again: a steady solver is expected");
+  if (!s->initial_done) {
+    build_first_rhs(s);
+    do_initial(s, opts, st);
+    return;
+  }
+  const pg_krylov_opts o = opts ? *opts : default_opts();
+  hipStream_t stream = ctx().stream;
+  const i64 n = s->nb.n_own;
+  ensure_bconst(s, PG_SCHEME_STEADY);
+  if (n > 0) apply_left(s->A_ctor, s->bconst.p, s->b.p, stream);      // b̂ = B⁻¹ S b
+  if (o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
+    spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);       // z: the previous solution, scaled by this matrix's S
+    PG_HIP(hipGetLastError());
+    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
+  } else {
+    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
+  }
+  std::swap(s->z.p, s->ysol.p);
+  s->z_matrix = &s->A_ctor;
+  s->x_valid = false;
+}
+
+// One step of iterative refinement: r̂ = b̂ - Â z from a product (every row to the accuracy of its OWN entries), Â d = r̂ from zero
+// to REFINE_RELTOL of ||r̂||, z += d.  A stopping test on ||r|| / ||b|| bounds the error by cond(Â) times the tolerance only.  The
+// vorticity system of a step can be close to singular: the bulk row of a solid cell that nothing but the convection stencil of
+// its cut neighbours reaches has a diagonal that is the residue of a cancellation (1e-20 next to off-diagonals of 1e-6 where
+// the flow is mirror symmetric about the cell) -- a constraint between the neighbours, its unknown their multiplier,
+// cond(Â) = 5e5.  A direct solve, which is what the reference runs, resolves it; the Krylov solve stopped at 1e-13 leaves 1e-8
+// ... 1e-6 in that unknown.  The residual of such a row is far below ||b|| but well above the rounding of its own entries, and the
+// correction is solved relative to it: the error bound falls by REFINE_RELTOL.  About half the products of the solve again.
+constexpr double REFINE_RELTOL = 1e-6;
+
+__global__ void k_refine_residual(i64 n, i64 nvec, const double* __restrict__ b, const double* __restrict__ y, double* __restrict__ r) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < nvec; i += (i64)gridDim.x * blockDim.x) r[i] = i < n ? b[i] - y[i] : 0.0;
+}
+
+__global__ void k_refine_add(i64 n, const double* __restrict__ d, double* __restrict__ z) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) z[i] += d[i];
+}
+
+static void refine_once(pg_solver* s, const pg_krylov_opts& o, SolveStats& st) {
+  const i64 n = s->nb.n_own, nv = s->nb.n_vec();
+  if (n <= 0) return;
+  hipStream_t stream = ctx().stream;
+  const CsrMatrix& A = s->A_ctor;
+  spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
+  DevBuf<double> r(nv);
+  hipLaunchKernelGGL(k_refine_residual, dim3(grid_for(nv, BLOCK)), dim3(BLOCK), 0, stream, n, nv, (const double*)s->b.p,
+                     (const double*)s->y.p, r.p);
+  PG_HIP(hipGetLastError());
+  pg_krylov_opts oc = o;
+  oc.reltol = REFINE_RELTOL;
+  oc.abstol = 0.0;
+  SolveStats more;
+  krylov_solve(A, s->nb, s->slab, r.p, s->ysol.p, s->work, oc, more);
+  hipLaunchKernelGGL(k_refine_add, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, (const double*)s->ysol.p, s->z.p);
+  PG_HIP(hipGetLastError());
+  st.iters += more.iters;
+  st.products += more.products + 1;
+  s->x_valid = false;
+}
+
+// The first (and only) solve of a time step that was built as a new solver: as do_initial, but BiCGStab starts from the state
+// the solver was built from (s->x on this system's active set, written by k_rhs_first) instead of zero -- what do_initial
+// does for a slab of the moving solvers.  One step of iterative refinement follows (refine_once).
+void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
+  const pg_krylov_opts o = opts ? *opts : default_opts();
+  const i64 n = s->nb.n_own;
+  if (!(o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) || s->initial_done) {
+    do_initial(s, opts, st);
+    refine_once(s, o, st);
+    return;
+  }
+  hipStream_t stream = ctx().stream;
+  hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, s->A_ctor.ds.p, s->x.p, s->z.p, 1);
+  spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);
+  PG_HIP(hipGetLastError());
+  krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
+  std::swap(s->z.p, s->ysol.p);
+  s->z_matrix = &s->A_ctor;
+  s->x_valid = false;
+  s->initial_done = true;
+  s->hist_cnt = 0;
+  s->spec_y_valid = false;
+  refine_once(s, o, st);
+}
+
+// padded = zeros(K * Mloc); padded[active] = x     (solver.jl:186-187), device to device
+void solver_state_padded(pg_solver* s, double* padded) {
+  hipStream_t st = ctx().stream;
+  materialize_x(s);
+  PG_HIP(hipMemsetAsync(padded, 0, sizeof(double) * (size_t)((i64)s->K * s->Mloc), st));
+  if (s->nb.n_own > 0) {
+    hipLaunchKernelGGL(k_scatter_active, dim3(grid_for(s->nb.n_own, BLOCK)), dim3(BLOCK), 0, st, make_segs(s->nb), s->nb.n_own,
+                       s->Mloc, s->nb.row_cell.p, s->x.p, padded);
+    PG_HIP(hipGetLastError());
+  }
+}
+
+void solver_step_info(pg_solver* s, const SolveStats& st, double time, pg_step_info* info) {
+  if (!info) return;
+  fill_info(s, st, info);
+  info->time = time;
+}
+
+}  // namespace pg

@@ -1,0 +1,34 @@
+// pg_solver_internal.h -- what a composite handle (pg_streamvort.hip) needs of a pg_solver without seeing inside it.
+// Implemented at the end of pg_solver.hip; nothing here crosses the C ABI.
+#pragma once
+#include "pg_krylov.h"
+
+struct pg_solver;
+
+namespace pg {
+
+// data of one phase that already lives on the device: Mloc doubles each in the local layout, or nullptr (D: 1, sources: 0,
+// interface values: the constant of the descriptor; g_n == nullptr with g_np1 set: g_n = g_np1)
+struct SolverDeviceData {
+  const double* D = nullptr;
+  const double* f_n = nullptr;
+  const double* f_np1 = nullptr;
+  const double* g_n = nullptr;
+  const double* g_np1 = nullptr;
+};
+
+// pg_solver_create_unsteady_mono with device-resident data and, optionally, the state of a solved solver on the same mesh
+// as the initial state (device to device; its active unknowns overwrite T0's).  The system is planned for ONE solve.
+// Returns the status of an ABI call (pg_last_error holds the message).
+int32_t solver_create_unsteady_mono_dev(pg_capacity* c, pg_diffops* o, const pg_bc_desc* bc_interface, const pg_border_desc* borders,
+                                        int32_t nborders, const SolverDeviceData& dev, double dt, const double* T0,
+                                        pg_solver* previous, int32_t scheme, pg_solver** out);
+i64 solver_mloc(const pg_solver* s);
+double* solver_source_dev(pg_solver* s);       // the source f(t+Δt) of phase 1 (Mloc, zero when first asked for): written by the caller ...
+void solver_data_changed(pg_solver* s);        // ... who then says so
+void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st);
+void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st);
+void solver_state_padded(pg_solver* s, double* padded /* K * Mloc, device */);
+void solver_step_info(pg_solver* s, const SolveStats& st, double time, pg_step_info* info);
+
+}  // namespace pg
