@@ -464,6 +464,10 @@ int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart);
 /* ramp != 0: the virtual-rank runs that follow change the interface value every step, g = interface_value (1 + ramp step)
    (host-driven steps): rows alone on their diagonal move in every step, on every rank */
 int32_t pg_debug_set_virtual_rank_ramp(double ramp);
+/* step >= 1: the virtual-rank runs that follow take single steps with constant data, and before step `step` (1 = the first)
+   every rank multiplies the state at its rows alone on their diagonal by `factor` (pg_debug_scale_diagonal_rows; a rank
+   whose loop keeps no such row skips it): the step must end at the state one rank ends at.  step < 0 (default): off */
+int32_t pg_debug_set_virtual_rank_kick(int64_t step, double factor);
 /* per virtual rank of the last run: rows of the full system, rows / bytes per launch / ghost entries of the system the
    warm loop iterated on (the compact one when loop_rows < full_rows) */
 int32_t pg_debug_virtual_rank_info(int32_t rank, int64_t* full_rows, int64_t* loop_rows, int64_t* loop_bytes,
@@ -471,6 +475,10 @@ int32_t pg_debug_virtual_rank_info(int32_t rank, int64_t* full_rows, int64_t* lo
 /* test hook: multiply the state at every row that is alone on its diagonal by `factor` WITHOUT telling the time loop --
    the next quiet step must notice (S_MOVED) and still end at the right state */
 int32_t pg_debug_scale_diagonal_rows(pg_solver* s, double factor);
+/* test hook, process-global: iterations > 0 replaces the count (40 + 400 / degree) after which a solve preconditioned with
+   the polynomial is given up as stagnated and continues with the plain iteration -- on the full system when it ran on the
+   compact one; 0 restores the built-in rule */
+int32_t pg_debug_set_poly_give_up(int32_t iterations);
 
 /* The extrapolated start of the time loop's quiet steps (constant data, one rank; no reference counterpart: the reference
    starts every Krylov solve from zero, solver.jl:158-181): `kept` older states are held; the next step starts from

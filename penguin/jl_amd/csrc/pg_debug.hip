@@ -13,6 +13,7 @@
 #include <unistd.h>
 
 #include "pg_common.h"
+#include "pg_krylov.h"
 
 using namespace pg;
 
@@ -44,6 +45,11 @@ int g_method = PG_METHOD_BICGSTAB, g_restart = 0;
 // alone on their diagonal then MOVE in every step and the compact loop has to carry their change to the rows coupled to
 // them, across slab faces too (pg_reduce.hip diag_fix with the exchange of the deltas)
 double g_ramp = 0.0;
+// pg_debug_set_virtual_rank_kick: g_kick_step >= 1: constant data, single steps, and before step g_kick_step (1 = the first)
+// every rank multiplies the rows alone on its diagonal by g_kick_factor -- rows that count as solved in a step with unchanged
+// data move all the same, and the ranks have to agree on finishing that step on the full system (pg_solver.hip, S_MOVED)
+int64_t g_kick_step = -1;
+double g_kick_factor = 1.0;
 // what the loop of each rank iterated on in the last run (pg_debug_virtual_rank_info)
 int64_t g_loop_rows[8], g_loop_bytes[8], g_loop_ghosts[8], g_full_rows[8];
 
@@ -87,7 +93,17 @@ void rank_main(const VArgs& a, int rank, LocalComm* lc, int device, std::string*
                                          a.scheme_ctor, &sol), "solver");
     pg_krylov_opts o{g_method, 1e-13, 0.0, 0, 4, g_method == PG_METHOD_BICGSTAB ? 1 : 0, g_restart};
     pg_run_info info{};
-    if (g_ramp == 0.0) {
+    if (g_kick_step >= 0) {
+      pg_step_info sti{};
+      check(pg_solver_initial_solve(sol, &o, &sti), "initial solve");
+      info.total_iters = sti.iters;
+      for (int64_t k = 0; k < a.steps; ++k) {
+        // (not checked: a rank whose loop keeps no such row -- or has no run matrix yet -- is refused and skips the kick)
+        if (k + 1 == g_kick_step) (void)pg_debug_scale_diagonal_rows(sol, g_kick_factor);
+        check(pg_solver_step(sol, a.scheme_run, &o, &sti), "step");
+        info.total_iters += sti.iters;
+      }
+    } else if (g_ramp == 0.0) {
       check(pg_solver_run(sol, 1e300, a.scheme_run, &o, 1, a.steps, 0, &info), "run");
     } else {
       pg_step_info sti{};
@@ -146,6 +162,20 @@ extern "C" int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t rest
 extern "C" int32_t pg_debug_set_virtual_rank_ramp(double ramp) {
   PG_API_BEGIN
   g_ramp = ramp;
+  PG_API_END
+}
+
+extern "C" int32_t pg_debug_set_virtual_rank_kick(int64_t step, double factor) {
+  PG_API_BEGIN
+  g_kick_step = step;
+  g_kick_factor = factor;
+  PG_API_END
+}
+
+extern "C" int32_t pg_debug_set_poly_give_up(int32_t iterations) {
+  PG_API_BEGIN
+  PG_REQUIRE(iterations >= 0, "pg_debug_set_poly_give_up: a count of iterations, or 0 for the built-in rule");
+  pg::g_poly_give_up = iterations;
   PG_API_END
 }
 

@@ -46,6 +46,12 @@ struct KrylovWork {
   // set by the caller whose start kernel has already reset the scalars, summed the start sums and derived PH_INIT
   // (k_rhs_init_c with a ticket): krylov_solve launches no start kernel.  Reset by krylov_solve.
   bool start_folded = false;
+  // set by the caller of a prepared start on SEVERAL ranks that has not looked at the rows alone on their diagonal (a compact
+  // step with unchanged data, pg_solver.hip): *moved_flag == moved_stamp says that one of them moved on this rank all the
+  // same.  The verdict rides as a fourth slot in the start phase's all-reduce and every rank finds the same S_MOVED in the
+  // scalars of the solve.  Reset by krylov_solve.
+  const int* moved_flag = nullptr;
+  int moved_stamp = 0;
   // polynomial right preconditioner (pg_krylov.hip), n_vec each, on first use: ya = M⁻¹p, yb = M⁻¹s of the running
   // iteration (the updates of x read them) and the two work vectors the Horner chain alternates between
   DevBuf<double> ya, yb, wa, wb;
@@ -89,7 +95,7 @@ void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st);
 // halo exchange of x (when the matrix needs one) overlapped with y[0..n) = A * x
 void spmv_halo(const CsrMatrix& A, const Numbering& nb, const Slab& slab, double* x, double* y, hipStream_t st);
 // x (n_vec, overwritten) = A^{-1} b.  x0 == nullptr: zero initial guess; else start from x0 with Ax0 = A*x0 given
-// (BiCGStab only).  x must not alias x0.
+// (BiCGStab only).  x0 may be x itself (the iteration continues from the iterate x holds).
 // preinit (BiCGStab only): the caller has already written x, w.r = w.rhat = w.p = r0 and the partial sums of (r0,r0)
 // / (b,b) in slots 0 / 1 of w.partials with a w.grid-block launch (pg_solver.hip fuses that with the right-hand side).
 void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x,
@@ -99,6 +105,10 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
 // will krylov_solve(A, ..., opts) run BiCGStab right-preconditioned with the polynomial?  (Only that loop can solve a
 // compact system: it updates x through KrylovWork::scatter.)
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts);
+
+// iterations after which a polynomial-preconditioned solve that has not converged is given up as stagnated; 0: the built-in
+// rule 40 + 400 / m.  Process-global, set by tests only (pg_debug_set_poly_give_up).
+extern int g_poly_give_up;
 
 // restarted GMRES (pg_gmres.hip): zero initial guess, x (n_vec, overwritten) = A^{-1} b
 void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,

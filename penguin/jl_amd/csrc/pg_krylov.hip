@@ -41,9 +41,10 @@ namespace {
 // x0 == nullptr: zero initial guess (IterativeSolvers' default).  Otherwise x = x0 and r = b - Ax0 (warm start with
 // the previous time level; Ax0 is the SpMV the CN right-hand side needs anyway).  partials: slot 0 = r.r, slot 1 =
 // (b,b)_W, slot 2 = (r,r)_W with the weights ds² of the convergence test (pg_spmv.h; ds == nullptr: unweighted)
+// (x0 may be x itself: the fallback from a stagnated polynomial continues from the iterate reached)
 __global__ __launch_bounds__(BLOCK) void k_bicg_init(i64 n, i64 nvec, const double* __restrict__ b,
-                                                     const double* __restrict__ x0, const double* __restrict__ Ax0,
-                                                     double* __restrict__ x, double* __restrict__ r,
+                                                     const double* x0, const double* __restrict__ Ax0,
+                                                     double* x, double* __restrict__ r,
                                                      double* __restrict__ rhat, double* __restrict__ p,
                                                      double* __restrict__ v, double* __restrict__ partials,
                                                      const double* __restrict__ ds) {
@@ -373,6 +374,26 @@ __global__ void k_derive(int phase, double* sc, int check_done) {
   derive(phase, sc);
 }
 
+// The start phase of a prepared start on several ranks that carries KrylovWork::moved_flag: k_finalize's sums of the three
+// start slots, and S_RED3 = 1 when a row alone on its diagonal moved on this rank (0 otherwise) ...
+__global__ __launch_bounds__(BLOCK) void k_start_sums_moved(int grid, const double* __restrict__ partials, double* __restrict__ sc,
+                                                            const int* __restrict__ flag, int stamp) {
+  __shared__ double s_red[BLOCK / 64];
+  for (int s = 0; s < 3; ++s) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < grid; i += BLOCK) a += partials[(size_t)s * grid + i];
+    const double t = block_sum(a, s_red);
+    if (threadIdx.x == 0) sc[S_RED0 + s] = t;
+  }
+  if (threadIdx.x == 0) sc[S_RED0 + 3] = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == stamp ? 1.0 : 0.0;
+}
+
+// ... and, behind the all-reduce of the four: PH_INIT and the verdict every rank shares (how many ranks saw one move)
+__global__ void k_derive_start_moved(double* sc) {
+  derive(PH_INIT, sc);
+  sc[S_MOVED] = sc[S_RED0 + 3] != 0.0 ? 1.0 : 0.0;
+}
+
 // after a launch whose last block already summed (and, on one rank, derived) the phase: only what is left to do
 void finalize_folded(int phase, int nslots, KrylovWork& w, hipStream_t st) {
   Context& cx = ctx();
@@ -478,6 +499,7 @@ struct SpmvTimer {
 namespace pg {
 
 double g_host_wait_us = 0.0;
+int g_poly_give_up = 0;
 
 void KrylovWork::init(i64 n_own, i64 n_vec) {
   n = n_own;
@@ -634,6 +656,9 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   w.xguess = XGuess();
   const bool start_folded = w.start_folded && preinit && opts.method == PG_METHOD_BICGSTAB;
   w.start_folded = false;
+  const int* moved_flag = w.moved_flag;
+  const int moved_stamp = w.moved_stamp;
+  w.moved_flag = nullptr;
   const bool fused_start = !start_folded && preinit && opts.method == PG_METHOD_BICGSTAB && cx.nranks == 1 && !cx.comm;   // k_start below
   if (!fused_start && !start_folded)
     hipLaunchKernelGGL(k_sc_reset, dim3(1), dim3(S_COUNT), 0, st, w.sc.p, opts.reltol * opts.reltol, opts.abstol * opts.abstol);
@@ -684,7 +709,13 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     } else if (fused_start)
       hipLaunchKernelGGL(k_start, dim3(1), dim3(BLOCK), 0, st, (int)PH_INIT, 3, w.grid, (const double*)w.partials.p, w.sc.p,
                          opts.reltol * opts.reltol, opts.abstol * opts.abstol);
-    else
+    else if (moved_flag && preinit && !(cx.nranks == 1 && !cx.comm)) {
+      // finalize(PH_INIT) with one more slot in the same all-reduce: did a row alone on its diagonal move on ANY rank?
+      hipLaunchKernelGGL(k_start_sums_moved, dim3(1), dim3(BLOCK), 0, st, w.grid, (const double*)w.partials.p, w.sc.p, moved_flag,
+                         moved_stamp);
+      comm_allreduce_sum_f64(w.sc.p + S_RED0, 4, st);
+      hipLaunchKernelGGL(k_derive_start_moved, dim3(1), dim3(1), 0, st, w.sc.p);
+    } else
       finalize(PH_INIT, 3, w, st, false);
   } else {
     hipLaunchKernelGGL(k_cg_init, dim3(G), dim3(BLOCK), 0, st, n, nvec, b, x, w.r.p, w.p.p, w.partials.p, (const double*)A.ds.p);
@@ -702,7 +733,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   int launched = 0, polls = 0;          // launched: iterations whose first half is queued
   bool mid = false;                     // ... and the second half of the last one is not
   bool done = false, poly_failed = false;
-  const int poly_give_up = 40 + 400 / std::max(m, 1);   // iterations; an admitted system needs 2 .. 10
+  const int poly_give_up = g_poly_give_up > 0 ? g_poly_give_up : 40 + 400 / std::max(m, 1);   // iterations; an admitted system needs 2 .. 10
   const int derive_here = (cx.nranks == 1 && !cx.comm) ? 1 : 0;
   // out = C in = Â q(Â) in with the dots of the phase (mode 1: (r̂,out); 3: (out,in), (out,out), (r̂,out)); q(Â) in stays in
   // ya (first half) / yb (second half) for the update of x.  The plain iteration applies Â itself.

@@ -1518,6 +1518,9 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       guess_after_rhs(s, gp, n, (const int*)DE.cmap.p, (const double*)A.ds.p, (const double*)w.rhat.p, single, w, stream);
       if (!same_data) diag_fix(DE, s->nb, s->slab, stamp, !single, w.rhat.p, w.partials.p, w.grid, stream);
       w.start_folded = quiet;
+      // several ranks, unchanged data: nobody looks at the rows alone on their diagonal (no diag_fix), so the flag k_rhs_init_c
+      // raised goes through the start phase's all-reduce and comes back as S_MOVED, the same on every rank
+      if (same_data && !single) { w.moved_flag = DE.flag.p; w.moved_stamp = stamp; }
       DE.snapped_version = s->bconst_version;
       used_de = &DE;
       w.scatter = DE.rlist.p;
@@ -1542,6 +1545,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       } catch (...) {
         w.scatter = nullptr;
         w.after_first_batch = nullptr;
+        w.moved_flag = nullptr;
         throw;
       }
       w.scatter = nullptr;
@@ -1552,16 +1556,22 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       solved = st.poly_degree >= 0;            // -1: the polynomial stagnated on the compact system -> the full system below
       DE.last_products = (double)st.products;
 
-      // A quiet step rests on "no row alone on its diagonal moves while the data are unchanged"; k_rhs_init_c checks it
-      // anyway and the start phase reports it (S_MOVED): the residual the iteration started from then lacked the coupling
-      // term, and the step is finished on the full system from the state reached.
-      const bool moved_unseen = solved && quiet && w.h_sc[S_MOVED] != 0.0;
+      // A step with unchanged data rests on "no row alone on its diagonal moves while the data are unchanged"; k_rhs_init_c
+      // checks it anyway and the start phase reports it (S_MOVED): the residual the iteration started from then lacked the
+      // coupling term, and the step is finished on the full system from the state reached.  Several ranks read the verdict
+      // out of the start phase's all-reduce: a row that moved on one rank sends all of them this way, or none.
+      const bool moved_unseen = solved && same_data && w.h_sc[S_MOVED] != 0.0;
       if (!solved || moved_unseen) {
         s->spec_y_valid = false;
         // z has moved (the rows left out hold their solution, the x-space iteration has updated the rest): the right-hand
         // side b̂ of this step -- written for every row by k_rhs_init_c -- stands, the iteration continues on the full
         // system from the state reached, r = b̂ - Âz
-        if (!solved) DE.active = false;
+        if (!solved) {
+          DE.active = false;
+          // the compact matrix is made of the full one's rows: the verdict on the polynomial holds for both, and the solve
+          // below goes plain at once instead of stagnating a second time
+          const_cast<CsrMatrix&>(A).poly_ok = false;
+        }
         used_de = nullptr;
         const SolveStats first = st;
         st = SolveStats();

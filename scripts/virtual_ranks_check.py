@@ -68,6 +68,22 @@ for nr in (2, 3):
                                 "n_ghost": ngh.tolist(), "iters": its.tolist(), "iters_1": int(it1[0]), "loop": loop_info(nr),
                                 "ref_max": float(np.max(np.abs(ref)))}
 L.check(lib.pg_debug_set_virtual_rank_ramp(C.c_double(0.0)))
+# a row that counts as solved moves all the same: constant data, single steps, and before step 3 every rank scales its rows
+# alone on their diagonal by 1.5 (pg_debug_set_virtual_rank_kick).  Step 3 has the data of step 2, so no rank looks at
+# those rows; the start phase's all-reduce tells every rank that one moved somewhere, and all of them finish the step on
+# the full system, as one rank does.  ref_max_plain: the same run without the kick (step 0: single steps, nobody kicks)
+L.check(lib.pg_debug_set_virtual_rank_kick(C.c_int64(0), C.c_double(1.0)))
+plain = run(1, 24, 1, [(2.01, 2.01, 2.01)], 6, 1)[0]
+L.check(lib.pg_debug_set_virtual_rank_kick(C.c_int64(3), C.c_double(1.5)))
+ref, n1, nnz1, _, it1 = run(1, 24, 1, [(2.01, 2.01, 2.01)], 6, 1)
+for nr in (2, 3):
+    x, n_own, nnz, ngh, its = run(nr, 24, 1, [(2.01, 2.01, 2.01)], 6, 1)
+    out[f"kick_sphere_{nr}"] = {"rel_l2": float(np.linalg.norm(x - ref) / np.linalg.norm(ref)), "n_own": n_own.tolist(),
+                                "n_total_1": int(n1[0]), "nnz": nnz.tolist(), "nnz_total_1": int(nnz1[0]),
+                                "n_ghost": ngh.tolist(), "iters": its.tolist(), "iters_1": int(it1[0]), "loop": loop_info(nr),
+                                "ref_max": float(np.max(np.abs(ref))), "ref_max_plain": float(np.max(np.abs(plain))),
+                                "kick_effect": float(np.max(np.abs(ref - plain)))}
+L.check(lib.pg_debug_set_virtual_rank_kick(C.c_int64(-1), C.c_double(1.0)))
 # random slab problems: anisotropic 2-D / 3-D grids, a ball anywhere in the box (cut by slab faces, touching borders),
 # 2-4 ranks, BE / CN -- against the same problem on one rank
 rng = np.random.default_rng(77)

@@ -18,7 +18,7 @@ def test_virtual_ranks_reproduce_single_rank():
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert set(out) >= {"sphere_2", "sphere_3", "sphere_4", "two_spheres_2", "two_spheres_4", "gmres_sphere_2", "ramp_sphere_2",
-                        "ramp_sphere_3"}
+                        "ramp_sphere_3", "kick_sphere_2", "kick_sphere_3"}
     assert sum(1 for k in out if k.startswith("random")) == 8
     for case, v in out.items():
         assert v["rel_l2"] <= 1e-12, (case, v)                       # same solution as one rank
@@ -37,10 +37,17 @@ def test_virtual_ranks_reproduce_single_rank():
             for (full, rows, ghosts), ng in zip(v["loop"], v["n_ghost"]):
                 assert 0 < rows < full, (case, v["loop"])
                 assert 0 <= ghosts <= ng, (case, v["loop"], v["n_ghost"])
-                if case.startswith(("sphere", "ramp")):
+                if case.startswith(("sphere", "ramp", "kick")):
                     assert ghosts > 0, (case, v["loop"])             # one body across all slabs: every face exchanges
     for case in ("ramp_sphere_2", "ramp_sphere_3"):
         assert out[case]["ref_max"] > 1.2                            # the ramp reached the field
+    # rows that count as solved were scaled by 1.5 before a step with unchanged data: some rank saw one move, the verdict went
+    # through the start phase's all-reduce and EVERY rank finished that step on the full system, as one rank does (bars above:
+    # the one-rank state to 1e-12, the same iteration count on every rank and as on one rank).  Without it the slabs converge
+    # to a state that lacks the coupling of the moved rows: rel_l2 = 0.104 on both cases, 13 iterations instead of 23.
+    for case in ("kick_sphere_2", "kick_sphere_3"):
+        v = out[case]
+        assert v["ref_max"] > 1.2 and v["ref_max_plain"] < 1.2 and v["kick_effect"] > 0.2, (case, v)   # the kick reached the field
     # one sphere per slab (the weak-scaling body): the partition by active rows is balanced
     v = out["two_spheres_2"]
     assert max(v["n_own"]) <= 1.15 * min(v["n_own"])
