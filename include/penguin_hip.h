@@ -140,7 +140,7 @@ typedef struct {
   int64_t spmv_bytes;     /* bytes one y = A x launch has to move with this format               */
   int64_t spmv_slices;    /* U + P slices + G chunks                                             */
   int64_t rows_uniform;   /* rows in U slices (shared offsets and values, nothing streamed)      */
-  int64_t rows_pattern;   /* rows in P slices (shared offsets, 8 B/entry value stream)           */
+  int64_t rows_pattern;   /* rows in P slices (shared offsets, 8 B/entry value stream) + rows_edge */
   int64_t rows_irregular; /* rows in G chunks (packed CSR, 12 B/entry)                           */
   int64_t neumann_ok;     /* 1: the spectrum of the preconditioned matrix is provably inside |z - 1| < 0.95: BiCGStab
                              runs right-preconditioned with a Chebyshev polynomial in Â (pg_krylov_opts.precond)   */
@@ -153,6 +153,9 @@ typedef struct {
                              keeps the remaining ghosts only; otherwise = n_ghost)                                      */
   int64_t loop_is_compact;/* 1: the warm loop of this system iterates on the compact system (rows alone on their diagonal
                              solved in the right-hand-side pass, pg_reduce.hip) -- on several ranks with halos too     */
+  int64_t rows_edge;      /* edge rows of the marching units: rows at the ends of the marched ranges that share their offsets
+                             but not their values, computed by the units from an 8 B/entry value stream (counted in
+                             rows_pattern too; they are in no slice)                                                    */
 } pg_system_info;
 
 typedef struct {
@@ -445,9 +448,16 @@ int32_t pg_slab_numbering_host(int32_t K, int64_t plane, int64_t nplanes, int64_
 
 /* ---- diagnostics (not part of the reference-facing boundary) ------------------------------------------------ */
 /* y = A x with two kernel variants (PG_SPMV_VARIANT numbering: 70 stencil slices, 38 chunked CSR, 1 first CSR kernel)
-   on the same deterministic vector: max |y_a - y_b| and max |y_a| */
+   on the same deterministic vector: max |y_a - y_b| and max |y_a|.  which: 0 constructor matrix, bit 0 run matrix, bit 2
+   the matrix the warm loop iterates on (as pg_solver_system_info) */
 int32_t pg_debug_spmv_compare(pg_solver* s, int32_t which, int32_t variant_a, int32_t variant_b, double* max_abs_diff,
                               double* max_abs);
+/* one launch mode of the slice kernel (0 plain, 1 and 3 with fused dots, 8 Horner step) against the chunked CSR kernel on the
+   same deterministic vectors: max |y_a - y_b| (the products are accumulated in the same order: 0 is expected), max |y_a|,
+   and the largest relative difference of the fused dot sums (0 for the modes without dots; the partial sums are formed
+   in another order).  which as above */
+int32_t pg_debug_spmv_mode_compare(pg_solver* s, int32_t which, int32_t mode, double* max_abs_diff, double* max_abs,
+                                   double* max_dot_rel);
 /* read-only streaming probe: `bytes` read `reps` times with elem_bytes (4|8) per lane, optional non-temporal hint */
 int32_t pg_debug_read_probe(int64_t bytes, int32_t elem_bytes, int32_t nt, int32_t blocks, int32_t reps, double* gbs);
 /* run the slab-decomposed monophasic path with `nranks` VIRTUAL ranks (host threads sharing this GPU, in-process

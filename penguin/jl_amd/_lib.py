@@ -83,7 +83,7 @@ class pg_system_info(C.Structure):
                 ("rows_uniform", C.c_int64), ("rows_pattern", C.c_int64), ("rows_irregular", C.c_int64),
                 ("neumann_ok", C.c_int64), ("gershgorin", C.c_double), ("spmv_units", C.c_int64),
                 ("rows_marched", C.c_int64), ("rows_matrix", C.c_int64), ("n_ghost_loop", C.c_int64),
-                ("loop_is_compact", C.c_int64)]
+                ("loop_is_compact", C.c_int64), ("rows_edge", C.c_int64)]
 
 
 class pg_streamvort_run_info(C.Structure):

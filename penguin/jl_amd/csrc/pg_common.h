@@ -92,6 +92,7 @@ struct Config {
   int spmv_march_k = 0;           // PG_SPMV_MARCH_K (0: the compiled-in unit depth)
   int spmv_minrun = 24;           // PG_SPMV_MINRUN
   bool spmv_march = true;         // PG_SPMV_MARCH
+  bool spmv_edges = true;         // PG_SPMV_EDGES: irregular rows at the ends of the marched ranges ride with the units
   int spmv_tile_units = 0;        // PG_SPMV_TILE_UNITS
   int spmv_blocks_per_cu = 0;     // PG_SPMV_BLOCKS_PER_CU (0: 4 slice kernel / 6 CSR kernels)
   bool halo_overlap = true;       // PG_HALO_OVERLAP

@@ -56,6 +56,7 @@ const Config& config() {
     k.spmv_march_k = (int)geti("PG_SPMV_MARCH_K", 0);
     k.spmv_minrun = (int)geti("PG_SPMV_MINRUN", 24);
     k.spmv_march = geti("PG_SPMV_MARCH", 1) != 0;
+    k.spmv_edges = geti("PG_SPMV_EDGES", 1) != 0;
     k.spmv_tile_units = (int)geti("PG_SPMV_TILE_UNITS", 0);
     k.spmv_blocks_per_cu = (int)geti("PG_SPMV_BLOCKS_PER_CU", 0);
     k.halo_overlap = geti("PG_HALO_OVERLAP", 1) != 0;
@@ -394,11 +395,11 @@ int32_t pg_config_string(char* buf, size_t n) {
   const Config& k = config();
   char tmp[1024];
   snprintf(tmp, sizeof(tmp),
-           "spmv_variant=%d spmv_xcd=%d spmv_strip=%d spmv_unit_order=%d spmv_march=%d spmv_march_k=%d spmv_minrun=%d spmv_tile_units=%d "
+           "spmv_variant=%d spmv_xcd=%d spmv_strip=%d spmv_unit_order=%d spmv_march=%d spmv_edges=%d spmv_march_k=%d spmv_minrun=%d spmv_tile_units=%d "
            "spmv_blocks_per_cu=%d halo_overlap=%d speculate=%d poly=%d poly_degree=%d poly_adapt=%d "
            "poly_margin=%g poly_slack=%g poly_hist=%d poly_trend=%d poly_maxdeg=%d gamma_elim=%d diag_elim=%d "
            "guess_states=%d guess_depth=%d guess_defer=%d async_alloc=%d cache_limit_mb=%lld alloc_poison=%d alloc_guard=%d profile_sample=%d debug=%d",
-           k.spmv_variant, k.spmv_xcd, k.spmv_strip, k.unit_order, (int)k.spmv_march, k.spmv_march_k, k.spmv_minrun, k.spmv_tile_units,
+           k.spmv_variant, k.spmv_xcd, k.spmv_strip, k.unit_order, (int)k.spmv_march, (int)k.spmv_edges, k.spmv_march_k, k.spmv_minrun, k.spmv_tile_units,
            k.spmv_blocks_per_cu, (int)k.halo_overlap, (int)k.speculate_product, (int)k.poly, k.poly_degree, (int)k.poly_adapt,
            k.poly_margin, k.poly_slack, k.poly_hist, (int)k.poly_trend, k.poly_maxdeg,
            (int)k.gamma_elim, (int)k.diag_elim, k.guess_n, k.guess_depth, (int)k.guess_defer, k.async_alloc, k.pool_limit_mb, k.alloc_poison, k.alloc_guard, k.profile_sample, (int)k.debug);

@@ -106,6 +106,32 @@ struct MarchGeometry {
   int unit_order = 0;
 };
 
+// Edge rows (pg_spmv.hip "edge rows"): irregular rows that sit next to the marched rows of a plane, on the same line of
+// consecutive row numbers, and couple to the same neighbours -- the cells at the ends of a chord, whose values differ from
+// the interior's and whose missing neighbours are missing entries.  A unit computes them from the lines it holds, with
+// per-row values from a stream of their own.  cand: the rows that may become edge rows (the irregular rows), as a compact CSR.
+struct EdgeCands {
+  const int* rows = nullptr;     // row numbers, ascending
+  int64_t nrows = 0;
+  const int* rowptr = nullptr;   // nrows + 1: the entries of candidate q are [rowptr[q], rowptr[q + 1])
+  const int* col = nullptr;
+};
+constexpr int EDGE_SLOTS = 8;      // value slots per edge row in the stream: the 7 of the stencil (5 in 2-D) and padding to 64 bytes
+constexpr int EDGE_PER_END = 8;    // edge rows at one end of a plane
+constexpr int EDGE_PER_UNIT = 64;  // ... of a unit: one lane each
+constexpr int EDGE_REC = 34;       // unit record: dword 34 = first edge row of the unit in the stream, 35 = edge rows of the
+                                   // unit, 36 + i = plane i: rows at the low end | at the high end << 8 | first edge row of the
+                                   // plane, counted from the unit's first << 16
+struct EdgePlan {
+  EdgeCands cand;
+  // out, 4 ints per edge row in stream order: row; index of its slot 0 in the value stream; distance between two of its
+  // PAIRS of slots (the rows of a unit are stored pair-major: slots 2p, 2p + 1 of the unit's e-th row at
+  // 8 first + 2 (p rows_of_unit + e)); slot of the stored entry k in bits 3k..3k+2 | entries << 24
+  std::vector<int> meta;
+  int64_t rows_e = 0;
+  int64_t slots_read = 0;   // value slots the units read for them (the stencil's entries per row)
+};
+
 // place of a grid cell in the order of the work items: strip of lateral lines, then plane; ties by row number
 inline int64_t march_order(int64_t cell, int64_t ext0, int64_t lines, int strip) {
   const int64_t line = (cell / ext0) % lines, plane = cell / (ext0 * lines);
@@ -125,7 +151,7 @@ inline int64_t march_order(int64_t cell, int64_t ext0, int64_t lines, int strip)
 // outside the vector); rows_m: rows covered by units.
 inline void plan_march_units(int64_t n, const std::vector<MRun>& runs, const std::vector<int>& info, const MarchGeometry& geo,
                              std::vector<int>& mrec, std::vector<RowRange>& fallback, int64_t& rows_m,
-                             std::vector<int64_t>* okeys = nullptr) {
+                             std::vector<int64_t>* okeys = nullptr, EdgePlan* edges = nullptr) {
   typedef int64_t i64;
   rows_m = 0;
   const i64 nr = (i64)runs.size();
@@ -167,7 +193,38 @@ inline void plan_march_units(int64_t n, const std::vector<MRun>& runs, const std
     }
     if (best >= 0) { succ[i] = (int)best; pred[best] = (int)i; }
   }
-  struct Unit { int key; int64_t order; int64_t sub; std::vector<int> rec; };
+  struct Unit { int key; int64_t order; int64_t sub; std::vector<int> rec; std::vector<int> erows; };   // erows: (row, slots) pairs
+  // edge rows: candidate `row` against the stencil of run `run` -- its entries, in stored order, must be a subsequence of the
+  // run's entries with the same col - row offsets (and no ghost column); smap: slot per entry (EdgePlan::meta)
+  const bool want_edges = edges && edges->cand.nrows > 0 && geo.REC >= EDGE_REC + 2 + geo.K;
+  std::vector<char> claimed(want_edges ? (size_t)edges->cand.nrows : 0, 0);
+  auto edge_row = [&](i64 row, i64 run, int cnt, int& smap, i64& q) {
+    const EdgeCands& c = edges->cand;
+    if (row < 0 || row >= n) return false;
+    q = std::lower_bound(c.rows, c.rows + c.nrows, (int)row) - c.rows;
+    if (q >= c.nrows || c.rows[q] != row || claimed[q]) return false;
+    const int a = c.rowptr[q], len = c.rowptr[q + 1] - a;
+    if (len < 1 || len > cnt) return false;
+    // a slot the row has no entry for is still multiplied, +0.0 times the element the slot points to: that element must be
+    // one of the matrix' own unknowns too (finite), not the slack behind the vector or a ghost that has not arrived
+    auto inside = [&](int s) { const i64 t = row + off(run, s); return t >= 0 && t < n; };
+    int sl = 0;
+    smap = len << 24;
+    for (int e = 0; e < len; ++e) {
+      const i64 cc = c.col[a + e];
+      if (cc < 0 || cc >= n) return false;
+      while (sl < cnt && off(run, sl) != cc - row) {
+        if (!inside(sl)) return false;
+        ++sl;
+      }
+      if (sl == cnt) return false;
+      smap |= sl << (3 * e);
+      ++sl;
+    }
+    for (; sl < cnt; ++sl)
+      if (!inside(sl)) return false;
+    return true;
+  };
   const bool aligned = geo.unit_order == 1 && geo.strip > 0 && geo.ext0 > 0 && geo.lines > 0 && RI > 24;
   // absolute plane of a run (-1: unknown)
   auto plane_of = [&](i64 run) -> i64 {
@@ -263,6 +320,35 @@ inline void plan_march_units(int64_t n, const std::vector<MRun>& runs, const std
           u.rec[21 + 4 * i] = (int)(lo - W) | ((int)(hi - W) << 8);
           rows_m += hi - lo;
         }
+        if (want_edges) {
+          // rows next to [lo, hi) where the run ends inside the window, outwards until one does not qualify
+          int budget = EDGE_PER_UNIT;
+          for (int i = 0; i < K; ++i) {
+            const i64 q = k + i, run = chain[q];
+            range(q, lo, hi);
+            const i64 a = runs[run].r0 - B[q], b = a + runs[run].len;
+            std::vector<int> lows, highs;
+            int smap = 0;
+            i64 cq = 0;
+            if (lo == a)
+              for (i64 pos = lo - 1; pos >= W + 1 && lo - pos <= EDGE_PER_END && budget > 0 && edge_row(B[q] + pos, run, cnt, smap, cq); --pos) {
+                claimed[cq] = 1; --budget;
+                lows.push_back(smap); lows.push_back((int)(B[q] + pos));
+              }
+            if (hi == b)
+              for (i64 pos = hi; pos <= W + geo.W && pos - hi < EDGE_PER_END && budget > 0 && edge_row(B[q] + pos, run, cnt, smap, cq); ++pos) {
+                claimed[cq] = 1; --budget;
+                highs.push_back((int)(B[q] + pos)); highs.push_back(smap);
+              }
+            const int nlo = (int)lows.size() / 2, nhi = (int)highs.size() / 2;
+            u.rec[EDGE_REC + 2 + i] = nlo | (nhi << 8) | ((int)(u.erows.size() / 2) << 16);
+            u.erows.insert(u.erows.end(), lows.rbegin(), lows.rend());   // ascending rows
+            u.erows.insert(u.erows.end(), highs.begin(), highs.end());
+            hi_max = std::max(hi_max, (int)(hi - W) + nhi);
+          }
+          u.rec[EDGE_REC + 1] = (int)(u.erows.size() / 2);
+          for (int i = K; i < Kp; ++i) u.rec[EDGE_REC + 2 + i] = u.rec[EDGE_REC + 1] << 16;   // closing planes: none
+        }
         // rows < hi_max need elements <= hi_max of the lines: lanes 0 .. hi_max / 2
         u.rec[0] |= std::min(64, hi_max / 2 + 1) << 16;
         for (int i = K; i < Kp; ++i) {
@@ -283,6 +369,24 @@ inline void plan_march_units(int64_t n, const std::vector<MRun>& runs, const std
     return a.sub != b.sub ? a.sub < b.sub : a.key < b.key;
   });
   mrec.reserve(units.size() * geo.REC);
+  if (want_edges) {   // the value stream follows the order of the units
+    i64 first = 0;
+    edges->meta.clear();
+    edges->slots_read = 0;
+    for (auto& u : units) {
+      const int ne = (int)(u.erows.size() / 2);
+      u.rec[EDGE_REC] = (int)first;
+      for (int e = 0; e < ne; ++e) {
+        edges->meta.push_back(u.erows[2 * e]);
+        edges->meta.push_back((int)(EDGE_SLOTS * first + 2 * e));
+        edges->meta.push_back(2 * ne);
+        edges->meta.push_back(u.erows[2 * e + 1]);
+      }
+      first += ne;
+      edges->slots_read += (int64_t)ne * ((((u.rec[0] >> 8) & 255) + 1) & ~1);   // whole pairs
+    }
+    edges->rows_e = first;
+  }
   for (auto& u : units) mrec.insert(mrec.end(), u.rec.begin(), u.rec.end());
   if (okeys) {   // the order as one number per unit (build_tiles lines the slices up with it)
     okeys->clear();

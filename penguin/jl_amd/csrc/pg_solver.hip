@@ -2119,7 +2119,8 @@ int32_t pg_solver_system_info(const pg_solver* s, int32_t which, pg_system_info*
   out->spmv_bytes = A.spmv_bytes;
   out->spmv_slices = A.nslices;
   out->rows_uniform = A.rows_u;
-  out->rows_pattern = A.rows_p;
+  out->rows_pattern = A.rows_p + A.rows_e;
+  out->rows_edge = A.rows_e;
   out->rows_irregular = A.rows_g;
   out->neumann_ok = A.poly_ok ? 1 : 0;
   out->gershgorin = A.gersh;
@@ -2252,15 +2253,29 @@ __global__ void k_test_vector(i64 n, double* x) {
   }
 }
 
+// the matrix pg_solver_system_info(which) describes (bit 0: run matrix, bit 2: the matrix the warm loop iterates on) and the
+// length of the vectors it works on
+static const CsrMatrix& debug_matrix(const pg_solver* s, int32_t which, i64* nv) {
+  if (which & 1) PG_REQUIRE(s->have_run, "run matrix not assembled yet");
+  const CsrMatrix& Af = (which & 1) == 0 ? s->A_ctor : run_matrix(s);
+  const GammaElim& E = (&Af == &s->A_ctor) ? s->elim_ctor : s->elim_run;
+  const DiagElim& DE = (&Af == &s->A_ctor) ? s->diag_ctor : s->diag_run;
+  if ((which & 4) && DE.active) { *nv = DE.nb.n_vec(); return DE.A; }
+  if ((which & 4) && E.active) { *nv = E.nb.n_vec(); return E.A; }
+  *nv = s->nb.n_vec();
+  return Af;
+}
+
 int32_t pg_debug_spmv_compare(pg_solver* s, int32_t which, int32_t variant_a, int32_t variant_b, double* max_abs_diff,
                               double* max_abs) {
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(s && max_abs_diff && max_abs, "pg_debug_spmv_compare: NULL argument");
-  if (which == 1) PG_REQUIRE(s->have_run, "run matrix not assembled yet");
-  const CsrMatrix& A = which == 0 ? s->A_ctor : run_matrix(s);
+  i64 nv = 0;
+  const CsrMatrix& A = debug_matrix(s, which, &nv);
   hipStream_t st = ctx().stream;
-  const i64 n = s->nb.n_own, nv = s->nb.n_vec();
+  const i64 n = A.n;
+  nv = std::max(nv, n);
   *max_abs_diff = 0.0;
   *max_abs = 0.0;
   if (n > 0) {
@@ -2277,6 +2292,18 @@ int32_t pg_debug_spmv_compare(pg_solver* s, int32_t which, int32_t variant_a, in
       *max_abs = std::max(*max_abs, std::fabs(ha[i]));
     }
   }
+  PG_API_END
+}
+
+int32_t pg_debug_spmv_mode_compare(pg_solver* s, int32_t which, int32_t mode, double* max_abs_diff, double* max_abs,
+                                   double* max_dot_rel) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && max_abs_diff && max_abs && max_dot_rel, "pg_debug_spmv_mode_compare: NULL argument");
+  PG_REQUIRE(mode == 0 || mode == 1 || mode == 3 || mode == 8, "pg_debug_spmv_mode_compare: launch modes 0, 1, 3 and 8");
+  i64 nv = 0;
+  const CsrMatrix& A = debug_matrix(s, which, &nv);
+  spmv_mode_compare(A, std::max(nv, A.n), mode, max_abs_diff, max_abs, max_dot_rel);
   PG_API_END
 }
 

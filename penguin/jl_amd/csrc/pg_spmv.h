@@ -226,6 +226,9 @@ bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Sla
                     double* partials, const double* sc, int grid, hipStream_t st, const FinArgs* fin = nullptr);
 // plain y = A x with an explicit kernel variant (PG_SPMV_VARIANT numbering): kernel-vs-kernel parity checks
 void launch_spmv_variant(int variant, const CsrMatrix& A, const double* x, double* y, hipStream_t st);
+// diagnostics: launch mode `mode` (0, 1, 3, 8) of the slice kernel against the chunked CSR kernel on deterministic vectors of
+// length nv: max |y_a - y_b|, max |y_a|, largest relative difference of the fused dot sums
+void spmv_mode_compare(const CsrMatrix& A, i64 nv, int mode, double* max_abs_diff, double* max_abs, double* max_dot_rel);
 int spmv_default_grid(i64 n);
 bool spmv_supports_preconditioner_product();   // mode 8 and FinArgs::dotx exist in the slice kernel only (PG_SPMV_VARIANT)
 

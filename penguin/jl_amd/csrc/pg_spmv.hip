@@ -299,7 +299,9 @@ struct ModeInfo {
 // y of one row from its product s; b = the operand B at the row.  The ONE expression every path of the kernel uses.
 template <int MODE>
 __device__ __forceinline__ double mode_out(double s, double own, double b, double pc0, double pc1, double pc2) {
-  if (MODE == 8) return pc2 * b + (pc0 * own + pc1 * s);
+  // (spelled out: which product of `pc2 b + (pc0 own + pc1 s)` is rounded before the fused adds is otherwise the compiler's
+  // choice, path by path; this is the form it has been emitting -- pc1 s rounded, two fused multiply-adds)
+  if (MODE == 8) return __builtin_fma(pc2, b, __builtin_fma(pc0, own, pc1 * s));
   return s;
 }
 
@@ -435,7 +437,22 @@ __device__ __forceinline__ void slice_dispatch(int cnt, const SDesc& d, int nrow
 //   dword 16, 17       row index held by lane 0 (.x) in the line below the first / above the last plane of the unit
 //   dwords 18 + 4i..   plane i: row index held by lane 0 (.x); offset to the lower / upper lateral neighbour line
 //                      (col - row; 3-D only); lo | hi << 8 = window-relative range [lo, hi) of the rows computed here
+//   dword 34, 35       edge rows of the unit: the first one's number in the stream of edge rows, their count (<= 64)
+//   dwords 36 + i      plane i: edge rows below lo | above hi << 8 | number of the plane's first edge row in the unit << 16
 // build_march_units() forms chains and units on the host from the same row flags the slices are cut from.
+//
+// EDGE ROWS.  The irregular rows at the two ends of a plane's marched range -- the cells where a chord of the fluid meets the
+// body, and their neighbours -- are irregular in their VALUES only: their (col - row) offsets are those of the marched rows
+// next to them on the line, a neighbour that does not exist is a missing entry.  The planner (pg_host_algos.h) hands up to 8 of
+// them per end (64 per unit) to the unit: the lane that computes a window position holds the row's seven x operands already,
+// so all such a row needs from memory is its values -- 7 slots per row in the slot order of the marched rows, +0.0 where the
+// row has no entry (an eighth slot pads the row to 64 bytes), unit by unit and in PAIRS of slots inside a unit: slots 2p, 2p+1
+// of the unit's e-th edge row at e_val[8 first + 2 (p count + e)].  Lane e of the wave loads the pairs of row e with the
+// unit's other loads -- straight into the wave's slice of LDS (global_load_lds_dwordx4: the values never occupy a VGPR while
+// they are in flight, which is when the unit's registers are scarce) -- and the lane that owns the row reads them from there
+// and takes them as the row's coefficients: the products are accumulated in slot order, a +0.0 x term leaves a partial sum as
+// it is, so y is bitwise the CSR kernels' y.  No column index, row pointer or row id is read for these rows, no x element is
+// gathered.
 #ifndef PG_MARCH_K
 #define PG_MARCH_K 4
 #endif
@@ -443,7 +460,8 @@ __device__ __forceinline__ void slice_dispatch(int cnt, const SDesc& d, int nrow
 #define PG_MARCH_SPLIT 1
 #endif
 constexpr int MARCH_K = PG_MARCH_K, MARCH_KS = 2, MARCH_REC = 64, MARCH_W = 126;   // planes per unit: full / short units
-static_assert(MARCH_K > MARCH_KS && 18 + 4 * MARCH_K <= MARCH_REC, "unit record layout");
+constexpr int MARCH_EDGE = pghost::EDGE_REC, MARCH_ESLOTS = pghost::EDGE_SLOTS;   // edge rows: record dwords 34.., slots per row
+static_assert(MARCH_K > MARCH_KS && 18 + 4 * MARCH_K <= MARCH_EDGE && MARCH_EDGE + 2 + MARCH_K <= MARCH_REC, "unit record layout");
 
 __device__ inline double lane_up(double v) {   // the value lane l + 1 holds (lane 63: unspecified)
   return __shfl_down(v, 1, 64);
@@ -454,29 +472,57 @@ struct MarchSide {   // per-plane operands besides the chain's own lines: latera
 };
 
 // rows 2l+1, 2l+2 of one plane from the lines in registers; returns lane l+1's xc.x (the next plane's xm_n)
-template <int CNT, int MODE>
+template <int CNT, int MODE, bool EDGE>
 __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, int l2, double* __restrict__ yrow, const d2_t& xm,
                                               double xm_n, const d2_t& xc, const d2_t& xp, const MarchSide& sd, double pc0,
-                                              double pc1, double pc2, double& acc0, double& acc1, double& acc2, int dbg) {
+                                              double pc1, double pc2, double& acc0, double& acc1, double& acc2, int dbg,
+                                              int einfo, int e_first, const d2_t* el, const d2_t* cl) {
   using MI = ModeInfo<MODE>;
   constexpr bool Y = CNT == 7;
   const double xc_nx = lane_up(xc.x), xc_ny = lane_up(xc.y), xp_n = lane_up(xp.x);
   // entry order of the assembled rows (eval_row, pg_stencil.h): +1, -1, [+lateral, -lateral,] +plane, -plane, diagonal
-  double s1 = 0.0, s2 = 0.0;
-  int j = 0;
-  s1 += c[j] * xc_nx; s2 += c[j] * xc_ny; ++j;
-  s1 += c[j] * xc.x;  s2 += c[j] * xc.y;  ++j;
-  if (Y) {
-    s1 += c[j] * sd.yp.x; s2 += c[j] * sd.yp.y; ++j;
-    s1 += c[j] * sd.ym.x; s2 += c[j] * sd.ym.y; ++j;
+  double a1[CNT], a2[CNT];   // the x operands of rows 2l+1, 2l+2 by slot
+  {
+    int j = 0;
+    a1[j] = xc_nx; a2[j] = xc_ny; ++j;
+    a1[j] = xc.x;  a2[j] = xc.y;  ++j;
+    if (Y) {
+      a1[j] = sd.yp.x; a2[j] = sd.yp.y; ++j;
+      a1[j] = sd.ym.x; a2[j] = sd.ym.y; ++j;
+    }
+    a1[j] = xp.y;  a2[j] = xp_n;  ++j;
+    a1[j] = xm.y;  a2[j] = xm_n;  ++j;
+    a1[j] = xc.y;  a2[j] = xc_nx;
   }
-  s1 += c[j] * xp.y;  s2 += c[j] * xp_n;  ++j;
-  s1 += c[j] * xm.y;  s2 += c[j] * xm_n;  ++j;
-  s1 += c[j] * xc.y;  s2 += c[j] * xc_nx;
+  double s1 = 0.0, s2 = 0.0;
+  int lo = rng & 255, hi = rng >> 8;
+  if (EDGE) {   // edge rows below lo / above hi (einfo; none: no lane takes part): the row's own values out of LDS, not the unit's
+    const int nlo = einfo & 255, nhi = (einfo >> 8) & 255, e0 = (einfo >> 16) - e_first;
+    const int elo = lo - nlo, ehi = hi + nhi, p1 = l2 + 1, p2 = l2 + 2;
+    const bool g1 = p1 >= elo && p1 < ehi && !(p1 >= lo && p1 < hi), g2 = p2 >= elo && p2 < ehi && !(p2 >= lo && p2 < hi);
+    // every lane reads its coefficients from LDS: an edge row's own, or the unit's shared ones (cl) -- a select between a
+    // loaded value and a wave-uniform one would need the latter in VGPRs, 14 of them for the whole unit
+    const d2_t* q1 = g1 ? el + (e0 + (p1 - elo) - (p1 >= hi ? hi - lo : 0)) : cl;
+    const d2_t* q2 = g2 ? el + (e0 + (p2 - elo) - (p2 >= hi ? hi - lo : 0)) : cl;
+#pragma unroll
+    for (int jp = 0; jp < (CNT + 1) / 2; ++jp) {
+      const d2_t w1 = q1[64 * jp], w2 = q2[64 * jp];
+      s1 += w1.x * a1[2 * jp];
+      s2 += w2.x * a2[2 * jp];
+      if (2 * jp + 1 < CNT) {
+        s1 += w1.y * a1[2 * jp + 1];
+        s2 += w2.y * a2[2 * jp + 1];
+      }
+    }
+    lo = elo;
+    hi = ehi;
+  } else {
+#pragma unroll
+    for (int j = 0; j < CNT; ++j) { s1 += c[j] * a1[j]; s2 += c[j] * a2[j]; }
+  }
   // (the row's own x: elements 2l+1, 2l+2 of the centre line)
   s1 = mode_out<MODE>(s1, xc.y, sd.ax2.x, pc0, pc1, pc2);
   s2 = mode_out<MODE>(s2, xc_nx, sd.ax2.y, pc0, pc1, pc2);
-  const int lo = rng & 255, hi = rng >> 8;
   const bool nost = (dbg & 32) && s1 != 1.2345e-300;   // diagnostics: no stores
   const bool allst = (dbg & 512) != 0;                  // diagnostics: every lane stores its pair (whole windows)
   const bool v1 = ((l2 + 1 >= lo && l2 + 1 < hi) || allst) && !nost, v2 = ((l2 + 2 >= lo && l2 + 2 < hi) || allst) && !nost;
@@ -509,10 +555,13 @@ __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, i
 // and a copy waits for the load that fills it (2.2 us per plane, measured).
 // (Q0, KTOT: planes [Q0, Q0 + KK) of a unit of KTOT planes -- the launches with fused dots take a full unit in two halves,
 // see march_dispatch)
-template <int CNT, int MODE, int KK, int Q0 = 0, int KTOT = KK>
+// EDGE: the unit has edge rows.  The two forms are two straight-line bodies: a branch per plane inside one body pins every
+// load of the unit above the first branch and costs ~25 spilled VGPRs (the compiler's report).
+template <int CNT, int MODE, bool EDGE, int KK, int Q0 = 0, int KTOT = KK>
 __device__ __forceinline__ void march_unit(int rec, int lane, const double* __restrict__ x, double* __restrict__ y,
                                   const double* __restrict__ pa, const double* __restrict__ pb, double pc0, double pc1,
-                                  double pc2, double& acc0, double& acc1, double& acc2, int dbg) {
+                                  double pc2, double& acc0, double& acc1, double& acc2, int dbg,
+                                  const double* __restrict__ e_val, double* sv, double* sx) {
   using MI = ModeInfo<MODE>;
   constexpr bool Y = CNT == 7;
   const int amask = (dbg & 128) ? ~1 : ~0;          // diagnostics: every access 16-byte aligned (wrong results)
@@ -552,30 +601,59 @@ __device__ __forceinline__ void march_unit(int rec, int lane, const double* __re
       if (MI::HAS_B) sd[q].ax2 = load_pair<false>(pb + rb[q] + l2 + one);   // (no stream hint: the chain's input is re-read by every launch of the chain and stays in the Infinity Cache -- with the hint a Horner step took 65.7 instead of 53.8 us)
     }
   }
+  // the values of the edge rows of these planes, a row per lane, issued with the lines: pair p of lane e's row lands at
+  // sv[2 (64 p + e)] (a wave instruction writes lane x 16 bytes from its LDS base on)
+  const int e_first = rlane(rec, MARCH_EDGE + 2 + Q0) >> 16;
+  const int e_cnt = (Q0 + KK == KTOT ? rlane(rec, MARCH_EDGE + 1) : rlane(rec, MARCH_EDGE + 2 + Q0 + KK) >> 16) - e_first;
+  // (the lane number as the edge rows' addresses see it is made opaque: hoisted out of the kernel's loops as loop invariants,
+  // those addresses would occupy VGPRs through the slices' code as well, which has none to spare)
+  int elane = lane;
+  if (EDGE) asm volatile("" : "+v"(elane));
+  if (EDGE && e_cnt > 0) {
+    const int e_all = rlane(rec, MARCH_EDGE + 1);
+    const double* ep = e_val + (i64)MARCH_ESLOTS * rlane(rec, MARCH_EDGE) + 2 * (e_first + elane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (the previous unit's reads of these LDS slots have returned)
+    if (elane < e_cnt) {
+#pragma unroll
+      for (int jp = 0; jp < (CNT + 1) / 2; ++jp)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ep + 2 * jp * e_all),
+                                         (__attribute__((address_space(3))) void*)(sv + 128 * jp), 16, 0, 0);
+    }
+    // the LDS writes of these loads count on vmcnt like the loads around them; everything the unit loads is needed now anyway
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  if (EDGE) {
+    // the unit's shared coefficients in the same layout (pair p at sx[128 p]): record dwords 2..15, lane l holds dword l
+    const int k = elane - 2;
+    if (k >= 0 && k < 2 * CNT) reinterpret_cast<int*>(sx)[256 * (k >> 2) + (k & 3)] = rec;
+  }
+  const d2_t* el = reinterpret_cast<const d2_t*>(sv);
+  const d2_t* cl = reinterpret_cast<const d2_t*>(sx);
   double xm_n = lane_up(ln[0].x);
 #pragma unroll
   for (int q = 0; q < KK; ++q)
-    xm_n = march_plane<CNT, MODE>(c, rlane(rec, 21 + 4 * (Q0 + q)), l2, y + rb[q] + l2 + one, ln[q], xm_n, ln[q + 1], ln[q + 2], sd[q], pc0,
-                                  pc1, pc2, acc0, acc1, acc2, dbg);
+    xm_n = march_plane<CNT, MODE, EDGE>(c, rlane(rec, 21 + 4 * (Q0 + q)), l2, y + rb[q] + l2 + one, ln[q], xm_n, ln[q + 1], ln[q + 2], sd[q], pc0,
+                                  pc1, pc2, acc0, acc1, acc2, dbg, rlane(rec, MARCH_EDGE + 2 + Q0 + q), e_first, el, cl);
 }
 
-template <int CNT, int MODE>
+template <int CNT, int MODE, bool EDGE>
 __device__ __forceinline__ void march_dispatch(int rec, int lane, const double* __restrict__ x, double* __restrict__ y,
                                       const double* __restrict__ pa, const double* __restrict__ pb, double pc0, double pc1,
-                                      double pc2, double& acc0, double& acc1, double& acc2, int dbg) {
-  // The launches with fused dots and one or two more operand vectors per plane (modes 1, 3: the closing launch of an
-  // application of the operator) do not fit a unit of MARCH_K planes into the 128 VGPRs of four waves per SIMD: they take it
-  // in two halves -- two more line loads per unit, which hit L1
-  constexpr bool SPLIT = (MODE == 1 || MODE == 3) && MARCH_K == 2 * MARCH_KS && PG_MARCH_SPLIT;
+                                      double pc2, double& acc0, double& acc1, double& acc2, int dbg,
+                                      const double* __restrict__ e_val, double* sv, double* sx) {
+  // The launch with three fused dots and two more operand vectors per plane (mode 3) does not fit a unit of MARCH_K planes into
+  // the 128 VGPRs of four waves per SIMD: it takes it in two halves -- two more line loads per unit, which hit L1.  (Mode 1, one
+  // operand vector, fits a whole unit: 127 VGPRs, no scratch.)
+  constexpr bool SPLIT = MODE == 3 && MARCH_K == 2 * MARCH_KS && PG_MARCH_SPLIT;
   if ((rlane(rec, 0) & 255) == MARCH_K) {
     if (SPLIT) {
-      march_unit<CNT, MODE, MARCH_KS, 0, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg);
-      march_unit<CNT, MODE, MARCH_KS, MARCH_KS, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg);
+      march_unit<CNT, MODE, EDGE, MARCH_KS, 0, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+      march_unit<CNT, MODE, EDGE, MARCH_KS, MARCH_KS, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
     } else {
-      march_unit<CNT, MODE, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg);
+      march_unit<CNT, MODE, EDGE, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
     }
   } else {
-    march_unit<CNT, MODE, MARCH_KS>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg);
+    march_unit<CNT, MODE, EDGE, MARCH_KS>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
   }
 }
 
@@ -590,7 +668,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
                                                   double* __restrict__ y, const double* __restrict__ aux,
                                                   double* __restrict__ partials, const double* __restrict__ sc, int xcd,
                                                   FinArgs fin, int pstride, int accum, const int* __restrict__ mrec,
-                                                  i64 nunits, const int* __restrict__ tiles, int tpx) {
+                                                  i64 nunits, const int* __restrict__ tiles, int tpx,
+                                                  const double* __restrict__ e_val) {
   __shared__ __attribute__((aligned(16))) double s_val[BLOCK / 64][512];
   __shared__ __attribute__((aligned(16))) double s_x[BLOCK / 64][512];   // G chunks: x[col] of every entry of the chunk
   __shared__ double s_red[BLOCK / 64];
@@ -644,40 +723,45 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
     ubase = ulo = 0; uhi = nunits;
     sbase = slo = 0; shi = nslices;
   }
-#pragma nounroll
-  for (int phase = 0; phase < 2; ++phase) {
-  if ((phase == 0) != ((dbg & 4096) != 0)) {   // (diagnostics, bit 4096: slices before units)
+  // (two bodies in program order, not a loop over two phases: hoisted out of such a loop, the first record addresses of the
+  // slices were held -- spilled -- across the units)
+  auto run_units = [&]() __attribute__((always_inline)) {
   if (nunits > 0) {
     int d = (woff - (int)(ulo - ubase)) % wstr;
     d = d < 0 ? d + wstr : d;
     i64 ucur = ulo + d;
     const i64 ustride = wstr;
-    int urec = ucur < uhi ? mrec[MARCH_REC * ucur + lane] : 0;
+    // (record addresses as base + 32-bit offset: one VGPR instead of a 64-bit address pair held across the unit's body)
+    int urec = ucur < uhi ? mrec[(unsigned)(MARCH_REC * (int)ucur + lane)] : 0;
     for (; ucur < uhi; ucur += ustride) {
       const i64 un = ucur + ustride;
-      const int urec_n = mrec[MARCH_REC * (un < uhi ? un : ucur) + lane];   // the next unit's record is in flight meanwhile
+      const int urec_n = mrec[(unsigned)(MARCH_REC * (int)(un < uhi ? un : ucur) + lane)];   // the next unit's record is in flight meanwhile
       if (!(dbg & 16)) {
-        if (((rlane(urec, 0) >> 8) & 255) == 7)
-          march_dispatch<7, MODE>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg);
-        else
-          march_dispatch<5, MODE>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg);
+        const bool edge = rlane(urec, MARCH_EDGE + 1) > 0;
+        if (((rlane(urec, 0) >> 8) & 255) == 7) {
+          if (edge) march_dispatch<7, MODE, true>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+          else march_dispatch<7, MODE, false>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+        } else {
+          if (edge) march_dispatch<5, MODE, true>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+          else march_dispatch<5, MODE, false>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+        }
       }
       urec = urec_n;
     }
   }
-  continue;
-  }
+  };
+  auto run_slices = [&]() __attribute__((always_inline)) {
   int ds_ = (woff - (int)(slo - sbase)) % wstr;
   ds_ = ds_ < 0 ? ds_ + wstr : ds_;
   const i64 first = slo + ds_, wstride = wstr, hi = shi;
   const i64 lastc = hi - 1;
   // the record of a slice is fetched with ONE vector load TWO slices ahead (lane l reads dword l & 31) and its
   // wave-uniform fields are broadcast with v_readlane
-  int rec = first < hi ? srec[SL_REC * first + l31] : 0;
-  int rec_n = srec[SL_REC * (first + wstride < hi ? first + wstride : (first < hi ? lastc : 0)) + l31];
+  int rec = first < hi ? srec[(unsigned)(SL_REC * (int)first + l31)] : 0;
+  int rec_n = srec[(unsigned)(SL_REC * (int)(first + wstride < hi ? first + wstride : (first < hi ? lastc : 0)) + l31)];
   for (i64 chunk = first; chunk < hi; chunk += wstride) {
     const i64 cnn = chunk + 2 * wstride;
-    const int rec_nn = srec[SL_REC * (cnn < hi ? cnn : lastc) + l31];
+    const int rec_nn = srec[(unsigned)(SL_REC * (int)(cnn < hi ? cnn : lastc) + l31)];
     SDesc d;
     d.r0 = rlane(rec, 0); d.meta = rlane(rec, 1); d.base = rlane(rec, 2); d.aux = rlane(rec, 3);
     const int nrows = d.meta & 255, type = (d.meta >> 8) & 3, cnt = d.meta >> 16;
@@ -751,7 +835,9 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
     rec = rec_n;
     rec_n = rec_nn;
   }
-  }   // phases
+  };
+  if (DIAG && (dbg & 4096)) { run_slices(); run_units(); }   // (diagnostics, bit 4096: slices before units)
+  else { run_units(); run_slices(); }
   }   // tiles
   // (write-through stores: the last block of this launch may read them, see fold_scalar_phase)
   // pstride = blocks per partial slot (the grid the Krylov workspace was sized for; >= gridDim.x).  accum: this launch
@@ -817,7 +903,7 @@ __global__ void k_gpack(i64 ng, const int* __restrict__ g_rowid, const int* __re
     const int r = g_rowid[q], a = rowptr[r], len = rowptr[r + 1] - a, ga = g_rowptr[q];
     for (int k = 0; k < len; ++k) {
       g_col[ga + k] = col[a + k];
-      g_val[ga + k] = val[a + k];
+      if (g_val) g_val[ga + k] = val[a + k];   // (nullptr: the columns alone)
     }
   }
 }
@@ -852,6 +938,9 @@ int xcd_map() {
 void ensure_csr_chunks(const CsrMatrix& A);
 namespace {
 
+#define PG_LAUNCH_C_ARGS(KERNEL, X, Y, AUX, PART)                                                               \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), dim3(grid), dim3(BLOCK), 0, st, A.n, A.nchunks, A.chunk_desc.p, \
+                     A.rowptr.p, A.col.p, A.val.p, X, Y, AUX, PART, (const double*)nullptr)
 #define PG_LAUNCH_C(KERNEL)                                                                                    \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL), dim3(grid), dim3(BLOCK), 0, st, A.n, A.nchunks, A.chunk_desc.p, \
                      A.rowptr.p, A.col.p, A.val.p, x, y, aux, partials, sc)
@@ -870,15 +959,15 @@ bool launch_slices(int v, const CsrMatrix& A, i64 s0, i64 ns, const double* x, d
   if (xcd_map() >= 256)   // diagnostic switches set: the diagnostic build (wrong products; ablation runs only)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_s<MODE, true, true>), dim3(grid), dim3(BLOCK), 0, st, ns, rec, A.pval.p,
                        A.g_rowid.p, A.g_rowptr.p, A.g_col.p, A.g_val.p, x, y, aux, partials, sc, xcd_map(), fa, pstride, accum,
-                       (const int*)A.mrec.p, nu, tiles, tpx);
+                       (const int*)A.mrec.p, nu, tiles, tpx, (const double*)A.e_val.p);
   else if (v & 4)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_s<MODE, true, false>), dim3(grid), dim3(BLOCK), 0, st, ns, rec, A.pval.p,
                        A.g_rowid.p, A.g_rowptr.p, A.g_col.p, A.g_val.p, x, y, aux, partials, sc, xcd_map(), fa, pstride, accum,
-                       (const int*)A.mrec.p, nu, tiles, tpx);
+                       (const int*)A.mrec.p, nu, tiles, tpx, (const double*)A.e_val.p);
   else
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_s<MODE, false, false>), dim3(grid), dim3(BLOCK), 0, st, ns, rec, A.pval.p,
                        A.g_rowid.p, A.g_rowptr.p, A.g_col.p, A.g_val.p, x, y, aux, partials, sc, xcd_map(), fa, pstride, accum,
-                       (const int*)A.mrec.p, nu, tiles, tpx);
+                       (const int*)A.mrec.p, nu, tiles, tpx, (const double*)A.e_val.p);
   return fa.ticket != nullptr;
 }
 
@@ -942,6 +1031,34 @@ __global__ void k_fill_units(i64 nunits, int* __restrict__ mrec, const int* __re
       rec[3 + 2 * k] = __double2hiint(val[a + k]);
     }
   }
+}
+
+// value stream of the edge rows (pghost::EdgePlan::meta: row, slot 0, distance between pairs of slots, slot per entry): +0.0
+// where the row has no entry
+__global__ void k_fill_edges(i64 ne, const int* __restrict__ meta, const int* __restrict__ rowptr, const double* __restrict__ val,
+                             double* __restrict__ e_val) {
+  for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < ne; q += (i64)gridDim.x * blockDim.x) {
+    const int r = meta[4 * q], dst = meta[4 * q + 1], dist = meta[4 * q + 2], sm = meta[4 * q + 3];
+    const int a = rowptr[r], len = sm >> 24;
+    for (int j = 0; j < MARCH_ESLOTS; ++j) e_val[dst + (i64)(j >> 1) * dist + (j & 1)] = 0.0;
+    for (int k = 0; k < len; ++k) {
+      const int j = (sm >> (3 * k)) & 7;
+      e_val[dst + (i64)(j >> 1) * dist + (j & 1)] = val[a + k];
+    }
+  }
+}
+
+// do the edge rows of T's image have T's columns in A as well?
+__global__ void k_edges_invalid(i64 ne, const int* __restrict__ meta, const int* __restrict__ rowptr_t, const int* __restrict__ col_t,
+                                const int* __restrict__ rowptr, const int* __restrict__ col, unsigned long long* __restrict__ out) {
+  unsigned long long c = 0;
+  for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < ne; q += (i64)gridDim.x * blockDim.x) {
+    const int r = meta[4 * q], a = rowptr[r], at = rowptr_t[r], len = rowptr[r + 1] - a;
+    bool same = len == rowptr_t[r + 1] - at && len == (meta[4 * q + 3] >> 24);
+    for (int k = 0; same && k < len; ++k) same = col[a + k] == col_t[at + k];
+    c += same ? 0 : 1;
+  }
+  if (c) atomicAdd(out, c);
 }
 
 // do the rows of every unit still share one stencil?  (rows after the first of a plane repeat their predecessor --
@@ -1011,7 +1128,7 @@ void emit_u_rows(std::vector<Slice>& up, i64 a, i64 b, int cnt) {
 // AddressSanitizer / UBSan, into the CPU test-suite); here: the run descriptors come from the device and the result goes
 // back.  Rows that cannot march are appended to `up` as U slices.
 void build_march_units(CsrMatrix& A, const std::vector<MRun>& runs, std::vector<int>& mrec, std::vector<Slice>& up,
-                       std::vector<i64>& ukeys) {
+                       std::vector<i64>& ukeys, pghost::EdgePlan* edges) {
   A.rows_m = 0;
   const i64 nr = (i64)runs.size();
   if (nr == 0) return;
@@ -1032,7 +1149,7 @@ void build_march_units(CsrMatrix& A, const std::vector<MRun>& runs, std::vector<
                             has_geo(A) ? config().unit_order : 0};
   std::vector<pghost::RowRange> fallback;
   i64 rows_m = 0;
-  pghost::plan_march_units(A.n, runs, info, geo, mrec, fallback, rows_m, &ukeys);
+  pghost::plan_march_units(A.n, runs, info, geo, mrec, fallback, rows_m, &ukeys, edges);
   A.rows_m = rows_m;
   for (const auto& f : fallback) emit_u_rows(up, f.a, f.b, f.cnt);
 }
@@ -1150,7 +1267,43 @@ void build_slices(CsrMatrix& A, const int* rp) {
   // marching units out of the stencil runs; what cannot march comes back as U slices
   std::vector<int> mrec;
   std::vector<i64> ukeys;
-  build_march_units(A, runs, mrec, up, ukeys);
+  // the irregular rows are the candidates for edge rows: their columns, as a compact CSR (the rows arrive in ascending order)
+  pghost::EdgePlan edges;
+  std::vector<int> c_ptr, c_col;
+  if (!runs.empty() && !grows.empty() && config().spmv_edges) {
+    const i64 nc = (i64)grows.size();
+    c_ptr.assign(nc + 1, 0);
+    for (i64 q = 0; q < nc; ++q) c_ptr[q + 1] = c_ptr[q] + (rp[grows[q] + 1] - rp[grows[q]]);
+    c_col.resize((size_t)c_ptr[nc] + 1);
+    DevBuf<int> d_rows(nc), d_ptr(nc + 1), d_col(c_ptr[nc] + 8);
+    d_rows.upload(grows.data(), nc);
+    d_ptr.upload(c_ptr.data(), nc + 1);
+    hipLaunchKernelGGL(k_gpack, dim3(grid_for(nc, 256)), dim3(256), 0, st, nc, d_rows.p, d_ptr.p, A.rowptr.p, A.col.p, A.val.p,
+                       d_col.p, (double*)nullptr);
+    PG_HIP(hipGetLastError());
+    if (c_ptr[nc] > 0) d_col.download(c_col.data(), c_ptr[nc]);
+    edges.cand = pghost::EdgeCands{grows.data(), nc, c_ptr.data(), c_col.data()};
+  }
+  build_march_units(A, runs, mrec, up, ukeys, &edges);
+  A.rows_e = edges.rows_e;
+  A.e_slots = edges.slots_read;
+  A.e_meta.alloc(std::max<i64>((i64)edges.meta.size(), 1));
+  A.e_val.alloc((i64)MARCH_ESLOTS * A.rows_e + 8);
+  A.e_val.zero();
+  if (A.rows_e > 0) {
+    A.e_meta.upload(edges.meta.data(), (i64)edges.meta.size());
+    hipLaunchKernelGGL(k_fill_edges, dim3(grid_for(A.rows_e, 256)), dim3(256), 0, st, A.rows_e, (const int*)A.e_meta.p, A.rowptr.p,
+                       A.val.p, A.e_val.p);
+    PG_HIP(hipGetLastError());
+    // they leave the irregular rows
+    std::vector<int> er((size_t)A.rows_e);
+    for (i64 q = 0; q < A.rows_e; ++q) er[q] = edges.meta[4 * q];
+    std::sort(er.begin(), er.end());
+    size_t w = 0;
+    for (size_t q = 0; q < grows.size(); ++q)
+      if (!std::binary_search(er.begin(), er.end(), grows[q])) grows[w++] = grows[q];
+    grows.resize(w);
+  }
   A.nunits = (i64)mrec.size() / MARCH_REC;
   A.mrec.alloc(std::max<i64>((i64)mrec.size(), 1));
   if (!mrec.empty()) A.mrec.upload(mrec.data(), (i64)mrec.size());
@@ -1280,10 +1433,10 @@ void build_slices(CsrMatrix& A, const int* rp) {
   }
   PG_HIP(hipStreamSynchronize(st));
   laps.lap("    slices: packing + records");
-  A.spmv_bytes = 4 * SL_REC * A.nslices + 4 * MARCH_REC * A.nunits + 8 * A.nnz_p + 12 * A.nnz_g + 8 * ng + 16 * n;
+  A.spmv_bytes = 4 * SL_REC * A.nslices + 4 * MARCH_REC * A.nunits + 8 * A.nnz_p + 12 * A.nnz_g + 8 * ng + 8 * A.e_slots + 16 * n;
   if (config().debug)
-    fprintf(stderr, "[pg_spmv] slices %lld (%lld wait for the halo), marching units %lld (%lld rows): rows U %lld P %lld G %lld of %lld; nnz P %lld G %lld of %lld; bytes/launch %lld (CSR %lld)\n",
-            (long long)A.nslices, (long long)(A.nslices - A.nslices_int), (long long)A.nunits, (long long)A.rows_m, (long long)A.rows_u, (long long)A.rows_p, (long long)A.rows_g,
+    fprintf(stderr, "[pg_spmv] slices %lld (%lld wait for the halo), marching units %lld (%lld rows, %lld edge rows): rows U %lld P %lld G %lld of %lld; nnz P %lld G %lld of %lld; bytes/launch %lld (CSR %lld)\n",
+            (long long)A.nslices, (long long)(A.nslices - A.nslices_int), (long long)A.nunits, (long long)A.rows_m, (long long)A.rows_e, (long long)A.rows_u, (long long)A.rows_p, (long long)A.rows_g,
             (long long)n, (long long)A.nnz_p, (long long)A.nnz_g, (long long)A.nnz, (long long)A.spmv_bytes,
             (long long)(12 * A.nnz + 20 * n));
 }
@@ -1363,6 +1516,9 @@ bool build_slices_like(const CsrMatrix& T, CsrMatrix& A) {
   if (T.nunits > 0)
     hipLaunchKernelGGL(k_units_invalid, dim3((unsigned)std::min<i64>(T.nunits, 16384)), dim3(64), 0, st, T.nunits, T.mrec.p,
                        A.rowptr.p, A.val.p, A.rowflags.p, diff.p);
+  if (T.rows_e > 0)
+    hipLaunchKernelGGL(k_edges_invalid, dim3(grid_for(T.rows_e, 256)), dim3(256), 0, st, T.rows_e, (const int*)T.e_meta.p,
+                       (const int*)T.rowptr.p, (const int*)T.col.p, (const int*)A.rowptr.p, (const int*)A.col.p, diff.p);
   PG_HIP(hipGetLastError());
   unsigned long long h = 0;
   diff.download(&h, 1);
@@ -1381,6 +1537,13 @@ bool build_slices_like(const CsrMatrix& T, CsrMatrix& A) {
   clone_buf(A.mrec, T.mrec, st);
   if (A.nunits > 0)
     hipLaunchKernelGGL(k_fill_units, dim3(grid_for(A.nunits, 256)), dim3(256), 0, st, A.nunits, A.mrec.p, A.rowptr.p, A.val.p);
+  A.rows_e = T.rows_e; A.e_slots = T.e_slots;
+  clone_buf(A.e_meta, T.e_meta, st);
+  A.e_val.alloc((i64)MARCH_ESLOTS * A.rows_e + 8);
+  A.e_val.zero();
+  if (A.rows_e > 0)
+    hipLaunchKernelGGL(k_fill_edges, dim3(grid_for(A.rows_e, 256)), dim3(256), 0, st, A.rows_e, (const int*)A.e_meta.p, A.rowptr.p,
+                       A.val.p, A.e_val.p);
   clone_buf(A.srec, T.srec, st);
   clone_buf(A.g_rowid, T.g_rowid, st);
   clone_buf(A.g_rowptr, T.g_rowptr, st);
@@ -1460,6 +1623,80 @@ bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Sla
   else { PG_REQUIRE(mode == 3, "unknown SpMV launch mode"); PG_SPLIT(3); }
 #undef PG_SPLIT
   return folded;
+}
+
+namespace {
+
+__global__ void k_hash_vector(i64 n, unsigned long long seed, double* x) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
+    unsigned long long h = ((unsigned long long)i + seed) * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+    h ^= h >> 29; h *= 0xBF58476D1CE4E5B9ull; h ^= h >> 32;
+    x[i] = (double)(h >> 11) * (1.0 / 9007199254740992.0) - 0.5;
+  }
+}
+
+// the epilogue of launch mode MODE on a plain product s (in y): the expression the slice kernel uses
+template <int MODE>
+__global__ void k_mode_epilogue(i64 n, double* __restrict__ y, const double* __restrict__ x, const double* __restrict__ b, double pc0,
+                                double pc1, double pc2) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x)
+    y[i] = mode_out<MODE>(y[i], x[i], b[i], pc0, pc1, pc2);
+}
+
+template <int MODE>
+void mode_compare(const CsrMatrix& A, i64 nv, double* max_abs_diff, double* max_abs, double* max_dot_rel) {
+  hipStream_t st = ctx().stream;
+  const i64 n = A.n;
+  const int grid = spmv_default_grid(n);
+  DevBuf<double> x(nv), aux(nv), base(nv), ya(n), yb(n), pa(5 * (i64)grid), pb(5 * (i64)grid);
+  hipLaunchKernelGGL(k_hash_vector, dim3(grid_for(nv, BLOCK)), dim3(BLOCK), 0, st, nv, 0ull, x.p);
+  hipLaunchKernelGGL(k_hash_vector, dim3(grid_for(nv, BLOCK)), dim3(BLOCK), 0, st, nv, 0x5851F42D4C957F2Dull, aux.p);
+  hipLaunchKernelGGL(k_hash_vector, dim3(grid_for(nv, BLOCK)), dim3(BLOCK), 0, st, nv, 0x14057B7EF767814Full, base.p);
+  pa.zero();
+  pb.zero();
+  FinArgs fin{nullptr, nullptr, PH_NONE, 0, 0, nullptr};
+  fin.pc0 = 0.75; fin.pc1 = -0.4375; fin.pc2 = 1.25;
+  fin.base = base.p;
+  launch_slices<MODE>(70, A, 0, A.nslices, x.p, ya.p, aux.p, pa.p, nullptr, grid, grid, 0, st, MODE == 8 ? &fin : nullptr);
+  ensure_csr_chunks(A);
+  if (MODE == 8) {
+    PG_LAUNCH_C_ARGS((k_spmv_cw<0, true>), x.p, yb.p, aux.p, pb.p);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mode_epilogue<MODE>), dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, st, n, yb.p,
+                       (const double*)x.p, (const double*)base.p, fin.pc0, fin.pc1, fin.pc2);
+  } else {
+    PG_LAUNCH_C_ARGS((k_spmv_cw<(MODE == 8 ? 0 : MODE), true>), x.p, yb.p, aux.p, pb.p);
+  }
+  PG_HIP(hipGetLastError());
+  std::vector<double> ha(n), hb(n), qa(5 * (size_t)grid), qb(5 * (size_t)grid);
+  ya.download(ha.data(), n);
+  yb.download(hb.data(), n);
+  pa.download(qa.data(), 5 * (i64)grid);
+  pb.download(qb.data(), 5 * (i64)grid);
+  *max_abs_diff = *max_abs = *max_dot_rel = 0.0;
+  for (i64 i = 0; i < n; ++i) {
+    *max_abs_diff = std::max(*max_abs_diff, std::fabs(ha[i] - hb[i]));
+    *max_abs = std::max(*max_abs, std::fabs(ha[i]));
+  }
+  // dot slots of the launch modes (pg_spmv.h): 0 always, 1 and 4 with mode 3
+  const int slots[3] = {0, 1, 4};
+  const int nslot = MODE == 1 ? 1 : (MODE == 3 ? 3 : 0);
+  for (int k = 0; k < nslot; ++k) {
+    double a = 0.0, b = 0.0;
+    for (int i = 0; i < grid; ++i) { a += qa[(size_t)slots[k] * grid + i]; b += qb[(size_t)slots[k] * grid + i]; }
+    *max_dot_rel = std::max(*max_dot_rel, std::fabs(a - b) / std::max(std::fabs(b), 1e-300));
+  }
+}
+
+}  // namespace
+
+void spmv_mode_compare(const CsrMatrix& A, i64 nv, int mode, double* max_abs_diff, double* max_abs, double* max_dot_rel) {
+  *max_abs_diff = *max_abs = *max_dot_rel = 0.0;
+  if (A.n == 0) return;
+  PG_REQUIRE(A.srec.p, "spmv_mode_compare: the matrix has no slice image");
+  if (mode == 0) mode_compare<0>(A, nv, max_abs_diff, max_abs, max_dot_rel);
+  else if (mode == 1) mode_compare<1>(A, nv, max_abs_diff, max_abs, max_dot_rel);
+  else if (mode == 3) mode_compare<3>(A, nv, max_abs_diff, max_abs, max_dot_rel);
+  else mode_compare<8>(A, nv, max_abs_diff, max_abs, max_dot_rel);
 }
 
 void launch_spmv_variant(int v, const CsrMatrix& A, const double* x, double* y, hipStream_t st) {

@@ -62,6 +62,12 @@ struct CsrMatrix {
   // stencil rows; these rows are in no slice
   DevBuf<int> mrec;
   i64 nunits = 0, rows_m = 0;
+  // edge rows of the units (pg_spmv.hip "edge rows"): irregular rows at the ends of the marched ranges, computed by the units
+  // from per-row values; e_val = 7 slots per row, e_meta = where each row's entries go (pghost::EdgePlan::meta); these rows
+  // are in no slice either.  e_slots = value slots the units read for them
+  DevBuf<int> e_meta;
+  DevBuf<double> e_val;
+  i64 rows_e = 0, e_slots = 0;
   // tile table of the slice kernel (pg_host_algos.h plan_tiles): 8 x (tiles_per_xcd + 1) x {first unit, first slice}; covers
   // the units and the slices [0, tile_ns) = [0, nslices_int)
   DevBuf<int> tiles;
