@@ -425,7 +425,10 @@ int32_t pg_solver_get_state(const pg_solver* s, int64_t state_index, double* x, 
           interface rows") once a loop step has built it; identical to 2 / 3 otherwise. */
 int32_t pg_solver_system_info(const pg_solver* s, int32_t which, pg_system_info* out);
 /* reduced system of this rank as CSR (rowptr n_own+1, col nnz (local numbering: owned then ghosts), val nnz)
-   plus b (n_own) and the map idx[n_own] -> index in the full 2M/4M vector (the reference's common_idx). */
+   plus b (n_own) and the map idx[n_own] -> index in the full 2M/4M vector (the reference's common_idx).
+   which = 6 / 7: the matrix pg_solver_system_info(6 / 7) describes, i.e. what the warm loop multiplies by: rowptr has
+   rows_matrix + 1 entries, col is in THAT matrix's local numbering (pg_debug_spmv_sizes gives the vector length), nnz as
+   pg_solver_system_info(6 / 7); b and idx belong to the full system and must be NULL. */
 int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* rowptr, int64_t* col, double* val,
                                  double* b, int64_t* idx);
 /* S = diag(|a_ii|^-1/2) of system `which` (0 constructor, 1 run): the weights of the convergence test
@@ -455,9 +458,39 @@ int32_t pg_debug_spmv_compare(pg_solver* s, int32_t which, int32_t variant_a, in
 /* one launch mode of the slice kernel (0 plain, 1 and 3 with fused dots, 8 Horner step) against the chunked CSR kernel on the
    same deterministic vectors: max |y_a - y_b| (the products are accumulated in the same order: 0 is expected), max |y_a|,
    and the largest relative difference of the fused dot sums (0 for the modes without dots; the partial sums are formed
-   in another order).  which as above */
+   in another order).  which as above.  Kernel against kernel on one vector pattern: launch mode 2, a dot operand other than
+   x (FinArgs::dotx), the scalar phase folded into the launch and the done flag are not reached from here -- they are covered
+   by pg_debug_spmv_apply and its tests against a host product (tests/test_gpu_spmv_host_reference.py) */
 int32_t pg_debug_spmv_mode_compare(pg_solver* s, int32_t which, int32_t mode, double* max_abs_diff, double* max_abs,
                                    double* max_dot_rel);
+/* sizes of the matrix pg_debug_spmv_compare / _apply work on (which as above): its rows n, the length n_vec >= n of the
+   vectors it multiplies (own rows, then ghosts, in its own local numbering), its entries, and the grid (blocks) the Krylov
+   driver launches the product with = the number of partial sums per dot slot */
+int32_t pg_debug_spmv_sizes(pg_solver* s, int32_t which, int64_t* n, int64_t* n_vec, int64_t* nnz, int32_t* grid);
+/* ONE product launch as the Krylov driver issues it (launch_spmv of pg_spmv.h, grid as above), on host data, with everything
+   it wrote handed back: what the kernel-vs-kernel comparisons above cannot see -- launch mode 2, a (y, .) dot whose operand
+   is not the launch's x, mode 8 with base == x, the scalar phase folded into the launch, the return at the done flag -- is
+   checked against an extended-precision product on the host (tests/spmv_reference.py, tests/test_gpu_spmv_host_reference.py).
+     variant  70 slices, 38 / 2 chunked CSR, 1 first CSR kernel.  Mode 8, dotx and fold exist in the slice kernel only: refused
+              elsewhere, never emulated.
+     mode     0: y = A x; 1: + (aux, y); 2: + (d, y), (y, y); 3: + (d, y), (y, y), (aux, y), d = dotx or, when NULL, x;
+              8: y = pc2 base + pc0 x + pc1 A x (base NULL: base is the device copy of x itself, as the first step of the
+              preconditioner's chain passes it).
+     x n_vec; aux (modes 1, 3), dotx (modes 2, 3; optional), base (mode 8; optional): n each, NULL otherwise.
+     fold     0: partial sums only.  1 (modes 1 - 3): the last block sums the slots [0, nslots) of the partials into the scalar
+              block, nslots = 1 / 2 / 5 for modes 1 / 2 / 3 (mode 3 writes slots 0, 1 and 4; 2 and 3 hold zeros here), without
+              deriving a phase.
+     done     stored at the done flag of the scalar block before the launch (!= 0: the kernel must return at once).
+     repeat   1 or 2 launches back to back on the same buffers.
+   Out: y (n + 64: 64 guard words behind row n), partials (5 * grid, slot-major; may be NULL), slot_sums (5: every slot's
+   partials summed on the host in index order), folded (5: what the launch left in the scalar block's sum slots) and the
+   ticket word after the last launch.  y, partials and the sum slots are filled with PG_DEBUG_SPMV_SENTINEL (a NaN) before
+   the first launch: whatever the launch did not write still holds it. */
+#define PG_DEBUG_SPMV_SENTINEL 0x7FF8C0DE5EED0BADull
+int32_t pg_debug_spmv_apply(pg_solver* s, int32_t which, int32_t variant, int32_t mode, const double* x, const double* aux,
+                            const double* dotx, const double* base, double pc0, double pc1, double pc2, int32_t fold,
+                            int32_t done, int32_t repeat, double* y, double* partials, double* slot_sums, double* folded,
+                            int64_t* ticket);
 /* read-only streaming probe: `bytes` read `reps` times with elem_bytes (4|8) per lane, optional non-temporal hint */
 int32_t pg_debug_read_probe(int64_t bytes, int32_t elem_bytes, int32_t nt, int32_t blocks, int32_t reps, double* gbs);
 /* run the slab-decomposed monophasic path with `nranks` VIRTUAL ranks (host threads sharing this GPU, in-process

@@ -216,3 +216,56 @@ def config_string() -> str:
     buf = C.create_string_buffer(2048)
     check(lib().pg_config_string(buf, 2048))
     return buf.value.decode() + f" hip_runtime={hip_runtime_source}"
+
+
+# ---- diagnostics: one SpMV launch against the host ---------------------------------------------------------------------------
+DEBUG_SPMV_SENTINEL = 0x7FF8C0DE5EED0BAD      # PG_DEBUG_SPMV_SENTINEL
+DEBUG_SPMV_GUARD = 64
+
+
+def debug_spmv_sizes(handle, which: int) -> tuple[int, int, int, int]:
+    """pg_debug_spmv_sizes: (rows n, vector length n_vec, entries, grid) of the matrix pg_solver_system_info(which) describes.
+    pg_system_info has no n_vec of the loop matrix's own numbering (its layout is pinned by the Julia twin): this gives it."""
+    n, nv, nnz, grid = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    check(lib().pg_debug_spmv_sizes(handle, C.c_int32(which), C.byref(n), C.byref(nv), C.byref(nnz), C.byref(grid)))
+    return n.value, nv.value, nnz.value, grid.value
+
+
+def loop_system_csr(handle, which: int):
+    """pg_solver_get_system_csr for the preconditioned matrices, 6 / 7 included (the matrix the warm loop multiplies by, which
+    no host could form before): (rowptr, col, val) with the columns in that matrix's own local numbering."""
+    n, _, nnz, _ = debug_spmv_sizes(handle, which)
+    rowptr, col, val = np.zeros(n + 1, dtype=np.int64), np.zeros(max(nnz, 1), dtype=np.int64), np.zeros(max(nnz, 1))
+    check(lib().pg_solver_get_system_csr(handle, C.c_int32(which), iptr(rowptr), iptr(col), dptr(val), None, None))
+    return rowptr, col[:nnz], val[:nnz]
+
+
+def debug_spmv_apply(handle, which: int, variant: int, mode: int, x, aux=None, dotx=None, base=None, pc=(0.0, 0.0, 0.0),
+                     fold: int = 0, done: int = 0, repeat: int = 1) -> dict:
+    """pg_debug_spmv_apply: ONE launch of the product as the Krylov driver issues it, on host vectors, everything it wrote
+    handed back.  Checks what pg_debug_spmv_compare / _mode_compare (kernel against kernel, device-made vectors, two numbers
+    back) cannot: launch mode 2, a dot operand that is not x, mode 8 on aliased vectors, the folded scalar phase, the done
+    flag -- against a host product (tests/spmv_reference.py).  Returns y (n + 64 guard words), partials (5 x grid),
+    slot_sums (5), folded (5), ticket."""
+    n, nv, _, grid = debug_spmv_sizes(handle, which)
+
+    def arr(a, length, name):
+        if a is None:
+            return None, None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size != length:
+            raise ValueError(f"debug_spmv_apply: {name} has {a.size} entries, the matrix needs {length}")
+        return a, dptr(a)
+
+    xs, xp = arr(x, nv, "x")
+    auxs, auxp = arr(aux, n, "aux")
+    dots, dotp = arr(dotx, n, "dotx")
+    bases, basep = arr(base, n, "base")
+    y = np.zeros(n + DEBUG_SPMV_GUARD)
+    partials = np.zeros((5, grid))
+    sums, folded = np.zeros(5), np.zeros(5)
+    ticket = C.c_int64(-1)
+    check(lib().pg_debug_spmv_apply(handle, C.c_int32(which), C.c_int32(variant), C.c_int32(mode), xp, auxp, dotp, basep,
+                                    C.c_double(pc[0]), C.c_double(pc[1]), C.c_double(pc[2]), C.c_int32(fold), C.c_int32(done),
+                                    C.c_int32(repeat), dptr(y), dptr(partials), dptr(sums), dptr(folded), C.byref(ticket)))
+    return {"y": y, "partials": partials, "slot_sums": sums, "folded": folded, "ticket": ticket.value, "grid": grid, "n": n}

@@ -2132,6 +2132,8 @@ int32_t pg_solver_system_info(const pg_solver* s, int32_t which, pg_system_info*
   PG_API_END
 }
 
+static const CsrMatrix& debug_matrix(const pg_solver* s, int32_t which, i64* nv);
+
 int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* rowptr, int64_t* col, double* val, double* b,
                                  int64_t* idx) {
   PG_API_BEGIN
@@ -2140,6 +2142,25 @@ int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* row
   const bool precond = (which & 2) != 0;   // 2/3: the preconditioned system (Â, b̂) exactly as the Krylov solver sees it
   const int sel = which & 1;
   if (sel == 1) PG_REQUIRE(s->have_run, "run matrix not assembled yet");
+  if (which & 4) {
+    // 6/7: the matrix the warm loop iterates on, in its own numbering (pg_solver_system_info(6/7), pg_debug_spmv_sizes)
+    PG_REQUIRE(precond, "pg_solver_get_system_csr: which = 6 / 7 (the loop's matrix is a preconditioned one)");
+    PG_REQUIRE(!b && !idx, "pg_solver_get_system_csr: b and idx belong to the full system: NULL for which = 6 / 7");
+    i64 nv = 0;
+    const CsrMatrix& L = debug_matrix(s, which, &nv);
+    if (rowptr) {
+      std::vector<int> h(L.n + 1, 0);
+      if (L.n > 0) L.rowptr.download(h.data(), L.n + 1);
+      for (i64 i = 0; i <= L.n; ++i) rowptr[i] = h[i];
+    }
+    if (col && L.nnz > 0) {
+      std::vector<int> h(L.nnz);
+      L.col.download(h.data(), L.nnz);
+      for (i64 i = 0; i < L.nnz; ++i) col[i] = h[i];
+    }
+    if (val && L.nnz > 0) L.val.download(val, L.nnz);
+    return 0;
+  }
   const CsrMatrix& Ah = sel == 0 ? s->A_ctor : run_matrix(s);
   const i64 n = s->nb.n_own;
   // 0/1: the reference's reduced system A x = b: the matrix is re-assembled without scaling (export is a test /
@@ -2304,6 +2325,95 @@ int32_t pg_debug_spmv_mode_compare(pg_solver* s, int32_t which, int32_t mode, do
   i64 nv = 0;
   const CsrMatrix& A = debug_matrix(s, which, &nv);
   spmv_mode_compare(A, std::max(nv, A.n), mode, max_abs_diff, max_abs, max_dot_rel);
+  PG_API_END
+}
+
+int32_t pg_debug_spmv_sizes(pg_solver* s, int32_t which, int64_t* n, int64_t* n_vec, int64_t* nnz, int32_t* grid) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s, "pg_debug_spmv_sizes: NULL argument");
+  i64 nv = 0;
+  const CsrMatrix& A = debug_matrix(s, which, &nv);
+  if (n) *n = A.n;
+  if (n_vec) *n_vec = std::max(nv, A.n);
+  if (nnz) *nnz = A.nnz;
+  if (grid) *grid = spmv_default_grid(A.n);
+  PG_API_END
+}
+
+int32_t pg_debug_spmv_apply(pg_solver* s, int32_t which, int32_t variant, int32_t mode, const double* x, const double* aux,
+                            const double* dotx, const double* base, double pc0, double pc1, double pc2, int32_t fold,
+                            int32_t done, int32_t repeat, double* y, double* partials, double* slot_sums, double* folded,
+                            int64_t* ticket) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && x && y && slot_sums && folded && ticket, "pg_debug_spmv_apply: NULL argument");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "pg_debug_spmv_apply: one rank (the split launch of a slab is not covered)");
+  PG_REQUIRE(variant == 70 || variant == 38 || variant == 2 || variant == 1, "pg_debug_spmv_apply: variants 70, 38, 2 and 1");
+  PG_REQUIRE(mode == 0 || mode == 1 || mode == 2 || mode == 3 || mode == 8, "pg_debug_spmv_apply: launch modes 0, 1, 2, 3 and 8");
+  PG_REQUIRE(repeat == 1 || repeat == 2, "pg_debug_spmv_apply: repeat is 1 or 2");
+  PG_REQUIRE(fold == 0 || fold == 1, "pg_debug_spmv_apply: fold is 0 or 1");
+  const bool slices = (variant & 64) != 0;
+  PG_REQUIRE(slices || (mode != 8 && !dotx && !fold),
+             "pg_debug_spmv_apply: mode 8, a separate dot operand and the folded scalar phase exist in the slice kernel (variant 70) only");
+  PG_REQUIRE(!fold || (mode >= 1 && mode <= 3), "pg_debug_spmv_apply: only the modes with dots (1, 2, 3) fold a scalar phase");
+  PG_REQUIRE((mode == 1 || mode == 3) == (aux != nullptr), "pg_debug_spmv_apply: aux goes with modes 1 and 3, and only with them");
+  PG_REQUIRE(!dotx || mode == 2 || mode == 3, "pg_debug_spmv_apply: dotx goes with modes 2 and 3");
+  PG_REQUIRE(!base || mode == 8, "pg_debug_spmv_apply: base goes with mode 8");
+  i64 nv = 0;
+  const CsrMatrix& A = debug_matrix(s, which, &nv);
+  const i64 n = A.n;
+  PG_REQUIRE(n > 0, "pg_debug_spmv_apply: the matrix has no rows");
+  PG_REQUIRE(!slices || A.srec.p, "pg_debug_spmv_apply: the matrix has no slice image");
+  nv = std::max(nv, n);
+  hipStream_t st = ctx().stream;
+  const int grid = spmv_default_grid(n);
+  constexpr i64 GUARD = 64;
+  double sentinel;
+  const unsigned long long sbits = PG_DEBUG_SPMV_SENTINEL;
+  std::memcpy(&sentinel, &sbits, sizeof(double));
+  // operands as long as the driver's vectors (n_vec), zeros behind row n
+  DevBuf<double> dx(nv), daux(nv), ddot(nv), dbase(nv), dy(n + GUARD), dpart(5 * (i64)grid), dsc(S_COUNT);
+  DevBuf<unsigned> dticket(1);
+  daux.zero(); ddot.zero(); dbase.zero(); dsc.zero(); dticket.zero();
+  dx.upload(x, nv);
+  if (aux) daux.upload(aux, n);
+  if (dotx) ddot.upload(dotx, n);
+  if (base) dbase.upload(base, n);
+  {
+    std::vector<double> fill((size_t)std::max<i64>(n + GUARD, 5 * (i64)grid), sentinel);
+    dy.upload(fill.data(), n + GUARD);
+    if (fold && mode == 3) std::fill(fill.begin() + 2 * (size_t)grid, fill.begin() + 4 * (size_t)grid, 0.0);   // slots of another kernel
+    dpart.upload(fill.data(), 5 * (i64)grid);
+    std::vector<double> hsc(S_COUNT, 0.0);
+    for (int k = 0; k < 5; ++k) hsc[S_RED0 + k] = sentinel;
+    hsc[S_DONE] = (double)done;
+    dsc.upload(hsc.data(), S_COUNT);
+  }
+  FinArgs f{fold ? dticket.p : nullptr, fold ? dsc.p : nullptr, PH_NONE, fold ? (mode == 1 ? 1 : (mode == 2 ? 2 : 5)) : 0, 0,
+            dotx ? ddot.p : nullptr};
+  if (mode == 8) { f.pc0 = pc0; f.pc1 = pc1; f.pc2 = pc2; f.base = base ? dbase.p : dx.p; }
+  const bool with_fin = mode == 8 || fold || dotx;
+  for (int r = 0; r < repeat; ++r) {
+    const bool folded_here = launch_spmv_as(variant, mode, A, dx.p, dy.p, aux ? daux.p : nullptr, mode >= 1 && mode <= 3 ? dpart.p : nullptr,
+                                            dsc.p, grid, st, with_fin ? &f : nullptr);
+    PG_REQUIRE(folded_here == (fold != 0), "pg_debug_spmv_apply: the launch did not report the scalar phase as asked");
+  }
+  PG_HIP(hipGetLastError());
+  dy.download(y, n + GUARD);
+  std::vector<double> hp(5 * (size_t)grid), hsc(S_COUNT);
+  dpart.download(hp.data(), 5 * (i64)grid);
+  dsc.download(hsc.data(), S_COUNT);
+  if (partials) std::memcpy(partials, hp.data(), sizeof(double) * hp.size());
+  for (int k = 0; k < 5; ++k) {
+    double a = 0.0;
+    for (int i = 0; i < grid; ++i) a += hp[(size_t)k * grid + i];
+    slot_sums[k] = a;
+    folded[k] = hsc[S_RED0 + k];
+  }
+  unsigned ht = 0;
+  dticket.download(&ht, 1);
+  *ticket = (int64_t)ht;
   PG_API_END
 }
 

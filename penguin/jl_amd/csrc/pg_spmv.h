@@ -217,6 +217,10 @@ __device__ inline void fold_scalar_phase(const FinArgs& fin, const double* __res
 // does that (the stencil-slice kernel), false when the caller still has to launch the scalar kernel itself.
 bool launch_spmv(int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
                  const double* sc, int grid, hipStream_t st, const FinArgs* fin = nullptr);
+// launch_spmv with the kernel variant given (PG_SPMV_VARIANT numbering) instead of read from the configuration: what
+// launch_spmv itself calls, and the diagnostics that check one launch against the host (pg_debug_spmv_apply)
+bool launch_spmv_as(int variant, int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
+                    const double* sc, int grid, hipStream_t st, const FinArgs* fin = nullptr);
 // y = A x on a slab whose x needs a halo exchange first (C1 of SURVEY.md 2.3): the exchange of x's ghost segments runs on
 // the communication stream while the slices that reference no ghost column are multiplied; the slices that do (rows of
 // the first / last owned plane) follow in a second, small launch once the halo has landed, adding their partial sums

@@ -1580,16 +1580,28 @@ int spmv_default_grid(i64 n) {
   return grid_for(n, BLOCK, cus * per_cu);
 }
 
-bool launch_spmv(int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
-                 const double* sc, int grid, hipStream_t st, const FinArgs* fin) {
-  if (A.n == 0) return false;
-  const int v = variant();
+// the launch of mode `mode` with kernel variant v: the one body of launch_spmv and launch_spmv_as
+static inline __attribute__((always_inline)) bool launch_by_mode(int v, int mode, const CsrMatrix& A, const double* x, double* y,
+                                                                 const double* aux, double* partials, const double* sc, int grid,
+                                                                 hipStream_t st, const FinArgs* fin) {
   if (mode == 0) return launch_mode<0>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 1) return launch_mode<1>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 2) return launch_mode<2>(v, A, x, y, aux, partials, sc, grid, st, fin);
   if (mode == 8) return launch_mode<8>(v, A, x, y, aux, partials, sc, grid, st, fin);
   PG_REQUIRE(mode == 3, "unknown SpMV launch mode");
   return launch_mode<3>(v, A, x, y, aux, partials, sc, grid, st, fin);
+}
+
+bool launch_spmv(int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
+                 const double* sc, int grid, hipStream_t st, const FinArgs* fin) {
+  if (A.n == 0) return false;
+  return launch_by_mode(variant(), mode, A, x, y, aux, partials, sc, grid, st, fin);
+}
+
+bool launch_spmv_as(int v, int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
+                    const double* sc, int grid, hipStream_t st, const FinArgs* fin) {
+  if (A.n == 0) return false;
+  return launch_by_mode(v, mode, A, x, y, aux, partials, sc, grid, st, fin);
 }
 
 bool spmv_with_halo(int mode, const CsrMatrix& A, const Numbering& nb, const Slab& slab, double* x, double* y, const double* aux,
