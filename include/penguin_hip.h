@@ -91,8 +91,26 @@ typedef struct {
   int32_t precond;     /* BiCGStab only: polynomial right preconditioner in Â (DESIGN.md "Krylov driver").  0: automatic
                           (on where Gershgorin bounds the spectrum; degree 6 for a first solve, then chosen per solve of the
                           warm time loop from the previous solve's convergence rate, 4 .. 32); -1: off (the plain
-                          iteration IterativeSolvers runs); m >= 1: m products with Â per application where admissible (<= 40) */
+                          iteration IterativeSolvers runs); m >= 1: m products with Â per application where admissible (<= 40);
+                          PG_PRECOND_MG: the aggregation multigrid V-cycle (DESIGN.md "Multigrid") -- steady monophasic diffusion
+                          with a Dirichlet interface and the stream-function solve of a pg_streamvort, one rank; refused with an
+                          error that names the failed condition anywhere else, never replaced by another iteration.  Such a
+                          solve reports poly_degree = 0 and poly_xspace = 0 like a plain one (pg_solver_mg_info tells whether a
+                          hierarchy exists); with profiling on, each V-cycle counts as one lean launch in spmv_lean_* */
 } pg_krylov_opts;
+enum { PG_PRECOND_MG = -2 };   /* a value of pg_krylov_opts.precond */
+
+/* the multigrid hierarchy of a solver (pg_solver_mg_info), built by the first solve that asks for PG_PRECOND_MG */
+#define PG_MG_MAX_LEVELS 16
+typedef struct {
+  int32_t levels;                    /* 0: no hierarchy has been built                                             */
+  int32_t tail_level;                /* first level of the fused tail: the levels [tail_level, levels) run in one launch by one
+                                        workgroup with their vectors in LDS; the last level is solved exactly there  */
+  int64_t rows[PG_MG_MAX_LEVELS];    /* per level; level 0 is the Krylov matrix Â itself                            */
+  int64_t nnz[PG_MG_MAX_LEVELS];
+  double setup_ms;                   /* wall time of the set-up (device kernels + the host inverse of the last level) */
+  int64_t bytes;                     /* device memory held by the hierarchy (level 0's matrix not counted)           */
+} pg_mg_info;
 
 typedef struct {
   int32_t iters;      /* Krylov iterations of this step                        */
@@ -434,6 +452,8 @@ int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* row
 /* S = diag(|a_ii|^-1/2) of system `which` (0 constructor, 1 run): the weights of the convergence test
    ||S r̂|| <= reltol ||S b̂|| (DESIGN.md "Krylov driver") and the map x = S y of the preconditioned system.  ds: n_own. */
 int32_t pg_solver_get_row_scaling(const pg_solver* s, int32_t which, double* ds);
+/* the multigrid hierarchy of the solver's constructor system (levels = 0 before the first PG_PRECOND_MG solve) */
+int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out);
 /* bench helper: `reps` launches of y = A x on the run matrix, HIP-event timed on the library stream. */
 int32_t pg_solver_time_spmv(pg_solver* s, int32_t which, int32_t reps, double* avg_ms);
 
@@ -504,6 +524,9 @@ int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const int64_t* n, 
                                    int64_t* n_ghost_out, int64_t* iters_out);
 /* Krylov method (PG_METHOD_*) and GMRES restart length of the virtual-rank runs that follow (default BiCGStab) */
 int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart);
+/* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG makes pg_debug_run_virtual_ranks fail
+   with the multigrid's one-rank refusal before any rank starts */
+int32_t pg_debug_set_virtual_rank_precond(int32_t precond);
 /* ramp != 0: the virtual-rank runs that follow change the interface value every step, g = interface_value (1 + ramp step)
    (host-driven steps): rows alone on their diagonal move in every step, on every rank */
 int32_t pg_debug_set_virtual_rank_ramp(double ramp);
@@ -522,6 +545,16 @@ int32_t pg_debug_scale_diagonal_rows(pg_solver* s, double factor);
    the polynomial is given up as stagnated and continues with the plain iteration -- on the full system when it ran on the
    compact one; 0 restores the built-in rule */
 int32_t pg_debug_set_poly_give_up(int32_t iterations);
+
+/* Multigrid diagnostics (tests/test_gpu_multigrid.py compares them with the numpy restatement tests/mg_reference.py).  All
+   build the hierarchy of the solver's constructor system when it does not exist yet, and refuse what PG_PRECOND_MG refuses.
+   Two-call size pattern: with the array arguments NULL only the sizes are written.
+   pg_debug_mg_aggregates: agg[i] = the row of level + 1 that row i of `level` belongs to (n rows; level < levels - 1).
+   pg_debug_mg_level_csr: the matrix of `level` (0: Â; l >= 1: the Galerkin product P_(l-1)ᵀ A_(l-1) P_(l-1), not equilibrated).
+   pg_debug_mg_apply: z = M⁻¹ r, ONE application of the V-cycle as the Krylov loop runs it; r, z: n_own host doubles. */
+int32_t pg_debug_mg_aggregates(pg_solver* s, int32_t level, int64_t* n, int32_t* agg);
+int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val);
+int32_t pg_debug_mg_apply(pg_solver* s, const double* r, double* z);
 
 /* The extrapolated start of the time loop's quiet steps (constant data, one rank; no reference counterpart: the reference
    starts every Krylov solve from zero, solver.jl:158-181): `kept` older states are held; the next step starts from

@@ -24,7 +24,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!,
        MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
-       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info,
+       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
        ∇, ∇₋, gmres, bicgstabl, cg
 
@@ -88,11 +88,19 @@ mutable struct pg_streamvort_run_info
 end
 # kwargs... of solve_system! (src/solver.jl:158-188) -> the options of the device Krylov solve.  reltol defaults to 1e-12,
 # not IterativeSolvers' sqrt(eps): the parity target is the direct-solve path; warm_start and precond are not in the
-# reference (warm_start=false, precond=-1 give IterativeSolvers' plain iteration from a zero initial guess)
+# reference (warm_start=false, precond=-1 give IterativeSolvers' plain iteration from a zero initial guess).
+# precond = :mg (PG_PRECOND_MG): the aggregation multigrid V-cycle -- steady monophasic diffusion with a Dirichlet interface and
+# the stream-function solve of a StreamVorticity; the library refuses it anywhere else.
+const PG_PRECOND_MG = Int32(-2)
+function _precond_id(p)
+    p isa Symbol || return Int32(p)
+    p === :mg || error("precond must be an integer or :mg, not :$(p)")
+    PG_PRECOND_MG
+end
 function _opts(method, kw; warm_default::Bool=true)
     pg_krylov_opts(_method_id(method), Float64(get(kw, :reltol, 1e-12)), Float64(get(kw, :abstol, 0.0)),
                    Int32(get(kw, :maxiter, 0)), Int32(4), Int32(get(kw, :warm_start, warm_default) ? 1 : 0),
-                   Int32(get(kw, :restart, 0)), Int32(get(kw, :precond, 0)))
+                   Int32(get(kw, :restart, 0)), _precond_id(get(kw, :precond, 0)))
 end
 
 # ---------------------------------------------------------------------------------- Mesh  (src/mesh.jl:41-79)
@@ -1435,6 +1443,54 @@ function guess_info(s)
                 (Ptr{Cvoid}, Ref{Int32}, Ref{Int32}, Ptr{Int32}, Ptr{Float64}, Ref{Float64}, Ref{Float64}),
                 s.handle, kept, ns, off, cf, ru, rw))
     (kept = Int(kept[]), offsets = Int.(off[1:ns[]]), coef = cf[1:ns[]], rr_plain = ru[], rr_taken = rw[])
+end
+
+"""
+The multigrid hierarchy of a solver's constructor system (`pg_solver_mg_info`): levels (0 before the first solve with
+`precond = :mg`), the first level of the fused tail, rows and nnz per level, set-up time, device memory.
+"""
+function mg_info(s)
+    # pg_mg_info: int32 levels, int32 tail_level, int64 rows[16], int64 nnz[16], double setup_ms, int64 bytes = 35 words
+    buf = zeros(Int64, 35)
+    GC.@preserve buf begin
+        check(ccall((:pg_solver_mg_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), s.handle, pointer(buf)))
+    end
+    levels = Int(buf[1] & 0xffffffff); tail = Int((buf[1] >> 32) & 0xffffffff)
+    (levels = levels, tail_level = tail, rows = buf[2:1 + levels], nnz = buf[18:17 + levels],
+     setup_ms = reinterpret(Float64, buf[34]), bytes = buf[35])
+end
+
+"`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg` makes them fail with the one-rank refusal)."
+set_virtual_rank_precond(p) = check(ccall((:pg_debug_set_virtual_rank_precond, libpg), Int32, (Int32,), _precond_id(p)))
+
+"One application z = M⁻¹ r of the multigrid V-cycle on host vectors (`pg_debug_mg_apply`; builds the hierarchy if need be)."
+function mg_apply(s, r::Vector{Float64})
+    z = zeros(Float64, length(r))
+    check(ccall((:pg_debug_mg_apply, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, r, z))
+    z
+end
+
+"Aggregate map of `level` (`pg_debug_mg_aggregates`): the 0-based row of level + 1 every row of `level` belongs to."
+function mg_aggregates(s, level::Integer)
+    n = Ref{Int64}(0)
+    check(ccall((:pg_debug_mg_aggregates, libpg), Int32, (Ptr{Cvoid}, Int32, Ref{Int64}, Ptr{Int32}), s.handle, level, n, C_NULL))
+    agg = zeros(Int32, n[])
+    check(ccall((:pg_debug_mg_aggregates, libpg), Int32, (Ptr{Cvoid}, Int32, Ref{Int64}, Ptr{Int32}), s.handle, level, n, agg))
+    agg
+end
+
+"The matrix of `level` of the hierarchy (`pg_debug_mg_level_csr`) as a SparseMatrixCSC."
+function mg_level_matrix(s, level::Integer)
+    n = Ref{Int64}(0); nnz = Ref{Int64}(0)
+    check(ccall((:pg_debug_mg_level_csr, libpg), Int32,
+                (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                s.handle, level, n, nnz, C_NULL, C_NULL, C_NULL))
+    rowptr = zeros(Int64, n[] + 1); col = zeros(Int64, max(nnz[], 1)); val = zeros(Float64, max(nnz[], 1))
+    check(ccall((:pg_debug_mg_level_csr, libpg), Int32,
+                (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                s.handle, level, n, nnz, rowptr, col, val))
+    rows = [i for i in 1:n[] for _ in rowptr[i] + 1:rowptr[i + 1]]
+    sparse(rows, col[1:nnz[]] .+ 1, val[1:nnz[]], n[], n[])
 end
 
 end # module

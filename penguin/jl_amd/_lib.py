@@ -33,6 +33,8 @@ PG_KEY = {"left": 0, "right": 1, "bottom": 2, "top": 3, "backward": 4, "forward"
 PG_SCHEME = {"BE": 0, "CN": 1, "STEADY": 2}
 PG_METHOD = {"bicgstab": 0, "cg": 1, "gmres": 2}
 PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a pg_streamvort
+PG_PRECOND_MG = -2                   # pg_krylov_opts.precond: the aggregation multigrid V-cycle
+PG_MG_MAX_LEVELS = 16
 
 c_double_p = C.POINTER(C.c_double)
 c_i64_p = C.POINTER(C.c_int64)
@@ -91,6 +93,11 @@ class pg_streamvort_run_info(C.Structure):
                 ("omega_products", C.c_int64), ("unconverged", C.c_int64), ("worst_relres", C.c_double), ("t_final", C.c_double),
                 ("total_ms", C.c_double), ("psi_ms", C.c_double), ("velocity_ms", C.c_double), ("build_ms", C.c_double),
                 ("omega_ms", C.c_double)]
+
+
+class pg_mg_info(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("tail_level", C.c_int32), ("rows", C.c_int64 * PG_MG_MAX_LEVELS),
+                ("nnz", C.c_int64 * PG_MG_MAX_LEVELS), ("setup_ms", C.c_double), ("bytes", C.c_int64)]
 
 
 def declared_symbols() -> list[str]:
@@ -216,6 +223,42 @@ def config_string() -> str:
     buf = C.create_string_buffer(2048)
     check(lib().pg_config_string(buf, 2048))
     return buf.value.decode() + f" hip_runtime={hip_runtime_source}"
+
+
+# ---- diagnostics: the multigrid hierarchy against the numpy restatement (tests/mg_reference.py) -----------------------------
+def solver_mg_info(handle) -> dict:
+    """pg_solver_mg_info: levels, first level of the fused tail, rows and nnz per level, set-up ms, device bytes."""
+    info = pg_mg_info()
+    check(lib().pg_solver_mg_info(handle, C.byref(info)))
+    n = info.levels
+    return {"levels": n, "tail_level": info.tail_level, "rows": list(info.rows[:n]), "nnz": list(info.nnz[:n]),
+            "setup_ms": info.setup_ms, "bytes": info.bytes}
+
+
+def debug_mg_aggregates(handle, level: int) -> np.ndarray:
+    """pg_debug_mg_aggregates: the row of level + 1 every row of `level` belongs to."""
+    n = C.c_int64(0)
+    check(lib().pg_debug_mg_aggregates(handle, C.c_int32(level), C.byref(n), None))
+    agg = np.zeros(max(n.value, 1), dtype=np.int32)
+    check(lib().pg_debug_mg_aggregates(handle, C.c_int32(level), C.byref(n), agg.ctypes.data_as(c_i32_p)))
+    return agg[: n.value]
+
+
+def debug_mg_level_csr(handle, level: int):
+    """pg_debug_mg_level_csr: (rowptr, col, val) of the matrix of `level` (0: the Krylov matrix)."""
+    n, nnz = C.c_int64(0), C.c_int64(0)
+    check(lib().pg_debug_mg_level_csr(handle, C.c_int32(level), C.byref(n), C.byref(nnz), None, None, None))
+    rowptr, col, val = np.zeros(n.value + 1, dtype=np.int64), np.zeros(max(nnz.value, 1), dtype=np.int64), np.zeros(max(nnz.value, 1))
+    check(lib().pg_debug_mg_level_csr(handle, C.c_int32(level), C.byref(n), C.byref(nnz), iptr(rowptr), iptr(col), dptr(val)))
+    return rowptr, col[: nnz.value], val[: nnz.value]
+
+
+def debug_mg_apply(handle, r: np.ndarray) -> np.ndarray:
+    """pg_debug_mg_apply: z = M⁻¹ r, one application of the V-cycle as the Krylov loop runs it."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    z = np.zeros_like(r)
+    check(lib().pg_debug_mg_apply(handle, dptr(r), dptr(z)))
+    return z
 
 
 # ---- diagnostics: one SpMV launch against the host ---------------------------------------------------------------------------

@@ -649,6 +649,11 @@ class Solver:
         return {"kept": kept.value, "offsets": list(off[: ns.value]), "coef": list(cf[: ns.value]), "rr_plain": ru.value,
                 "rr_taken": rw.value}
 
+    def mg_info(self) -> dict:
+        """The multigrid hierarchy of the constructor system (pg_solver_mg_info): levels (0 before the first solve with
+        precond="mg"), tail_level, rows and nnz per level, setup_ms, bytes."""
+        return L.solver_mg_info(self._h)
+
     def system_info(self, which: int = 0) -> L.pg_system_info:
         info = L.pg_system_info()
         L.check(L.lib().pg_solver_system_info(self._h, C.c_int32(which), C.byref(info)))
@@ -769,14 +774,22 @@ def _step_info_check(s: "Solver", info: L.pg_step_info, what: str) -> None:
 def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     """method may be "bicgstab" / "cg" / "gmres" or a callable named like IterativeSolvers' (bicgstabl, cg, gmres...).
     gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; `\\`, bicgstabl and anything else ->
-    BiCGStab.  reltol defaults to 1e-12: the parity target is the direct-solve path."""
+    BiCGStab.  reltol defaults to 1e-12: the parity target is the direct-solve path.
+    precond: an integer as pg_krylov_opts.precond takes it (0 automatic, -1 off, m >= 1 the polynomial's degree), or "mg":
+    the aggregation multigrid V-cycle (steady monophasic diffusion with a Dirichlet interface and the ψ solve of a
+    StreamVorticity; the library refuses it anywhere else)."""
     name = method if isinstance(method, str) else getattr(method, "__name__", "bicgstab")
     name = name.lower()
     m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])
+    precond = kwargs.get("precond", 0)
+    if isinstance(precond, str):
+        if precond.lower() != "mg":
+            raise ValueError(f'precond must be an integer or "mg", not {precond!r}')
+        precond = L.PG_PRECOND_MG
     return L.pg_krylov_opts(m, float(kwargs.get("reltol", 1e-12)), float(kwargs.get("abstol", 0.0)),
                             int(kwargs.get("maxiter", 0)), int(kwargs.get("check_every", 4)),
                             int(bool(kwargs.get("warm_start", True))), int(kwargs.get("restart", 0)),
-                            int(kwargs.get("precond", 0)))
+                            int(precond))
 
 
 def DiffusionUnsteadyMono(phase: Phase, bc_b: BorderConditions, bc_i, Δt: float, Tᵢ: np.ndarray, scheme: str,

@@ -106,6 +106,8 @@ struct Config {
   double guess_gain = 0.8;        // PG_GUESS_GAIN: products saved per product the fit predicts (what is left after the
                                   // extrapolation sits where the polynomial is weakest)
   bool speculate_product = true;  // PG_SPECULATE: pg_solver_run queues the next step's first product behind a solve's first batch
+  int mg_tail_rows = 2048;        // PG_MG_TAIL_ROWS: multigrid levels of at most this many rows run in the fused one-workgroup tail, as far
+                                  // as their vectors fit its LDS (pg_multigrid.hip; DESIGN.md "Multigrid")
   int unit_order = 0;             // PG_SPMV_UNIT_ORDER: 0 by first row within (strip, plane); 1 units cut at common planes, window-major
                                   // (a block's four waves on four neighbouring lines; measured 59.0 vs 54.6 us per Horner launch: off)
 };

@@ -63,6 +63,7 @@ const Config& config() {
     k.speculate_product = geti("PG_SPECULATE", 1) != 0;
     k.guess_n = (int)std::max<long long>(0, std::min<long long>(4, geti("PG_GUESS_STATES", 4)));
     k.guess_depth = (int)std::max<long long>(1, std::min<long long>(7, geti("PG_GUESS_DEPTH", 7)));
+    k.mg_tail_rows = (int)std::max<long long>(0, geti("PG_MG_TAIL_ROWS", 2048));
     k.guess_monitor = (int)std::max<long long>(1, geti("PG_GUESS_MONITOR", 256));
     k.guess_pass_cost = getd("PG_GUESS_PASS_COST", 0.34);
     k.guess_always = geti("PG_GUESS_ALWAYS", 0) != 0;

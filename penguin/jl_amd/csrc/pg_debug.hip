@@ -41,6 +41,8 @@ struct VArgs {
 
 // Krylov method of the virtual-rank runs (pg_debug_set_virtual_rank_method): BiCGStab unless a test asks otherwise
 int g_method = PG_METHOD_BICGSTAB, g_restart = 0;
+// pg_krylov_opts.precond of the virtual-rank runs (pg_debug_set_virtual_rank_precond): 0, the automatic choice, unless a test asks
+int g_precond = 0;
 // pg_debug_set_virtual_rank_ramp: != 0: the interface value changes from step to step, g = value (1 + ramp step) -- the rows
 // alone on their diagonal then MOVE in every step and the compact loop has to carry their change to the rows coupled to
 // them, across slab faces too (pg_reduce.hip diag_fix with the exchange of the deltas)
@@ -91,7 +93,7 @@ void rank_main(const VArgs& a, int rank, LocalComm* lc, int device, std::string*
     // T0 = zeros stays implicit (NULL): 2M doubles per rank would be 17 GB of host memory at 8 x 512^3
     check(pg_solver_create_unsteady_mono(cap, ops, &bc, borders.data(), a.nkeys, nullptr, nullptr, a.dt, nullptr,
                                          a.scheme_ctor, &sol), "solver");
-    pg_krylov_opts o{g_method, 1e-13, 0.0, 0, 4, g_method == PG_METHOD_BICGSTAB ? 1 : 0, g_restart};
+    pg_krylov_opts o{g_method, 1e-13, 0.0, 0, 4, g_method == PG_METHOD_BICGSTAB ? 1 : 0, g_restart, g_precond};
     pg_run_info info{};
     if (g_kick_step >= 0) {
       pg_step_info sti{};
@@ -159,6 +161,12 @@ extern "C" int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t rest
   PG_API_END
 }
 
+extern "C" int32_t pg_debug_set_virtual_rank_precond(int32_t precond) {
+  PG_API_BEGIN
+  g_precond = precond;
+  PG_API_END
+}
+
 extern "C" int32_t pg_debug_set_virtual_rank_ramp(double ramp) {
   PG_API_BEGIN
   g_ramp = ramp;
@@ -199,6 +207,9 @@ extern "C" int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const i
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(nranks >= 1 && nranks <= 8, "1..8 virtual ranks");
+  // refused HERE, before a rank thread exists: a rank that fails ends the process (it must not leave the others in a barrier)
+  PG_REQUIRE(g_precond != PG_PRECOND_MG, "multigrid preconditioner (precond = PG_PRECOND_MG) refused: it runs on one rank only "
+                                         "(virtual ranks included)");
   VArgs a{nranks, N, n, L, body_kind, params, nparams, interface_value, border_value, nkeys, keys, dt,
           scheme_ctor, scheme_run, steps, x_out, n_own_out, nnz_out, n_ghost_out, iters_out};
   std::unique_ptr<LocalComm, void (*)(LocalComm*)> lc(local_comm_create(nranks), local_comm_destroy);

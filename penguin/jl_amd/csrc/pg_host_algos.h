@@ -420,4 +420,53 @@ inline void plan_tiles(const std::vector<int64_t>& ukey, const std::vector<int64
   }
 }
 
+// ---- multigrid preconditioner (pg_multigrid.hip): the host side of its set-up ----------------------------------------
+// Row-major inverse of the n x n matrix a (row-major) by Gauss-Jordan elimination with partial pivoting, carried in long double
+// and rounded once: the exact solve of the hierarchy's last level (<= 200 rows), applied on the device as one small
+// matrix-vector product.  false: a pivot vanished (singular to working precision); inv is then unspecified.
+inline bool mg_dense_inverse(int n, const double* a, double* inv) {
+  if (n <= 0) return true;
+  const size_t w = 2 * (size_t)n;
+  std::vector<long double> m((size_t)n * w, 0.0L);
+  for (int i = 0; i < n; ++i) {
+    for (int j = 0; j < n; ++j) m[i * w + j] = a[(size_t)i * n + j];
+    m[i * w + n + i] = 1.0L;
+  }
+  for (int c = 0; c < n; ++c) {
+    int piv = c;
+    long double best = m[c * w + c] < 0 ? -m[c * w + c] : m[c * w + c];
+    for (int i = c + 1; i < n; ++i) {
+      const long double v = m[i * w + c] < 0 ? -m[i * w + c] : m[i * w + c];
+      if (v > best) { best = v; piv = i; }
+    }
+    if (!(best > 0.0L)) return false;
+    if (piv != c)
+      for (size_t j = 0; j < w; ++j) std::swap(m[c * w + j], m[piv * w + j]);
+    const long double d = 1.0L / m[c * w + c];
+    for (size_t j = 0; j < w; ++j) m[c * w + j] *= d;
+    for (int i = 0; i < n; ++i) {
+      if (i == c) continue;
+      const long double f = m[i * w + c];
+      if (f == 0.0L) continue;
+      for (size_t j = 0; j < w; ++j) m[i * w + j] -= f * m[c * w + j];
+    }
+  }
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) inv[(size_t)i * n + j] = (double)m[i * w + n + j];
+  return true;
+}
+
+// First level of the multigrid's fused tail -- the levels [t, L) that one workgroup runs in one launch with their vectors in
+// LDS: the smallest t with rows[t] <= tail_rows whose levels fit lds_doubles (three vectors per level, two on the last).  The
+// last level always runs there (its exact solve is part of that kernel): L - 1 when nothing more fits.  L >= 1.
+inline int mg_plan_tail(const int64_t* rows, int L, int64_t tail_rows, int64_t lds_doubles) {
+  int t = L - 1;
+  int64_t need = 2 * rows[L - 1];
+  while (t > 0 && rows[t - 1] <= tail_rows && need + 3 * rows[t - 1] <= lds_doubles) {
+    --t;
+    need += 3 * rows[t];
+  }
+  return t;
+}
+
 }  // namespace pghost

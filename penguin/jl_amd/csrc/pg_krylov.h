@@ -6,6 +6,8 @@
 
 namespace pg {
 
+struct MgHierarchy;   // pg_multigrid.h
+
 struct XGuess {
   const double* zbase = nullptr;
   const double* zr[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -35,6 +37,9 @@ struct KrylovWork {
   // set by the caller around one krylov_solve: the system is a compact image of the caller's (pg_reduce.hip, DiagElim) and
   // x is the caller's FULL vector -- the updates x += α M⁻¹p, x += ω M⁻¹s land at x[scatter[i]].  Needs the polynomial path.
   const int* scatter = nullptr;
+  // set by the caller around one krylov_solve with opts.precond = PG_PRECOND_MG: the multigrid hierarchy of THIS matrix (the
+  // caller has checked that the system admits it, pg_solver.hip mg_prepare).  Reset by krylov_solve.
+  MgHierarchy* mg = nullptr;
   // set by the caller of a compact solve whose start was extrapolated from older states (pg_solver.hip, GuessArgs) and who left
   // the extrapolated state unformed: the FIRST update of x then writes  x[map] = z_g[map] + α M⁻¹p,  z_g = zbase + Σ c_j (zr[o_j] -
   // zbase)  (coef: [0..3] c_j, [4] how many, [5..8] which of zr), instead of adding to x.  Reset by krylov_solve.

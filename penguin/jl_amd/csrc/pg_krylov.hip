@@ -27,7 +27,14 @@
 // k_bicg_xrp): x and r move by the SAME computed vectors, so r stays the residual of x whatever rounding does inside the
 // chain, and the stopping test is unchanged.  The vector passes, the reductions and, with several ranks, the all-reduces
 // of a time step fall with the iteration count.
+//
+// Multigrid right preconditioner (opts.precond = PG_PRECOND_MG, never automatic): the same x-space loop with M⁻¹ = one V-cycle
+// of pg_multigrid.hip where the Horner chain stands -- ya = M⁻¹p, yb = M⁻¹s, then the plain product with its dots.  It is a
+// branch of its own: no degree, no adaptation, no give-up rule; the half-step test runs in every iteration (an application
+// costs five to six products' worth of bytes).  SolveStats::products counts the products with Â of the outer loop, i.e. the
+// applications.
 #include "pg_krylov.h"
+#include "pg_multigrid.h"
 #include "pg_spmv.h"
 
 using namespace pg;
@@ -680,6 +687,17 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   if (adaptive && w.adapt_matrix == &A && w.adapt_m >= 2) { m = w.adapt_m; expect_halves = w.adapt_h; }
   if (m < 2) m = 0;
   const bool poly = m > 0;
+  MgHierarchy* const mgh = w.mg;
+  w.mg = nullptr;
+  const bool mg = opts.precond == PG_PRECOND_MG;
+  if (mg) {
+    PG_REQUIRE(!cg, "multigrid preconditioner refused: the method must be BiCGStab");
+    PG_REQUIRE(spmv_supports_preconditioner_product(), "multigrid preconditioner refused: the x-space loop needs the slice kernel (PG_SPMV_VARIANT)");
+    mg_require_one_rank();
+    PG_REQUIRE(mgh && !w.scatter && !xg.zbase && n > 0, "multigrid preconditioner refused: this solve has no hierarchy (steady monophasic "
+               "diffusion systems and the stream-function solve only)");
+  }
+  const bool pre = poly || mg;   // right-preconditioned: x moves by α M⁻¹p (k_bicg_s_x) and ω M⁻¹s (k_bicg_xrp)
   stats.poly_degree = m;
   stats.poly_xspace = poly ? 1 : 0;
   PG_REQUIRE(!w.scatter || (poly && preinit), "a compact system needs the polynomial path and a prepared start");
@@ -690,14 +708,14 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     double lam[MAX_POLY_DEGREE];
     for (int k = 0; k < m; ++k) lam[k] = 1.0 + g * std::cos(M_PI * (2.0 * k + 1.0) / (2.0 * m));   // descending
     for (int k = 0, lo = 0, hi = m - 1; k < m; ++k) tau[k] = 1.0 / ((k & 1) ? lam[hi--] : lam[lo++]);
-    if (w.ya.n < nvec) {
-      w.ya.alloc(nvec); w.wa.alloc(nvec); w.wb.alloc(nvec); w.yb.alloc(nvec);
-      w.ya.zero(); w.wa.zero(); w.wb.zero(); w.yb.zero();
-    }
+  }
+  if (pre && w.ya.n < nvec) {
+    w.ya.alloc(nvec); w.wa.alloc(nvec); w.wb.alloc(nvec); w.yb.alloc(nvec);
+    w.ya.zero(); w.wa.zero(); w.wb.zero(); w.yb.zero();
   }
   // convergence is also tested after the first half of an iteration when a half costs several products (the test itself
   // costs two small launches)
-  const bool half_test = m >= 3;
+  const bool half_test = m >= 3 || mg;
   PG_REQUIRE(!xg.zbase || (poly && p_in_rhat && w.scatter), "an unformed extrapolated state needs the polynomial loop on a compact system");
   PG_REQUIRE(!preinit || !cg, "preinit is a BiCGStab path");
   if (!cg) {
@@ -754,11 +772,17 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
         src = dst;
       }
       timer.end(st);
+    } else if (mg) {
+      double* hat = second ? w.yb.p : w.ya.p;
+      timer.begin(st, itn, true, second, 1);              // (profiling: a V-cycle is bracketed as a whole and counted as ONE lean launch)
+      mg_apply(*mgh, A, nb, slab, in, hat, w.sc.p, st);   // hat = M⁻¹ in: one V-cycle
+      timer.end(st);
+      src = hat;
     }
     // the scalar phase that follows is evaluated by the last block of the launch (stencil-slice kernel); with
     // several ranks the halo exchange of the input overlaps the rows that need no ghost value (spmv_with_halo).
     // Mode 3 after the chain: `in` (= s) is the operand of the (out, .) dot, not the launch's x
-    FinArgs f{w.ticket.p, w.sc.p, phase, nslots, derive_here, poly ? in : nullptr};
+    FinArgs f{w.ticket.p, w.sc.p, phase, nslots, derive_here, pre ? in : nullptr};
     timer.begin(st, itn, false, second);
     const bool folded = spmv_with_halo(phase == PH_BICG_1 ? 1 : 3, A, nb, slab, src, out, w.rhat.p, w.partials.p, w.sc.p, G, st, &f);
     timer.end(st);
@@ -772,7 +796,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     unsigned* tk = (test && derive_here) ? w.ticket.p : nullptr;   // the half-step test inside the s kernel
     // s, its dots, the half-step test -- and with the polynomial x += α M⁻¹p -- in one pass; without the test in this
     // iteration the sums of slot 4 are simply not looked at
-    if (poly)
+    if (pre)
       hipLaunchKernelGGL(k_bicg_s_x, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.v.p, w.rhat.p, w.r.p, w.partials.p, (const double*)A.ds.p, tk,
                          p_in_rhat ? 1 : 0, (const double*)w.ya.p, x, w.scatter, xg, itn == 0 ? 1 : 0);
     else
@@ -783,7 +807,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   auto second_half = [&](int itn) {
     apply(w.r.p, w.t.p, PH_BICG_2, 5, itn);     // t = C s (r holds s), (t,s), (t,t), (r̂,t); then ω, ρ, β / restart
     hipLaunchKernelGGL(k_bicg_xrp, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.t.p, w.v.p, x, w.r.p, w.p.p, w.rhat.p, w.partials.p,
-                       (const double*)A.ds.p, p_in_rhat ? 1 : 0, poly ? (const double*)w.yb.p : nullptr, w.scatter);
+                       (const double*)A.ds.p, p_in_rhat ? 1 : 0, pre ? (const double*)w.yb.p : nullptr, w.scatter);
   };
   while (!done) {
     int want = check_every;

@@ -15,6 +15,7 @@
 
 #include "pg_krylov.h"
 #include "pg_reduce.h"
+#include "pg_multigrid.h"
 #include "pg_solver_internal.h"
 #include "pg_spmv.h"
 
@@ -69,6 +70,9 @@ struct pg_solver {
   const CsrMatrix* z_matrix = nullptr;   // the matrix whose S the current z refers to
   DevBuf<double> T0pad;       // K*Mloc, ctor initial condition
   KrylovWork work;
+  // multigrid hierarchy of A_ctor (pg_multigrid.hip), built by the first solve that asks for PG_PRECOND_MG and kept with the
+  // system: a steady solver is solved again and again on the same matrix (the stream-function solver of a pg_streamvort)
+  MgHierarchy mg;
   // ŷ = Â z of the NEXT step, queued speculatively behind the previous solve's first batch (KrylovWork::after_first_batch):
   // valid when that solve ended inside the batch (nothing moved z afterwards) and the next step runs on the same matrix
   bool spec_y_valid = false, spec_pending = false, hint_more_steps = false;
@@ -1294,8 +1298,40 @@ pg_krylov_opts default_opts() {
   return o;
 }
 
+// opts.precond = PG_PRECOND_MG: the conditions under which the multigrid preconditioner is offered -- anything else is refused
+// with the condition that failed, never served by another iteration -- then the hierarchy, on first use, and its hand-over to
+// the Krylov driver for the solve that follows.
+void mg_conditions(const pg_solver* s, int method) {
+  const std::string who = "multigrid preconditioner (precond = PG_PRECOND_MG) refused: ";
+  mg_require_one_rank();
+  PG_REQUIRE(s->scheme_ctor == PG_SCHEME_STEADY && !s->moving,
+             who + "the system is an unsteady one (steady monophasic diffusion and the stream-function solve only)");
+  PG_REQUIRE(s->nphase == 1, who + "the system is diphasic (its jump rows need the cell-block left preconditioner)");
+  PG_REQUIRE(!s->advdiff && !(s->ops[0] && s->ops[0]->has_velocity), who + "the operator is a ConvectionOps (DiffusionOps only)");
+  PG_REQUIRE(s->bc_i.kind == PG_BC_DIRICHLET,
+             who + (s->bc_i.kind == PG_BC_ROBIN ? "the interface condition is Robin (Dirichlet only)"
+                                                : "the interface condition is Neumann (Dirichlet only)"));
+  // (not "no blocked rows": the cut cells of a Dirichlet interface are blocked too -- their γ row is a row of the identity, and
+  //  B⁻¹ only takes the same-cell γ entry out of the ω row.  Â keeps its unit diagonal; the hierarchy is built on Â as it is.)
+  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + (method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
+                                                                          : "the method is GMRES (BiCGStab only)"));
+}
+
+void mg_ensure(pg_solver* s) {
+  if (s->mg.matrix != &s->A_ctor || s->mg.lev.empty()) mg_build(s->mg, s->A_ctor, s->nb, s->slab);
+}
+
+// before every krylov_solve on A_ctor that takes the caller's options
+void mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
+  if (o.precond != PG_PRECOND_MG) return;
+  mg_conditions(s, o.method);
+  mg_ensure(s);
+  s->work.mg = &s->mg;
+}
+
 void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
+  mg_prepare(s, o);
   // solve_system!(s) with the constructor's A and b (diffusion.jl:275)
   const i64 n = s->nb.n_own;
   if (s->moving && o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
@@ -1427,6 +1463,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   PG_REQUIRE(!s->moving, "a moving-body solver is one space-time step: create the next one from the next time slab");
   PG_REQUIRE(s->initial_done, "Solver is not initialized. Call pg_solver_initial_solve first.");
   const pg_krylov_opts o = opts ? *opts : default_opts();
+  if (o.precond == PG_PRECOND_MG) mg_conditions(s, o.method);   // (refuses: a time step is an unsteady system)
   hipStream_t stream = ctx().stream;
   ensure_run_matrix(s, scheme);
   const CsrMatrix& A = run_matrix(s);
@@ -2255,6 +2292,82 @@ int32_t pg_solver_stefan_terms(const pg_solver* s, double* out) {
   PG_API_END
 }
 
+int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out) {
+  PG_API_BEGIN
+  PG_REQUIRE(s && out, "pg_solver_mg_info: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  const MgHierarchy& H = s->mg;
+  if (H.matrix != &s->A_ctor) return 0;
+  out->levels = (int32_t)H.lev.size();
+  out->tail_level = H.tail0;
+  for (size_t l = 0; l < H.lev.size() && l < PG_MG_MAX_LEVELS; ++l) {
+    out->rows[l] = H.lev[l]->n;
+    out->nnz[l] = H.lev[l]->nnz;
+  }
+  out->setup_ms = H.setup_ms;
+  out->bytes = H.bytes;
+  PG_API_END
+}
+
+static MgHierarchy& debug_mg(pg_solver* s) {
+  require_init();
+  PG_REQUIRE(s, "multigrid diagnostics: NULL solver");
+  mg_conditions(s, PG_METHOD_BICGSTAB);
+  mg_ensure(s);
+  return s->mg;
+}
+
+int32_t pg_debug_mg_aggregates(pg_solver* s, int32_t level, int64_t* n, int32_t* agg) {
+  PG_API_BEGIN
+  MgHierarchy& H = debug_mg(s);
+  PG_REQUIRE(level >= 0 && level + 1 < (int)H.lev.size(), "pg_debug_mg_aggregates: level has no aggregates (0 <= level < levels - 1)");
+  const MgLevel& v = *H.lev[level];
+  if (n) *n = v.n;
+  if (agg) v.agg.download(agg, v.n);
+  PG_API_END
+}
+
+int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val) {
+  PG_API_BEGIN
+  MgHierarchy& H = debug_mg(s);
+  PG_REQUIRE(level >= 0 && level < (int)H.lev.size(), "pg_debug_mg_level_csr: no such level");
+  const MgLevel& v = *H.lev[level];
+  if (n) *n = v.n;
+  if (nnz) *nnz = v.nnz;
+  hipStream_t st = ctx().stream;
+  if (rowptr) {
+    std::vector<int> h(v.n + 1);
+    PG_HIP(hipMemcpyAsync(h.data(), v.rowptr, sizeof(int) * (size_t)(v.n + 1), hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    for (i64 i = 0; i <= v.n; ++i) rowptr[i] = h[i];
+  }
+  if (col && v.nnz > 0) {
+    std::vector<int> h(v.nnz);
+    PG_HIP(hipMemcpyAsync(h.data(), v.col, sizeof(int) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    for (i64 i = 0; i < v.nnz; ++i) col[i] = h[i];
+  }
+  if (val && v.nnz > 0) {
+    PG_HIP(hipMemcpyAsync(val, v.val, sizeof(double) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+  }
+  PG_API_END
+}
+
+int32_t pg_debug_mg_apply(pg_solver* s, const double* r, double* z) {
+  PG_API_BEGIN
+  MgHierarchy& H = debug_mg(s);
+  PG_REQUIRE(r && z, "pg_debug_mg_apply: NULL argument");
+  const i64 n = s->nb.n_own, nv = s->nb.n_vec();
+  DevBuf<double> din(nv), dout(nv);
+  din.zero();
+  dout.zero();
+  din.upload(r, n);
+  mg_apply(H, s->A_ctor, s->nb, s->slab, din.p, dout.p, nullptr, ctx().stream);
+  dout.download(z, n);
+  PG_API_END
+}
+
 int32_t pg_solver_get_row_scaling(const pg_solver* s, int32_t which, double* ds) {
   PG_API_BEGIN
   require_init();
@@ -2555,6 +2668,7 @@ void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st
     return;
   }
   const pg_krylov_opts o = opts ? *opts : default_opts();
+  mg_prepare(s, o);
   hipStream_t stream = ctx().stream;
   const i64 n = s->nb.n_own;
   ensure_bconst(s, PG_SCHEME_STEADY);
@@ -2616,6 +2730,7 @@ static void refine_once(pg_solver* s, const pg_krylov_opts& o, SolveStats& st) {
 // does for a slab of the moving solvers.  One step of iterative refinement follows (refine_once).
 void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
+  if (o.precond == PG_PRECOND_MG) mg_conditions(s, o.method);   // (a solver built for one time step: refused)
   const i64 n = s->nb.n_own;
   if (!(o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) || s->initial_done) {
     do_initial(s, opts, st);

@@ -150,7 +150,11 @@ void do_step(pg_streamvort* sv, int scheme, const pg_krylov_opts* opts, SolveSta
   std::unique_ptr<pg_solver, int32_t (*)(pg_solver*)> guard(next, pg_solver_destroy);
   if (!sv->border_values_omega.empty()) check_status(pg_solver_set_border_values(next, sv->border_values_omega.data()));
   if (clk) sp->build_ms += clk->lap();
-  solver_first_solve_from_state(next, opts, st_omega);
+  // the call's one set of options serves both solves: PG_PRECOND_MG is meant for ψ, the vorticity solve runs as with precond = 0
+  pg_krylov_opts o_omega;
+  const pg_krylov_opts* opts_omega = opts;
+  if (opts && opts->precond == PG_PRECOND_MG) { o_omega = *opts; o_omega.precond = 0; opts_omega = &o_omega; }
+  solver_first_solve_from_state(next, opts_omega, st_omega);
   solver_state_padded(next, sv->omega.p);
   if (sv->omega_solver) (void)pg_solver_destroy(sv->omega_solver);          // the new one has taken its state
   sv->omega_solver = guard.release();

@@ -82,6 +82,7 @@ class StreamVorticity:
         self.source = source
         self.unconverged = 0
         self.last_run: Optional[L.pg_streamvort_run_info] = None
+        self.last_step = None         # (pg_step_info of ψ, pg_step_info of ω) of the last step_StreamVorticity_b
         mesh = capacity.mesh
         M = self._M = int(np.prod(mesh.ext))
         D = _dcoef(Phase(capacity, self.operator, source, ν), M)
@@ -272,6 +273,7 @@ def step_StreamVorticity_b(s: StreamVorticity, scheme: str = "BE", method="bicgs
     L.check(L.lib().pg_streamvort_step(s._h, C.c_int32(sch), C.byref(opts), C.byref(ip), C.byref(iw)))
     s._have_velocity = True
     s._touch()
+    s.last_step = (ip, iw)            # pg_step_info of the stream-function and of the vorticity solve
     _step_info_check(s, ip, "the stream-function solve")
     _step_info_check(s, iw, "the vorticity solve")
     return s.ω

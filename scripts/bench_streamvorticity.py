@@ -4,6 +4,12 @@ convection operators stay on the device) against the same step composed from the
 PCIe), same geometry, same data, same Krylov tolerance, one process, the two paths alternating.
 
     python scripts/bench_streamvorticity.py [out.json] [n ...]        (default: profiles/streamvorticity_bench.json 512 1024)
+    python scripts/bench_streamvorticity.py --precond mg [out.json] [n ...]
+                                                   (default: profiles/streamvorticity_mg_bench.json 512 1024)
+
+With --precond the two alternating paths are StreamVorticity with the default options and StreamVorticity with that
+preconditioner on the stream-function solve ("mg": the aggregation multigrid V-cycle; an integer: as pg_krylov_opts.precond):
+steps/s, the ψ solve's ms, iterations and products per step, the hierarchy's set-up time, memory and levels.
 
 Geometry of the test suite's shape C: flow past the cylinder r = 0.15 at (0.5, 0.47) in the unit box, ψ = y on the borders (a
 uniform stream), ψ = 0.47 on the body, ω = 0 on borders and body, ω0 = 20 exp(-((x-0.25)² + (y-0.6)²)/0.01), ν = 1e-3,
@@ -22,8 +28,14 @@ sys.path.insert(0, ".")
 import penguin.jl_amd as pj
 from penguin.jl_amd import _lib as L
 
-OUT = sys.argv[1] if len(sys.argv) > 1 else "profiles/streamvorticity_bench.json"
-SIZES = [int(a) for a in sys.argv[2:]] or [512, 1024]
+ARGS = sys.argv[1:]
+PRECOND = None
+if "--precond" in ARGS:
+    k = ARGS.index("--precond")
+    PRECOND = ARGS[k + 1] if ARGS[k + 1] == "mg" else int(ARGS[k + 1])
+    del ARGS[k:k + 2]
+OUT = ARGS[0] if ARGS else ("profiles/streamvorticity_bench.json" if PRECOND is None else "profiles/streamvorticity_mg_bench.json")
+SIZES = [int(a) for a in ARGS[1:]] or [512, 1024]
 WARMUP, STEPS, REPEATS = 5, 20, 3
 KEYS = ("left", "right", "bottom", "top")
 SCHEME = "BE"
@@ -133,7 +145,67 @@ def measure(n):
                 state_finite=bool(np.all(np.isfinite(new.ω)) and np.all(np.isfinite(new.ψ))))
 
 
+def _sv_result(win, runs, tot):
+    return dict(steps_per_s=STEPS / statistics.median(win), windows_s=win,
+                psi_products_per_step=sum(r.psi_products for r in runs) / tot,
+                omega_products_per_step=sum(r.omega_products for r in runs) / tot,
+                psi_iters_per_step=sum(r.psi_iters for r in runs) / tot, omega_iters_per_step=sum(r.omega_iters for r in runs) / tot,
+                per_step_ms=dict(psi_solve=sum(r.psi_ms for r in runs) / tot, velocity_and_convection=sum(r.velocity_ms for r in runs) / tot,
+                                 omega_solver_construction=sum(r.build_ms for r in runs) / tot, omega_solve=sum(r.omega_ms for r in runs) / tot))
+
+
+def measure_precond(n):
+    """default options against --precond on the ψ solve: two StreamVorticity solvers on the same problem, windows alternating"""
+    P = problem(n)
+    make = lambda: pj.StreamVorticity(P["cap"], P["nu"], P["dt"], bc_stream=pj.Dirichlet(0.47), bc_stream_border=P["bs"],
+                                      bc_vorticity_border=P["bw"], ω0=P["w0"])
+    plain, pre = make(), make()
+    pj.run_StreamVorticity_b(plain, WARMUP, SCHEME, save_every=0)
+    pj.run_StreamVorticity_b(pre, WARMUP, SCHEME, save_every=0, precond=PRECOND)
+    agree_after_warmup = float(np.linalg.norm(pre.ω - plain.ω) / np.linalg.norm(plain.ω))
+    win = {"plain": [], "pre": []}
+    runs = {"plain": [], "pre": []}
+    for _ in range(REPEATS):
+        for key, sv, kw in (("plain", plain, {}), ("pre", pre, {"precond": PRECOND})):
+            sync()
+            t0 = time.perf_counter()
+            pj.run_StreamVorticity_b(sv, STEPS, SCHEME, save_every=0, **kw)
+            sync()
+            win[key].append(time.perf_counter() - t0)
+            runs[key].append(sv.last_run)
+            assert sv.last_run.unconverged == 0
+    tot = REPEATS * STEPS
+    info = pre.psi_solver.system_info(0)
+    a, b = _sv_result(win["plain"], runs["plain"], tot), _sv_result(win["pre"], runs["pre"], tot)
+    spread = lambda w: (max(w) - min(w)) / statistics.median(w)
+    out = dict(n=n, cells=P["M"], rows_per_system=int(info.n_own), dt=P["dt"], scheme=SCHEME, precond=PRECOND, default_options=a,
+               with_precond=b, speedup_steps=b["steps_per_s"] / a["steps_per_s"],
+               speedup_psi_solve=a["per_step_ms"]["psi_solve"] / b["per_step_ms"]["psi_solve"],
+               window_spread=dict(default_options=spread(win["plain"]), with_precond=spread(win["pre"])),
+               omega_rel_l2_between_paths_after_warmup=agree_after_warmup,
+               omega_rel_l2_between_paths_at_end=float(np.linalg.norm(pre.ω - plain.ω) / np.linalg.norm(plain.ω)),
+               psi_rel_l2_between_paths_at_end=float(np.linalg.norm(pre.ψ - plain.ψ) / np.linalg.norm(plain.ψ)),
+               state_finite=bool(np.all(np.isfinite(pre.ω)) and np.all(np.isfinite(pre.ψ))))
+    if PRECOND == "mg":
+        out["hierarchy"] = pre.psi_solver.mg_info()
+    return out
+
+
 pj.init(0)
+if PRECOND is not None:
+    from penguin.jl_amd.build import source_hash
+
+    res = dict(what="stream function - vorticity step, flow past a cylinder (shape C of tests/test_gpu_streamvorticity.py), one rank: "
+                    "default options against --precond on the stream-function solve",
+               warmup_steps=WARMUP, steps_per_window=STEPS, windows=REPEATS, reltol=1e-12, device=pj.device_name(),
+               config=pj.config_string(), source_hash=source_hash(), sizes=[])
+    for n in SIZES:
+        res["sizes"].append(measure_precond(n))
+        print(json.dumps(res["sizes"][-1]), flush=True)
+        with open(OUT, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    sys.exit(0)
 res = dict(what="stream function - vorticity step, flow past a cylinder (shape C of tests/test_gpu_streamvorticity.py), one rank",
            warmup_steps=WARMUP, steps_per_window=STEPS, windows=REPEATS, reltol=1e-12, device=pj.device_name(),
            config=pj.config_string(), sizes=[])
