@@ -96,9 +96,17 @@ typedef struct {
                           with a Dirichlet interface and the stream-function solve of a pg_streamvort, one rank; refused with an
                           error that names the failed condition anywhere else, never replaced by another iteration.  Such a
                           solve reports poly_degree = 0 and poly_xspace = 0 like a plain one (pg_solver_mg_info tells whether a
-                          hierarchy exists); with profiling on, each V-cycle counts as one lean launch in spmv_lean_* */
+                          hierarchy exists); with profiling on, each V-cycle counts as one lean launch in spmv_lean_*;
+                          PG_PRECOND_MG_CELL: the same V-cycle on a cell-aggregated hierarchy (DESIGN.md "Cell-aggregated
+                          multigrid") -- steady monophasic diffusion (DarcyFlow included) with a Dirichlet, Robin or Neumann
+                          interface, one rank; refused like PG_PRECOND_MG anywhere else, a pg_streamvort included */
 } pg_krylov_opts;
 enum { PG_PRECOND_MG = -2 };   /* a value of pg_krylov_opts.precond */
+/* a value of pg_krylov_opts.precond: multigrid whose first coarsening merges ALL unknowns, bulk and interface, of a 2 x 2 (x 2)
+   block of cells into one coarse unknown.  With a Robin or Neumann interface the interface rows are equations of their own and
+   the kind-separated aggregates of PG_PRECOND_MG give non-positive coarse diagonals; this rule serves those systems.  A solver
+   holds one hierarchy per value: a solve with one neither reuses nor disturbs the other's. */
+enum { PG_PRECOND_MG_CELL = -3 };
 
 /* the multigrid hierarchy of a solver (pg_solver_mg_info), built by the first solve that asks for PG_PRECOND_MG */
 #define PG_MG_MAX_LEVELS 16
@@ -454,6 +462,8 @@ int32_t pg_solver_get_system_csr(const pg_solver* s, int32_t which, int64_t* row
 int32_t pg_solver_get_row_scaling(const pg_solver* s, int32_t which, double* ds);
 /* the multigrid hierarchy of the solver's constructor system (levels = 0 before the first PG_PRECOND_MG solve) */
 int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out);
+/* ... and the hierarchy of `precond` = PG_PRECOND_MG (the call above) or PG_PRECOND_MG_CELL */
+int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* out);
 /* bench helper: `reps` launches of y = A x on the run matrix, HIP-event timed on the library stream. */
 int32_t pg_solver_time_spmv(pg_solver* s, int32_t which, int32_t reps, double* avg_ms);
 
@@ -524,8 +534,8 @@ int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const int64_t* n, 
                                    int64_t* n_ghost_out, int64_t* iters_out);
 /* Krylov method (PG_METHOD_*) and GMRES restart length of the virtual-rank runs that follow (default BiCGStab) */
 int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart);
-/* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG makes pg_debug_run_virtual_ranks fail
-   with the multigrid's one-rank refusal before any rank starts */
+/* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG and PG_PRECOND_MG_CELL make
+   pg_debug_run_virtual_ranks fail with the multigrid's one-rank refusal before any rank starts */
 int32_t pg_debug_set_virtual_rank_precond(int32_t precond);
 /* ramp != 0: the virtual-rank runs that follow change the interface value every step, g = interface_value (1 + ramp step)
    (host-driven steps): rows alone on their diagonal move in every step, on every rank */
@@ -555,6 +565,12 @@ int32_t pg_debug_set_poly_give_up(int32_t iterations);
 int32_t pg_debug_mg_aggregates(pg_solver* s, int32_t level, int64_t* n, int32_t* agg);
 int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val);
 int32_t pg_debug_mg_apply(pg_solver* s, const double* r, double* z);
+/* the same three on the hierarchy of `precond` = PG_PRECOND_MG (the calls above) or PG_PRECOND_MG_CELL (compared with
+   tests/mgc_reference.py by tests/test_gpu_mg_cell.py); they refuse what that value refuses */
+int32_t pg_debug_mg_aggregates_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int32_t* agg);
+int32_t pg_debug_mg_level_csr_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
+                                  double* val);
+int32_t pg_debug_mg_apply_for(pg_solver* s, int32_t precond, const double* r, double* z);
 
 /* The extrapolated start of the time loop's quiet steps (constant data, one rank; no reference counterpart: the reference
    starts every Krylov solve from zero, solver.jl:158-181): `kept` older states are held; the next step starts from

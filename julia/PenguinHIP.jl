@@ -91,11 +91,15 @@ end
 # reference (warm_start=false, precond=-1 give IterativeSolvers' plain iteration from a zero initial guess).
 # precond = :mg (PG_PRECOND_MG): the aggregation multigrid V-cycle -- steady monophasic diffusion with a Dirichlet interface and
 # the stream-function solve of a StreamVorticity; the library refuses it anywhere else.
+# precond = :mg_cell (PG_PRECOND_MG_CELL): the same V-cycle on the cell-aggregated hierarchy -- steady monophasic diffusion
+# (DarcyFlow included) with a Dirichlet, Robin or Neumann interface.
 const PG_PRECOND_MG = Int32(-2)
+const PG_PRECOND_MG_CELL = Int32(-3)
 function _precond_id(p)
     p isa Symbol || return Int32(p)
-    p === :mg || error("precond must be an integer or :mg, not :$(p)")
-    PG_PRECOND_MG
+    p === :mg && return PG_PRECOND_MG
+    p === :mg_cell || error("precond must be an integer, :mg or :mg_cell, not :$(p)")
+    PG_PRECOND_MG_CELL
 end
 function _opts(method, kw; warm_default::Bool=true)
     pg_krylov_opts(_method_id(method), Float64(get(kw, :reltol, 1e-12)), Float64(get(kw, :abstol, 0.0)),
@@ -1447,26 +1451,27 @@ end
 
 """
 The multigrid hierarchy of a solver's constructor system (`pg_solver_mg_info`): levels (0 before the first solve with
-`precond = :mg`), the first level of the fused tail, rows and nnz per level, set-up time, device memory.
+that `precond`), the first level of the fused tail, rows and nnz per level, set-up time, device memory.  `precond`: `:mg` or
+`:mg_cell` -- a solver holds one hierarchy per value.
 """
-function mg_info(s)
+function mg_info(s; precond=:mg)
     # pg_mg_info: int32 levels, int32 tail_level, int64 rows[16], int64 nnz[16], double setup_ms, int64 bytes = 35 words
     buf = zeros(Int64, 35)
     GC.@preserve buf begin
-        check(ccall((:pg_solver_mg_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}), s.handle, pointer(buf)))
+        check(ccall((:pg_solver_mg_info_for, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), s.handle, _precond_id(precond), pointer(buf)))
     end
     levels = Int(buf[1] & 0xffffffff); tail = Int((buf[1] >> 32) & 0xffffffff)
     (levels = levels, tail_level = tail, rows = buf[2:1 + levels], nnz = buf[18:17 + levels],
      setup_ms = reinterpret(Float64, buf[34]), bytes = buf[35])
 end
 
-"`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg` makes them fail with the one-rank refusal)."
+"`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg` and `:mg_cell` make them fail with the one-rank refusal)."
 set_virtual_rank_precond(p) = check(ccall((:pg_debug_set_virtual_rank_precond, libpg), Int32, (Int32,), _precond_id(p)))
 
-"One application z = M⁻¹ r of the multigrid V-cycle on host vectors (`pg_debug_mg_apply`; builds the hierarchy if need be)."
-function mg_apply(s, r::Vector{Float64})
+"One application z = M⁻¹ r of the multigrid V-cycle on host vectors (`pg_debug_mg_apply_for`; builds the hierarchy if need be)."
+function mg_apply(s, r::Vector{Float64}; precond=:mg)
     z = zeros(Float64, length(r))
-    check(ccall((:pg_debug_mg_apply, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), s.handle, r, z))
+    check(ccall((:pg_debug_mg_apply_for, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), s.handle, _precond_id(precond), r, z))
     z
 end
 

@@ -34,6 +34,7 @@ PG_SCHEME = {"BE": 0, "CN": 1, "STEADY": 2}
 PG_METHOD = {"bicgstab": 0, "cg": 1, "gmres": 2}
 PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a pg_streamvort
 PG_PRECOND_MG = -2                   # pg_krylov_opts.precond: the aggregation multigrid V-cycle
+PG_PRECOND_MG_CELL = -3              # ... on the cell-aggregated hierarchy (Dirichlet, Robin and Neumann interfaces)
 PG_MG_MAX_LEVELS = 16
 
 c_double_p = C.POINTER(C.c_double)
@@ -226,38 +227,40 @@ def config_string() -> str:
 
 
 # ---- diagnostics: the multigrid hierarchy against the numpy restatement (tests/mg_reference.py) -----------------------------
-def solver_mg_info(handle) -> dict:
-    """pg_solver_mg_info: levels, first level of the fused tail, rows and nnz per level, set-up ms, device bytes."""
+# (precond: PG_PRECOND_MG or PG_PRECOND_MG_CELL, the hierarchy that is meant)
+def solver_mg_info(handle, precond: int = PG_PRECOND_MG) -> dict:
+    """pg_solver_mg_info_for: levels, first level of the fused tail, rows and nnz per level, set-up ms, device bytes."""
     info = pg_mg_info()
-    check(lib().pg_solver_mg_info(handle, C.byref(info)))
+    check(lib().pg_solver_mg_info_for(handle, C.c_int32(precond), C.byref(info)))
     n = info.levels
     return {"levels": n, "tail_level": info.tail_level, "rows": list(info.rows[:n]), "nnz": list(info.nnz[:n]),
             "setup_ms": info.setup_ms, "bytes": info.bytes}
 
 
-def debug_mg_aggregates(handle, level: int) -> np.ndarray:
-    """pg_debug_mg_aggregates: the row of level + 1 every row of `level` belongs to."""
+def debug_mg_aggregates(handle, level: int, precond: int = PG_PRECOND_MG) -> np.ndarray:
+    """pg_debug_mg_aggregates_for: the row of level + 1 every row of `level` belongs to."""
     n = C.c_int64(0)
-    check(lib().pg_debug_mg_aggregates(handle, C.c_int32(level), C.byref(n), None))
+    check(lib().pg_debug_mg_aggregates_for(handle, C.c_int32(precond), C.c_int32(level), C.byref(n), None))
     agg = np.zeros(max(n.value, 1), dtype=np.int32)
-    check(lib().pg_debug_mg_aggregates(handle, C.c_int32(level), C.byref(n), agg.ctypes.data_as(c_i32_p)))
+    check(lib().pg_debug_mg_aggregates_for(handle, C.c_int32(precond), C.c_int32(level), C.byref(n), agg.ctypes.data_as(c_i32_p)))
     return agg[: n.value]
 
 
-def debug_mg_level_csr(handle, level: int):
-    """pg_debug_mg_level_csr: (rowptr, col, val) of the matrix of `level` (0: the Krylov matrix)."""
+def debug_mg_level_csr(handle, level: int, precond: int = PG_PRECOND_MG):
+    """pg_debug_mg_level_csr_for: (rowptr, col, val) of the matrix of `level` (0: the Krylov matrix)."""
     n, nnz = C.c_int64(0), C.c_int64(0)
-    check(lib().pg_debug_mg_level_csr(handle, C.c_int32(level), C.byref(n), C.byref(nnz), None, None, None))
+    pc = C.c_int32(precond)
+    check(lib().pg_debug_mg_level_csr_for(handle, pc, C.c_int32(level), C.byref(n), C.byref(nnz), None, None, None))
     rowptr, col, val = np.zeros(n.value + 1, dtype=np.int64), np.zeros(max(nnz.value, 1), dtype=np.int64), np.zeros(max(nnz.value, 1))
-    check(lib().pg_debug_mg_level_csr(handle, C.c_int32(level), C.byref(n), C.byref(nnz), iptr(rowptr), iptr(col), dptr(val)))
+    check(lib().pg_debug_mg_level_csr_for(handle, pc, C.c_int32(level), C.byref(n), C.byref(nnz), iptr(rowptr), iptr(col), dptr(val)))
     return rowptr, col[: nnz.value], val[: nnz.value]
 
 
-def debug_mg_apply(handle, r: np.ndarray) -> np.ndarray:
-    """pg_debug_mg_apply: z = M⁻¹ r, one application of the V-cycle as the Krylov loop runs it."""
+def debug_mg_apply(handle, r: np.ndarray, precond: int = PG_PRECOND_MG) -> np.ndarray:
+    """pg_debug_mg_apply_for: z = M⁻¹ r, one application of the V-cycle as the Krylov loop runs it."""
     r = np.ascontiguousarray(r, dtype=np.float64)
     z = np.zeros_like(r)
-    check(lib().pg_debug_mg_apply(handle, dptr(r), dptr(z)))
+    check(lib().pg_debug_mg_apply_for(handle, C.c_int32(precond), dptr(r), dptr(z)))
     return z
 
 

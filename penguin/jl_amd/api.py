@@ -649,10 +649,11 @@ class Solver:
         return {"kept": kept.value, "offsets": list(off[: ns.value]), "coef": list(cf[: ns.value]), "rr_plain": ru.value,
                 "rr_taken": rw.value}
 
-    def mg_info(self) -> dict:
+    def mg_info(self, precond="mg") -> dict:
         """The multigrid hierarchy of the constructor system (pg_solver_mg_info): levels (0 before the first solve with
-        precond="mg"), tail_level, rows and nnz per level, setup_ms, bytes."""
-        return L.solver_mg_info(self._h)
+        that `precond`), tail_level, rows and nnz per level, setup_ms, bytes.  precond: "mg" or "mg-cell" -- a solver holds
+        one hierarchy per value."""
+        return L.solver_mg_info(self._h, _precond_value(precond))
 
     def system_info(self, which: int = 0) -> L.pg_system_info:
         info = L.pg_system_info()
@@ -771,21 +772,30 @@ def _step_info_check(s: "Solver", info: L.pg_step_info, what: str) -> None:
     _check_converged(s, bool(info.converged), what, info.resnorm / info.bnorm if info.bnorm > 0 else info.resnorm)
 
 
+_PRECOND_NAMES = {"mg": L.PG_PRECOND_MG, "mg-cell": L.PG_PRECOND_MG_CELL}
+
+
+def _precond_value(precond) -> int:
+    """pg_krylov_opts.precond of a `precond` keyword: an integer as it is, "mg" -> PG_PRECOND_MG, "mg-cell" -> PG_PRECOND_MG_CELL."""
+    if isinstance(precond, str):
+        if precond.lower() not in _PRECOND_NAMES:
+            raise ValueError(f'precond must be an integer, "mg" or "mg-cell", not {precond!r}')
+        return _PRECOND_NAMES[precond.lower()]
+    return int(precond)
+
+
 def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     """method may be "bicgstab" / "cg" / "gmres" or a callable named like IterativeSolvers' (bicgstabl, cg, gmres...).
     gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; `\\`, bicgstabl and anything else ->
     BiCGStab.  reltol defaults to 1e-12: the parity target is the direct-solve path.
     precond: an integer as pg_krylov_opts.precond takes it (0 automatic, -1 off, m >= 1 the polynomial's degree), or "mg":
     the aggregation multigrid V-cycle (steady monophasic diffusion with a Dirichlet interface and the ψ solve of a
-    StreamVorticity; the library refuses it anywhere else)."""
+    StreamVorticity; the library refuses it anywhere else), or "mg-cell": the same V-cycle on the cell-aggregated hierarchy
+    (steady monophasic diffusion, DarcyFlow included, with a Dirichlet, Robin or Neumann interface)."""
     name = method if isinstance(method, str) else getattr(method, "__name__", "bicgstab")
     name = name.lower()
     m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])
-    precond = kwargs.get("precond", 0)
-    if isinstance(precond, str):
-        if precond.lower() != "mg":
-            raise ValueError(f'precond must be an integer or "mg", not {precond!r}')
-        precond = L.PG_PRECOND_MG
+    precond = _precond_value(kwargs.get("precond", 0))
     return L.pg_krylov_opts(m, float(kwargs.get("reltol", 1e-12)), float(kwargs.get("abstol", 0.0)),
                             int(kwargs.get("maxiter", 0)), int(kwargs.get("check_every", 4)),
                             int(bool(kwargs.get("warm_start", True))), int(kwargs.get("restart", 0)),

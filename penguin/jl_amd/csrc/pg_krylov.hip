@@ -28,7 +28,7 @@
 // chain, and the stopping test is unchanged.  The vector passes, the reductions and, with several ranks, the all-reduces
 // of a time step fall with the iteration count.
 //
-// Multigrid right preconditioner (opts.precond = PG_PRECOND_MG, never automatic): the same x-space loop with M⁻¹ = one V-cycle
+// Multigrid right preconditioner (opts.precond = PG_PRECOND_MG or PG_PRECOND_MG_CELL, never automatic): the same x-space loop with M⁻¹ = one V-cycle
 // of pg_multigrid.hip where the Horner chain stands -- ya = M⁻¹p, yb = M⁻¹s, then the plain product with its dots.  It is a
 // branch of its own: no degree, no adaptation, no give-up rule; the half-step test runs in every iteration (an application
 // costs five to six products' worth of bytes).  SolveStats::products counts the products with Â of the outer loop, i.e. the
@@ -689,13 +689,16 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   const bool poly = m > 0;
   MgHierarchy* const mgh = w.mg;
   w.mg = nullptr;
-  const bool mg = opts.precond == PG_PRECOND_MG;
+  const bool mg = mg_is_precond(opts.precond);
   if (mg) {
     PG_REQUIRE(!cg, "multigrid preconditioner refused: the method must be BiCGStab");
     PG_REQUIRE(spmv_supports_preconditioner_product(), "multigrid preconditioner refused: the x-space loop needs the slice kernel (PG_SPMV_VARIANT)");
-    mg_require_one_rank();
+    mg_require_one_rank(mg_rule_of(opts.precond));
     PG_REQUIRE(mgh && !w.scatter && !xg.zbase && n > 0, "multigrid preconditioner refused: this solve has no hierarchy (steady monophasic "
                "diffusion systems and the stream-function solve only)");
+    PG_REQUIRE(mgh->rule == mg_rule_of(opts.precond),
+               std::string("multigrid preconditioner: the hierarchy handed over was not built for precond = ") +
+                   mg_precond_name(mg_rule_of(opts.precond)));
   }
   const bool pre = poly || mg;   // right-preconditioned: x moves by α M⁻¹p (k_bicg_s_x) and ω M⁻¹s (k_bicg_xrp)
   stats.poly_degree = m;

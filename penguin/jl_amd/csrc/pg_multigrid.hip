@@ -5,9 +5,11 @@
 //   level 0        Â = B⁻¹ S A S, the matrix the Krylov loop iterates on (unit diagonal), borrowed.  Under a Dirichlet interface
 //                  B⁻¹ only removes the same-cell γ entry of the ω rows of cut cells (their γ rows are rows of the identity)
 //   aggregates     unknown of kind k in padded cell (i, j, k3) -> (k, i >> 1, j >> 1, k3 >> 1); coarse unknowns numbered kind-major,
-//                  then by coarse cell, dimension 0 fastest (flag + scan, the layout of Numbering)
+//                  then by coarse cell, dimension 0 fastest (flag + scan, the layout of Numbering).  Cell rule (MG_RULE_CELL,
+//                  PG_PRECOND_MG_CELL): level 0 -> 1 drops the kind -- every unknown of the 2 x 2 (x 2) cells shares one coarse
+//                  unknown, <= 8 K children in slot parity + 8 kind; the levels below have one kind and coarsen as above
 //   transfers      P̂_0 has 1 / s_i at fine unknown i (piecewise constant in the unknowns of A: P̂ᵀ S A S P̂ = Pᵀ A P); 0 / 1 below
-//   operators      Galerkin, A_(l+1) = P_lᵀ A_l P_l, one thread per coarse row gathering its <= 8 fine rows
+//   operators      Galerkin, A_(l+1) = P_lᵀ A_l P_l, one thread per coarse row gathering its <= 8 (cell rule, level 1: 8 K) fine rows
 //   smoother       damped Jacobi, ω = 0.7, 2 + 2 sweeps (the first from zero: a pointwise scale)
 //   correction     x += 1.8 P e_c, fused with the prolongation; the residual is fused with the restriction, written as a gather
 //                  over coarse rows: no atomics anywhere, an application is bitwise reproducible.  (Level 0 above the tail:
@@ -39,12 +41,19 @@ struct MgGrid {
 };
 
 // ---- set-up ---------------------------------------------------------------------------------------------------------
+// slot0 == nullptr: the kind rule, key = kind * M + cell.  Otherwise the cell rule: the kind-free key, and the kind's offset
+// 8 * kind into the child table of the coarse unknown the cell's unknowns share (k_mg_agg adds the parity of the cell).
 __global__ void k_mg_key0(i64 n, MgSegs seg, const int* __restrict__ row_cell, i64 M, const double* __restrict__ ds, int* __restrict__ key,
-                          double* __restrict__ pw) {
+                          double* __restrict__ pw, unsigned char* __restrict__ slot0) {
   for (i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x; r < n; r += (i64)gridDim.x * blockDim.x) {
     int k = 0;
     while (k + 1 < seg.K && r >= seg.off_own[k + 1]) ++k;
-    key[r] = (int)((i64)k * M + row_cell[r]);
+    if (slot0) {
+      key[r] = row_cell[r];
+      slot0[r] = (unsigned char)(8 * k);
+    } else {
+      key[r] = (int)((i64)k * M + row_cell[r]);
+    }
     pw[r] = 1.0 / ds[r];
   }
 }
@@ -74,15 +83,17 @@ __global__ void k_mg_flag(i64 n, MgGrid g, const int* __restrict__ key, unsigned
   }
 }
 
-// idx: exclusive scan of the flags = the coarse numbering.  The <= 8 fine rows of a coarse row have distinct slots.
-__global__ void k_mg_agg(i64 n, MgGrid g, const int* __restrict__ key, const int* __restrict__ idx, int* __restrict__ agg,
-                         int* __restrict__ child, int* __restrict__ keyc) {
+// idx: exclusive scan of the flags = the coarse numbering.  The <= cw fine rows of a coarse row have distinct slots (slot0, cell
+// rule between levels 0 and 1: the offset of the row's kind; nullptr elsewhere, cw = 8).
+__global__ void k_mg_agg(i64 n, MgGrid g, const int* __restrict__ key, const int* __restrict__ idx, const unsigned char* __restrict__ slot0,
+                         int cw, int* __restrict__ agg, int* __restrict__ child, int* __restrict__ keyc) {
   for (i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x; r < n; r += (i64)gridDim.x * blockDim.x) {
     int slot;
     const i64 ck = mg_coarse_key(g, key[r], &slot);
+    if (slot0) slot += slot0[r];
     const int a = idx[ck];
     agg[r] = a;
-    child[(i64)a * 8 + slot] = (int)r;
+    child[(i64)a * cw + slot] = (int)r;
     keyc[a] = (int)ck;   // (the same value from every child)
   }
 }
@@ -91,7 +102,7 @@ __global__ void k_mg_agg(i64 n, MgGrid g, const int* __restrict__ key, const int
 // sorted by coarse column.  FILL = false counts the row (cnt[c]); FILL = true writes it at crowptr[c] and 1 / its diagonal.
 // *err = 2: a row longer than MG_MAX_ROW (count pass); = 4: a coarse diagonal that is not positive (fill pass).
 template <bool FILL>
-__global__ void k_mg_galerkin(i64 nc, const int* __restrict__ child, const int* __restrict__ rowptr, const int* __restrict__ col,
+__global__ void k_mg_galerkin(i64 nc, const int* __restrict__ child, int cw, const int* __restrict__ rowptr, const int* __restrict__ col,
                               const double* __restrict__ val, const int* __restrict__ agg, const double* __restrict__ pw,
                               int* __restrict__ cnt, const int* __restrict__ crowptr, int* __restrict__ ccol, double* __restrict__ cval,
                               double* __restrict__ dinv, int* __restrict__ err) {
@@ -100,8 +111,8 @@ __global__ void k_mg_galerkin(i64 nc, const int* __restrict__ child, const int* 
     double vals[FILL ? MG_MAX_ROW : 1];
     int m = 0;
     bool over = false;
-    for (int s = 0; s < 8; ++s) {
-      const int i = child[c * 8 + s];
+    for (int s = 0; s < cw; ++s) {
+      const int i = child[c * cw + s];
       if (i < 0) continue;
       const double wi = pw ? pw[i] : 1.0;
       for (int e = rowptr[i]; e < rowptr[i + 1]; ++e) {
@@ -153,11 +164,11 @@ __device__ inline double mg_jacobi(const int* rowptr, const int* col, const doub
                                    const double* x, int i) {
   return x[i] + MG_OMEGA * (dinv ? dinv[i] : 1.0) * (r[i] - mg_row_dot(rowptr, col, val, i, x));
 }
-__device__ inline double mg_restrict(const int* child, const int* rowptr, const int* col, const double* val, const double* pw,
+__device__ inline double mg_restrict(const int* child, int cw, const int* rowptr, const int* col, const double* val, const double* pw,
                                      const double* r, const double* x, int c) {
   double acc = 0.0;
-  for (int s = 0; s < 8; ++s) {
-    const int i = child[(i64)c * 8 + s];
+  for (int s = 0; s < cw; ++s) {
+    const int i = child[(i64)c * cw + s];
     if (i >= 0) acc += (pw ? pw[i] : 1.0) * (r[i] - mg_row_dot(rowptr, col, val, i, x));
   }
   return acc;
@@ -182,25 +193,25 @@ __global__ __launch_bounds__(MG_BLOCK) void k_mg_jacobi(i64 n, const int* __rest
 }
 
 // r_c = Pᵀ (r - A x): the residual fused with the restriction, a gather over coarse rows
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(i64 nc, const int* __restrict__ child, const int* __restrict__ rowptr,
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict(i64 nc, const int* __restrict__ child, int cw, const int* __restrict__ rowptr,
                                                           const int* __restrict__ col, const double* __restrict__ val,
                                                           const double* __restrict__ pw, const double* __restrict__ r,
                                                           const double* __restrict__ x, double* __restrict__ rc,
                                                           const double* __restrict__ sc) {
   if (sc && sc[S_DONE] != 0.0) return;
   for (i64 c = blockIdx.x * (i64)MG_BLOCK + threadIdx.x; c < nc; c += (i64)gridDim.x * MG_BLOCK)
-    rc[c] = mg_restrict(child, rowptr, col, val, pw, r, x, (int)c);
+    rc[c] = mg_restrict(child, cw, rowptr, col, val, pw, r, x, (int)c);
 }
 
 // r_c = Pᵀ res with the residual already formed (level 0, where the marching-unit SpMV forms it: see mg_apply)
-__global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict_vec(i64 nc, const int* __restrict__ child, const double* __restrict__ pw,
+__global__ __launch_bounds__(MG_BLOCK) void k_mg_restrict_vec(i64 nc, const int* __restrict__ child, int cw, const double* __restrict__ pw,
                                                               const double* __restrict__ res, double* __restrict__ rc,
                                                               const double* __restrict__ sc) {
   if (sc && sc[S_DONE] != 0.0) return;
   for (i64 c = blockIdx.x * (i64)MG_BLOCK + threadIdx.x; c < nc; c += (i64)gridDim.x * MG_BLOCK) {
     double acc = 0.0;
-    for (int s = 0; s < 8; ++s) {
-      const int i = child[c * 8 + s];
+    for (int s = 0; s < cw; ++s) {
+      const int i = child[c * cw + s];
       if (i >= 0) acc += (pw ? pw[i] : 1.0) * res[i];
     }
     rc[c] = acc;
@@ -227,7 +238,8 @@ struct MgTailLevel {
   const double* dinv;
   const double* pw;
   const int* agg;
-  const int* child;   // 8 per row of the next level
+  const int* child;   // cw per row of the next level
+  int cw;
 };
 struct MgTailArgs {
   int nl;
@@ -254,7 +266,7 @@ __global__ __launch_bounds__(MG_TAIL_BLOCK) void k_mg_tail(MgTailArgs a, const d
     __syncthreads();
     const MgTailLevel& c = a.L[l + 1];
     double* rc = sm + c.off;
-    for (int q = tid; q < c.n; q += nt) rc[q] = mg_restrict(v.child, v.rowptr, v.col, v.val, v.pw, r, xb, q);
+    for (int q = tid; q < c.n; q += nt) rc[q] = mg_restrict(v.child, v.cw, v.rowptr, v.col, v.val, v.pw, r, xb, q);
     __syncthreads();
   }
   {
@@ -300,16 +312,16 @@ void check_err(const DevBuf<int>& err, const char* where) {
 
 namespace pg {
 
-void mg_require_one_rank() {
+void mg_require_one_rank(MgRule rule) {
   Context& cx = ctx();
-  PG_REQUIRE(cx.nranks == 1 && !cx.comm && !cx.local,
-             "multigrid preconditioner (precond = PG_PRECOND_MG) refused: it runs on one rank only (virtual ranks included)");
+  PG_REQUIRE(cx.nranks == 1 && !cx.comm && !cx.local, std::string("multigrid preconditioner (precond = ") + mg_precond_name(rule) +
+                                                          ") refused: it runs on one rank only (virtual ranks included)");
 }
 
-void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Slab& slab) {
+void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Slab& slab, MgRule rule) {
   Context& cx = ctx();
   hipStream_t st = cx.stream;
-  mg_require_one_rank();
+  mg_require_one_rank(rule);
   PG_REQUIRE(nb.n_ghost == 0 && slab.s0 == 0 && slab.Mloc() == slab.M, "multigrid set-up: the numbering of one rank (no ghosts, every plane) is expected");
   PG_REQUIRE(nb.K == 2, "multigrid preconditioner refused: a monophasic system (two kinds of unknowns) is expected");
   PG_REQUIRE(A.n > 0 && A.n == nb.n_own, "multigrid preconditioner refused: empty system");
@@ -318,12 +330,19 @@ void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
   const auto t0 = std::chrono::steady_clock::now();
   H.lev.clear();
   H.bytes = 0;
+  H.rule = rule;
+  H.matrix = nullptr;
+  const bool cells = rule == MG_RULE_CELL;
   DevBuf<int> err(1);
   err.zero();
+  DevBuf<unsigned char> slot0;   // cell rule: 8 * kind of every row of level 0 (set-up only)
 
   {
     std::unique_ptr<MgLevel> l0(new MgLevel());
-    l0->n = A.n; l0->nnz = A.nnz; l0->K = nb.K;
+    l0->n = A.n; l0->nnz = A.nnz;
+    l0->K = cells ? 1 : nb.K;
+    l0->cw = cells ? 8 * nb.K : 8;
+    if (cells) slot0.alloc(A.n);
     for (int d = 0; d < 3; ++d) l0->ext[d] = slab.ext[d];
     l0->rowptr = A.rowptr.p; l0->col = A.col.p; l0->val = A.val.p;
     l0->key.alloc(A.n);
@@ -332,7 +351,7 @@ void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
     seg.K = nb.K;
     for (int k = 0; k < MAX_KINDS; ++k) seg.off_own[k] = nb.off_own[k];
     hipLaunchKernelGGL(k_mg_key0, dim3(mg_grid(A.n)), dim3(MG_BLOCK), 0, st, A.n, seg, (const int*)nb.row_cell.p, slab.M,
-                       (const double*)A.ds.p, l0->key.p, l0->pw.p);
+                       (const double*)A.ds.p, l0->key.p, l0->pw.p, cells ? slot0.p : (unsigned char*)nullptr);
     hipLaunchKernelGGL(k_mg_check_diag, dim3(mg_grid(A.n)), dim3(MG_BLOCK), 0, st, A.n, l0->rowptr, l0->col, l0->val, err.p);
     PG_HIP(hipGetLastError());
     check_err(err, "level 0");
@@ -360,12 +379,14 @@ void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
     total.download(&nc, 1);
     PG_REQUIRE(nc > 0 && nc < f.n, "multigrid set-up: the aggregation does not coarsen");
     c->n = nc;
+    const bool first = H.lev.size() == 1;
+    const int cw = f.cw;
     f.agg.alloc(f.n);
-    f.child.alloc((i64)nc * 8);
+    f.child.alloc((i64)nc * cw);
     c->key.alloc(nc);
-    PG_HIP(hipMemsetAsync(f.child.p, 0xFF, sizeof(int) * (size_t)nc * 8, st));
-    hipLaunchKernelGGL(k_mg_agg, dim3(mg_grid(f.n)), dim3(MG_BLOCK), 0, st, f.n, g, (const int*)f.key.p, (const int*)idx.p, f.agg.p,
-                       f.child.p, c->key.p);
+    PG_HIP(hipMemsetAsync(f.child.p, 0xFF, sizeof(int) * (size_t)nc * cw, st));
+    hipLaunchKernelGGL(k_mg_agg, dim3(mg_grid(f.n)), dim3(MG_BLOCK), 0, st, f.n, g, (const int*)f.key.p, (const int*)idx.p,
+                       (const unsigned char*)(cells && first ? slot0.p : nullptr), cw, f.agg.p, f.child.p, c->key.p);
     PG_HIP(hipGetLastError());
     // Galerkin product: count, scan, fill
     DevBuf<int> cnt(nc);
@@ -373,24 +394,25 @@ void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
     c->dinv.alloc(nc);
     const double* pw = f.pw.n > 0 ? f.pw.p : nullptr;
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_galerkin<false>), dim3(mg_grid(nc)), dim3(MG_BLOCK), 0, st, (i64)nc, (const int*)f.child.p,
-                       f.rowptr, f.col, f.val, (const int*)f.agg.p, pw, cnt.p, (const int*)nullptr, (int*)nullptr, (double*)nullptr,
+                       cw, f.rowptr, f.col, f.val, (const int*)f.agg.p, pw, cnt.p, (const int*)nullptr, (int*)nullptr, (double*)nullptr,
                        (double*)nullptr, err.p);
     PG_HIP(hipGetLastError());
     scan_exclusive<int>(cnt.p, c->o_rowptr.p, nc, c->o_rowptr.p + nc, st);
     int nnz = 0;
     c->o_rowptr.download(&nnz, 1, nc);
-    check_err(err, "row count");
+    const std::string where = "level " + std::to_string(H.lev.size());
+    check_err(err, (where + ", row count").c_str());
     PG_REQUIRE(nnz > 0, "multigrid set-up: empty coarse matrix");
     c->nnz = nnz;
     c->o_col.alloc(nnz);
     c->o_val.alloc(nnz);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mg_galerkin<true>), dim3(mg_grid(nc)), dim3(MG_BLOCK), 0, st, (i64)nc, (const int*)f.child.p,
-                       f.rowptr, f.col, f.val, (const int*)f.agg.p, pw, (int*)nullptr, (const int*)c->o_rowptr.p, c->o_col.p, c->o_val.p,
+                       cw, f.rowptr, f.col, f.val, (const int*)f.agg.p, pw, (int*)nullptr, (const int*)c->o_rowptr.p, c->o_col.p, c->o_val.p,
                        c->dinv.p, err.p);
     PG_HIP(hipGetLastError());
-    check_err(err, "coarse operator");
+    check_err(err, where.c_str());
     c->rowptr = c->o_rowptr.p; c->col = c->o_col.p; c->val = c->o_val.p;
-    H.bytes += f.n * (i64)sizeof(int) + (i64)nc * (8 * sizeof(int) + sizeof(int) + sizeof(int) + sizeof(double)) +
+    H.bytes += f.n * (i64)sizeof(int) + (i64)nc * (cw * sizeof(int) + sizeof(int) + sizeof(int) + sizeof(double)) +
                (i64)nnz * (sizeof(int) + sizeof(double));
     H.lev.push_back(std::move(c));
   }
@@ -470,13 +492,13 @@ void mg_apply(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
       FinArgs g{nullptr, nullptr, PH_NONE, 0, 0, nullptr};
       g.pc0 = 0.0; g.pc1 = -1.0; g.pc2 = 1.0; g.base = in;
       spmv_with_halo(8, A, nb, slab, out, v.xa.p, nullptr, nullptr, sc, G0, st, &g);
-      hipLaunchKernelGGL(k_mg_restrict_vec, dim3(mg_grid(c.n)), dim3(MG_BLOCK), 0, st, c.n, (const int*)v.child.p,
+      hipLaunchKernelGGL(k_mg_restrict_vec, dim3(mg_grid(c.n)), dim3(MG_BLOCK), 0, st, c.n, (const int*)v.child.p, v.cw,
                          (const double*)(v.pw.n > 0 ? v.pw.p : nullptr), (const double*)v.xa.p, R(1), sc);
       continue;
     }
     hipLaunchKernelGGL(k_mg_scale, dim3(mg_grid(v.n)), dim3(MG_BLOCK), 0, st, v.n, dinv, (const double*)R(l), v.xa.p, sc);
     jacobi(l, R(l), v.xa.p, XB(l));
-    hipLaunchKernelGGL(k_mg_restrict, dim3(mg_grid(c.n)), dim3(MG_BLOCK), 0, st, c.n, (const int*)v.child.p, v.rowptr, v.col, v.val,
+    hipLaunchKernelGGL(k_mg_restrict, dim3(mg_grid(c.n)), dim3(MG_BLOCK), 0, st, c.n, (const int*)v.child.p, v.cw, v.rowptr, v.col, v.val,
                        (const double*)(v.pw.n > 0 ? v.pw.p : nullptr), (const double*)R(l), (const double*)XB(l), R(l + 1), sc);
   }
   {
@@ -491,7 +513,7 @@ void mg_apply(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Sla
       q.rowptr = v.rowptr; q.col = v.col; q.val = v.val;
       q.dinv = v.dinv.n > 0 ? v.dinv.p : nullptr;
       q.pw = v.pw.n > 0 ? v.pw.p : nullptr;
-      q.agg = v.agg.p; q.child = v.child.p;
+      q.agg = v.agg.p; q.child = v.child.p; q.cw = v.cw;
       off += (l == L - 1 ? 2 : 3) * (int)v.n;
     }
     a.invT = H.inv.p;

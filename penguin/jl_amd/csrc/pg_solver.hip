@@ -73,6 +73,8 @@ struct pg_solver {
   // multigrid hierarchy of A_ctor (pg_multigrid.hip), built by the first solve that asks for PG_PRECOND_MG and kept with the
   // system: a steady solver is solved again and again on the same matrix (the stream-function solver of a pg_streamvort)
   MgHierarchy mg;
+  // ... and the one of the cell rule (PG_PRECOND_MG_CELL): one hierarchy per rule, neither reuses or disturbs the other's
+  MgHierarchy mg_cell;
   // ŷ = Â z of the NEXT step, queued speculatively behind the previous solve's first batch (KrylovWork::after_first_batch):
   // valid when that solve ended inside the batch (nothing moved z afterwards) and the next step runs on the same matrix
   bool spec_y_valid = false, spec_pending = false, hint_more_steps = false;
@@ -1301,14 +1303,16 @@ pg_krylov_opts default_opts() {
 // opts.precond = PG_PRECOND_MG: the conditions under which the multigrid preconditioner is offered -- anything else is refused
 // with the condition that failed, never served by another iteration -- then the hierarchy, on first use, and its hand-over to
 // the Krylov driver for the solve that follows.
-void mg_conditions(const pg_solver* s, int method) {
-  const std::string who = "multigrid preconditioner (precond = PG_PRECOND_MG) refused: ";
-  mg_require_one_rank();
+// PG_PRECOND_MG_CELL (the cell rule) asks the same but for the interface condition: Dirichlet, Robin and Neumann are all served.
+void mg_conditions(const pg_solver* s, int method, MgRule rule = MG_RULE_KIND) {
+  const std::string who = std::string("multigrid preconditioner (precond = ") + mg_precond_name(rule) + ") refused: ";
+  mg_require_one_rank(rule);
   PG_REQUIRE(s->scheme_ctor == PG_SCHEME_STEADY && !s->moving,
-             who + "the system is an unsteady one (steady monophasic diffusion and the stream-function solve only)");
+             who + (rule == MG_RULE_CELL ? "the system is an unsteady one (steady monophasic diffusion only)"
+                                         : "the system is an unsteady one (steady monophasic diffusion and the stream-function solve only)"));
   PG_REQUIRE(s->nphase == 1, who + "the system is diphasic (its jump rows need the cell-block left preconditioner)");
   PG_REQUIRE(!s->advdiff && !(s->ops[0] && s->ops[0]->has_velocity), who + "the operator is a ConvectionOps (DiffusionOps only)");
-  PG_REQUIRE(s->bc_i.kind == PG_BC_DIRICHLET,
+  PG_REQUIRE(rule == MG_RULE_CELL || s->bc_i.kind == PG_BC_DIRICHLET,
              who + (s->bc_i.kind == PG_BC_ROBIN ? "the interface condition is Robin (Dirichlet only)"
                                                 : "the interface condition is Neumann (Dirichlet only)"));
   // (not "no blocked rows": the cut cells of a Dirichlet interface are blocked too -- their γ row is a row of the identity, and
@@ -1317,16 +1321,20 @@ void mg_conditions(const pg_solver* s, int method) {
                                                                           : "the method is GMRES (BiCGStab only)"));
 }
 
-void mg_ensure(pg_solver* s) {
-  if (s->mg.matrix != &s->A_ctor || s->mg.lev.empty()) mg_build(s->mg, s->A_ctor, s->nb, s->slab);
+MgHierarchy& mg_of(pg_solver* s, MgRule rule) { return rule == MG_RULE_CELL ? s->mg_cell : s->mg; }
+
+MgHierarchy& mg_ensure(pg_solver* s, MgRule rule = MG_RULE_KIND) {
+  MgHierarchy& H = mg_of(s, rule);
+  if (H.matrix != &s->A_ctor || H.lev.empty()) mg_build(H, s->A_ctor, s->nb, s->slab, rule);
+  return H;
 }
 
 // before every krylov_solve on A_ctor that takes the caller's options
 void mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
-  if (o.precond != PG_PRECOND_MG) return;
-  mg_conditions(s, o.method);
-  mg_ensure(s);
-  s->work.mg = &s->mg;
+  if (!mg_is_precond(o.precond)) return;
+  const MgRule rule = mg_rule_of(o.precond);
+  mg_conditions(s, o.method, rule);
+  s->work.mg = &mg_ensure(s, rule);
 }
 
 void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
@@ -1463,7 +1471,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   PG_REQUIRE(!s->moving, "a moving-body solver is one space-time step: create the next one from the next time slab");
   PG_REQUIRE(s->initial_done, "Solver is not initialized. Call pg_solver_initial_solve first.");
   const pg_krylov_opts o = opts ? *opts : default_opts();
-  if (o.precond == PG_PRECOND_MG) mg_conditions(s, o.method);   // (refuses: a time step is an unsteady system)
+  if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (refuses: a time step is an unsteady system)
   hipStream_t stream = ctx().stream;
   ensure_run_matrix(s, scheme);
   const CsrMatrix& A = run_matrix(s);
@@ -2292,11 +2300,18 @@ int32_t pg_solver_stefan_terms(const pg_solver* s, double* out) {
   PG_API_END
 }
 
-int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out) {
+static MgRule debug_mg_rule(int32_t precond) {
+  PG_REQUIRE(mg_is_precond(precond), "multigrid diagnostics: precond must be PG_PRECOND_MG or PG_PRECOND_MG_CELL");
+  return mg_rule_of(precond);
+}
+
+int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out) { return pg_solver_mg_info_for(s, PG_PRECOND_MG, out); }
+
+int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* out) {
   PG_API_BEGIN
   PG_REQUIRE(s && out, "pg_solver_mg_info: NULL argument");
   std::memset(out, 0, sizeof(*out));
-  const MgHierarchy& H = s->mg;
+  const MgHierarchy& H = debug_mg_rule(precond) == MG_RULE_CELL ? s->mg_cell : s->mg;
   if (H.matrix != &s->A_ctor) return 0;
   out->levels = (int32_t)H.lev.size();
   out->tail_level = H.tail0;
@@ -2309,17 +2324,25 @@ int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out) {
   PG_API_END
 }
 
-static MgHierarchy& debug_mg(pg_solver* s) {
+static MgHierarchy& debug_mg(pg_solver* s, int32_t precond) {
   require_init();
   PG_REQUIRE(s, "multigrid diagnostics: NULL solver");
-  mg_conditions(s, PG_METHOD_BICGSTAB);
-  mg_ensure(s);
-  return s->mg;
+  const MgRule rule = debug_mg_rule(precond);
+  mg_conditions(s, PG_METHOD_BICGSTAB, rule);
+  return mg_ensure(s, rule);
 }
 
 int32_t pg_debug_mg_aggregates(pg_solver* s, int32_t level, int64_t* n, int32_t* agg) {
+  return pg_debug_mg_aggregates_for(s, PG_PRECOND_MG, level, n, agg);
+}
+int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val) {
+  return pg_debug_mg_level_csr_for(s, PG_PRECOND_MG, level, n, nnz, rowptr, col, val);
+}
+int32_t pg_debug_mg_apply(pg_solver* s, const double* r, double* z) { return pg_debug_mg_apply_for(s, PG_PRECOND_MG, r, z); }
+
+int32_t pg_debug_mg_aggregates_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int32_t* agg) {
   PG_API_BEGIN
-  MgHierarchy& H = debug_mg(s);
+  MgHierarchy& H = debug_mg(s, precond);
   PG_REQUIRE(level >= 0 && level + 1 < (int)H.lev.size(), "pg_debug_mg_aggregates: level has no aggregates (0 <= level < levels - 1)");
   const MgLevel& v = *H.lev[level];
   if (n) *n = v.n;
@@ -2327,9 +2350,10 @@ int32_t pg_debug_mg_aggregates(pg_solver* s, int32_t level, int64_t* n, int32_t*
   PG_API_END
 }
 
-int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val) {
+int32_t pg_debug_mg_level_csr_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
+                                  double* val) {
   PG_API_BEGIN
-  MgHierarchy& H = debug_mg(s);
+  MgHierarchy& H = debug_mg(s, precond);
   PG_REQUIRE(level >= 0 && level < (int)H.lev.size(), "pg_debug_mg_level_csr: no such level");
   const MgLevel& v = *H.lev[level];
   if (n) *n = v.n;
@@ -2354,9 +2378,9 @@ int32_t pg_debug_mg_level_csr(pg_solver* s, int32_t level, int64_t* n, int64_t* 
   PG_API_END
 }
 
-int32_t pg_debug_mg_apply(pg_solver* s, const double* r, double* z) {
+int32_t pg_debug_mg_apply_for(pg_solver* s, int32_t precond, const double* r, double* z) {
   PG_API_BEGIN
-  MgHierarchy& H = debug_mg(s);
+  MgHierarchy& H = debug_mg(s, precond);
   PG_REQUIRE(r && z, "pg_debug_mg_apply: NULL argument");
   const i64 n = s->nb.n_own, nv = s->nb.n_vec();
   DevBuf<double> din(nv), dout(nv);
@@ -2730,7 +2754,7 @@ static void refine_once(pg_solver* s, const pg_krylov_opts& o, SolveStats& st) {
 // does for a slab of the moving solvers.  One step of iterative refinement follows (refine_once).
 void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
-  if (o.precond == PG_PRECOND_MG) mg_conditions(s, o.method);   // (a solver built for one time step: refused)
+  if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (a solver built for one time step: refused)
   const i64 n = s->nb.n_own;
   if (!(o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) || s->initial_done) {
     do_initial(s, opts, st);

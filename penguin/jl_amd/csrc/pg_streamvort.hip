@@ -104,6 +104,10 @@ void upload_m(DevBuf<double>& dst, const double* h, i64 M) {
 
 // steps 1-3: b from ω, ψ = Aψ⁻¹ b, (u, v)
 void solve_stream(pg_streamvort* sv, const pg_krylov_opts* opts, SolveStats& st, Clock* clk, Split* sp) {
+  // (before anything is launched: every entry point that takes options comes through here first)
+  PG_REQUIRE(!(opts && opts->precond == PG_PRECOND_MG_CELL),
+             "multigrid preconditioner (precond = PG_PRECOND_MG_CELL) refused: a StreamVorticity solver -- its stream-function solve "
+             "has a Dirichlet interface and is served by PG_PRECOND_MG");
   hipStream_t stream = ctx().stream;
   const i64 M = sv->M;
   const int gr = grid_for(M, SV_BLOCK);
