@@ -99,7 +99,14 @@ typedef struct {
                           hierarchy exists); with profiling on, each V-cycle counts as one lean launch in spmv_lean_*;
                           PG_PRECOND_MG_CELL: the same V-cycle on a cell-aggregated hierarchy (DESIGN.md "Cell-aggregated
                           multigrid") -- steady monophasic diffusion (DarcyFlow included) with a Dirichlet, Robin or Neumann
-                          interface, one rank; refused like PG_PRECOND_MG anywhere else, a pg_streamvort included */
+                          interface, one rank; refused like PG_PRECOND_MG anywhere else, a pg_streamvort included;
+                          PG_PRECOND_POLY_EST: the polynomial preconditioner of precond = 0, admitted on an estimated spectral disc
+                          where Gershgorin refuses it (DESIGN.md "Estimated spectral interval") -- diphasic systems and Robin /
+                          Neumann interfaces of the unsteady diffusion solvers.  Where Gershgorin admits the matrix the solve IS
+                          the precond = 0 solve and no estimate runs; where it refuses, the first solve on a matrix runs 30
+                          Arnoldi steps (pg_solver_spectral_estimate) and the polynomial runs on |z - 1| <= g_ritz + margin when
+                          that is < 0.95, the plain iteration otherwise (no error).  One rank, BiCGStab, DiffusionOps, no moving
+                          body: refused with an error that names the failed condition anywhere else */
 } pg_krylov_opts;
 enum { PG_PRECOND_MG = -2 };   /* a value of pg_krylov_opts.precond */
 /* a value of pg_krylov_opts.precond: multigrid whose first coarsening merges ALL unknowns, bulk and interface, of a 2 x 2 (x 2)
@@ -107,6 +114,27 @@ enum { PG_PRECOND_MG = -2 };   /* a value of pg_krylov_opts.precond */
    the kind-separated aggregates of PG_PRECOND_MG give non-positive coarse diagonals; this rule serves those systems.  A solver
    holds one hierarchy per value: a solve with one neither reuses nor disturbs the other's. */
 enum { PG_PRECOND_MG_CELL = -3 };
+/* a value of pg_krylov_opts.precond: the polynomial preconditioner of precond = 0, admitted on an estimated spectral disc where
+   Gershgorin refuses it.  Opt-in; a flag of its own on the matrix: nothing else that Gershgorin's verdict switches on (the
+   elimination of rows alone on their diagonal, the compact loop system) starts because of it. */
+enum { PG_PRECOND_POLY_EST = -4 };
+/* added to the largest |theta - 1| of the Ritz values before the test against 0.95: twice the largest shortfall of the estimate
+   against the true spectrum measured on the oracle's systems (DESIGN.md "Estimated spectral interval" has the table) */
+#define PG_SPECEST_MARGIN 0.0205
+
+/* the spectral estimate of one matrix of a solver (pg_solver_spectral_estimate) */
+typedef struct {
+  int32_t steps;              /* Arnoldi steps taken (30, or fewer after a happy breakdown); 0: no estimate has run       */
+  int32_t admitted;           /* 1: g_used < 0.95 -- PG_PRECOND_POLY_EST runs the polynomial on this matrix               */
+  int32_t gershgorin_admits;  /* 1: Gershgorin admits the matrix (pg_system_info.neumann_ok): the estimate is not used    */
+  int32_t reserved;
+  double g_ritz;              /* max |theta - 1| over the Ritz values theta (complex modulus)                              */
+  double g_used;              /* g_ritz + margin: the radius the Chebyshev nodes are placed on                             */
+  double margin;              /* PG_SPECEST_MARGIN                                                                         */
+  double gershgorin;          /* pg_system_info.gershgorin of the same matrix                                              */
+  double ritz_re_min, ritz_re_max, ritz_im_max;   /* smallest / largest real part, largest |imaginary part| of the Ritz values */
+  double estimate_ms;         /* wall time the estimate took (once per assembled matrix)                                   */
+} pg_specest_info;
 
 /* the multigrid hierarchy of a solver (pg_solver_mg_info), built by the first solve that asks for PG_PRECOND_MG */
 #define PG_MG_MAX_LEVELS 16
@@ -464,6 +492,10 @@ int32_t pg_solver_get_row_scaling(const pg_solver* s, int32_t which, double* ds)
 int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out);
 /* ... and the hierarchy of `precond` = PG_PRECOND_MG (the call above) or PG_PRECOND_MG_CELL */
 int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* out);
+/* The spectral estimate behind PG_PRECOND_POLY_EST of system `which` (0 constructor, 1 run system; + 4: report only).  Runs the
+   estimate if it has not run on that matrix (a solve with PG_PRECOND_POLY_EST runs it only where Gershgorin refuses; this call
+   runs it on any matrix) and refuses what the option refuses.  With + 4 nothing runs: steps = 0 says no estimate exists. */
+int32_t pg_solver_spectral_estimate(pg_solver* s, int32_t which, pg_specest_info* out);
 /* bench helper: `reps` launches of y = A x on the run matrix, HIP-event timed on the library stream. */
 int32_t pg_solver_time_spmv(pg_solver* s, int32_t which, int32_t reps, double* avg_ms);
 
@@ -535,7 +567,7 @@ int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const int64_t* n, 
 /* Krylov method (PG_METHOD_*) and GMRES restart length of the virtual-rank runs that follow (default BiCGStab) */
 int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart);
 /* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG and PG_PRECOND_MG_CELL make
-   pg_debug_run_virtual_ranks fail with the multigrid's one-rank refusal before any rank starts */
+   pg_debug_run_virtual_ranks fail with the multigrid's one-rank refusal before any rank starts, PG_PRECOND_POLY_EST with its own */
 int32_t pg_debug_set_virtual_rank_precond(int32_t precond);
 /* ramp != 0: the virtual-rank runs that follow change the interface value every step, g = interface_value (1 + ramp step)
    (host-driven steps): rows alone on their diagonal move in every step, on every rank */
@@ -571,6 +603,11 @@ int32_t pg_debug_mg_aggregates_for(pg_solver* s, int32_t precond, int32_t level,
 int32_t pg_debug_mg_level_csr_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
                                   double* val);
 int32_t pg_debug_mg_apply_for(pg_solver* s, int32_t precond, const double* r, double* z);
+
+/* The Hessenberg matrix of the estimate pg_solver_spectral_estimate(s, which) describes (tests/test_gpu_specest.py compares it
+   with the numpy restatement tests/specest_reference.py): (steps + 1) x steps doubles, column major.  Two-call size pattern:
+   with H NULL only `steps` is written. */
+int32_t pg_debug_specest_hessenberg(pg_solver* s, int32_t which, int32_t* steps, double* H);
 
 /* The extrapolated start of the time loop's quiet steps (constant data, one rank; no reference counterpart: the reference
    starts every Krylov solve from zero, solver.jl:158-181): `kept` older states are held; the next step starts from

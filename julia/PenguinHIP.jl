@@ -24,7 +24,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!,
        MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
-       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info,
+       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, spectral_estimate,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
        ∇, ∇₋, gmres, bicgstabl, cg
 
@@ -93,12 +93,17 @@ end
 # the stream-function solve of a StreamVorticity; the library refuses it anywhere else.
 # precond = :mg_cell (PG_PRECOND_MG_CELL): the same V-cycle on the cell-aggregated hierarchy -- steady monophasic diffusion
 # (DarcyFlow included) with a Dirichlet, Robin or Neumann interface.
+# precond = :poly_est (PG_PRECOND_POLY_EST): the polynomial preconditioner of precond = 0, admitted on an estimated spectral disc
+# where Gershgorin refuses it -- diphasic systems and Robin / Neumann interfaces of the unsteady diffusion solvers; one rank,
+# BiCGStab, DiffusionOps, no moving body; the library refuses it anywhere else (spectral_estimate tells what the estimate found).
 const PG_PRECOND_MG = Int32(-2)
 const PG_PRECOND_MG_CELL = Int32(-3)
+const PG_PRECOND_POLY_EST = Int32(-4)
 function _precond_id(p)
     p isa Symbol || return Int32(p)
     p === :mg && return PG_PRECOND_MG
-    p === :mg_cell || error("precond must be an integer, :mg or :mg_cell, not :$(p)")
+    p === :poly_est && return PG_PRECOND_POLY_EST
+    p === :mg_cell || error("precond must be an integer, :mg, :mg_cell or :poly_est, not :$(p)")
     PG_PRECOND_MG_CELL
 end
 function _opts(method, kw; warm_default::Bool=true)
@@ -1463,6 +1468,24 @@ function mg_info(s; precond=:mg)
     levels = Int(buf[1] & 0xffffffff); tail = Int((buf[1] >> 32) & 0xffffffff)
     (levels = levels, tail_level = tail, rows = buf[2:1 + levels], nnz = buf[18:17 + levels],
      setup_ms = reinterpret(Float64, buf[34]), bytes = buf[35])
+end
+
+"""
+The spectral estimate behind `precond = :poly_est` of system `which` (0 constructor, 1 run system; `pg_solver_spectral_estimate`).
+Runs the estimate if it has not run on that matrix; `run = false` only reports (`steps == 0`: none has run).
+"""
+function spectral_estimate(s, which::Integer=0; run::Bool=true)
+    # pg_specest_info: int32 steps, admitted, gershgorin_admits, reserved; double g_ritz, g_used, margin, gershgorin,
+    # ritz_re_min, ritz_re_max, ritz_im_max, estimate_ms = 10 words
+    buf = zeros(Int64, 10)
+    GC.@preserve buf begin
+        check(ccall((:pg_solver_spectral_estimate, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), s.handle,
+                    Int32(which | (run ? 0 : 4)), pointer(buf)))
+    end
+    f(k) = reinterpret(Float64, buf[k])
+    (steps = Int(buf[1] & 0xffffffff), admitted = ((buf[1] >> 32) & 0xffffffff) != 0, gershgorin_admits = (buf[2] & 0xffffffff) != 0,
+     g_ritz = f(3), g_used = f(4), margin = f(5), gershgorin = f(6), ritz_re_min = f(7), ritz_re_max = f(8), ritz_im_max = f(9),
+     estimate_ms = f(10))
 end
 
 "`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg` and `:mg_cell` make them fail with the one-rank refusal)."

@@ -35,6 +35,8 @@ PG_METHOD = {"bicgstab": 0, "cg": 1, "gmres": 2}
 PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a pg_streamvort
 PG_PRECOND_MG = -2                   # pg_krylov_opts.precond: the aggregation multigrid V-cycle
 PG_PRECOND_MG_CELL = -3              # ... on the cell-aggregated hierarchy (Dirichlet, Robin and Neumann interfaces)
+PG_PRECOND_POLY_EST = -4             # ... the polynomial of precond = 0, admitted on an estimated spectral disc where Gershgorin refuses
+PG_SPECEST_MARGIN = 0.0205           # added to the estimate's max |theta - 1| before the test against 0.95
 PG_MG_MAX_LEVELS = 16
 
 c_double_p = C.POINTER(C.c_double)
@@ -99,6 +101,12 @@ class pg_streamvort_run_info(C.Structure):
 class pg_mg_info(C.Structure):
     _fields_ = [("levels", C.c_int32), ("tail_level", C.c_int32), ("rows", C.c_int64 * PG_MG_MAX_LEVELS),
                 ("nnz", C.c_int64 * PG_MG_MAX_LEVELS), ("setup_ms", C.c_double), ("bytes", C.c_int64)]
+
+
+class pg_specest_info(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("admitted", C.c_int32), ("gershgorin_admits", C.c_int32), ("reserved", C.c_int32),
+                ("g_ritz", C.c_double), ("g_used", C.c_double), ("margin", C.c_double), ("gershgorin", C.c_double),
+                ("ritz_re_min", C.c_double), ("ritz_re_max", C.c_double), ("ritz_im_max", C.c_double), ("estimate_ms", C.c_double)]
 
 
 def declared_symbols() -> list[str]:
@@ -262,6 +270,25 @@ def debug_mg_apply(handle, r: np.ndarray, precond: int = PG_PRECOND_MG) -> np.nd
     z = np.zeros_like(r)
     check(lib().pg_debug_mg_apply_for(handle, C.c_int32(precond), dptr(r), dptr(z)))
     return z
+
+
+# ---- the spectral estimate behind precond = PG_PRECOND_POLY_EST against the numpy restatement (tests/specest_reference.py) ----
+def solver_spectral_estimate(handle, which: int = 0, run: bool = True) -> dict:
+    """pg_solver_spectral_estimate of system `which` (0 constructor, 1 run system).  run=False: report only (steps = 0 when no
+    estimate has run on that matrix)."""
+    info = pg_specest_info()
+    check(lib().pg_solver_spectral_estimate(handle, C.c_int32(which | (0 if run else 4)), C.byref(info)))
+    return {k: getattr(info, k) for k, _ in pg_specest_info._fields_ if k != "reserved"}
+
+
+def debug_specest_hessenberg(handle, which: int = 0, run: bool = True) -> np.ndarray:
+    """pg_debug_specest_hessenberg: the (steps + 1) x steps Hessenberg matrix of that estimate."""
+    w = C.c_int32(which | (0 if run else 4))
+    k = C.c_int32(0)
+    check(lib().pg_debug_specest_hessenberg(handle, w, C.byref(k), None))
+    H = np.zeros((k.value + 1) * max(k.value, 1))
+    check(lib().pg_debug_specest_hessenberg(handle, w, C.byref(k), dptr(H)))
+    return H[: (k.value + 1) * k.value].reshape((k.value + 1, k.value), order="F")
 
 
 # ---- diagnostics: one SpMV launch against the host ---------------------------------------------------------------------------

@@ -655,6 +655,13 @@ class Solver:
         one hierarchy per value."""
         return L.solver_mg_info(self._h, _precond_value(precond))
 
+    def spectral_estimate(self, which: int = 0, run: bool = True) -> dict:
+        """The spectral estimate behind precond="poly-est" of system `which` (0 constructor, 1 run system;
+        pg_solver_spectral_estimate): steps, g_ritz, g_used, margin, admitted, gershgorin, gershgorin_admits, the smallest /
+        largest real part and the largest |imaginary part| of the Ritz values, estimate_ms.  Runs the estimate if it has not
+        run on that matrix; run=False only reports (steps = 0: none has run)."""
+        return L.solver_spectral_estimate(self._h, which, run)
+
     def system_info(self, which: int = 0) -> L.pg_system_info:
         info = L.pg_system_info()
         L.check(L.lib().pg_solver_system_info(self._h, C.c_int32(which), C.byref(info)))
@@ -772,14 +779,15 @@ def _step_info_check(s: "Solver", info: L.pg_step_info, what: str) -> None:
     _check_converged(s, bool(info.converged), what, info.resnorm / info.bnorm if info.bnorm > 0 else info.resnorm)
 
 
-_PRECOND_NAMES = {"mg": L.PG_PRECOND_MG, "mg-cell": L.PG_PRECOND_MG_CELL}
+_PRECOND_NAMES = {"mg": L.PG_PRECOND_MG, "mg-cell": L.PG_PRECOND_MG_CELL, "poly-est": L.PG_PRECOND_POLY_EST}
 
 
 def _precond_value(precond) -> int:
-    """pg_krylov_opts.precond of a `precond` keyword: an integer as it is, "mg" -> PG_PRECOND_MG, "mg-cell" -> PG_PRECOND_MG_CELL."""
+    """pg_krylov_opts.precond of a `precond` keyword: an integer as it is, "mg" -> PG_PRECOND_MG, "mg-cell" -> PG_PRECOND_MG_CELL,
+    "poly-est" -> PG_PRECOND_POLY_EST (names in any case)."""
     if isinstance(precond, str):
         if precond.lower() not in _PRECOND_NAMES:
-            raise ValueError(f'precond must be an integer, "mg" or "mg-cell", not {precond!r}')
+            raise ValueError(f'precond must be an integer, "mg", "mg-cell" or "poly-est", not {precond!r}')
         return _PRECOND_NAMES[precond.lower()]
     return int(precond)
 
@@ -791,7 +799,10 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     precond: an integer as pg_krylov_opts.precond takes it (0 automatic, -1 off, m >= 1 the polynomial's degree), or "mg":
     the aggregation multigrid V-cycle (steady monophasic diffusion with a Dirichlet interface and the ψ solve of a
     StreamVorticity; the library refuses it anywhere else), or "mg-cell": the same V-cycle on the cell-aggregated hierarchy
-    (steady monophasic diffusion, DarcyFlow included, with a Dirichlet, Robin or Neumann interface)."""
+    (steady monophasic diffusion, DarcyFlow included, with a Dirichlet, Robin or Neumann interface), or "poly-est": the
+    polynomial preconditioner of precond = 0, admitted on an estimated spectral disc where Gershgorin refuses it (diphasic
+    systems, Robin / Neumann interfaces of the unsteady diffusion solvers; one rank, BiCGStab, DiffusionOps, no moving body --
+    refused anywhere else; Solver.spectral_estimate tells what the estimate found)."""
     name = method if isinstance(method, str) else getattr(method, "__name__", "bicgstab")
     name = name.lower()
     m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])

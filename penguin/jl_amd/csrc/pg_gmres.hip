@@ -26,12 +26,13 @@
 // ~4j + 6 per SpMV); it is here so that `method = gmres` means GMRES.
 #include "pg_krylov.h"
 #include "pg_spmv.h"
+#include "pg_specest.h"
 
 using namespace pg;
 
 namespace {
 
-constexpr int GRP = 8;   // basis vectors handled per launch of the dot / update kernels
+constexpr int GRP = GM_GRP;   // basis vectors handled per launch of the dot / update kernels
 
 // device scalar block of GMRES (KrylovWork::gm), after the H / cs / sn / g / y / h arrays
 struct GmLayout {
@@ -70,6 +71,11 @@ __global__ __launch_bounds__(BLOCK) void k_gm_resid(i64 n, i64 nvec, const doubl
   if (threadIdx.x == 0) partials[gridDim.x + blockIdx.x] = tw;
 }
 
+}  // namespace
+
+// ---- shared with the spectral estimate (pg_specest.hip), declared in pg_specest.h ----
+namespace pg {
+
 // sums of `nslots` partial slots (fixed order: deterministic) into out[0..nslots)
 __global__ __launch_bounds__(BLOCK) void k_gm_reduce(int nslots, int grid, const double* __restrict__ partials,
                                                      double* __restrict__ out, const double* __restrict__ sc, int check_done) {
@@ -82,6 +88,10 @@ __global__ __launch_bounds__(BLOCK) void k_gm_reduce(int nslots, int grid, const
     if (threadIdx.x == 0) out[s] = t;
   }
 }
+
+}  // namespace pg
+
+namespace {
 
 // start of a restart cycle (and verdict on the one before): rr = (r,r), rrw = (r,r)_W of the TRUE residual; beta = ||r||.
 // Inner tolerance (Givens estimate) from the first residual (zero initial guess: ||r0|| = ||b||), lowered when the estimate
@@ -112,6 +122,11 @@ __global__ void k_gm_begin(GmLayout L, double* __restrict__ gm, double* __restri
     if (aim < sc[S_TOL2]) sc[S_TOL2] = aim;
   }
 }
+
+}  // namespace
+
+// ---- shared with the spectral estimate (pg_specest.hip), declared in pg_specest.h ----
+namespace pg {
 
 __global__ __launch_bounds__(BLOCK) void k_gm_scale(i64 n, const double* __restrict__ sc, const double* __restrict__ gm,
                                                     int invn_at, double* __restrict__ v) {
@@ -170,6 +185,10 @@ __global__ __launch_bounds__(BLOCK) void k_gm_update(i64 n, i64 stride, int k0, 
     if (threadIdx.x == 0) partials[(size_t)norm_slot * gridDim.x + blockIdx.x] = t;
   }
 }
+
+}  // namespace pg
+
+namespace {
 
 // column j of the Hessenberg matrix: h = h1 + h2 (CGS2), previous rotations, new rotation, residual estimate
 __global__ void k_gm_hess(GmLayout L, int j, double* __restrict__ gm, double* __restrict__ sc) {

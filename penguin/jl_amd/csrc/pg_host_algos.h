@@ -1,9 +1,12 @@
 // pg_host_algos.h -- the pure HOST algorithms of the library, free of HIP so that the CPU test-suite can compile them with
 // AddressSanitizer + UndefinedBehaviorSanitizer (tests/host_asan.cpp): the slab partition of the
 // planes and the planning of the SpMV's marching units (index arithmetic over run descriptors: the place where an
-// off-by-one reads outside a vector on the GPU).  Included by pg_context.hip and pg_spmv.hip.
+// off-by-one reads outside a vector on the GPU), the host side of the multigrid set-up (tests/mg_host_asan.cpp) and the
+// eigenvalues of the spectral estimate's Hessenberg matrix (tests/specest_host.cpp).  Included by pg_context.hip, pg_spmv.hip,
+// pg_multigrid.hip and pg_specest.hip.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
@@ -467,6 +470,125 @@ inline int mg_plan_tail(const int64_t* rows, int L, int64_t tail_rows, int64_t l
     need += 3 * rows[t];
   }
   return t;
+}
+
+// ---- spectral estimate (pg_specest.hip): the Ritz values of an Arnoldi recursion -------------------------------------------
+// Eigenvalues (wr + i wi, n each) of the leading n x n block of a real upper Hessenberg matrix h, stored column major with
+// leading dimension ld (entry (i, j) at h[j * ld + i]; entries below the subdiagonal are not read): EISPACK's `hqr` (Martin,
+// Peters and Wilkinson, "The QR algorithm for real Hessenberg matrices", Numer. Math. 14, 1970) restated for 0-based column-major
+// storage -- compare it against that routine; only the sweep limit differs (60 here, 30 there).  Francis' double-shift QR
+// iteration on a copy, deflating at negligible subdiagonal entries, complex pairs read off the final 2 x 2 blocks (the pair's
+// member with the positive imaginary part first), exceptional shifts after 10 and 20 sweeps on the same block.  Eigenvalues
+// only: rows above the active block are not updated.  false: a block took more than 60 sweeps (n <= 200 expected: never seen).
+inline bool hessenberg_eigenvalues(int n, const double* h, int ld, double* wr, double* wi) {
+  if (n <= 0) return true;
+  std::vector<double> A((size_t)n * n, 0.0);
+  auto a = [&](int i, int j) -> double& { return A[(size_t)i * n + j]; };
+  auto fabs_ = [](double v) { return v < 0.0 ? -v : v; };
+  auto sign_ = [](double v, double s) { return s < 0.0 ? (v < 0.0 ? v : -v) : (v < 0.0 ? -v : v); };
+  double anorm = 0.0;
+  for (int i = 0; i < n; ++i)
+    for (int j = (i > 0 ? i - 1 : 0); j < n; ++j) {
+      a(i, j) = h[(size_t)j * ld + i];
+      anorm += fabs_(a(i, j));
+    }
+  int nn = n - 1;
+  double t = 0.0;
+  while (nn >= 0) {
+    int its = 0, l;
+    do {
+      for (l = nn; l >= 1; --l) {   // a negligible subdiagonal entry splits the matrix
+        double s = fabs_(a(l - 1, l - 1)) + fabs_(a(l, l));
+        if (s == 0.0) s = anorm;
+        if (fabs_(a(l, l - 1)) + s == s) { a(l, l - 1) = 0.0; break; }
+      }
+      double x = a(nn, nn);
+      if (l == nn) {                // one root
+        wr[nn] = x + t; wi[nn] = 0.0;
+        --nn;
+      } else {
+        double y = a(nn - 1, nn - 1), w = a(nn, nn - 1) * a(nn - 1, nn);
+        if (l == nn - 1) {          // two roots
+          const double p = 0.5 * (y - x), q = p * p + w;
+          double z = std::sqrt(fabs_(q));
+          x += t;
+          if (q >= 0.0) {
+            z = p + sign_(z, p);
+            wr[nn - 1] = wr[nn] = x + z;
+            if (z != 0.0) wr[nn] = x - w / z;
+            wi[nn - 1] = wi[nn] = 0.0;
+          } else {
+            wr[nn - 1] = wr[nn] = x + p;
+            wi[nn - 1] = z; wi[nn] = -z;
+          }
+          nn -= 2;
+        } else {                    // no root yet: one double-shift sweep on rows / columns l .. nn
+          if (its >= 60) return false;
+          if (its == 10 || its == 20) {   // exceptional shift
+            t += x;
+            for (int i = 0; i <= nn; ++i) a(i, i) -= x;
+            const double s = fabs_(a(nn, nn - 1)) + fabs_(a(nn - 1, nn - 2));
+            y = x = 0.75 * s;
+            w = -0.4375 * s * s;
+          }
+          ++its;
+          int m;
+          double p = 0.0, q = 0.0, r = 0.0, z;
+          for (m = nn - 2; m >= l; --m) {   // two consecutive small subdiagonal entries: the sweep may start at m
+            z = a(m, m);
+            r = x - z;
+            double s = y - z;
+            p = (r * s - w) / a(m + 1, m) + a(m, m + 1);
+            q = a(m + 1, m + 1) - z - r - s;
+            r = a(m + 2, m + 1);
+            s = fabs_(p) + fabs_(q) + fabs_(r);
+            if (s != 0.0) { p /= s; q /= s; r /= s; }
+            if (m == l) break;
+            const double u = fabs_(a(m, m - 1)) * (fabs_(q) + fabs_(r));
+            const double v = fabs_(p) * (fabs_(a(m - 1, m - 1)) + fabs_(z) + fabs_(a(m + 1, m + 1)));
+            if (u + v == v) break;
+          }
+          for (int i = m + 2; i <= nn; ++i) {
+            a(i, i - 2) = 0.0;
+            if (i != m + 2) a(i, i - 3) = 0.0;
+          }
+          for (int k = m; k <= nn - 1; ++k) {
+            if (k != m) {
+              p = a(k, k - 1);
+              q = a(k + 1, k - 1);
+              r = k != nn - 1 ? a(k + 2, k - 1) : 0.0;
+              x = fabs_(p) + fabs_(q) + fabs_(r);
+              if (x != 0.0) { p /= x; q /= x; r /= x; }
+            }
+            const double s = sign_(std::sqrt(p * p + q * q + r * r), p);
+            if (s == 0.0) continue;
+            if (k == m) {
+              if (l != m) a(k, k - 1) = -a(k, k - 1);
+            } else {
+              a(k, k - 1) = -s * x;
+            }
+            p += s;
+            x = p / s; y = q / s; z = r / s;
+            q /= p; r /= p;
+            for (int j = k; j <= nn; ++j) {           // rows k .. k+2
+              double pp = a(k, j) + q * a(k + 1, j);
+              if (k != nn - 1) { pp += r * a(k + 2, j); a(k + 2, j) -= pp * z; }
+              a(k + 1, j) -= pp * y;
+              a(k, j) -= pp * x;
+            }
+            const int mmin = nn < k + 3 ? nn : k + 3;
+            for (int i = l; i <= mmin; ++i) {         // columns k .. k+2
+              double pp = x * a(i, k) + y * a(i, k + 1);
+              if (k != nn - 1) { pp += z * a(i, k + 2); a(i, k + 2) -= pp * r; }
+              a(i, k + 1) -= pp * q;
+              a(i, k) -= pp;
+            }
+          }
+        }
+      }
+    } while (l < nn - 1);
+  }
+  return true;
 }
 
 }  // namespace pghost

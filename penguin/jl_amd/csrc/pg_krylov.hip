@@ -27,6 +27,9 @@
 // k_bicg_xrp): x and r move by the SAME computed vectors, so r stays the residual of x whatever rounding does inside the
 // chain, and the stopping test is unchanged.  The vector passes, the reductions and, with several ranks, the all-reduces
 // of a time step fall with the iteration count.
+// opts.precond = PG_PRECOND_POLY_EST (opt-in): the same branch on matrices Gershgorin refuses, with g = the radius of the
+// spectral estimate (pg_specest.hip, CsrMatrix::est -- a flag of its own: poly_ok stays false, so neither the diagonal-row
+// elimination nor the compact loop system starts); exactly precond = 0 where Gershgorin admits.
 //
 // Multigrid right preconditioner (opts.precond = PG_PRECOND_MG or PG_PRECOND_MG_CELL, never automatic): the same x-space loop with M⁻¹ = one V-cycle
 // of pg_multigrid.hip where the Horner chain stands -- ya = M⁻¹p, yb = M⁻¹s, then the plain product with its dots.  It is a
@@ -36,6 +39,7 @@
 #include "pg_krylov.h"
 #include "pg_multigrid.h"
 #include "pg_spmv.h"
+#include "pg_specest.h"
 
 using namespace pg;
 
@@ -541,9 +545,11 @@ void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st) {
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts) {
   const bool poly_env = config().poly;
   const int degree_env = config().poly_degree;
-  if (!(poly_env && opts.precond >= 0 && opts.method == PG_METHOD_BICGSTAB && A.poly_ok && spmv_supports_preconditioner_product() && A.n > 0))
+  // (PG_PRECOND_POLY_EST on a matrix Gershgorin admits is precond = 0; one it refuses never comes here as a compact system)
+  const int precond = opts.precond == PG_PRECOND_POLY_EST ? 0 : opts.precond;
+  if (!(poly_env && precond >= 0 && opts.method == PG_METHOD_BICGSTAB && A.poly_ok && spmv_supports_preconditioner_product() && A.n > 0))
     return false;
-  return (opts.precond > 0 ? opts.precond : degree_env) >= 2;
+  return (precond > 0 ? precond : degree_env) >= 2;
 }
 
 constexpr int MAX_POLY_DEGREE = 40;   // products per application of the polynomial preconditioner
@@ -643,6 +649,21 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   PG_REQUIRE(w.n >= n && w.nvec >= nvec, "krylov workspace too small");   // (a reduced system works on prefixes, pg_reduce.hip)
   PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB || opts.method == PG_METHOD_CG || opts.method == PG_METHOD_GMRES,
              "unknown Krylov method");
+  // PG_PRECOND_POLY_EST: precond = 0 wherever Gershgorin admits the matrix; where it refuses, the verdict of the spectral
+  // estimate the caller has run on this matrix (CsrMatrix::est, pg_specest.hip) -- a flag of its own, poly_ok stays false
+  const bool est_opt = opts.precond == PG_PRECOND_POLY_EST;
+  if (est_opt) {
+    PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB,
+               std::string("estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST) refused: ") +
+                   (opts.method == PG_METHOD_CG ? "the method is CG (BiCGStab only)" : "the method is GMRES (BiCGStab only)"));
+    specest_require_one_rank();
+    // the contract: whoever passes the option has run the estimate on THIS matrix (pg_solver.hip specest_prepare) -- a
+    // matrix nobody looked at would otherwise run plain without a word.  (A matrix the polynomial stagnated on has its verdict:
+    // it runs plain, here as the plain finish of that very solve and in every later one.)
+    PG_REQUIRE(A.poly_ok || A.est.tried || A.poly_gave_up, "estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST): no spectral estimate "
+               "has run on this matrix (specest_run before krylov_solve)");
+  }
+  const int precond = est_opt ? 0 : opts.precond;
   if (opts.method == PG_METHOD_GMRES) {
     PG_REQUIRE(!preinit && !x0, "GMRES starts from zero (IterativeSolvers' default)");
     gmres_solve(A, nb, slab, b, x, w, opts, stats);
@@ -678,11 +699,12 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   // polynomial right preconditioner: BiCGStab on the slice kernel, where Gershgorin bounds the spectrum inside
   // |λ - 1| < 0.95; m products with Â per application of C = I - R(Â)  (m < 2: the plain iteration)
   int m = 0;
-  if (poly_env && opts.precond >= 0 && !cg && A.poly_ok && spmv_supports_preconditioner_product() && n > 0)
-    m = std::min(opts.precond > 0 ? opts.precond : degree_env, MAX_POLY_DEGREE);
+  const bool by_estimate = est_opt && !A.poly_ok && !A.poly_gave_up && A.est.tried && A.est.admitted;   // (Gershgorin admits: no estimate is looked at)
+  if (poly_env && precond >= 0 && !cg && (A.poly_ok || by_estimate) && spmv_supports_preconditioner_product() && n > 0)
+    m = std::min(precond > 0 ? precond : degree_env, MAX_POLY_DEGREE);
   // auto mode: the degree that fits the number of products the previous solve on this matrix would have needed (below)
   const bool adapt_env = cfg.poly_adapt;
-  const bool adaptive = adapt_env && m >= 2 && opts.precond == 0 && preinit;
+  const bool adaptive = adapt_env && m >= 2 && precond == 0 && preinit;
   int expect_halves = 0;
   if (adaptive && w.adapt_matrix == &A && w.adapt_m >= 2) { m = w.adapt_m; expect_halves = w.adapt_h; }
   if (m < 2) m = 0;
@@ -707,7 +729,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   double tau[MAX_POLY_DEGREE];
   if (poly) {
     // 1 / Chebyshev nodes of [1 - g, 1 + g], the largest and the smallest remaining root in turn
-    const double g = std::min(std::max(A.gersh, 0.05), 0.95);
+    const double g = std::min(std::max(by_estimate ? A.est.g_used : A.gersh, 0.05), 0.95);
     double lam[MAX_POLY_DEGREE];
     for (int k = 0; k < m; ++k) lam[k] = 1.0 + g * std::cos(M_PI * (2.0 * k + 1.0) / (2.0 * m));   // descending
     for (int k = 0, lo = 0, hi = m - 1; k < m; ++k) tau[k] = 1.0 / ((k & 1) ? lam[hi--] : lam[lo++]);
@@ -872,6 +894,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   }
   if (poly_failed) {                        // x is the iterate reached
     const_cast<CsrMatrix&>(A).poly_ok = false;
+    const_cast<CsrMatrix&>(A).est.admitted = false;
+    const_cast<CsrMatrix&>(A).poly_gave_up = true;
     timer.collect(stats, launched, false);
     if (w.scatter) {                        // (the caller solves again on its full system, which has a right-hand side vector)
       stats.iters = launched;

@@ -504,6 +504,8 @@ void decide_poly(CsrMatrix& A) {
   double h = 0.0;
   worst.download(&h, 1);
   A.gersh = h;
+  A.est = SpecEst();   // a (re)built matrix is estimated again (pg_specest.hip)
+  A.poly_gave_up = false;
   A.poly_ok = h < 0.95;
   if (config().debug && !(h < 1e300) && A.n > 0) {   // developer aid: the first rows whose disc is not finite
     std::vector<int> rp(A.n + 1), cl(A.nnz);

@@ -18,6 +18,7 @@
 #include "pg_multigrid.h"
 #include "pg_solver_internal.h"
 #include "pg_spmv.h"
+#include "pg_specest.h"
 
 using namespace pg;
 
@@ -98,6 +99,7 @@ struct pg_solver {
   // moving advection-diffusion (pg_solver_create_moving_advdiff_*): psip_conv.(Vn, Vn_1) / psim_conv.(Vn, Vn_1), per phase
   // (prescribedmotionsolver/advectiondiffusion.jl:35-61); the convection data come from the ConvectionOps in ops[]
   bool advdiff = false;
+  bool convection = false;   // an operator handed to the constructor was a ConvectionOps (noted there: the caller owns the operators)
   DevBuf<double> psi_cp[2], psi_cm[2];
   // the Stefan diphasic blocks (pg_solver_create_moving_stefan_diph, liquidmotionsolver/diffusion.jl:445-651)
   bool stefan = false;
@@ -1337,9 +1339,29 @@ void mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
   s->work.mg = &mg_ensure(s, rule);
 }
 
+// opts.precond = PG_PRECOND_POLY_EST: what it is refused on (with the condition that failed, as the multigrid does), then --
+// before every krylov_solve on A that takes the caller's options, and only where Gershgorin refuses A -- the spectral estimate of
+// A (pg_specest.hip), once per assembled matrix.  Where Gershgorin admits A nothing runs: the solve is the precond = 0 solve.
+void specest_conditions(const pg_solver* s, int method) {
+  const std::string who = "estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST) refused: ";
+  specest_require_one_rank();
+  PG_REQUIRE(!s->moving, who + "a moving-body solver (every space-time slab is a new matrix that is solved once)");
+  PG_REQUIRE(!s->advdiff && !s->convection, who + "the operator is a ConvectionOps (DiffusionOps only)");
+  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + (method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
+                                                                          : "the method is GMRES (BiCGStab only)"));
+}
+
+void specest_prepare(pg_solver* s, const CsrMatrix& A, const pg_krylov_opts& o) {
+  if (o.precond != PG_PRECOND_POLY_EST) return;
+  specest_conditions(s, o.method);
+  if (A.poly_ok || A.est.tried || A.poly_gave_up) return;   // (stagnated: it runs plain, as with precond = 0 -- no second chance)
+  specest_run(const_cast<CsrMatrix&>(A), s->nb, s->slab);
+}
+
 void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
   mg_prepare(s, o);
+  specest_prepare(s, s->A_ctor, o);
   // solve_system!(s) with the constructor's A and b (diffusion.jl:275)
   const i64 n = s->nb.n_own;
   if (s->moving && o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
@@ -1475,6 +1497,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   hipStream_t stream = ctx().stream;
   ensure_run_matrix(s, scheme);
   const CsrMatrix& A = run_matrix(s);
+  specest_prepare(s, A, o);
   const i64 n = s->nb.n_own;
   const bool warm = o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0;
   const DiagElim* used_de = nullptr;   // the compact path taken in this step (its "quiet" bookkeeping stays valid)
@@ -1616,6 +1639,8 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
           // the compact matrix is made of the full one's rows: the verdict on the polynomial holds for both, and the solve
           // below goes plain at once instead of stagnating a second time
           const_cast<CsrMatrix&>(A).poly_ok = false;
+          const_cast<CsrMatrix&>(A).est.admitted = false;
+          const_cast<CsrMatrix&>(A).poly_gave_up = true;
         }
         used_de = nullptr;
         const SolveStats first = st;
@@ -1657,7 +1682,11 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     guess_after_rhs(s, gp, n, nullptr, (const double*)A.ds.p, (const double*)w.rhat.p, true, w, stream);
     if (E.active) {
       gamma_fix(E, s->z.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, w.grid, stream);
-      krylov_solve(E.A, E.nb, s->slab, s->b.p, s->z.p, w, o, st, nullptr, nullptr, true);
+      // the sub-matrix carries Gershgorin's verdict on Â but no spectral estimate: PG_PRECOND_POLY_EST is precond = 0 here (the
+      // polynomial where Gershgorin admits, the plain loop where it refuses -- DESIGN.md section 16)
+      pg_krylov_opts oe = o;
+      if (oe.precond == PG_PRECOND_POLY_EST) oe.precond = 0;
+      krylov_solve(E.A, E.nb, s->slab, s->b.p, s->z.p, w, oe, st, nullptr, nullptr, true);
     } else {
       // y0 = z (in place), r0 = b̂ - ŷ: same solution as a zero start, fewer iterations
       krylov_solve(A, s->nb, s->slab, s->b.p, s->z.p, w, o, st, nullptr, nullptr, true);
@@ -1775,6 +1804,7 @@ static int32_t create_solver(const SolverSpec& d) {
   for (int q = 0; q < d.nphase; ++q) {
     s->cap[q] = d.cap[q];
     s->ops[q] = d.ops[q];
+    s->convection = s->convection || (d.ops[q] && d.ops[q]->has_velocity);
     if (d.moving) {
       s->psi_p[q].alloc(Ml);
       s->psi_m[q].alloc(Ml);
@@ -2324,6 +2354,48 @@ int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* o
   PG_API_END
 }
 
+// the matrix `which` names (0 constructor, 1 run system) and, unless bit 2 says "report only", its spectral estimate
+static CsrMatrix& specest_matrix(pg_solver* s, int32_t which, const char* entry) {
+  require_init();
+  PG_REQUIRE(s, std::string(entry) + ": NULL solver");
+  PG_REQUIRE((which & ~5) == 0, std::string(entry) + ": which = 0 (constructor system) or 1 (run system), + 4: report only");
+  PG_REQUIRE((which & 1) == 0 || s->have_run, std::string(entry) + ": the solver has no run system yet (take a step first)");
+  CsrMatrix& A = const_cast<CsrMatrix&>((which & 1) == 0 ? s->A_ctor : run_matrix(s));
+  if ((which & 4) == 0) {
+    specest_conditions(s, PG_METHOD_BICGSTAB);
+    specest_run(A, s->nb, s->slab);
+  }
+  return A;
+}
+
+int32_t pg_solver_spectral_estimate(pg_solver* s, int32_t which, pg_specest_info* out) {
+  PG_API_BEGIN
+  PG_REQUIRE(out, "pg_solver_spectral_estimate: NULL argument");
+  std::memset(out, 0, sizeof(*out));
+  const CsrMatrix& A = specest_matrix(s, which, "pg_solver_spectral_estimate");
+  out->margin = SPECEST_MARGIN;
+  out->gershgorin = A.gersh;
+  out->gershgorin_admits = A.poly_ok ? 1 : 0;
+  if (!A.est.tried) return 0;
+  out->steps = A.est.steps;
+  out->admitted = A.est.admitted ? 1 : 0;
+  out->g_ritz = A.est.g_ritz;
+  out->g_used = A.est.g_used;
+  out->ritz_re_min = A.est.re_min;
+  out->ritz_re_max = A.est.re_max;
+  out->ritz_im_max = A.est.im_max;
+  out->estimate_ms = A.est.ms;
+  PG_API_END
+}
+
+int32_t pg_debug_specest_hessenberg(pg_solver* s, int32_t which, int32_t* steps, double* H) {
+  PG_API_BEGIN
+  const CsrMatrix& A = specest_matrix(s, which, "pg_debug_specest_hessenberg");
+  if (steps) *steps = A.est.tried ? A.est.steps : 0;
+  if (H && A.est.tried && A.est.steps > 0) std::memcpy(H, A.est.H.data(), sizeof(double) * (size_t)(A.est.steps + 1) * A.est.steps);
+  PG_API_END
+}
+
 static MgHierarchy& debug_mg(pg_solver* s, int32_t precond) {
   require_init();
   PG_REQUIRE(s, "multigrid diagnostics: NULL solver");
@@ -2693,6 +2765,7 @@ void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st
   }
   const pg_krylov_opts o = opts ? *opts : default_opts();
   mg_prepare(s, o);
+  specest_prepare(s, s->A_ctor, o);
   hipStream_t stream = ctx().stream;
   const i64 n = s->nb.n_own;
   ensure_bconst(s, PG_SCHEME_STEADY);
@@ -2755,6 +2828,7 @@ static void refine_once(pg_solver* s, const pg_krylov_opts& o, SolveStats& st) {
 void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
   if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (a solver built for one time step: refused)
+  specest_prepare(s, s->A_ctor, o);
   const i64 n = s->nb.n_own;
   if (!(o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) || s->initial_done) {
     do_initial(s, opts, st);

@@ -1,8 +1,23 @@
 // pg_system.h -- reduced (active-set) linear system of one slab: numbering (K10) + CSR matrix (K7/K9).
 #pragma once
+#include <vector>
+
 #include "pg_stencil.h"
 
 namespace pg {
+
+// Spectral estimate of a matrix (pg_specest.hip; pg_krylov_opts.precond = PG_PRECOND_POLY_EST): the Ritz values of 30 Arnoldi
+// steps put the spectrum of Â in the disc |λ - 1| <= g_ritz; the polynomial preconditioner is admitted on g_used = g_ritz +
+// margin < 0.95.  Run at most once per assembled matrix (decide_poly resets it), and only where Gershgorin refuses.
+struct SpecEst {
+  bool tried = false;
+  bool admitted = false;   // the verdict; cleared when the polynomial stagnates on this matrix (pg_krylov.hip)
+  int steps = 0;           // Arnoldi steps taken (fewer than asked for: happy breakdown)
+  double g_ritz = 0.0, g_used = 0.0;
+  double re_min = 0.0, re_max = 0.0, im_max = 0.0;   // of the Ritz values
+  double ms = 0.0;         // wall time of the estimate
+  std::vector<double> H;   // (steps + 1) x steps, column major (pg_debug_specest_hessenberg)
+};
 
 // Local vector layout (length n_own + n_ghost):
 //   [ kind0 owned | kind1 owned | ... | lower ghost: kind0.. | upper ghost: kind0.. ]
@@ -92,6 +107,13 @@ struct CsrMatrix {
   // M⁻¹ = 2I - Â = Â⁻¹(I - (I - Â)²) is then a safe right preconditioner for BiCGStab (pg_krylov.hip).  Collective.
   bool poly_ok = false;
   double gersh = 0.0;   // the largest disc radius found (all ranks)
+  // A flag of its own, not poly_ok: poly_ok also starts the diagonal-row elimination and the compact loop system
+  // (pg_reduce.hip), which must not start on matrices they have never seen because of an opt-in option.
+  SpecEst est;
+  // the polynomial stagnated on this matrix (pg_krylov.hip poly_give_up; pg_solver.hip for the full matrix of a compact system
+  // that stagnated): poly_ok and est.admitted were cleared, every later solve runs plain and PG_PRECOND_POLY_EST estimates
+  // nothing on it -- as precond = 0 does.  Reset by decide_poly with the rest.
+  bool poly_gave_up = false;
   i64 n_blk = 0;
   i64 nnz_raw = 0;   // entries of the un-preconditioned reduced matrix (what pg_solver_get_system_csr(0/1) returns)
   DevBuf<int> blk_rows, blk_idx;
