@@ -54,8 +54,13 @@ enum { PG_KEY_LEFT = 0 /* dim2 = 1 */, PG_KEY_RIGHT = 1 /* dim2 = n2 */, PG_KEY_
 enum { PG_SCHEME_BE = 0, PG_SCHEME_CN = 1,                   /* "BE" / "CN" strings of the reference */
        PG_SCHEME_STEADY = 2 };                                /* internal: the steady constructors */
 enum { PG_SV_PSI = 0, PG_SV_OMEGA = 1, PG_SV_U = 2, PG_SV_V = 3 };   /* fields / systems of a pg_streamvort */
-enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2 };   /* IterativeSolvers methods kept:
-   bicgstab (also serves `\` and bicgstabl), cg, gmres (solve_system!'s default, src/solver.jl:158) */
+enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2, PG_METHOD_BICGSTABL = 3 };   /* IterativeSolvers methods
+   kept: bicgstab (also serves `\`, and bicgstabl when no l is given), cg, gmres (solve_system!'s default, src/solver.jl:158),
+   bicgstabl with l = pg_krylov_opts.restart (BiCGStab(l), DESIGN.md "BiCGStab(l)"): opt-in, one rank, zero initial guess
+   (warm_start is ignored), plain -- refused together with precond = m >= 1, PG_PRECOND_MG, PG_PRECOND_MG_CELL or
+   PG_PRECOND_POLY_EST; with precond = 0 or -1 it runs unpreconditioned.  Its `iters` count BiCG sub-steps, two products each
+   (the unit of BiCGStab's iterations: l = 1 is directly comparable) and maxiter caps that unit (no outer iteration starts at
+   iters >= maxiter); products = 2 iters + the products that confirm the true residual before convergence is reported */
 
 /* ---- plain structs ------------------------------------------------------------------- */
 typedef struct {
@@ -87,7 +92,8 @@ typedef struct {
   int32_t check_every; /* host convergence poll period in iterations (<=0: default 4) */
   int32_t warm_start;  /* != 0: pg_solver_step starts BiCGStab from the previous time level instead of zero
                           (IterativeSolvers starts from zero; same solution to reltol, fewer iterations) */
-  int32_t restart;     /* GMRES only: Krylov vectors per restart cycle (<= 0: 20, IterativeSolvers' default) */
+  int32_t restart;     /* GMRES: Krylov vectors per restart cycle (<= 0: 20, IterativeSolvers' default);
+                          BiCGStab(l): l, <= 0 means 2, more than 8 is refused */
   int32_t precond;     /* BiCGStab only: polynomial right preconditioner in Â (DESIGN.md "Krylov driver").  0: automatic
                           (on where Gershgorin bounds the spectrum; degree 6 for a first solve, then chosen per solve of the
                           warm time loop from the previous solve's convergence rate, 4 .. 32); -1: off (the plain

@@ -52,10 +52,16 @@ end
 function gmres end
 function bicgstabl end
 function cg end
-# method -> PG_METHOD_*: cg -> 1, gmres -> 2 (restarted GMRES on the device), everything else (`\`, bicgstabl) -> 0 = BiCGStab
-function _method_id(m)
-    n = m isa Symbol ? String(m) : (m isa Function ? String(nameof(m)) : "")
-    n == "cg" ? Int32(1) : (n == "gmres" ? Int32(2) : Int32(0))
+# method -> PG_METHOD_*: cg -> 1, gmres -> 2 (restarted GMRES on the device), bicgstabl WITH the keyword l -> 3 (BiCGStab(l),
+# l = 1 .. 8, DESIGN.md "BiCGStab(l)"), everything else (`\`, bicgstabl without l) -> 0 = BiCGStab
+function _method_name(m)
+    m isa Symbol ? String(m) : (m isa Function ? String(nameof(m)) : "")
+end
+function _method_id(m, kw = NamedTuple())
+    n = _method_name(m)
+    n == "cg" && return Int32(1)
+    n == "gmres" && return Int32(2)
+    (n == "bicgstabl" && haskey(kw, :l)) ? Int32(3) : Int32(0)
 end
 
 # ---------------------------------------------------------------------------------- plain structs of the ABI
@@ -106,10 +112,17 @@ function _precond_id(p)
     p === :mg_cell || error("precond must be an integer, :mg, :mg_cell or :poly_est, not :$(p)")
     PG_PRECOND_MG_CELL
 end
+# method = bicgstabl, l = 2 (4, ...): BiCGStab(l) -- one rank, zero initial guess, plain (refused with precond = m >= 1, :mg,
+# :mg_cell, :poly_est; l > 8 is refused).  Its iteration counts are BiCG sub-steps, two products each, the unit maxiter caps;
+# max_mv_products (IterativeSolvers' spelling) is converted: maxiter = max_mv_products ÷ 2.  Without l the name means BiCGStab.
 function _opts(method, kw; warm_default::Bool=true)
-    pg_krylov_opts(_method_id(method), Float64(get(kw, :reltol, 1e-12)), Float64(get(kw, :abstol, 0.0)),
-                   Int32(get(kw, :maxiter, 0)), Int32(4), Int32(get(kw, :warm_start, warm_default) ? 1 : 0),
-                   Int32(get(kw, :restart, 0)), _precond_id(get(kw, :precond, 0)))
+    id = _method_id(method, kw)
+    maxiter = haskey(kw, :maxiter) ? Int32(kw[:maxiter]) :
+              (haskey(kw, :max_mv_products) ? Int32(max(1, Int(kw[:max_mv_products]) ÷ 2)) : Int32(0))
+    restart = id == Int32(3) ? Int32(kw[:l]) : Int32(get(kw, :restart, 0))
+    pg_krylov_opts(id, Float64(get(kw, :reltol, 1e-12)), Float64(get(kw, :abstol, 0.0)),
+                   maxiter, Int32(4), Int32(get(kw, :warm_start, warm_default) ? 1 : 0),
+                   restart, _precond_id(get(kw, :precond, 0)))
 end
 
 # ---------------------------------------------------------------------------------- Mesh  (src/mesh.jl:41-79)

@@ -794,8 +794,13 @@ def _precond_value(precond) -> int:
 
 def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     """method may be "bicgstab" / "cg" / "gmres" or a callable named like IterativeSolvers' (bicgstabl, cg, gmres...).
-    gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; `\\`, bicgstabl and anything else ->
-    BiCGStab.  reltol defaults to 1e-12: the parity target is the direct-solve path.
+    gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; bicgstabl WITH the keyword l (l=2, l=4, ..,
+    at most 8) -> BiCGStab(l) on the device (DESIGN.md "BiCGStab(l)": one rank, zero initial guess, plain -- the library refuses
+    it together with precond = m >= 1, "mg", "mg-cell" or "poly-est"); `\\`, bicgstabl WITHOUT l and anything else -> BiCGStab.
+    BiCGStab(l) counts BiCG sub-steps as its iterations, two products each -- the unit of BiCGStab's iterations, and the unit
+    maxiter caps (no outer iteration starts at iters >= maxiter); products = 2 iters + the products that confirm the true residual.
+    max_mv_products (IterativeSolvers' spelling of the cap) is accepted when maxiter is not given: maxiter = max_mv_products // 2.
+    reltol defaults to 1e-12: the parity target is the direct-solve path.
     precond: an integer as pg_krylov_opts.precond takes it (0 automatic, -1 off, m >= 1 the polynomial's degree), or "mg":
     the aggregation multigrid V-cycle (steady monophasic diffusion with a Dirichlet interface and the ψ solve of a
     StreamVorticity; the library refuses it anywhere else), or "mg-cell": the same V-cycle on the cell-aggregated hierarchy
@@ -805,11 +810,22 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     refused anywhere else; Solver.spectral_estimate tells what the estimate found)."""
     name = method if isinstance(method, str) else getattr(method, "__name__", "bicgstab")
     name = name.lower()
-    m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])
+    restart = int(kwargs.get("restart", 0))
+    if name == "bicgstabl":
+        # the bare name keeps meaning BiCGStab (every existing call takes the path it took); the keyword l opts in
+        if kwargs.get("l") is not None:
+            m, restart = L.PG_METHOD["bicgstabl"], int(kwargs["l"])
+        else:
+            m = L.PG_METHOD["bicgstab"]
+    else:
+        m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])
     precond = _precond_value(kwargs.get("precond", 0))
+    maxiter = int(kwargs.get("maxiter", 0))
+    if "maxiter" not in kwargs and kwargs.get("max_mv_products") is not None:
+        maxiter = max(1, int(kwargs["max_mv_products"]) // 2)
     return L.pg_krylov_opts(m, float(kwargs.get("reltol", 1e-12)), float(kwargs.get("abstol", 0.0)),
-                            int(kwargs.get("maxiter", 0)), int(kwargs.get("check_every", 4)),
-                            int(bool(kwargs.get("warm_start", True))), int(kwargs.get("restart", 0)),
+                            maxiter, int(kwargs.get("check_every", 4)),
+                            int(bool(kwargs.get("warm_start", True))), restart,
                             int(precond))
 
 
@@ -1126,7 +1142,7 @@ def DiffusionSteadyMono(phase: Phase, bc_b: BorderConditions, bc_i, verbose: boo
                                                  p(D_arr), p(f_arr), C.byref(s._h)))
     if bvals is not None:
         L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(bvals)))
-    s._ctx = dict(M=M)
+    s._ctx = dict(M=M, phase=phase)   # (the handle points into the phase's capacity and operators: they live as long as it)
     s._ctor_scheme = "STEADY"
     return s
 
@@ -1176,7 +1192,7 @@ def DiffusionSteadyDiph(phase1: Phase, phase2: Phase, bc_b: BorderConditions, ic
         C.c_int32(nb), p(D1), p(D2), p(f1), p(f2), C.byref(s._h)))
     if bvals is not None:
         L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(bvals)))
-    s._ctx = dict(M=M)
+    s._ctx = dict(M=M, phase1=phase1, phase2=phase2)   # (as the monophasic constructor: the handle points into them)
     s._ctor_scheme = "STEADY"
     return s
 

@@ -591,4 +591,74 @@ inline bool hessenberg_eigenvalues(int n, const double* h, int ld, double* wr, d
   return true;
 }
 
+// ---- minimal-residual step of BiCGStab(l) (pg_bicgstabl.hip; tests/bicgstabl_host.cpp) --------------------------------------
+// G: the Gram matrix of the power basis R[0..l] of the residual, (l+1) x (l+1), row major with leading dimension BL_LD.
+// Solves  G[1..k, 1..k] gamma[1..k] = G[1..k, 0]  by Cholesky with diagonal pivoting for the largest k <= l whose pivots all
+// exceed BL_PIV_TOL times their own diagonal entry (the squared sine of the angle between that basis vector and the span of
+// the ones eliminated before it); gamma[i] = 0 beyond k, gamma[0] = 0.  Returns k; 0: not even G11 is positive and finite
+// (Â r = 0).  Whatever gamma comes back, x += Σ gamma_i R[i-1] and r -= Σ gamma_i R[i] keep r the residual of x: a shrunk block
+// costs optimality of the step, never consistency.  Compiled for the device too (one thread), and by g++ for the host tests.
+#if defined(__HIPCC__)
+#define PGHOST_HD __host__ __device__
+#else
+#define PGHOST_HD
+#endif
+constexpr int BL_MAX_L = 8;
+constexpr int BL_LD = BL_MAX_L + 1;
+constexpr double BL_PIV_TOL = 1e-13;
+
+PGHOST_HD inline bool bl_finite(double v) { return v == v && v <= 1.7976931348623157e308 && v >= -1.7976931348623157e308; }
+
+PGHOST_HD inline int bicgstabl_small_solve(const double* G, int l, double* gamma) {
+  for (int i = 0; i <= BL_MAX_L; ++i) gamma[i] = 0.0;
+  if (l < 1 || l > BL_MAX_L) return 0;
+  double M[BL_MAX_L][BL_MAX_L], c[BL_MAX_L], d0[BL_MAX_L], y[BL_MAX_L];
+  int perm[BL_MAX_L];
+  for (int k = l; k >= 1; --k) {
+    for (int i = 0; i < k; ++i) {
+      for (int j = 0; j < k; ++j) M[i][j] = G[(i + 1) * BL_LD + (j + 1)];
+      c[i] = G[(i + 1) * BL_LD];
+      d0[i] = M[i][i];
+      perm[i] = i;
+    }
+    bool ok = true;
+    for (int s = 0; s < k && ok; ++s) {
+      int p = s;
+      for (int q = s + 1; q < k; ++q)
+        if (M[q][q] > M[p][p]) p = q;
+      if (p != s) {
+        for (int j = 0; j < k; ++j) { const double t = M[s][j]; M[s][j] = M[p][j]; M[p][j] = t; }
+        for (int i = 0; i < k; ++i) { const double t = M[i][s]; M[i][s] = M[i][p]; M[i][p] = t; }
+        { const double t = c[s]; c[s] = c[p]; c[p] = t; }
+        { const double t = d0[s]; d0[s] = d0[p]; d0[p] = t; }
+        { const int t = perm[s]; perm[s] = perm[p]; perm[p] = t; }
+      }
+      const double piv = M[s][s];
+      if (!(piv > BL_PIV_TOL * d0[s]) || !bl_finite(piv)) { ok = false; break; }
+      const double root = sqrt(piv);
+      M[s][s] = root;
+      c[s] = c[s] / root;
+      for (int q = s + 1; q < k; ++q) M[q][s] = M[q][s] / root;
+      for (int q = s + 1; q < k; ++q) {
+        for (int t = s + 1; t <= q; ++t) {
+          M[q][t] -= M[q][s] * M[t][s];
+          M[t][q] = M[q][t];
+        }
+        c[q] -= M[q][s] * c[s];
+      }
+    }
+    if (!ok) continue;
+    for (int s = k - 1; s >= 0; --s) {
+      double v = c[s];
+      for (int q = s + 1; q < k; ++q) v -= M[q][s] * y[q];
+      y[s] = v / M[s][s];
+      if (!bl_finite(y[s])) ok = false;
+    }
+    if (!ok) continue;
+    for (int s = 0; s < k; ++s) gamma[1 + perm[s]] = y[s];
+    return k;
+  }
+  return 0;
+}
+
 }  // namespace pghost

@@ -1,4 +1,4 @@
-// pg_krylov.h -- K11: Krylov solve of the reduced system on one slab (BiCGStab / CG / GMRES).
+// pg_krylov.h -- K11: Krylov solve of the reduced system on one slab (BiCGStab / CG / GMRES / BiCGStab(l)).
 #pragma once
 #include <functional>
 
@@ -63,6 +63,11 @@ struct KrylovWork {
   // GMRES(m) only, allocated on first use (pg_gmres.hip): m+1 basis vectors, H / rotations / g, per-block partial sums
   DevBuf<double> gm_basis, gm, gm_partials;
   int gm_m = -1;
+  // BiCGStab(l) only, allocated on first use (pg_bicgstabl.hip): R[0..l], U[0..l] and r̃ in one block (bl_stride apart), the
+  // method's device scalars (with the Gram matrix and γ), per-block partial sums of the Gram / update kernels
+  DevBuf<double> bl_vecs, bl, bl_partials;
+  int bl_l = -1;
+  i64 bl_stride = 0;
   // Set by the caller around one krylov_solve: work to queue right AFTER the first batch of iterations and the copy of the
   // scalars, BEFORE the host waits for that copy -- the next time step's first product, speculatively: the device then
   // has something to run while the host wakes up, reads the scalars and queues the next step (the wait is on an event
@@ -118,5 +123,12 @@ extern int g_poly_give_up;
 // restarted GMRES (pg_gmres.hip): zero initial guess, x (n_vec, overwritten) = A^{-1} b
 void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,
                  const pg_krylov_opts& opts, SolveStats& stats);
+
+// BiCGStab(l), l = opts.restart (<= 0: 2, > 8 refused) (pg_bicgstabl.hip): zero initial guess, x (n_vec, overwritten) = A^{-1} b;
+// one rank; stats.iters counts BiCG sub-steps (two products each), stats.products = 2 iters + true-residual confirmations
+void bicgstabl_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,
+                     const pg_krylov_opts& opts, SolveStats& stats);
+// "the method is CG (BiCGStab only)" and its kin: the refusal texts of what serves BiCGStab alone
+const char* krylov_method_refusal(int method);
 
 }  // namespace pg

@@ -542,6 +542,11 @@ void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st) {
   PG_HIP(hipGetLastError());
 }
 
+const char* krylov_method_refusal(int method) {
+  return method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
+         : method == PG_METHOD_BICGSTABL ? "the method is BiCGStab(l) (BiCGStab only)" : "the method is GMRES (BiCGStab only)";
+}
+
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts) {
   const bool poly_env = config().poly;
   const int degree_env = config().poly_degree;
@@ -647,7 +652,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   hipStream_t st = cx.stream;
   const i64 n = A.n, nvec = nb.n_vec();
   PG_REQUIRE(w.n >= n && w.nvec >= nvec, "krylov workspace too small");   // (a reduced system works on prefixes, pg_reduce.hip)
-  PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB || opts.method == PG_METHOD_CG || opts.method == PG_METHOD_GMRES,
+  PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB || opts.method == PG_METHOD_CG || opts.method == PG_METHOD_GMRES ||
+                 opts.method == PG_METHOD_BICGSTABL,
              "unknown Krylov method");
   // PG_PRECOND_POLY_EST: precond = 0 wherever Gershgorin admits the matrix; where it refuses, the verdict of the spectral
   // estimate the caller has run on this matrix (CsrMatrix::est, pg_specest.hip) -- a flag of its own, poly_ok stays false
@@ -655,7 +661,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   if (est_opt) {
     PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB,
                std::string("estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST) refused: ") +
-                   (opts.method == PG_METHOD_CG ? "the method is CG (BiCGStab only)" : "the method is GMRES (BiCGStab only)"));
+                   krylov_method_refusal(opts.method));
     specest_require_one_rank();
     // the contract: whoever passes the option has run the estimate on THIS matrix (pg_solver.hip specest_prepare) -- a
     // matrix nobody looked at would otherwise run plain without a word.  (A matrix the polynomial stagnated on has its verdict:
@@ -667,6 +673,21 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   if (opts.method == PG_METHOD_GMRES) {
     PG_REQUIRE(!preinit && !x0, "GMRES starts from zero (IterativeSolvers' default)");
     gmres_solve(A, nb, slab, b, x, w, opts, stats);
+    return;
+  }
+  if (opts.method == PG_METHOD_BICGSTABL) {
+    // opt-in, plain: every preconditioner of the BiCGStab loop is refused with it rather than dropped without a word
+    PG_REQUIRE(!preinit && !x0, "BiCGStab(l) starts from zero (IterativeSolvers' default)");
+    PG_REQUIRE(!mg_is_precond(opts.precond), std::string("multigrid preconditioner (precond = ") + mg_precond_name(mg_rule_of(opts.precond)) +
+                                                 ") refused: " + krylov_method_refusal(opts.method));
+    PG_REQUIRE(opts.precond <= 0, "polynomial preconditioner (precond = " + std::to_string(opts.precond) + ") refused: " +
+                                      krylov_method_refusal(opts.method) + "; precond = 0 or -1 runs BiCGStab(l) plain");
+    w.mg = nullptr;
+    w.xguess = XGuess();
+    w.p_in_rhat = w.start_folded = false;
+    w.moved_flag = nullptr;
+    w.after_first_batch = nullptr;
+    bicgstabl_solve(A, nb, slab, b, x, w, opts, stats);
     return;
   }
   const int G = w.grid;

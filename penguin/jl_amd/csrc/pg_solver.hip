@@ -1319,8 +1319,7 @@ void mg_conditions(const pg_solver* s, int method, MgRule rule = MG_RULE_KIND) {
                                                 : "the interface condition is Neumann (Dirichlet only)"));
   // (not "no blocked rows": the cut cells of a Dirichlet interface are blocked too -- their γ row is a row of the identity, and
   //  B⁻¹ only takes the same-cell γ entry out of the ω row.  Â keeps its unit diagonal; the hierarchy is built on Â as it is.)
-  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + (method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
-                                                                          : "the method is GMRES (BiCGStab only)"));
+  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + krylov_method_refusal(method));
 }
 
 MgHierarchy& mg_of(pg_solver* s, MgRule rule) { return rule == MG_RULE_CELL ? s->mg_cell : s->mg; }
@@ -1347,8 +1346,7 @@ void specest_conditions(const pg_solver* s, int method) {
   specest_require_one_rank();
   PG_REQUIRE(!s->moving, who + "a moving-body solver (every space-time slab is a new matrix that is solved once)");
   PG_REQUIRE(!s->advdiff && !s->convection, who + "the operator is a ConvectionOps (DiffusionOps only)");
-  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + (method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
-                                                                          : "the method is GMRES (BiCGStab only)"));
+  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + krylov_method_refusal(method));
 }
 
 void specest_prepare(pg_solver* s, const CsrMatrix& A, const pg_krylov_opts& o) {
