@@ -187,6 +187,12 @@ typedef struct {
                                 right-hand side and the start residual not counted)                                             */
   int64_t guess_states_read; /* older states read by the extrapolated starts of the run's quiet steps (pg_solver_guess_info):
                                 each is two more vector reads of the step's first kernel                                        */
+  /* mixed-precision Horner chain (PG_POLY_F32): */
+  int64_t poly_f32_launches; /* Horner launches that read or wrote an fp32 vector (first, middle and hand-over launches)        */
+  double poly_f32_ms_total;  /* profiling: HIP-event time of the sampled ones -- a bracket of their own: spmv_lean_* keeps the  */
+  int64_t poly_f32_timed;    /* fp64 Horner launches only -- and how many launches that time covers                             */
+  int64_t poly_f32_chains;   /* applications of the preconditioner that ran the mixed chain                                      */
+  int64_t poly_f32_tail_sum; /* sum over those of j, the launches of the chain's fp64 tail (hand-over included)                  */
 } pg_run_info;
 
 typedef struct {
@@ -559,6 +565,16 @@ int32_t pg_debug_spmv_apply(pg_solver* s, int32_t which, int32_t variant, int32_
                             const double* dotx, const double* base, double pc0, double pc1, double pc2, int32_t fold,
                             int32_t done, int32_t repeat, double* y, double* partials, double* slot_sums, double* folded,
                             int64_t* ticket);
+/* pg_debug_spmv_apply for the Horner launches with an element type per vector stream (launch_spmv_typed of pg_spmv.h: the
+   mixed-precision chain), y = pc2 base + pc0 x + pc1 A x with the arithmetic of launch mode 8 on the converted inputs:
+     kind 1  first launch: x n_vec doubles, base IS x (pass NULL); y32 = (float)y and p32 = (float)(sigma x) for every row
+          2  middle launch: x n_vec floats, base n floats; y32 = (float)y
+          3  hand-over launch: x n_vec floats, base n doubles; y64 = y
+   pc0, pc1, pc2 go to the kernel as given (the caller folds sigma in).  done as above.  Out: y32 / p32 (n + 64 floats) or y64
+   (n + 64 doubles), the others NULL; filled with PG_DEBUG_SPMV_SENTINEL_F32 / PG_DEBUG_SPMV_SENTINEL before the launch. */
+#define PG_DEBUG_SPMV_SENTINEL_F32 0x7FC5EED0u
+int32_t pg_debug_spmv_apply_typed(pg_solver* s, int32_t which, int32_t kind, const void* x, const void* base, double pc0, double pc1,
+                                  double pc2, double sigma, int32_t done, double* y64, float* y32, float* p32);
 /* read-only streaming probe: `bytes` read `reps` times with elem_bytes (4|8) per lane, optional non-temporal hint */
 int32_t pg_debug_read_probe(int64_t bytes, int32_t elem_bytes, int32_t nt, int32_t blocks, int32_t reps, double* gbs);
 /* run the slab-decomposed monophasic path with `nranks` VIRTUAL ranks (host threads sharing this GPU, in-process

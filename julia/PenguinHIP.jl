@@ -84,7 +84,8 @@ mutable struct pg_run_info
     spmv_ms_total::Float64; spmv_launches::Int64; unconverged_steps::Int64; worst_relres::Float64
     spmv_lean_ms_total::Float64; spmv_lean_launches::Int64; poly_degree::Int64; half_exits::Int64; poly_xspace::Int64
     products::Int64; guess_states_read::Int64
-    pg_run_info() = new(0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0, 0.0, 0, 0, 0, 0, 0, 0)
+    poly_f32_launches::Int64; poly_f32_ms_total::Float64; poly_f32_timed::Int64; poly_f32_chains::Int64; poly_f32_tail_sum::Int64
+    pg_run_info() = new(0, 0, 0.0, 0.0, 0.0, 0.0, 0, 0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0.0, 0, 0, 0)
 end
 mutable struct pg_streamvort_run_info
     steps::Int64; psi_iters::Int64; omega_iters::Int64; psi_products::Int64; omega_products::Int64; unconverged::Int64

@@ -79,7 +79,9 @@ class pg_run_info(C.Structure):
                 ("solve_ms", C.c_double), ("spmv_ms_total", C.c_double), ("spmv_launches", C.c_int64),
                 ("unconverged_steps", C.c_int64), ("worst_relres", C.c_double), ("spmv_lean_ms_total", C.c_double),
                 ("spmv_lean_launches", C.c_int64), ("poly_degree", C.c_int64), ("half_exits", C.c_int64),
-                ("poly_xspace", C.c_int64), ("products", C.c_int64), ("guess_states_read", C.c_int64)]
+                ("poly_xspace", C.c_int64), ("products", C.c_int64), ("guess_states_read", C.c_int64),
+                ("poly_f32_launches", C.c_int64), ("poly_f32_ms_total", C.c_double), ("poly_f32_timed", C.c_int64),
+                ("poly_f32_chains", C.c_int64), ("poly_f32_tail_sum", C.c_int64)]
 
 
 class pg_system_info(C.Structure):
@@ -342,3 +344,36 @@ def debug_spmv_apply(handle, which: int, variant: int, mode: int, x, aux=None, d
                                     C.c_double(pc[0]), C.c_double(pc[1]), C.c_double(pc[2]), C.c_int32(fold), C.c_int32(done),
                                     C.c_int32(repeat), dptr(y), dptr(partials), dptr(sums), dptr(folded), C.byref(ticket)))
     return {"y": y, "partials": partials, "slot_sums": sums, "folded": folded, "ticket": ticket.value, "grid": grid, "n": n}
+
+
+DEBUG_SPMV_SENTINEL_F32 = 0x7FC5EED0           # PG_DEBUG_SPMV_SENTINEL_F32
+TYPED_FIRST, TYPED_MIDDLE, TYPED_HANDOVER = 1, 2, 3
+
+
+def debug_spmv_apply_typed(handle, which: int, kind: int, x, base=None, pc=(0.0, 0.0, 0.0), sigma: float = 1.0, done: int = 0) -> dict:
+    """pg_debug_spmv_apply_typed: ONE Horner launch of the mixed-precision chain (kind 1 first, 2 middle, 3 hand-over) on host
+    vectors.  x: n_vec float64 (kind 1) or float32 (kinds 2, 3); base: None (kind 1: base is x), n float32 (kind 2), n float64
+    (kind 3); the arrays must already have these dtypes -- nothing is converted here.  Returns y (n + 64 guard words: float32 for
+    kinds 1 and 2, float64 for kind 3) and, for kind 1, p32 (n + 64 float32)."""
+    n, nv, _, _ = debug_spmv_sizes(handle, which)
+    want_x = np.float64 if kind == TYPED_FIRST else np.float32
+    want_b = {TYPED_FIRST: None, TYPED_MIDDLE: np.float32, TYPED_HANDOVER: np.float64}[kind]
+    x = np.ascontiguousarray(x)
+    if x.dtype != want_x or x.size != nv:
+        raise ValueError(f"debug_spmv_apply_typed: x must be {nv} x {np.dtype(want_x).name}")
+    if (base is None) != (want_b is None):
+        raise ValueError("debug_spmv_apply_typed: base goes with kinds 2 and 3, and only with them")
+    bp = None
+    if base is not None:
+        base = np.ascontiguousarray(base)
+        if base.dtype != want_b or base.size != n:
+            raise ValueError(f"debug_spmv_apply_typed: base must be {n} x {np.dtype(want_b).name}")
+        bp = base.ctypes.data_as(C.c_void_p)
+    y64 = np.zeros(n + DEBUG_SPMV_GUARD) if kind == TYPED_HANDOVER else None
+    y32 = np.zeros(n + DEBUG_SPMV_GUARD, dtype=np.float32) if kind != TYPED_HANDOVER else None
+    p32 = np.zeros(n + DEBUG_SPMV_GUARD, dtype=np.float32) if kind == TYPED_FIRST else None
+    ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    check(lib().pg_debug_spmv_apply_typed(handle, C.c_int32(which), C.c_int32(kind), x.ctypes.data_as(C.c_void_p), bp,
+                                          C.c_double(pc[0]), C.c_double(pc[1]), C.c_double(pc[2]), C.c_double(sigma), C.c_int32(done),
+                                          ptr(y64), ptr(y32), ptr(p32)))
+    return {"y": y64 if kind == TYPED_HANDOVER else y32, "p32": p32}

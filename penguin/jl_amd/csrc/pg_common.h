@@ -79,6 +79,8 @@ struct Config {
   bool poly_trend = true;         // PG_POLY_TREND: the degree estimate follows the trend of the last estimates
   int poly_maxdeg = 0;            // PG_POLY_MAXDEG (0: 32)
   int poly_mindeg = 4;            // PG_POLY_MINDEG: the smallest degree the per-solve choice takes (2 .. 8)
+  bool poly_f32 = true;           // PG_POLY_F32: the early Horner steps of the chain run on fp32 vectors (pg_krylov.hip, mixed chain)
+  int poly_f32_tail = -1;         // PG_POLY_F32_TAIL: launches of the chain's fp64 tail (-1: from the reduction the solve needs)
   int profile_sample = 3;         // PG_PROFILE_SAMPLE
   bool gamma_elim = true;         // PG_GAMMA_ELIM
   bool diag_elim = true;          // PG_DIAG_ELIM

@@ -661,4 +661,108 @@ PGHOST_HD inline int bicgstabl_small_solve(const double* G, int l, double* gamma
   return 0;
 }
 
+// ---- schedule of the mixed-precision Horner chain (pg_krylov.hip) ------------------------------------------
+// The chain applies the m factors (I - Â/λ_k), λ_k the Chebyshev nodes of [1 - g, 1 + g] (index 0 = the largest), in m - 1
+// launches: the first applied root is folded into the first launch's coefficients, launch i = 0 .. m-2 applies root
+// order[i + 1].  The mixed chain stores the results of its first n32 = m - 1 - j launches in fp32 and runs the last j launches
+// -- the TAIL, whose first launch reads fp32 and writes fp64 (the hand-over) -- as they have always run.  What a rounded
+// intermediate contributes to the result is its rounding times the product of the factors still to come, so
+//   * the tail is a DAMPING set: the j roots nearest the Chebyshev nodes of degree j of the same interval (a tie goes to the
+//     larger root), whose product is close to the minimax polynomial of degree j, 1 / T_j(1/g) ~ 2 ρ^j, ρ = g / (1 + √(1 - g²));
+//   * the other m - j roots come first, the largest and the smallest remaining root in turn, and the tail's own roots in
+//     the same manner: no product of the factors before or after a stored intermediate grows beyond what the all-fp64 order
+//     (the same alternation, applied from its far end) shows for the same m.
+// j = 0 would leave nothing between the last fp32 store and the result; the chain's result is fp64 anyway, so the smallest
+// tail is the hand-over launch alone and a request for j = 0 is served with j = 1.
+constexpr int MIXED_MAX_DEGREE = 40;
+constexpr double MIXED_FLOOR32 = 1e-7;   // reduction ||s|| / ||r|| an application reaches with every intermediate stored in fp32
+constexpr double MIXED_DAMP = 0.45;      // what one more fp64 launch at the end takes off that floor (g <= 0.72; ρ(g) beyond)
+constexpr double MIXED_SAFETY = 0.5;     // the floor left by the tail must be below this share of the reduction the solve needs
+enum { CHAIN_F64 = 0, CHAIN_FIRST = 1, CHAIN_MIDDLE = 2, CHAIN_HANDOVER = 3 };
+
+struct MixedChain {
+  int m = 0, j = 0, n32 = 0;          // degree, launches of the tail (hand-over included), launches that write fp32
+  int order[MIXED_MAX_DEGREE];        // order[i]: index of the root applied i-th (0 = the largest)
+  int kind[MIXED_MAX_DEGREE];         // kind[i], i = 0 .. m-2: CHAIN_* of the launch that applies order[i + 1]
+};
+
+inline double mixed_root(int m, double g, int k) { return 1.0 + g * std::cos(M_PI * (2.0 * k + 1.0) / (2.0 * m)); }
+inline double mixed_rho(double g) { return g / (1.0 + std::sqrt(std::max(0.0, 1.0 - g * g))); }
+
+// idx[0..n): root indices in ascending order (descending roots) -> out: first, last, second, last but one, ...
+inline void mixed_alternate(const int* idx, int n, int* out) {
+  for (int k = 0, lo = 0, hi = n - 1; k < n; ++k) out[k] = (k & 1) ? idx[hi--] : idx[lo++];
+}
+
+// the schedule for (m, g, j); false: fewer than two fp32 launches would remain (or m out of range) -- the chain runs all fp64,
+// in its own order, and `out` is not to be used
+inline bool mixed_chain_schedule(int m, double g, int j, MixedChain& out) {
+  if (m < 2 || m > MIXED_MAX_DEGREE || j < 0) return false;
+  if (j < 1) j = 1;
+  const int n32 = m - 1 - j;
+  if (n32 < 2) return false;
+  out.m = m; out.j = j; out.n32 = n32;
+  bool taken[MIXED_MAX_DEGREE];
+  for (int k = 0; k < m; ++k) taken[k] = false;
+  int tail[MIXED_MAX_DEGREE], head[MIXED_MAX_DEGREE];
+  for (int q = 0; q < j; ++q) {
+    const double c = mixed_root(j, g, q);
+    int best = -1;
+    double dbest = 0.0;
+    for (int k = 0; k < m; ++k) {
+      if (taken[k]) continue;
+      const double d = std::fabs(mixed_root(m, g, k) - c);
+      if (best < 0 || d < dbest) { best = k; dbest = d; }   // (strict: a tie keeps the smaller index, the larger root)
+    }
+    taken[best] = true;
+  }
+  int nt = 0, nh = 0;
+  for (int k = 0; k < m; ++k) (taken[k] ? tail[nt++] : head[nh++]) = k;
+  mixed_alternate(head, nh, out.order);
+  mixed_alternate(tail, nt, out.order + nh);
+  for (int i = 0; i < m - 1; ++i)
+    out.kind[i] = i == 0 ? CHAIN_FIRST : (i < n32 ? CHAIN_MIDDLE : (i == n32 ? CHAIN_HANDOVER : CHAIN_F64));
+  out.kind[m - 1] = CHAIN_F64;
+  return true;
+}
+
+// the tail for a solve whose application must reduce the residual by `needed` (||s|| / ||r||, 0 < needed < 1): the smallest
+// j >= 1 with  floor32 damp^j <= safety needed,  damp = max(MIXED_DAMP, ρ(g));  -1: all fp64 (fewer than two fp32 launches
+// would remain, or `needed` is no such number)
+inline int mixed_chain_tail(double needed, double g, int m) {
+  if (!(needed > 0.0) || !(needed < 1.0) || m < 2 || m > MIXED_MAX_DEGREE) return -1;
+  const double damp = std::max(MIXED_DAMP, mixed_rho(g));
+  int j = 1;
+  double left = MIXED_FLOOR32 * damp;
+  while (left > MIXED_SAFETY * needed && j < m) { left *= damp; ++j; }
+  return m - 1 - j >= 2 ? j : -1;
+}
+
+// max over [1 - g, 1 + g] of |Π (1 - λ / r)| over the tail's roots, in extended precision: the end points and the one
+// critical point between every two neighbouring roots (the logarithmic derivative Σ 1 / (λ - r) falls from +∞ to -∞ there:
+// bisection)
+inline long double mixed_tail_max(const MixedChain& c, double g) {
+  const int j = c.j;
+  long double r[MIXED_MAX_DEGREE];
+  for (int q = 0; q < j; ++q) {
+    const int k = c.order[c.m - j + q];
+    r[q] = 1.0L + (long double)g * cosl(3.141592653589793238462643383279502884L * (2.0L * k + 1.0L) / (2.0L * c.m));
+  }
+  std::sort(r, r + j);
+  auto P = [&](long double x) { long double p = 1.0L; for (int q = 0; q < j; ++q) p *= 1.0L - x / r[q]; return fabsl(p); };
+  long double best = std::max(P(1.0L - (long double)g), P(1.0L + (long double)g));
+  for (int q = 0; q + 1 < j; ++q) {
+    long double a = r[q], b = r[q + 1];
+    for (int it = 0; it < 200; ++it) {
+      const long double x = 0.5L * (a + b);
+      if (!(x > a && x < b)) break;
+      long double d = 0.0L;
+      for (int t = 0; t < j; ++t) d += 1.0L / (x - r[t]);
+      if (d > 0.0L) a = x; else b = x;
+    }
+    best = std::max(best, P(0.5L * (a + b)));
+  }
+  return best;
+}
+
 }  // namespace pghost

@@ -60,6 +60,15 @@ struct KrylovWork {
   // polynomial right preconditioner (pg_krylov.hip), n_vec each, on first use: ya = M⁻¹p, yb = M⁻¹s of the running
   // iteration (the updates of x read them) and the two work vectors the Horner chain alternates between
   DevBuf<double> ya, yb, wa, wb;
+  // mixed-precision chain (pg_krylov.hip): the two fp32 work vectors the early Horner steps alternate between and p32 =
+  // (float)(σ in), n_vec each, on first use; and what the previous solve on mix_matrix left for the next one: the power-of-two
+  // scale σ of the fp32 vectors (from its start norm), the reduction an application has to deliver (mix_need: sets the length
+  // of the fp64 tail) and the solves left in which the tail is two launches longer (after a solve whose mixed application
+  // missed the half-step test)
+  DevBuf<float> fa, fb, p32;
+  const void* mix_matrix = nullptr;
+  double mix_sigma = 0.0, mix_need = 0.0;
+  int mix_wait = 0;
   // GMRES(m) only, allocated on first use (pg_gmres.hip): m+1 basis vectors, H / rotations / g, per-block partial sums
   DevBuf<double> gm_basis, gm, gm_partials;
   int gm_m = -1;
@@ -91,6 +100,11 @@ struct SolveStats {
   int poly_xspace = 0;      // 1: the polynomial preconditioner ran (kept for the ABI field pg_run_info.poly_xspace)
   i64 products = 0;         // products with Â inside the solve (the caller's start product not counted)
   int polls = 0;            // host waits of the solve (1: it ended inside the first batch of queued launches)
+  // mixed-precision chain: launches that read or write an fp32 vector (first, middle, hand-over), their sampled HIP-event time
+  // and count (a bracket of their own: spmv_lean_* keeps the fp64 Horner launches only), chains that ran mixed and the sum of
+  // their fp64 tails' lengths j
+  i64 f32_launches = 0, f32_timed = 0, f32_chains = 0, f32_tail_sum = 0;
+  double f32_ms = 0.0;
 };
 
 // halo exchange of the ghost segments of `vec` (no-op on one rank)

@@ -36,6 +36,7 @@
 // branch of its own: no degree, no adaptation, no give-up rule; the half-step test runs in every iteration (an application
 // costs five to six products' worth of bytes).  SolveStats::products counts the products with Â of the outer loop, i.e. the
 // applications.
+#include "pg_host_algos.h"
 #include "pg_krylov.h"
 #include "pg_multigrid.h"
 #include "pg_spmv.h"
@@ -435,8 +436,9 @@ struct SpmvTimer {
   std::vector<char> lean_of;  // 1: lean launch (no dots), 0: launch with fused dots
   std::vector<char> second_of;   // 1: launch of the second half of its iteration (skipped when the half step was accepted)
   std::vector<int> count_of;     // launches between the two events (a chain of lean launches is bracketed as a whole)
+  std::vector<char> f32_of;      // 1: the fp32 launches of a mixed chain (counters of their own: spmv_lean_* stays the fp64 Horner step)
   int cur = 0, cur_count = 1;
-  bool cur_lean = false, cur_second = false;
+  bool cur_lean = false, cur_second = false, cur_f32 = false;
   bool armed = false;
   explicit SpmvTimer(bool on_) : on(on_) {}
   // events are recycled through a per-thread pool: nothing is created or destroyed inside the time loop after the
@@ -456,18 +458,20 @@ struct SpmvTimer {
     PG_HIP(hipEventCreate(&e));
     return e;
   }
-  void begin(hipStream_t st, int iteration, bool lean = false, bool second = false, int count = 1) {
+  void begin(hipStream_t st, int iteration, bool lean = false, bool second = false, int count = 1, bool f32 = false) {
     cur = iteration;
     cur_lean = lean;
     cur_second = second;
     cur_count = count;
+    cur_f32 = f32;
     // every `sample`-th bracket is timed (PG_PROFILE_SAMPLE, default 3 -- coprime with the 4 brackets of an iteration: the
     // chain of lean launches and the closing launch of each half, so all four are sampled in turn).  A pair of event
     // records costs the stream ~10 µs (the kernel behind a record starts late): a lean chain is bracketed as a WHOLE so
     // that this cost is spread over its m - 1 launches; rocprofv3's per-kernel durations (profiles/) are the cross-check
     const int sample = config().profile_sample;
-    static thread_local unsigned long long counter = 0;
-    armed = on && (counter++ % sample == 0);
+    // (the fp32 bracket of a mixed chain draws from a counter of its own: the turn of the other brackets is what it was)
+    static thread_local unsigned long long counter = 0, counter_f32 = 0;
+    armed = on && ((f32 ? counter_f32++ : counter++) % sample == 0);
     if (!armed) return;
     e0 = take();
     e1 = take();
@@ -481,6 +485,7 @@ struct SpmvTimer {
     lean_of.push_back(cur_lean ? 1 : 0);
     second_of.push_back(cur_second ? 1 : 0);
     count_of.push_back(cur_count);
+    f32_of.push_back(cur_f32 ? 1 : 0);
   }
   // launches queued after convergence return at their first instruction (done flag): they are not SpMVs and are
   // left out of the launch count and of the average
@@ -491,7 +496,8 @@ struct SpmvTimer {
       (void)hipEventSynchronize(pr.second);
       const bool ran = iter_of[q] < iters_done && !(half_exit && iter_of[q] == iters_done - 1 && second_of[q]);
       if (ran && hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) {
-        if (lean_of[q]) { s.spmv_lean_ms += ms; s.spmv_lean_launches += count_of[q]; }
+        if (f32_of[q]) { s.f32_ms += ms; s.f32_timed += count_of[q]; }
+        else if (lean_of[q]) { s.spmv_lean_ms += ms; s.spmv_lean_launches += count_of[q]; }
         else { s.spmv_ms += ms; s.spmv_launches += 1; }
       }
       pool().push_back(pr.first);
@@ -502,6 +508,7 @@ struct SpmvTimer {
     lean_of.clear();
     second_of.clear();
     count_of.clear();
+    f32_of.clear();
   }
 };
 
@@ -569,7 +576,14 @@ namespace {
 // a Chebyshev step with BiCGStab's α, its residual test and, if the estimate was short, its continuation (444 -> 546 steps/s
 // at 512^3 against 3 x 9).  No safety margin: a miss costs one more application once, and the next estimate is made from
 // that solve.
-void choose_next_degree(const CsrMatrix& A, const SolveStats& stats, int m, bool adaptive, KrylovWork& w) {
+// what an all-fp32 (middle) Horner launch costs, in fp64 Horner launches: 47.7 against 54.7 us per launch at 512^3 in the kernel
+// trace (profiles/f32_chain_kernel_stats_*.csv) -- the launch moves 0.61 of the bytes but is not bound by them.  The first launch
+// (two fp32 vectors out) and the hand-over (fp64 base in, fp64 out) are no cheaper than an fp64 launch and get no discount.
+constexpr double F32_LAUNCH_WEIGHT = 0.87;
+
+// mixed_g > 0: the next solve's first application may run the mixed chain on a spectrum of radius mixed_g (its fp32 launches
+// are cheaper); the reduction that application must deliver, and with it the length of the fp64 tail, goes with (h, m)
+void choose_next_degree(const CsrMatrix& A, const SolveStats& stats, int m, bool adaptive, KrylovWork& w, double mixed_g) {
   const Config& cfg = config();
   const bool keep_degree = adaptive && stats.converged && stats.iters == 0 && w.adapt_m >= 2;   // met the tolerance at the start:
   w.adapt_matrix = nullptr;                                                                      // the smallest polynomial next time
@@ -612,7 +626,11 @@ void choose_next_degree(const CsrMatrix& A, const SolveStats& stats, int m, bool
     if (mm > maxdeg) continue;
     // an application: a chain of one lean launch + mm - 2 Horner launches (1.18 lean launches each), the closing launch and
     // the vector kernel ≈ 3.6
-    const double cost = h * (1.0 + 1.18 * (mm - 2) + 3.6);
+    double cost = h * (1.0 + 1.18 * (mm - 2) + 3.6);
+    if (mixed_g > 0.0) {
+      const int jt = pghost::mixed_chain_tail(std::pow(std::sqrt(tol2 / rr0), 1.0 / h), mixed_g, mm);
+      if (jt >= 0) cost -= (1.0 - F32_LAUNCH_WEIGHT) * 1.18 * (mm - jt - 2);   // the middle launches: mm - 1 - jt fp32 stores less the first
+    }
     if (cost < best) { best = cost; w.adapt_m = mm; w.adapt_h = h; }
   }
   if (best < 1e300) w.adapt_matrix = &A;
@@ -759,6 +777,36 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     w.ya.alloc(nvec); w.wa.alloc(nvec); w.wb.alloc(nvec); w.yb.alloc(nvec);
     w.ya.zero(); w.wa.zero(); w.wb.zero(); w.yb.zero();
   }
+  // Mixed-precision chain.  The chain is only a preconditioner (x and r move by the same computed vectors), so
+  // its early intermediates need not be stored with 53 bits: the first application of a solve stores the results of its first
+  // n32 launches as fp32 (scaled by the power of two σ: the chain is linear) and hands over to the j fp64 launches of the tail,
+  // which damp that rounding below what the solve needs (pghost::mixed_chain_schedule / mixed_chain_tail).  It runs where the
+  // loop system references no ghost column on ONE rank (the root order has to be the same wherever a halo couples the ranks,
+  // and the halo exchange is fp64), with σ and the needed reduction left by the previous solve on this matrix -- scalars every
+  // rank holds identically; a solve without them (the first on a matrix) runs all fp64, and so does every application after
+  // the first of a solve: the continuation of a solve that missed its half-step test is exact, and the next 2 (m + 3) solves
+  // -- the horizon of the degree's backoff -- run a tail two launches longer.
+  pghost::MixedChain mc;
+  bool mixed = false;
+  double mix_sigma = 1.0;
+  double mtau[MAX_POLY_DEGREE];     // 1 / root, in the mixed chain's order of application
+  if (poly && cfg.poly_f32 && cx.nranks == 1 && !cx.comm && !A.halo_needed && spmv_supports_typed_chain() && w.mix_matrix == &A &&
+      w.mix_sigma > 0.0) {
+    const double g = std::min(std::max(by_estimate ? A.est.g_used : A.gersh, 0.05), 0.95);
+    int j = cfg.poly_f32_tail >= 0 ? cfg.poly_f32_tail : pghost::mixed_chain_tail(w.mix_need, g, m);
+    if (j >= 0 && w.mix_wait > 0 && cfg.poly_f32_tail < 0) j += 2;   // (a forced tail stays what was asked for)
+    if (w.mix_wait > 0) --w.mix_wait;
+    if (j >= 0 && pghost::mixed_chain_schedule(m, g, j, mc)) {
+      mixed = true;
+      mix_sigma = w.mix_sigma;
+      for (int i = 0; i < m; ++i) mtau[i] = 1.0 / pghost::mixed_root(m, g, mc.order[i]);
+      if (w.fa.n < nvec) {
+        w.fa.alloc(nvec); w.fb.alloc(nvec); w.p32.alloc(nvec);
+        w.fa.zero(); w.fb.zero(); w.p32.zero();
+      }
+    }
+  }
+  bool mixed_ran = false;
   // convergence is also tested after the first half of an iteration when a half costs several products (the test itself
   // costs two small launches)
   const bool half_test = m >= 3 || mg;
@@ -808,6 +856,53 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
       // hat = q(Â) in:  u_(m-1) = τ_(m-1) in,  u_k = τ_k in + (I - τ_k Â) u_(k+1),  hat = u_0   (mode 8: pc2 base + pc0 x + pc1 Â x;
       // the first launch has x = base = in)
       double* hat = second ? w.yb.p : w.ya.p;
+      if (mixed && itn == 0 && !second) {
+        // the mixed chain: launch i applies the root mtau[i + 1] (the first launch carries mtau[0] as its leading coefficient);
+        // fp32 vectors hold σ u -- σ and 1/σ ride in the coefficients of the first and the hand-over launch, exactly
+        const int n32 = mc.n32, nf32 = n32 + 1, nf64 = m - 1 - nf32;
+        const void* src32 = nullptr;
+        timer.begin(st, itn, true, second, nf32, true);
+        for (int i = 0; i <= n32; ++i) {
+          const double tk = mtau[i + 1];
+          FinArgs f{nullptr, nullptr, PH_NONE, 0, 0, nullptr};
+          if (i == 0) {
+            float* dst = w.fa.p;
+            f.pc0 = mix_sigma * mtau[0]; f.pc1 = -mix_sigma * (mtau[0] * tk); f.pc2 = mix_sigma * tk;
+            f.base = in; f.p32 = w.p32.p; f.psig = mix_sigma;
+            launch_spmv_typed(TYPED_FIRST, A, in, dst, w.sc.p, G, st, f);
+            src32 = dst;
+          } else if (i < n32) {
+            float* dst = (i & 1) ? w.fb.p : w.fa.p;
+            f.pc0 = 1.0; f.pc1 = -tk; f.pc2 = tk;
+            f.base = reinterpret_cast<const double*>(w.p32.p);
+            launch_spmv_typed(TYPED_MIDDLE, A, src32, dst, w.sc.p, G, st, f);
+            src32 = dst;
+          } else {
+            double* dst = i == m - 2 ? hat : ((i & 1) ? w.wb.p : w.wa.p);
+            const double inv = 1.0 / mix_sigma;
+            f.pc0 = inv; f.pc1 = -inv * tk; f.pc2 = tk;
+            f.base = in;
+            launch_spmv_typed(TYPED_HANDOVER, A, src32, dst, w.sc.p, G, st, f);
+            src = dst;
+          }
+        }
+        timer.end(st);
+        if (nf64 > 0) {
+          timer.begin(st, itn, true, second, nf64);
+          for (int i = n32 + 1; i <= m - 2; ++i) {
+            double* dst = i == m - 2 ? hat : ((i & 1) ? w.wb.p : w.wa.p);
+            FinArgs f{nullptr, nullptr, PH_NONE, 0, 0, nullptr};
+            f.pc0 = 1.0; f.pc1 = -mtau[i + 1]; f.pc2 = mtau[i + 1]; f.base = in;
+            launch_spmv(8, A, src, dst, nullptr, nullptr, w.sc.p, G, st, &f);
+            src = dst;
+          }
+          timer.end(st);
+        }
+        mixed_ran = true;
+        stats.f32_launches += nf32;
+        stats.f32_chains += 1;
+        stats.f32_tail_sum += mc.j;
+      } else {
       timer.begin(st, itn, true, second, m - 1);
       for (int k = m - 2; k >= 0; --k) {
         double* dst = k == 0 ? hat : ((k & 1) ? w.wb.p : w.wa.p);
@@ -818,6 +913,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
         src = dst;
       }
       timer.end(st);
+      }
     } else if (mg) {
       double* hat = second ? w.yb.p : w.ya.p;
       timer.begin(st, itn, true, second, 1);              // (profiling: a V-cycle is bracketed as a whole and counted as ONE lean launch)
@@ -949,7 +1045,26 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     const double rr0 = w.h_sc[S_RR0], rr = w.h_sc[S_HALF] != 0.0 ? w.h_sc[S_RED4] : w.h_sc[S_RR];
     if (rr0 > 0.0 && rr > 0.0 && rr < rr0) w.last_rate2 = std::log(rr0 / rr) / (double)stats.products;
   }
-  choose_next_degree(A, stats, m, adaptive, w);
+  // what the next solve's mixed chain goes by (scalars of this solve: identical on every rank, the same from run to run)
+  const bool mix_env = poly && cfg.poly_f32 && cx.nranks == 1 && !cx.comm && !A.halo_needed && spmv_supports_typed_chain();
+  choose_next_degree(A, stats, m, adaptive, w,
+                     mix_env && cfg.poly_f32_tail < 0 ? std::min(std::max(by_estimate ? A.est.g_used : A.gersh, 0.05), 0.95) : 0.0);
+  if (stats.iters == 0) stats.f32_launches = stats.f32_chains = stats.f32_tail_sum = 0;   // (the chain returned at the done flag)
+  if (mixed_ran && expect_halves == 1 && !(stats.iters == 1 && stats.half_exit)) w.mix_wait = 2 * (m + 3);
+  w.mix_matrix = nullptr;
+  if (mix_env && stats.converged) {
+    const double rr0 = w.h_sc[S_RR0], tol2 = w.h_sc[S_TOL2];
+    if (rr0 > 0.0 && rr0 < 1e300 && tol2 > 0.0) {
+      int e = 0;
+      (void)std::frexp(std::sqrt(rr0 / (double)n), &e);   // σ: the power of two that brings the start residual's rms near 1
+      const int h = (adaptive && w.adapt_matrix == &A && w.adapt_h >= 1) ? w.adapt_h : std::max(1, 2 * stats.iters - stats.half_exit);
+      if (e > -100 && e < 100) {
+        w.mix_matrix = &A;
+        w.mix_sigma = std::ldexp(1.0, -e);
+        w.mix_need = std::pow(std::sqrt(std::min(1.0, tol2 / rr0)), 1.0 / h);
+      }
+    }
+  }
 }
 
 }  // namespace pg

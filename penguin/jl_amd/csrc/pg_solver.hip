@@ -2084,6 +2084,8 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
     tot.poly_xspace = st.poly_xspace;
     tot.half_exit += st.half_exit;
     tot.products += st.products;
+    tot.f32_launches += st.f32_launches; tot.f32_ms += st.f32_ms; tot.f32_timed += st.f32_timed;
+    tot.f32_chains += st.f32_chains; tot.f32_tail_sum += st.f32_tail_sum;
     if (!st.converged) ++unconverged;
     if (st.bnorm > 0.0) worst = std::max(worst, st.resnorm / st.bnorm);
   };
@@ -2129,6 +2131,11 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
     info->poly_xspace = tot.poly_xspace;
     info->half_exits = tot.half_exit;
     info->products = tot.products;
+    info->poly_f32_launches = tot.f32_launches;
+    info->poly_f32_ms_total = tot.f32_ms;
+    info->poly_f32_timed = tot.f32_timed;
+    info->poly_f32_chains = tot.f32_chains;
+    info->poly_f32_tail_sum = tot.f32_tail_sum;
     info->guess_states_read = 0;
     if (s->guess_coef.n >= 16) {
       double hc[16];
@@ -2621,6 +2628,68 @@ int32_t pg_debug_spmv_apply(pg_solver* s, int32_t which, int32_t variant, int32_
   unsigned ht = 0;
   dticket.download(&ht, 1);
   *ticket = (int64_t)ht;
+  PG_API_END
+}
+
+int32_t pg_debug_spmv_apply_typed(pg_solver* s, int32_t which, int32_t kind, const void* x, const void* base, double pc0, double pc1,
+                                  double pc2, double sigma, int32_t done, double* y64, float* y32, float* p32) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && x, "pg_debug_spmv_apply_typed: NULL argument");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, "pg_debug_spmv_apply_typed: one rank");
+  PG_REQUIRE(kind == TYPED_FIRST || kind == TYPED_MIDDLE || kind == TYPED_HANDOVER, "pg_debug_spmv_apply_typed: kinds 1 (first), 2 (middle), 3 (hand-over)");
+  PG_REQUIRE((kind == TYPED_FIRST) == (base == nullptr), "pg_debug_spmv_apply_typed: the first launch's base is its x; the others take one");
+  PG_REQUIRE((kind == TYPED_FIRST) == (p32 != nullptr), "pg_debug_spmv_apply_typed: p32 is the first launch's output, and only its");
+  PG_REQUIRE(kind == TYPED_HANDOVER ? (y64 && !y32) : (y32 && !y64), "pg_debug_spmv_apply_typed: y32 for kinds 1 and 2, y64 for kind 3");
+  PG_REQUIRE(spmv_supports_typed_chain(), "pg_debug_spmv_apply_typed: the typed launches exist in the slice kernel with the stream hint only");
+  i64 nv = 0;
+  const CsrMatrix& A = debug_matrix(s, which, &nv);
+  const i64 n = A.n;
+  PG_REQUIRE(n > 0 && A.srec.p, "pg_debug_spmv_apply_typed: the matrix has no rows or no slice image");
+  nv = std::max(nv, n);
+  hipStream_t st = ctx().stream;
+  const int grid = spmv_default_grid(n);
+  constexpr i64 GUARD = 64;
+  double sentinel;
+  const unsigned long long sbits = PG_DEBUG_SPMV_SENTINEL;
+  std::memcpy(&sentinel, &sbits, sizeof(double));
+  float sentinel32;
+  const unsigned sbits32 = PG_DEBUG_SPMV_SENTINEL_F32;
+  std::memcpy(&sentinel32, &sbits32, sizeof(float));
+  // operands as long as the driver's vectors (n_vec), zeros behind row n of base; outputs with 64 guard words behind row n
+  DevBuf<double> dx64(nv), db64(nv), dy64(n + GUARD), dsc(S_COUNT);
+  DevBuf<float> dx32(nv), db32(nv), dy32(n + GUARD), dp32(n + GUARD);
+  db64.zero(); db32.zero();
+  if (kind == TYPED_FIRST) dx64.upload(static_cast<const double*>(x), nv);
+  else dx32.upload(static_cast<const float*>(x), nv);
+  if (kind == TYPED_MIDDLE) db32.upload(static_cast<const float*>(base), n);
+  if (kind == TYPED_HANDOVER) db64.upload(static_cast<const double*>(base), n);
+  {
+    std::vector<double> f64((size_t)(n + GUARD), sentinel);
+    std::vector<float> f32((size_t)(n + GUARD), sentinel32);
+    dy64.upload(f64.data(), n + GUARD);
+    dy32.upload(f32.data(), n + GUARD);
+    dp32.upload(f32.data(), n + GUARD);
+    std::vector<double> hsc(S_COUNT, 0.0);
+    hsc[S_DONE] = (double)done;
+    dsc.upload(hsc.data(), S_COUNT);
+  }
+  FinArgs f{nullptr, nullptr, PH_NONE, 0, 0, nullptr};
+  f.pc0 = pc0; f.pc1 = pc1; f.pc2 = pc2;
+  if (kind == TYPED_FIRST) {
+    f.base = dx64.p; f.p32 = dp32.p; f.psig = sigma;
+    launch_spmv_typed(kind, A, dx64.p, dy32.p, dsc.p, grid, st, f);
+  } else if (kind == TYPED_MIDDLE) {
+    f.base = reinterpret_cast<const double*>(db32.p);
+    launch_spmv_typed(kind, A, dx32.p, dy32.p, dsc.p, grid, st, f);
+  } else {
+    f.base = db64.p;
+    launch_spmv_typed(kind, A, dx32.p, dy64.p, dsc.p, grid, st, f);
+  }
+  PG_HIP(hipGetLastError());
+  if (y64) dy64.download(y64, n + GUARD);
+  if (y32) dy32.download(y32, n + GUARD);
+  if (p32) dp32.download(p32, n + GUARD);
   PG_API_END
 }
 

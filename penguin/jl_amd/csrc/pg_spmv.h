@@ -191,6 +191,9 @@ struct FinArgs {
   double pc0 = 0.0, pc1 = 0.0;    // mode 8: y = pc2 base + (pc0 x + pc1 A x)
   const double* base = nullptr;
   double pc2 = 0.0;
+  // typed launches of the mixed chain only (launch_spmv_typed): launch (a) also writes p32 = (float)(psig base) for the rows it computes
+  float* p32 = nullptr;
+  double psig = 0.0;
 };
 
 // executed by every block at the end of a producing launch (after its partials are stored); nparts = partial sums per
@@ -221,6 +224,17 @@ bool launch_spmv(int mode, const CsrMatrix& A, const double* x, double* y, const
 // launch_spmv itself calls, and the diagnostics that check one launch against the host (pg_debug_spmv_apply)
 bool launch_spmv_as(int variant, int mode, const CsrMatrix& A, const double* x, double* y, const double* aux, double* partials,
                     const double* sc, int grid, hipStream_t st, const FinArgs* fin = nullptr);
+// Horner step (mode 8) with an element type per vector stream: the launches of the mixed-precision chain (pg_krylov.hip).
+// Conversion at the load and at the store (round to nearest); every product and sum is the fp64 kernel's, in the same entry
+// order, so y is float(y64) (or y64 itself) of what launch mode 8 gives on the converted inputs.
+//   TYPED_FIRST  x = base = fin->base: double, y: float; also fin->p32[row] = (float)(fin->psig base[row])
+//   TYPED_MIDDLE x, base, y: float   (fin->base points at floats)
+//   TYPED_HANDOVER x: float, base: double, y: double
+// One rank / no halo exchange; slice kernel with the stream hint (spmv_supports_typed_chain).
+enum { TYPED_FIRST = 1, TYPED_MIDDLE = 2, TYPED_HANDOVER = 3 };
+void launch_spmv_typed(int kind, const CsrMatrix& A, const void* x, void* y, const double* sc, int grid, hipStream_t st,
+                       const FinArgs& fin);
+bool spmv_supports_typed_chain();
 // y = A x on a slab whose x needs a halo exchange first (C1 of SURVEY.md 2.3): the exchange of x's ghost segments runs on
 // the communication stream while the slices that reference no ghost column are multiplied; the slices that do (rows of
 // the first / last owned plane) follow in a second, small launch once the halo has landed, adding their partial sums

@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "pg_host_algos.h"
@@ -277,6 +278,76 @@ __device__ inline d2_t load_pair(const double* p) {
   return r;
 }
 
+// ---- element type per vector stream (mode 8 of the mixed-precision chain, launch_spmv_typed) ---------------------------
+// VecTypes names the element types of x (TX), of the operand B = base (TB) and of y (TY) in memory; P32: the launch also
+// writes p32 = (float)(psig B) for the rows it computes -- the chain's first launch, whose B IS x (same vector): the row's
+// own x serves as B and no B stream is loaded at all.  A float stream is converted at the load and at the store (round to
+// nearest); the arithmetic in between is the fp64 kernel's.  The all-double instantiation is the kernel as it was: its helpers
+// below are the very loads and stores it used.
+template <class TX_, class TB_, class TY_, bool P32_>
+struct VecTypes {
+  using TX = TX_;
+  using TB = TB_;
+  using TY = TY_;
+  static constexpr bool P32 = P32_;
+};
+using VecF64 = VecTypes<double, double, double, false>;
+
+typedef float f2u_t __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte access, 4-byte aligned
+
+template <bool NT>
+__device__ inline d2_t load_pair_t(const double* p) { return load_pair<NT>(p); }
+template <bool NT>
+__device__ inline d2_t load_pair_t(const float* p) {
+  const f2u_t* q = reinterpret_cast<const f2u_t*>(p);
+  f2u_t v = NT ? __builtin_nontemporal_load(q) : *q;
+  d2_t r;
+  r.x = (double)v.x; r.y = (double)v.y;
+  return r;
+}
+// a pair as it sits in registers between its load and its use: fp32 streams stay two dwords until the arithmetic widens them
+typedef float f2_t __attribute__((ext_vector_type(2)));
+template <class T> struct PairOf { typedef d2_t type; };
+template <> struct PairOf<float> { typedef f2_t type; };
+template <bool NT>
+__device__ inline d2_t load_raw(const double* p) { return load_pair<NT>(p); }
+template <bool NT>
+__device__ inline f2_t load_raw(const float* p) {
+  const f2u_t* q = reinterpret_cast<const f2u_t*>(p);
+  f2u_t v = NT ? __builtin_nontemporal_load(q) : *q;
+  f2_t r;
+  r.x = v.x; r.y = v.y;
+  return r;
+}
+__device__ inline d2_t widen(const d2_t& v) { return v; }
+__device__ inline d2_t widen(const f2_t& v) {
+  d2_t r;
+  r.x = (double)v.x; r.y = (double)v.y;
+  return r;
+}
+// a pair of rows of y (or of p32): stream hint unless `plain`
+__device__ inline void store_pair_t(double* p, double a, double b, bool plain) {
+  d2u_t out;
+  out.x = a; out.y = b;
+  if (!plain) __builtin_nontemporal_store(out, reinterpret_cast<d2u_t*>(p));
+  else *reinterpret_cast<d2u_t*>(p) = out;
+}
+// (an fp32 store saturates at the largest finite float: a start residual that outgrew the scale σ taken from the previous solve
+//  then costs this application its accuracy, not the solve its finiteness -- x and r still move by the same computed vectors,
+//  and every later application of the solve is fp64)
+__device__ inline float narrow(double a) {
+  const float f = (float)a;
+  return __builtin_fminf(__builtin_fmaxf(f, -3.402823466e+38f), 3.402823466e+38f);
+}
+__device__ inline void store_pair_t(float* p, double a, double b, bool plain) {
+  f2u_t out;
+  out.x = narrow(a); out.y = narrow(b);
+  if (!plain) __builtin_nontemporal_store(out, reinterpret_cast<f2u_t*>(p));
+  else *reinterpret_cast<f2u_t*>(p) = out;
+}
+__device__ inline void store_one_t(double* p, double a) { *p = a; }
+__device__ inline void store_one_t(float* p, double a) { *p = narrow(a); }
+
 // Launch modes of the slice kernel (MODE): what the epilogue does with s = (A x)_row.  A, B = operand vectors read at the
 // row (pa, pb below); own = x_row.
 //   0  y = s
@@ -307,18 +378,18 @@ __device__ __forceinline__ double mode_out(double s, double own, double b, doubl
 
 // rows of one U (PSL = false) or P (PSL = true) slice with CNT stencil slots; rec = the slice's record (lane & 31).
 // NB batches of 128 rows: every load of the slice is issued before the first FMA (one exposed latency per slice).
-template <int CNT, int NB, bool PSL, int MODE, bool NT>
+template <int CNT, int NB, bool PSL, int MODE, bool NT, class VT>
 __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, const double* __restrict__ pval,
-                                  const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ pa,
-                                  const double* __restrict__ pb, int lane, double& acc0, double& acc1, double& acc2, int dbg,
-                                  double pc0, double pc1, double pc2) {
+                                  const typename VT::TX* __restrict__ x, typename VT::TY* __restrict__ y, const double* __restrict__ pa,
+                                  const typename VT::TB* __restrict__ pb, int lane, double& acc0, double& acc1, double& acc2, int dbg,
+                                  double pc0, double pc1, double pc2, float* __restrict__ p32, double psig) {
   using MI = ModeInfo<MODE>;
   int o[CNT];
 #pragma unroll
   for (int j = 0; j < CNT; ++j) o[j] = (dbg & 4) ? 0 : rlane(rec, 4 + j);
   int l0[NB];
   bool live0[NB], live1[NB];
-  d2_t xv[NB][CNT];
+  typename PairOf<typename VT::TX>::type xv[NB][CNT];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     const int l = 128 * b + 2 * lane;
@@ -326,7 +397,7 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
     live1[b] = l + 1 < nrows;
     l0[b] = live0[b] ? l : 0;
 #pragma unroll
-    for (int j = 0; j < CNT; ++j) xv[b][j] = load_pair<false>(x + d.r0 + l0[b] + o[j]);
+    for (int j = 0; j < CNT; ++j) xv[b][j] = load_raw<false>(x + d.r0 + l0[b] + o[j]);
   }
   d2_t sum[NB];
 #pragma unroll
@@ -337,8 +408,9 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
       const double c = __hiloint2double(rlane(rec, 13 + 2 * j), rlane(rec, 12 + 2 * j));
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
-        sum[b].x += c * xv[b][j].x;
-        sum[b].y += c * xv[b][j].y;
+        const d2_t xw = widen(xv[b][j]);
+        sum[b].x += c * xw.x;
+        sum[b].y += c * xw.y;
       }
     }
   } else {
@@ -350,8 +422,9 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
       for (int j = 0; j < CNT; ++j) vv[j] = load_pair<NT>(pv + j * nrows);
 #pragma unroll
       for (int j = 0; j < CNT; ++j) {
-        sum[b].x += vv[j].x * xv[b][j].x;
-        sum[b].y += vv[j].y * xv[b][j].y;
+        const d2_t xw = widen(xv[b][j]);
+        sum[b].x += vv[j].x * xw.x;
+        sum[b].y += vv[j].y * xw.y;
       }
     }
   }
@@ -359,28 +432,29 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     own[b].x = own[b].y = ax[b].x = ax[b].y = ax2[b].x = ax2[b].y = 0.0;
-    if (MI::OWN) own[b] = load_pair<false>(x + d.r0 + l0[b]);
+    if (MI::OWN) own[b] = load_pair_t<false>(x + d.r0 + l0[b]);
     if (MI::HAS_A) ax[b] = load_pair<false>(pa + d.r0 + l0[b]);
-    if (MI::HAS_B) ax2[b] = load_pair<false>(pb + d.r0 + l0[b]);
+    if (MI::HAS_B && !VT::P32) ax2[b] = load_pair_t<false>(pb + d.r0 + l0[b]);
+    if (VT::P32) ax2[b] = own[b];
   }
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     sum[b].x = mode_out<MODE>(sum[b].x, own[b].x, ax2[b].x, pc0, pc1, pc2);
     sum[b].y = mode_out<MODE>(sum[b].y, own[b].y, ax2[b].y, pc0, pc1, pc2);
     const bool st = !(dbg & 8) || sum[b].x == 1.2345e-300;
-    double* yp = y + d.r0 + l0[b];
+    typename VT::TY* yp = y + d.r0 + l0[b];
+    if (VT::P32) {   // p32 = (float)(psig base) for the rows computed here
+      float* pp = p32 + d.r0 + l0[b];
+      if (live1[b]) store_pair_t(pp, psig * ax2[b].x, psig * ax2[b].y, false);
+      else if (live0[b]) store_one_t(pp, psig * ax2[b].x);
+    }
     if (live1[b]) {
-      if (st) {
-        d2u_t out;
-        out.x = sum[b].x; out.y = sum[b].y;
-        if (!(dbg & 2048)) __builtin_nontemporal_store(out, reinterpret_cast<d2u_t*>(yp));
-        else *reinterpret_cast<d2u_t*>(yp) = out;
-      }
+      if (st) store_pair_t(yp, sum[b].x, sum[b].y, (dbg & 2048) != 0);
       if (MI::DOT0) acc0 += ax[b].x * sum[b].x + ax[b].y * sum[b].y;
       if (MI::DOT1) acc1 += sum[b].x * sum[b].x + sum[b].y * sum[b].y;
       if (MI::DOT2) acc2 += ax2[b].x * sum[b].x + ax2[b].y * sum[b].y;
     } else if (live0[b]) {
-      if (st) *yp = sum[b].x;
+      if (st) store_one_t(yp, sum[b].x);
       if (MI::DOT0) acc0 += ax[b].x * sum[b].x;
       if (MI::DOT1) acc1 += sum[b].x * sum[b].x;
       if (MI::DOT2) acc2 += ax2[b].x * sum[b].x;
@@ -388,29 +462,30 @@ __device__ __forceinline__ void slice_rows(const SDesc& d, int nrows, int rec, c
   }
 }
 
-template <int CNT, bool PSL, int MODE, bool NT>
+template <int CNT, bool PSL, int MODE, bool NT, class VT>
 __device__ __forceinline__ void slice_nb(const SDesc& d, int nrows, int rec, const double* __restrict__ pval,
-                                const double* __restrict__ x, double* __restrict__ y, const double* __restrict__ pa,
-                                const double* __restrict__ pb, int lane, double& acc0, double& acc1, double& acc2, int dbg,
-                                double pc0, double pc1, double pc2) {
-  if (!PSL && nrows > 128) slice_rows<CNT, 2, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2);
-  else slice_rows<CNT, 1, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2);
+                                const typename VT::TX* __restrict__ x, typename VT::TY* __restrict__ y, const double* __restrict__ pa,
+                                const typename VT::TB* __restrict__ pb, int lane, double& acc0, double& acc1, double& acc2, int dbg,
+                                double pc0, double pc1, double pc2, float* __restrict__ p32, double psig) {
+  if (!PSL && nrows > 128) slice_rows<CNT, 2, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig);
+  else slice_rows<CNT, 1, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig);
 }
 
-template <bool PSL, int MODE, bool NT>
+template <bool PSL, int MODE, bool NT, class VT>
 __device__ __forceinline__ void slice_dispatch(int cnt, const SDesc& d, int nrows, int rec, const double* __restrict__ pval,
-                                      const double* __restrict__ x, double* __restrict__ y,
-                                      const double* __restrict__ pa, const double* __restrict__ pb, int lane, double& acc0,
-                                      double& acc1, double& acc2, int dbg, double pc0, double pc1, double pc2) {
+                                      const typename VT::TX* __restrict__ x, typename VT::TY* __restrict__ y,
+                                      const double* __restrict__ pa, const typename VT::TB* __restrict__ pb, int lane, double& acc0,
+                                      double& acc1, double& acc2, int dbg, double pc0, double pc1, double pc2,
+                                      float* __restrict__ p32, double psig) {
   switch (cnt) {   // wave-uniform
-    case 1: slice_nb<1, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 3: slice_nb<3, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 5: slice_nb<5, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 7: slice_nb<7, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 2: slice_nb<2, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 4: slice_nb<4, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    case 6: slice_nb<6, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
-    default: slice_nb<8, PSL, MODE, NT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2); break;
+    case 1: slice_nb<1, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 3: slice_nb<3, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 5: slice_nb<5, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 7: slice_nb<7, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 2: slice_nb<2, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 4: slice_nb<4, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    case 6: slice_nb<6, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
+    default: slice_nb<8, PSL, MODE, NT, VT>(d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, pc0, pc1, pc2, p32, psig); break;
   }
 }
 
@@ -467,18 +542,28 @@ __device__ inline double lane_up(double v) {   // the value lane l + 1 holds (la
   return __shfl_down(v, 1, 64);
 }
 
+template <class TX, class TB>
 struct MarchSide {   // per-plane operands besides the chain's own lines: lateral neighbour lines, dot operands
-  d2_t ym, yp, ax, ax2;
+  typename PairOf<TX>::type ym, yp;
+  d2_t ax;
+  typename PairOf<TB>::type ax2;
 };
 
 // rows 2l+1, 2l+2 of one plane from the lines in registers; returns lane l+1's xc.x (the next plane's xm_n)
-template <int CNT, int MODE, bool EDGE>
-__device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, int l2, double* __restrict__ yrow, const d2_t& xm,
-                                              double xm_n, const d2_t& xc, const d2_t& xp, const MarchSide& sd, double pc0,
+template <int CNT, int MODE, bool EDGE, class VT>
+__device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, int l2, typename VT::TY* __restrict__ yrow,
+                                              const typename PairOf<typename VT::TX>::type& xm_, double xm_n,
+                                              const typename PairOf<typename VT::TX>::type& xc_,
+                                              const typename PairOf<typename VT::TX>::type& xp_,
+                                              const MarchSide<typename VT::TX, typename VT::TB>& sd_, double pc0,
                                               double pc1, double pc2, double& acc0, double& acc1, double& acc2, int dbg,
-                                              int einfo, int e_first, const d2_t* el, const d2_t* cl) {
+                                              int einfo, int e_first, const d2_t* el, const d2_t* cl, float* __restrict__ prow,
+                                              double psig) {
   using MI = ModeInfo<MODE>;
   constexpr bool Y = CNT == 7;
+  const d2_t xm = widen(xm_), xc = widen(xc_), xp = widen(xp_);
+  struct { d2_t ym, yp, ax, ax2; } sd;
+  sd.ym = widen(sd_.ym); sd.yp = widen(sd_.yp); sd.ax = sd_.ax; sd.ax2 = widen(sd_.ax2);
   const double xc_nx = lane_up(xc.x), xc_ny = lane_up(xc.y), xp_n = lane_up(xp.x);
   // entry order of the assembled rows (eval_row, pg_stencil.h): +1, -1, [+lateral, -lateral,] +plane, -plane, diagonal
   double a1[CNT], a2[CNT];   // the x operands of rows 2l+1, 2l+2 by slot
@@ -521,23 +606,26 @@ __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, i
     for (int j = 0; j < CNT; ++j) { s1 += c[j] * a1[j]; s2 += c[j] * a2[j]; }
   }
   // (the row's own x: elements 2l+1, 2l+2 of the centre line)
-  s1 = mode_out<MODE>(s1, xc.y, sd.ax2.x, pc0, pc1, pc2);
-  s2 = mode_out<MODE>(s2, xc_nx, sd.ax2.y, pc0, pc1, pc2);
+  const double b1 = VT::P32 ? xc.y : sd.ax2.x, b2 = VT::P32 ? xc_nx : sd.ax2.y;   // (P32: B is x)
+  s1 = mode_out<MODE>(s1, xc.y, b1, pc0, pc1, pc2);
+  s2 = mode_out<MODE>(s2, xc_nx, b2, pc0, pc1, pc2);
   const bool nost = (dbg & 32) && s1 != 1.2345e-300;   // diagnostics: no stores
   const bool allst = (dbg & 512) != 0;                  // diagnostics: every lane stores its pair (whole windows)
   const bool v1 = ((l2 + 1 >= lo && l2 + 1 < hi) || allst) && !nost, v2 = ((l2 + 2 >= lo && l2 + 2 < hi) || allst) && !nost;
+  if (VT::P32) {   // p32 = (float)(psig base) for the rows computed here
+    if (v1 && v2) store_pair_t(prow, psig * b1, psig * b2, false);
+    else if (v1) store_one_t(prow, psig * b1);
+    else if (v2) store_one_t(prow + 1, psig * b2);
+  }
   if (v1 && v2) {
-    d2u_t out;
-    out.x = s1; out.y = s2;
     // y leaves with the stream hint: fewer dirty lines for the end-of-kernel write-back, which sits between every two
     // dependent launches of the loop (55.3 -> 52.6 µs per back-to-back launch at 512^3 on one box, within the noise on another; system-scope write-through
     // stores, `sc0 sc1`, double the launch; dbg bit 2048: plain stores)
-    if (!(dbg & 2048)) __builtin_nontemporal_store(out, reinterpret_cast<d2u_t*>(yrow));
-    else *reinterpret_cast<d2u_t*>(yrow) = out;
+    store_pair_t(yrow, s1, s2, (dbg & 2048) != 0);
   } else if (v1) {
-    yrow[0] = s1;
+    store_one_t(yrow, s1);
   } else if (v2) {
-    yrow[1] = s2;
+    store_one_t(yrow + 1, s2);
   }
   if (MI::DOT0) {
     const double w1 = v1 ? s1 : 0.0, w2 = v2 ? s2 : 0.0;
@@ -557,11 +645,11 @@ __device__ __forceinline__ double march_plane(const double (&c)[CNT], int rng, i
 // see march_dispatch)
 // EDGE: the unit has edge rows.  The two forms are two straight-line bodies: a branch per plane inside one body pins every
 // load of the unit above the first branch and costs ~25 spilled VGPRs (the compiler's report).
-template <int CNT, int MODE, bool EDGE, int KK, int Q0 = 0, int KTOT = KK>
-__device__ __forceinline__ void march_unit(int rec, int lane, const double* __restrict__ x, double* __restrict__ y,
-                                  const double* __restrict__ pa, const double* __restrict__ pb, double pc0, double pc1,
+template <int CNT, int MODE, bool EDGE, class VT, int KK, int Q0 = 0, int KTOT = KK>
+__device__ __forceinline__ void march_unit(int rec, int lane, const typename VT::TX* __restrict__ x, typename VT::TY* __restrict__ y,
+                                  const double* __restrict__ pa, const typename VT::TB* __restrict__ pb, double pc0, double pc1,
                                   double pc2, double& acc0, double& acc1, double& acc2, int dbg,
-                                  const double* __restrict__ e_val, double* sv, double* sx) {
+                                  const double* __restrict__ e_val, double* sv, double* sx, float* __restrict__ p32, double psig) {
   using MI = ModeInfo<MODE>;
   constexpr bool Y = CNT == 7;
   const int amask = (dbg & 128) ? ~1 : ~0;          // diagnostics: every access 16-byte aligned (wrong results)
@@ -572,33 +660,41 @@ __device__ __forceinline__ void march_unit(int rec, int lane, const double* __re
   for (int j = 0; j < CNT; ++j) c[j] = __hiloint2double(rlane(rec, 3 + 2 * j), rlane(rec, 2 + 2 * j));
   const int l2 = 2 * lane;
   int rb[KK];
-  d2_t ln[KK + 2];          // lines -1 .. KK of the chain
-  MarchSide sd[KK];
+  typedef typename PairOf<typename VT::TX>::type xpair_t;
+  typedef typename PairOf<typename VT::TB>::type bpair_t;
+  xpair_t ln[KK + 2];       // lines -1 .. KK of the chain
+  MarchSide<typename VT::TX, typename VT::TB> sd[KK];
   // lanes beyond the widest plane of the unit load nothing (a window at the end of a chord is mostly empty: what a load
   // costs the CU's memory pipe goes with its active lanes); they run the arithmetic on zeros and store nothing
   const bool act = lane < (rlane(rec, 0) >> 16);
   d2_t zero;
   zero.x = zero.y = 0.0;
+  xpair_t xzero;
+  xzero.x = xzero.y = 0;
+  bpair_t bzero;
+  bzero.x = bzero.y = 0;
 #pragma unroll
-  for (int q = 0; q < KK + 2; ++q) ln[q] = zero;
+  for (int q = 0; q < KK + 2; ++q) ln[q] = xzero;
 #pragma unroll
   for (int q = 0; q < KK; ++q) {
     rb[q] = rlane(rec, 18 + 4 * (Q0 + q)) & amask;
-    sd[q].ym = sd[q].yp = sd[q].ax = sd[q].ax2 = zero;
+    sd[q].ym = sd[q].yp = xzero;
+    sd[q].ax = zero;
+    sd[q].ax2 = bzero;
   }
   if (act) {
-    ln[0] = load_pair<false>(x + (rlane(rec, Q0 == 0 ? 16 : 18 + 4 * (Q0 - 1)) & amask) + l2);
+    ln[0] = load_raw<false>(x + (rlane(rec, Q0 == 0 ? 16 : 18 + 4 * (Q0 - 1)) & amask) + l2);
 #pragma unroll
-    for (int q = 0; q < KK; ++q) ln[q + 1] = load_pair<false>(x + rb[q] + l2);
-    ln[KK + 1] = load_pair<false>(x + (rlane(rec, Q0 + KK == KTOT ? 17 : 18 + 4 * (Q0 + KK)) & amask) + l2);
+    for (int q = 0; q < KK; ++q) ln[q + 1] = load_raw<false>(x + rb[q] + l2);
+    ln[KK + 1] = load_raw<false>(x + (rlane(rec, Q0 + KK == KTOT ? 17 : 18 + 4 * (Q0 + KK)) & amask) + l2);
 #pragma unroll
     for (int q = 0; q < KK; ++q) {
       if (Y && !nolat) {
-        sd[q].ym = load_pair<false>(x + rb[q] + (rlane(rec, 19 + 4 * (Q0 + q)) & amask) + l2 + one);
-        sd[q].yp = load_pair<false>(x + rb[q] + (rlane(rec, 20 + 4 * (Q0 + q)) & amask) + l2 + one);
+        sd[q].ym = load_raw<false>(x + rb[q] + (rlane(rec, 19 + 4 * (Q0 + q)) & amask) + l2 + one);
+        sd[q].yp = load_raw<false>(x + rb[q] + (rlane(rec, 20 + 4 * (Q0 + q)) & amask) + l2 + one);
       }
       if (MI::HAS_A) sd[q].ax = load_pair<false>(pa + rb[q] + l2 + one);
-      if (MI::HAS_B) sd[q].ax2 = load_pair<false>(pb + rb[q] + l2 + one);   // (no stream hint: the chain's input is re-read by every launch of the chain and stays in the Infinity Cache -- with the hint a Horner step took 65.7 instead of 53.8 us)
+      if (MI::HAS_B && !VT::P32) sd[q].ax2 = load_raw<false>(pb + rb[q] + l2 + one);   // (no stream hint: the chain's input is re-read by every launch of the chain and stays in the Infinity Cache -- with the hint a Horner step took 65.7 instead of 53.8 us)
     }
   }
   // the values of the edge rows of these planes, a row per lane, issued with the lines: pair p of lane e's row lands at
@@ -629,43 +725,44 @@ __device__ __forceinline__ void march_unit(int rec, int lane, const double* __re
   }
   const d2_t* el = reinterpret_cast<const d2_t*>(sv);
   const d2_t* cl = reinterpret_cast<const d2_t*>(sx);
-  double xm_n = lane_up(ln[0].x);
+  double xm_n = lane_up((double)ln[0].x);
 #pragma unroll
   for (int q = 0; q < KK; ++q)
-    xm_n = march_plane<CNT, MODE, EDGE>(c, rlane(rec, 21 + 4 * (Q0 + q)), l2, y + rb[q] + l2 + one, ln[q], xm_n, ln[q + 1], ln[q + 2], sd[q], pc0,
-                                  pc1, pc2, acc0, acc1, acc2, dbg, rlane(rec, MARCH_EDGE + 2 + Q0 + q), e_first, el, cl);
+    xm_n = march_plane<CNT, MODE, EDGE, VT>(c, rlane(rec, 21 + 4 * (Q0 + q)), l2, y + rb[q] + l2 + one, ln[q], xm_n, ln[q + 1], ln[q + 2], sd[q], pc0,
+                                  pc1, pc2, acc0, acc1, acc2, dbg, rlane(rec, MARCH_EDGE + 2 + Q0 + q), e_first, el, cl,
+                                  VT::P32 ? p32 + rb[q] + l2 + one : nullptr, psig);
 }
 
-template <int CNT, int MODE, bool EDGE>
-__device__ __forceinline__ void march_dispatch(int rec, int lane, const double* __restrict__ x, double* __restrict__ y,
-                                      const double* __restrict__ pa, const double* __restrict__ pb, double pc0, double pc1,
+template <int CNT, int MODE, bool EDGE, class VT>
+__device__ __forceinline__ void march_dispatch(int rec, int lane, const typename VT::TX* __restrict__ x, typename VT::TY* __restrict__ y,
+                                      const double* __restrict__ pa, const typename VT::TB* __restrict__ pb, double pc0, double pc1,
                                       double pc2, double& acc0, double& acc1, double& acc2, int dbg,
-                                      const double* __restrict__ e_val, double* sv, double* sx) {
+                                      const double* __restrict__ e_val, double* sv, double* sx, float* __restrict__ p32, double psig) {
   // The launch with three fused dots and two more operand vectors per plane (mode 3) does not fit a unit of MARCH_K planes into
   // the 128 VGPRs of four waves per SIMD: it takes it in two halves -- two more line loads per unit, which hit L1.  (Mode 1, one
   // operand vector, fits a whole unit: 127 VGPRs, no scratch.)
   constexpr bool SPLIT = MODE == 3 && MARCH_K == 2 * MARCH_KS && PG_MARCH_SPLIT;
   if ((rlane(rec, 0) & 255) == MARCH_K) {
     if (SPLIT) {
-      march_unit<CNT, MODE, EDGE, MARCH_KS, 0, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
-      march_unit<CNT, MODE, EDGE, MARCH_KS, MARCH_KS, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+      march_unit<CNT, MODE, EDGE, VT, MARCH_KS, 0, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
+      march_unit<CNT, MODE, EDGE, VT, MARCH_KS, MARCH_KS, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
     } else {
-      march_unit<CNT, MODE, EDGE, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+      march_unit<CNT, MODE, EDGE, VT, MARCH_K>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
     }
   } else {
-    march_unit<CNT, MODE, EDGE, MARCH_KS>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+    march_unit<CNT, MODE, EDGE, VT, MARCH_KS>(rec, lane, x, y, pa, pb, pc0, pc1, pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
   }
 }
 
 // DIAG: the diagnostic build of the kernel (ablations for profiles/: PG_SPMV_XCD bits 8.. skip parts of the work or force
 // access patterns and give WRONG products).  The shipped instantiation has DIAG = false: `dbg` is the constant 0 there and
 // none of the switches exists in its code.
-template <int MODE, bool NT, bool DIAG>
+template <int MODE, bool NT, bool DIAG, class VT = VecF64>
 __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __restrict__ srec,
                                                   const double* __restrict__ pval, const int* __restrict__ g_rowid,
                                                   const int* __restrict__ g_rowptr, const int* __restrict__ g_col,
-                                                  const double* __restrict__ g_val, const double* __restrict__ x,
-                                                  double* __restrict__ y, const double* __restrict__ aux,
+                                                  const double* __restrict__ g_val, const typename VT::TX* __restrict__ x,
+                                                  typename VT::TY* __restrict__ y, const double* __restrict__ aux,
                                                   double* __restrict__ partials, const double* __restrict__ sc, int xcd,
                                                   FinArgs fin, int pstride, int accum, const int* __restrict__ mrec,
                                                   i64 nunits, const int* __restrict__ tiles, int tpx,
@@ -676,10 +773,14 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
   if (sc && sc[S_DONE] != 0.0) return;
   using MI = ModeInfo<MODE>;
   constexpr bool DOTS = MI::DOT0;
-  const double* __restrict__ dx = fin.dotx ? fin.dotx : x;   // operand of the (y, .) dot of modes 2 / 3
+  static_assert(MODE == 8 || std::is_same<VT, VecF64>::value, "element types per stream exist for mode 8 only");
+  // operand of the (y, .) dot of modes 2 / 3 (their x is double)
+  const double* __restrict__ dx = fin.dotx ? fin.dotx : reinterpret_cast<const double*>(x);
   // operand vectors A and B of the epilogue (ModeInfo)
   const double* __restrict__ pa = MODE == 1 ? aux : ((MODE == 2 || MODE == 3) ? dx : nullptr);
-  const double* __restrict__ pb = MODE == 3 ? aux : (MODE == 8 ? fin.base : nullptr);
+  const typename VT::TB* __restrict__ pb = reinterpret_cast<const typename VT::TB*>(MODE == 3 ? aux : (MODE == 8 ? fin.base : nullptr));
+  float* __restrict__ p32 = VT::P32 ? fin.p32 : nullptr;
+  const double psig = fin.psig;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   double* __restrict__ sv = s_val[wave];
@@ -739,11 +840,11 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
       if (!(dbg & 16)) {
         const bool edge = rlane(urec, MARCH_EDGE + 1) > 0;
         if (((rlane(urec, 0) >> 8) & 255) == 7) {
-          if (edge) march_dispatch<7, MODE, true>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
-          else march_dispatch<7, MODE, false>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+          if (edge) march_dispatch<7, MODE, true, VT>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
+          else march_dispatch<7, MODE, false, VT>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
         } else {
-          if (edge) march_dispatch<5, MODE, true>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
-          else march_dispatch<5, MODE, false>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx);
+          if (edge) march_dispatch<5, MODE, true, VT>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
+          else march_dispatch<5, MODE, false, VT>(urec, lane, x, y, pa, pb, fin.pc0, fin.pc1, fin.pc2, acc0, acc1, acc2, dbg, e_val, sv, sx, p32, psig);
         }
       }
       urec = urec_n;
@@ -768,9 +869,9 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
     const bool skip = ((dbg & 1) && type == SL_G) || ((dbg & 2) && type != SL_G);
     if (skip) {
     } else if (type == SL_U) {
-      slice_dispatch<false, MODE, NT>(cnt, d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, fin.pc0, fin.pc1, fin.pc2);
+      slice_dispatch<false, MODE, NT, VT>(cnt, d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, fin.pc0, fin.pc1, fin.pc2, p32, psig);
     } else if (type == SL_P) {
-      slice_dispatch<true, MODE, NT>(cnt, d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, fin.pc0, fin.pc1, fin.pc2);
+      slice_dispatch<true, MODE, NT, VT>(cnt, d, nrows, rec, pval, x, y, pa, pb, lane, acc0, acc1, acc2, dbg, fin.pc0, fin.pc1, fin.pc2, p32, psig);
     } else {
       // packed irregular rows: same data flow as k_spmv_cw on the compact CSR, plus the row-id indirection
       Desc dd;
@@ -784,8 +885,9 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
 #pragma unroll
       for (int j = 0; j < XV_IT; ++j) sv2[lane + 64 * j] = q.v[j];
       // the dot operands of the row ride with the gathers (issued before the LDS phase, not after it)
-      const double opa = MI::HAS_A ? pa[rid] : 0.0, opb = MI::HAS_B ? pb[rid] : 0.0;
-      const double xown = MI::OWN ? x[rid] : 0.0;
+      const double opa = MI::HAS_A ? pa[rid] : 0.0, opb_ = (MI::HAS_B && !VT::P32) ? (double)pb[rid] : 0.0;
+      const double xown = MI::OWN ? (double)x[rid] : 0.0;
+      const double opb = VT::P32 ? xown : opb_;
       // ENTRY-parallel x gathers: lane l holds the columns of entries 4l..4l+3 (and 256 + 4l..), so neighbouring lanes
       // gather for the same or the next row and one gather instruction touches ~20 cache lines -- a row per lane (the CSR
       // kernel's way) touches 64, and the vector-memory unit serves a line per cycle.  The x values go to LDS next to the
@@ -793,7 +895,7 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
       double xg[XC_IT][4];
 #pragma unroll
       for (int j = 0; j < XC_IT; ++j) {
-        xg[j][0] = x[q.c[j].x]; xg[j][1] = x[q.c[j].y]; xg[j][2] = x[q.c[j].z]; xg[j][3] = x[q.c[j].w];
+        xg[j][0] = (double)x[q.c[j].x]; xg[j][1] = (double)x[q.c[j].y]; xg[j][2] = (double)x[q.c[j].z]; xg[j][3] = (double)x[q.c[j].w];
       }
 #pragma unroll
       for (int j = 0; j < XC_IT; ++j) {
@@ -826,7 +928,8 @@ __global__ __launch_bounds__(BLOCK, 4) void k_spmv_s(i64 nslices, const int* __r
       __builtin_amdgcn_wave_barrier();
       if (live) {
         sum = mode_out<MODE>(sum, xown, opb, fin.pc0, fin.pc1, fin.pc2);
-        y[rid] = sum;
+        store_one_t(y + rid, sum);
+        if (VT::P32) store_one_t(p32 + rid, psig * opb);
         if (MI::DOT0) acc0 += opa * sum;
         if (MI::DOT1) acc1 += sum * sum;
         if (MI::DOT2) acc2 += opb * sum;
@@ -988,7 +1091,36 @@ bool launch_mode(int v, const CsrMatrix& A, const double* x, double* y, const do
   return false;
 }
 
+// the whole image as a Horner step with the element types VT (the shipped build of the kernel: stream hint, no diagnostics)
+template <class VT>
+void launch_typed(const CsrMatrix& A, const void* x, void* y, const double* sc, int grid, hipStream_t st, const FinArgs& fin) {
+  const bool tiled = A.tiles_per_xcd > 0 && A.nslices == A.tile_ns && (xcd_map() & 1) && grid >= 8;
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_spmv_s<8, true, false, VT>), dim3(grid), dim3(BLOCK), 0, st, A.nslices, (const int*)A.srec.p,
+                     (const double*)A.pval.p, (const int*)A.g_rowid.p, (const int*)A.g_rowptr.p, (const int*)A.g_col.p,
+                     (const double*)A.g_val.p, static_cast<const typename VT::TX*>(x), static_cast<typename VT::TY*>(y),
+                     (const double*)nullptr, (double*)nullptr, sc, xcd_map(), fin, grid, 0, (const int*)A.mrec.p, A.nunits,
+                     tiled ? (const int*)A.tiles.p : (const int*)nullptr, tiled ? A.tiles_per_xcd : 0, (const double*)A.e_val.p);
+}
+
 }  // namespace
+
+bool spmv_supports_typed_chain() { return (variant() & 64) != 0 && (variant() & 4) != 0 && xcd_map() < 256; }
+
+void launch_spmv_typed(int kind, const CsrMatrix& A, const void* x, void* y, const double* sc, int grid, hipStream_t st,
+                       const FinArgs& fin) {
+  if (A.n == 0) return;
+  PG_REQUIRE(spmv_supports_typed_chain() && A.srec.p, "typed Horner launches need the slice kernel with the stream hint (PG_SPMV_VARIANT 70)");
+  PG_REQUIRE(!fin.ticket && fin.base, "typed Horner launch: a base operand and no scalar phase");
+  if (kind == TYPED_FIRST) {
+    PG_REQUIRE(fin.p32 && x == (const void*)fin.base, "typed Horner launch (first): x = base and a p32 output");
+    launch_typed<VecTypes<double, double, float, true>>(A, x, y, sc, grid, st, fin);
+  } else if (kind == TYPED_MIDDLE) {
+    launch_typed<VecTypes<float, float, float, false>>(A, x, y, sc, grid, st, fin);
+  } else {
+    PG_REQUIRE(kind == TYPED_HANDOVER, "unknown typed Horner launch");
+    launch_typed<VecTypes<float, double, double, false>>(A, x, y, sc, grid, st, fin);
+  }
+}
 
 
 namespace {
