@@ -471,6 +471,35 @@ int32_t pg_solver_set_source(pg_solver* s, int32_t phase, const double* f_n /*M*
 int32_t pg_solver_set_interface_value(pg_solver* s, const double* g_n /*M*/, const double* g_np1 /*M*/);
 int32_t pg_solver_set_border_values(pg_solver* s, const double* values /*nb, mesh border order*/);
 
+/* Time-separable data  sum_k phi_k(x) a_k(t),  k = 1..K <= PG_TD_MAX_TERMS: the spatial parts go to the device once, every step
+   then costs K scalars and one streaming kernel -- no per-step transfer (DESIGN.md "Time-separable data").
+   which: PG_TD_SOURCE (phase 0 / 1), PG_TD_INTERFACE (the monophasic interface value; phase = 0), PG_TD_BORDER (phase = 0).
+   modes: K x M padded fields (the source's phi_k at C_omega, the interface value's at C_gamma), or K x nb border values in the
+          mesh's border order (as pg_solver_set_border_values takes them: EVERY border value of the solver, the constant ones
+          as a term whose coefficients are 1).
+   coef : nrows x 2 x K, row q = the coefficients of step q: a_k at the step's "t" and at its "t + dt" -- the two times at which
+          the caller of pg_solver_set_source / _interface_value / _border_values evaluates its closures for that step (border
+          values are taken at "t" alone).  The library attaches no clock to the rows.
+   Every time step (pg_solver_step, or one step of pg_solver_run) consumes one row, the same row for every slot; a step past the
+   last row of an installed table fails and reuses nothing.  Installing a table rewinds the cursor to row 0.  Install after
+   pg_solver_initial_solve (the constructor's system has its data from the host).  pg_solver_set_source / _interface_value /
+   _border_values on a slot that holds separable data clear that slot.  Steps with separable data are steps with changed data:
+   no folded start, no extrapolated start.
+   Refused: K > PG_TD_MAX_TERMS; steady, moving and Stefan solvers; PG_TD_INTERFACE on a diphasic solver (its jump rows carry no
+   time); more than one rank (virtual ranks included). */
+enum { PG_TD_SOURCE = 0, PG_TD_INTERFACE = 1, PG_TD_BORDER = 2 };
+enum { PG_TD_MAX_TERMS = 8 };
+int32_t pg_solver_set_separable(pg_solver* s, int32_t which, int32_t phase, int32_t K, const double* modes, int64_t nrows,
+                                const double* coef);
+int32_t pg_solver_clear_separable(pg_solver* s, int32_t which, int32_t phase);
+/* terms: 4 counts -- source of phase 0, source of phase 1, interface value, border values (0: the slot is empty);
+   nrows: rows of the shortest installed table (0: none installed); cursor: the row the next step consumes */
+int32_t pg_solver_time_data_info(const pg_solver* s, int32_t* terms /*4*/, int64_t* nrows, int64_t* cursor);
+/* measurement: the per-step combine of the last consumed row, `repeats` launches between two events; modes = J installed terms,
+   bytes = (J + 2) * 8 * n_own, what one combine streams */
+int32_t pg_debug_td_combine_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_combine, int32_t* modes,
+                               int64_t* bytes);
+
 /* first solve of solve_DiffusionUnsteadyMono! (diffusion.jl:275): uses the ctor's A, b. */
 int32_t pg_solver_initial_solve(pg_solver* s, const pg_krylov_opts* opts, pg_step_info* info);
 /* one loop iteration (diffusion.jl:286-300): t += Δt; b; border rows; solve. scheme = run scheme. */

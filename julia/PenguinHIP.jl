@@ -26,7 +26,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
        MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, spectral_estimate,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
-       ∇, ∇₋, gmres, bicgstabl, cg
+       set_separable!, clear_separable!, time_data_info, ∇, ∇₋, gmres, bicgstabl, cg
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
 
@@ -444,6 +444,29 @@ end
 function _set_border_values!(s::Solver, bc_b::BorderConditions, mesh::Mesh, t)
     vals = _border_values(bc_b, mesh, t)
     check(ccall((:pg_solver_set_border_values, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}), s.handle, vals))
+end
+# Time-separable data Σ_k φ_k(x) a_k(t) (include/penguin_hip.h, DESIGN.md "Time-separable data"): the spatial parts once, then
+# one table row per step and no per-step transfer.  which: PG_TD_SOURCE (phase 0 / 1), PG_TD_INTERFACE, PG_TD_BORDER.
+# modes: M x K (padded fields at C_ω / C_γ) or nb x K (border values in the mesh's border order), one COLUMN per term;
+# coef: K x 2 x nrows, coef[k, 1, q] = a_k at step q's "t", coef[k, 2, q] = a_k at its "t + Δt" (column-major: the C layout
+# nrows x 2 x K).  Install after the first solve; every pg_solver_step / step of pg_solver_run consumes one row.
+const PG_TD_SOURCE = Int32(0)
+const PG_TD_INTERFACE = Int32(1)
+const PG_TD_BORDER = Int32(2)
+function set_separable!(s::Solver, which::Integer, phase::Integer, modes::Matrix{Float64}, coef::Array{Float64,3})
+    K = size(modes, 2)
+    (size(coef, 1) == K && size(coef, 2) == 2) || error("set_separable!: coef must be K x 2 x nrows with K = size(modes, 2)")
+    check(ccall((:pg_solver_set_separable, libpg), Int32, (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Float64}, Int64, Ptr{Float64}),
+                s.handle, which, phase, K, modes, size(coef, 3), coef))
+end
+clear_separable!(s::Solver, which::Integer, phase::Integer = 0) =
+    check(ccall((:pg_solver_clear_separable, libpg), Int32, (Ptr{Cvoid}, Int32, Int32), s.handle, which, phase))
+# (terms per slot: source of phase 0, source of phase 1, interface value, border values; table rows; the next step's row)
+function time_data_info(s::Solver)
+    terms = zeros(Int32, 4)
+    nrows, cursor = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:pg_solver_time_data_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ref{Int64}, Ref{Int64}), s.handle, terms, nrows, cursor))
+    (terms = Int.(terms), nrows = nrows[], cursor = cursor[])
 end
 function _interface_desc(bc_i::AbstractBoundary, g::Vector{Float64})
     kind = bc_i isa Dirichlet ? Int32(1) : bc_i isa Neumann ? Int32(2) : bc_i isa Robin ? Int32(3) :

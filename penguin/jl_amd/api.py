@@ -597,6 +597,133 @@ def _padded_field(val, M: int) -> Optional[np.ndarray]:
     return np.ascontiguousarray(val, dtype=np.float64)
 
 
+# =============================================================================== time-separable data
+
+
+def _space_value(φ, coords):
+    """φ at the space coordinates `coords` (a sequence of scalars or arrays): a scalar φ as it is; a callable φ with all of
+    them, or -- when it takes fewer, as a φ(x, y) handed the zero-padded z of a 2-D problem -- with the leading ones."""
+    if not callable(φ):
+        return float(φ)
+    for n in range(len(coords), -1, -1):
+        if _accepts(φ, n):
+            return φ(*coords[:n])
+    raise TypeError(f"{φ!r} accepts none of 0 .. {len(coords)} space coordinates")
+
+
+class TimeSeparable:
+    """Data of the form  Σ_k φ_k(x) · a_k(t),  k = 1 .. K <= 8:  TimeSeparable([(φ_1, a_1), (φ_2, a_2), ...]).
+
+    φ_k is a scalar or a callable of the space coordinates only, a_k a callable t -> float.  The object is itself callable as
+    ts(*coords, t) -- any number of coordinates followed by t -- and broadcasts over arrays, so it can be handed to anything
+    that takes a closure (the constructors, which evaluate data at t = 0 on the host; the host-driven loop; a CPU reference).
+    As Phase.source, as the value of the monophasic interface condition or of a Dirichlet border condition it lets the unsteady
+    drivers keep the time loop on the device: the spatial parts are sent once, every step then costs K scalars (DESIGN.md
+    "Time-separable data").  A pulse, a ramp, sinusoidal forcing, a uniform wall value g(t) are all of this form."""
+
+    MAX_TERMS = 8     # PG_TD_MAX_TERMS
+
+    def __init__(self, terms):
+        terms = list(terms)
+        if not 1 <= len(terms) <= self.MAX_TERMS:
+            raise ValueError(f"TimeSeparable takes 1 .. {self.MAX_TERMS} terms (φ, a), not {len(terms)}")
+        self.terms = []
+        for term in terms:
+            φ, a = term
+            if not callable(a):
+                raise TypeError(f"the time part of a term must be a callable t -> float, not {a!r}")
+            self.terms.append((φ if callable(φ) else float(φ), a))
+
+    def __call__(self, *args):
+        if not args:
+            raise TypeError("TimeSeparable is called as ts(*coords, t)")
+        *coords, t = args
+        out = 0.0
+        for φ, a in self.terms:
+            out = out + _space_value(φ, coords) * float(a(t))
+        return out
+
+    def __repr__(self):
+        return f"TimeSeparable({len(self.terms)} terms)"
+
+
+def _separable_table(coefs, Δt: float, Tₑ: float, max_steps: Optional[int] = None) -> np.ndarray:
+    """The coefficient table of pg_solver_set_separable for the time parts `coefs` (callables t -> float, or a
+    TimeSeparable): rows x 2 x K.  It walks the clock of the host-driven loop literally -- t = 0.0; while t < Tₑ: t += Δt,
+    at most max_steps times -- and stores for each step the coefficients at the two times that loop evaluates its closures
+    at: a_k(t) and a_k(t + Δt) with t ALREADY advanced (diffusion.jl:248-249, 287-290).  The library attaches no clock to the
+    rows, so the quirk lives here alone."""
+    if isinstance(coefs, TimeSeparable):
+        coefs = [a for _, a in coefs.terms]
+    coefs = list(coefs)
+    rows = []
+    t, steps = 0.0, 0
+    while t < Tₑ:
+        if max_steps is not None and steps >= max_steps:
+            break
+        t += Δt
+        rows.append([[float(a(t)) for a in coefs], [float(a(t + Δt)) for a in coefs]])
+        steps += 1
+    return np.array(rows, dtype=np.float64).reshape(len(rows), 2, len(coefs))
+
+
+_TD_SOURCE, _TD_INTERFACE, _TD_BORDER = 0, 1, 2      # PG_TD_*
+
+
+def _separable_fields(ts: TimeSeparable, coords, nspace: int, M: int) -> np.ndarray:
+    """K x M: the spatial parts of ts at the rows of coords (C_ω or C_γ, zero-padded to nspace columns)."""
+    out = np.empty((len(ts.terms), M))
+    for k, (φ, _) in enumerate(ts.terms):
+        out[k] = _eval(lambda *c, φ=φ: _space_value(φ, c), coords, None, nspace)
+    return out
+
+
+def _separable_border(bc_b: "BorderConditions", mesh: "Mesh"):
+    """Border values with TimeSeparable conditions as (modes K x nb in the mesh's border order, time parts): the terms of every
+    distinct TimeSeparable on the cells of its borders, and -- the library takes EVERY border value from the modes -- one term
+    with the coefficient 1 for the values that do not depend on time.  None when that makes more than 8 terms."""
+    idx, pos, key = mesh._border_arrays()
+    inv = {v: k for k, v in L.PG_KEY.items()}
+    modes, coefs, where = [], [], {}
+    const = np.zeros(len(key))
+    for kval in np.unique(key):
+        cond = bc_b.borders.get(inv[int(kval)])
+        if cond is None:
+            continue
+        sel = key == kval
+        v = getattr(cond, "value", 0.0)
+        if isinstance(v, TimeSeparable):
+            if id(v) not in where:
+                where[id(v)] = len(modes)
+                modes.extend(np.zeros(len(key)) for _ in v.terms)
+                coefs.extend(a for _, a in v.terms)
+            for k, (φ, _) in enumerate(v.terms):
+                modes[where[id(v)] + k][sel] = _eval(lambda *c, φ=φ: _space_value(φ, c), pos[sel], None, mesh.N)
+        elif callable(v):
+            const[sel] = _eval(v, pos[sel], 0.0, mesh.N)      # (no time in it, or the caller said time_independent)
+        elif v is not None:
+            const[sel] = float(v)
+    if np.any(const != 0.0):
+        modes.append(const)
+        coefs.append(lambda t: 1.0)
+    if len(modes) > TimeSeparable.MAX_TERMS:
+        return None
+    return np.ascontiguousarray(np.array(modes)), coefs
+
+
+def _install_separable(s: "Solver", which: int, phase: int, modes: np.ndarray, table: np.ndarray) -> None:
+    modes = np.ascontiguousarray(modes, dtype=np.float64)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    L.check(L.lib().pg_solver_set_separable(s._h, C.c_int32(which), C.c_int32(phase), C.c_int32(modes.shape[0]), L.dptr(modes),
+                                            C.c_int64(table.shape[0]), L.dptr(table)))
+
+
+def _clear_separable(s: "Solver", nphase: int) -> None:
+    """What an earlier call installed goes: every call of a driver starts its own clock at t = 0."""
+    for which, phase in [(_TD_SOURCE, q) for q in range(nphase)] + ([(_TD_INTERFACE, 0)] if nphase == 1 else []) + [(_TD_BORDER, 0)]:
+        L.check(L.lib().pg_solver_clear_separable(s._h, C.c_int32(which), C.c_int32(phase)))
+
+
 # =============================================================================== Solver
 
 
@@ -614,6 +741,10 @@ class Solver:
         self._initial_done = False
         self.last_run: Optional[L.pg_run_info] = None
         self.unconverged = 0          # solves that ended without meeting the tolerance (see _check_converged)
+        # where the last unsteady solve took its time-dependent data from: "device" (every one a TimeSeparable: spatial parts
+        # and a coefficient table installed once, the loop stays on the device), "host" (closures re-evaluated and uploaded
+        # every step), None (no time-dependent data, or no unsteady solve yet)
+        self.time_data: Optional[str] = None
 
     # reduced system of the constructor (which=0) or of the loop (which=1): (A_csr, b, idx)
     def system(self, which: int = 0):
@@ -907,7 +1038,24 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
     dyn_g = _time_dependent(bc.value, 3, time_independent)
     dyn_b = any(_time_dependent(getattr(c, "value", None), mesh.N, time_independent) for c in bc_b.borders.values())
     steps = 0
-    if not (dyn_f or dyn_g or dyn_b):
+    # every time-dependent datum a TimeSeparable: spatial parts and coefficient table go to the device once, and the loop
+    # is the one constant data take -- no pg_solver_set_* call inside it.  One plain closure among them: the host-driven loop.
+    _clear_separable(s, 1)
+    dyn_data = ([phase.source] if dyn_f else []) + ([bc.value] if dyn_g else []) + \
+        [c.value for c in bc_b.borders.values() if _time_dependent(getattr(c, "value", None), mesh.N, time_independent)]
+    border_sep = _separable_border(bc_b, mesh) if dyn_b and all(isinstance(v, TimeSeparable) for v in dyn_data) else None
+    device = bool(dyn_data) and all(isinstance(v, TimeSeparable) for v in dyn_data) and (not dyn_b or border_sep is not None)
+    s.time_data = "device" if device else ("host" if dyn_data else None)
+    if device:
+        table = lambda coefs: _separable_table(coefs, Δt, Tₑ, max_steps)
+        if len(table([])) > 0:
+            if dyn_f:
+                _install_separable(s, _TD_SOURCE, 0, _separable_fields(phase.source, cap._cw, 3, M), table(phase.source))
+            if dyn_g:
+                _install_separable(s, _TD_INTERFACE, 0, _separable_fields(bc.value, cap._cg, 3, M), table(bc.value))
+            if dyn_b:
+                _install_separable(s, _TD_BORDER, 0, border_sep[0], table(border_sep[1]))
+    if device or not (dyn_f or dyn_g or dyn_b):
         if save_states or verbose or log:
             while t < Tₑ:
                 if max_steps is not None and steps >= max_steps:
@@ -1036,6 +1184,26 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
     if verbose:
         print("Solver Extremum: ", info.extremum)
     steps = 0
+    # every time-dependent source a TimeSeparable: installed once, and no pg_solver_set_source inside the loop
+    _clear_separable(s, 2)
+    dyn_src = [(q, ph.source) for q, ph in enumerate((phase1, phase2)) if _time_dependent(ph.source, 3, time_independent)]
+    device = bool(dyn_src) and all(isinstance(f, TimeSeparable) for _, f in dyn_src)
+    s.time_data = "device" if device else ("host" if dyn_src else None)
+    if device:
+        if len(_separable_table([], Δt, Tₑ, max_steps)) > 0:
+            for q, f in dyn_src:
+                _install_separable(s, _TD_SOURCE, q, _separable_fields(f, (phase1, phase2)[q].capacity._cw, 3, M),
+                                   _separable_table(f, Δt, Tₑ, max_steps))
+        if not (save_states or verbose or kwargs.get("log", False)):
+            run = L.pg_run_info()
+            L.check(L.lib().pg_solver_run(s._h, C.c_double(Tₑ), C.c_int32(sch), C.byref(opts), C.c_int32(0),
+                                          C.c_int64(-1 if max_steps is None else max_steps), C.c_int32(0), C.byref(run)))
+            s._have_run = True
+            s.last_run = run
+            if run.unconverged_steps:
+                _check_converged(s, False, f"{run.unconverged_steps} of {run.steps} time-step solves", run.worst_relres)
+            s.x = s._fetch_state()
+            return s
     sent = _UploadCache()
     while t < Tₑ:
         if max_steps is not None and steps >= max_steps:
@@ -1043,7 +1211,7 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
         t += Δt
         if verbose:
             print("Time: ", t)
-        if dyn or scheme == "CN":
+        if not device and (dyn or scheme == "CN"):
             for q, ph in enumerate((phase1, phase2)):
                 fn = _padded_field(_eval(ph.source, ph.capacity._cw, t, 3), M)
                 fn1 = _padded_field(_eval(ph.source, ph.capacity._cw, t + Δt, 3), M)

@@ -56,6 +56,22 @@ struct pg_solver {
   int bconst_scheme = -1;
   bool bconst_dirty = true;
   long long bconst_version = 0;   // counts the recomputations of bconst
+  // time-separable data Σ_k φ_k(x) a_k(t) (pg_solver_set_separable).  A slot keeps the ROW-SPACE response of each of its terms
+  // to unit data without the scheme's factor -- V φ on bulk rows, Γ φ on interface rows, the border value on fixed rows, n_own
+  // doubles each -- and the table of coefficients on the host.  bconst of a step is td_base + Σ_j c_j mode_j (k_td_combine),
+  // td_base being what k_bconst gives with the separable slots empty; the scheme's factor (Δt, Δt/2, 1) rides in c_j, so a
+  // change of the scheme rebuilds td_base alone.
+  struct TdSlot {
+    int K = 0;                     // 0: empty
+    i64 nrows = 0;
+    DevBuf<double> mode[PG_TD_MAX_TERMS];
+    std::vector<double> coef;      // nrows x 2 x K
+  };
+  TdSlot td[4];                    // source of phase 0, source of phase 1, mono interface value, border values
+  DevBuf<double> td_base;
+  int td_base_scheme = -1;
+  i64 td_cursor = 0;               // the row the next step consumes
+  i64 td_row = -1;                 // the row of the step under way
   // block rows of the warm loop's right-hand side with everything that does not depend on the state folded into two tables
   // (k_blk_cache / k_rhs_block_c), valid for one (matrix, scheme, bconst)
   DevBuf<double> blk_wz, blk_c0;
@@ -997,6 +1013,68 @@ __global__ void k_set_border_values(i64 nb, const i64* cells_global, const doubl
   }
 }
 
+// ---- time-separable data: mode builders and the per-step combine ----------------------------------------------------------
+// the row-space response to unit data φ (a padded field) of a source (which = PG_TD_SOURCE: V φ on the bulk rows of `phase`
+// that are not fixed) or of the monophasic interface value (PG_TD_INTERFACE: Γ φ on the interface rows); zero on every other
+// row.  k_bconst multiplies the same products by the scheme's factor.
+__global__ void k_td_mode(SysParams P, RowSegs seg, i64 n_own, const int* row_cell, int which, int phase,
+                          const double* __restrict__ phi, const unsigned char* __restrict__ fixed, double* __restrict__ mode) {
+  for (i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x; r < n_own; r += (i64)gridDim.x * blockDim.x) {
+    const int k = seg_kind(seg, r);
+    const i64 lc = row_cell[r];
+    double v = 0.0;
+    if (which == PG_TD_SOURCE) {
+      if ((k & 1) == 0 && (k >> 1) == phase && !fixed[r]) v = P.cap[phase].V[lc] * phi[lc];
+    } else if ((k & 1) == 1 && P.nphase == 1) {
+      v = P.cap[0].G[lc] * phi[lc];
+    }
+    mode[r] = v;
+  }
+}
+
+// the fixed rows of the border cells, as k_set_border_values finds them: out[r] = values[q] (values == nullptr: 0)
+__global__ void k_td_border_rows(i64 nb, const i64* cells_global, const double* values, i64 first_cell, i64 Mloc, int nbulk,
+                                 const int* red, i64 n_own, const unsigned char* fixed, double* out) {
+  for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < nb; q += (i64)gridDim.x * blockDim.x) {
+    const i64 lc = cells_global[q] - first_cell;
+    if (lc < 0 || lc >= Mloc) continue;
+    for (int ph = 0; ph < nbulk; ++ph) {
+      const int r = red[(i64)(2 * ph) * Mloc + lc];
+      if (r >= 0 && r < n_own && fixed[r]) out[r] = values ? values[q] : 0.0;
+    }
+  }
+}
+
+struct TdTerms {
+  const double* m[PG_TD_MAX_TERMS];
+  double c[PG_TD_MAX_TERMS];
+};
+
+// out = base + Σ_{j<J} c_j mode_j, the sum taken in the order of j: (J + 2) · 8 · n bytes streamed, 16 bytes per access, the
+// coefficients by value in the launch (nothing is read back), no atomics, no LDS -- bitwise reproducible.  base may be out
+// itself (the second and later launches of more than PG_TD_MAX_TERMS modes): every element is read and written by one thread.
+template <int J>
+__global__ __launch_bounds__(256) void k_td_combine(i64 n, const double* base, TdTerms T, double* out) {
+  const i64 n2 = n >> 1;
+  const i64 stride = (i64)gridDim.x * blockDim.x;
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n2; i += stride) {
+    rd2_t v = reinterpret_cast<const rd2_t*>(base)[i];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const rd2_t m = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(T.m[j]) + i);
+      v.x += T.c[j] * m.x;
+      v.y += T.c[j] * m.y;
+    }
+    reinterpret_cast<rd2_t*>(out)[i] = v;
+  }
+  if ((n & 1) && blockIdx.x == 0 && threadIdx.x == 0) {   // the odd last row
+    double v = base[n - 1];
+#pragma unroll
+    for (int j = 0; j < J; ++j) v += T.c[j] * T.m[j][n - 1];
+    out[n - 1] = v;
+  }
+}
+
 SysParams make_params(const pg_solver* s, int scheme) {
   SysParams P;
   std::memset(&P, 0, sizeof(P));
@@ -1101,7 +1179,118 @@ SrcView src_view(const pg_solver* s) {
   return v;
 }
 
+bool td_installed(const pg_solver* s) {
+  for (const auto& t : s->td)
+    if (t.K > 0) return true;
+  return false;
+}
+
+void td_clear(pg_solver* s, int slot) {
+  pg_solver::TdSlot& t = s->td[slot];
+  if (t.K == 0) return;
+  for (auto& m : t.mode) m.release();
+  t.K = 0;
+  t.nrows = 0;
+  t.coef.clear();
+  s->bconst_dirty = true;            // bconst is k_bconst's again (or a td_base with this slot's own data back in it)
+  if (!td_installed(s)) {
+    s->td_base.release();
+    s->td_base_scheme = -1;
+    s->td_cursor = 0;
+    s->td_row = -1;
+  }
+}
+
+// global linear index of every border cell in the mesh's order, on the device (uploaded on first use); returns their count
+i64 ensure_border_cells(pg_solver* s) {
+  pg_mesh* m = s->cap[0]->mesh;
+  mesh_build_border(m);
+  const i64 nb = (i64)m->border_key.size();
+  if (!s->border_cells_lin.p) {
+    std::vector<i64> lin(nb);
+    for (i64 q = 0; q < nb; ++q) {
+      i64 li = 0;
+      for (int d = 0; d < m->N; ++d) li += (m->border_idx[q * m->N + d] - 1) * s->slab.stride[d];
+      lin[q] = li;
+    }
+    s->border_cells_lin.alloc(nb);
+    s->border_cells_lin.upload(lin.data(), nb);
+  }
+  return nb;
+}
+
+// bconst of the step whose table row is s->td_row: td_base (k_bconst with the separable slots empty, rebuilt when other data or
+// the scheme changed) + Σ_j c_j mode_j.  The factor k_bconst would put on the data is put on the coefficient:
+//   source      BE: Δt a(t+Δt)        CN: Δt/2 (a(t) + a(t+Δt))          diffusion.jl:257-261
+//   interface   BE: a(t+Δt)           CN: Δt/2 (a(t) + a(t+Δt))
+//   border      a(t)                                                      (the loop applies the border rows with t, :292)
+void td_bconst(pg_solver* s, int scheme) {
+  hipStream_t st = ctx().stream;
+  const i64 n = s->nb.n_own;
+  if (n > 0 && (s->bconst_dirty || s->td_base_scheme != scheme || s->td_base.n != n)) {
+    if (s->td_base.n != n) s->td_base.alloc(n);
+    SrcView v = src_view(s);
+    for (int q = 0; q < 2; ++q)
+      if (s->td[q].K > 0) v.f_n[q] = v.f_np1[q] = nullptr;
+    if (s->td[2].K > 0) { v.g_n = v.g_np1 = nullptr; v.g_const = 0.0; }
+    hipLaunchKernelGGL(k_bconst, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, st, make_params(s, scheme), make_segs(s->nb), n,
+                       s->nb.row_cell.p, v, scheme, s->dt, s->fixed.p, s->bcv.p, s->td_base.p, 0);
+    PG_HIP(hipGetLastError());
+    if (s->td[3].K > 0) {
+      const i64 nb = ensure_border_cells(s);
+      if (nb > 0)
+        hipLaunchKernelGGL(k_td_border_rows, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, st, nb, s->border_cells_lin.p,
+                           (const double*)nullptr, s->slab.first_cell(), s->Mloc, s->nphase, s->nb.red.p, n, s->fixed.p,
+                           s->td_base.p);
+      PG_HIP(hipGetLastError());
+    }
+  }
+  s->td_base_scheme = scheme;
+  const bool cn = scheme == PG_SCHEME_CN;
+  TdTerms T{};
+  int J = 0;
+  const double* base = s->td_base.p;
+  auto flush = [&]() {
+    if (J == 0 || n <= 0) return;
+    const int grid = grid_for((n + 1) / 2, BLOCK);
+    switch (J) {
+#define PG_TD_COMBINE(JV) \
+  case JV: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_td_combine<JV>), dim3(grid), dim3(BLOCK), 0, st, n, base, T, s->bconst.p); break;
+      PG_TD_COMBINE(1) PG_TD_COMBINE(2) PG_TD_COMBINE(3) PG_TD_COMBINE(4)
+      PG_TD_COMBINE(5) PG_TD_COMBINE(6) PG_TD_COMBINE(7) PG_TD_COMBINE(8)
+#undef PG_TD_COMBINE
+    }
+    PG_HIP(hipGetLastError());
+    base = s->bconst.p;
+    J = 0;
+  };
+  for (int slot = 0; slot < 4; ++slot) {
+    const pg_solver::TdSlot& t = s->td[slot];
+    if (t.K == 0) continue;
+    PG_REQUIRE(s->td_row >= 0 && s->td_row < t.nrows, "time-separable data: no table row for this right-hand side");
+    const double* c0 = t.coef.data() + (size_t)s->td_row * 2 * t.K;
+    const double* c1 = c0 + t.K;
+    for (int k = 0; k < t.K; ++k) {
+      double c;
+      if (slot == 3) c = c0[k];
+      else if (cn) c = s->dt / 2 * (c0[k] + c1[k]);
+      else c = slot == 2 ? c1[k] : s->dt * c1[k];
+      T.m[J] = t.mode[k].p;
+      T.c[J] = c;
+      if (++J == PG_TD_MAX_TERMS) flush();
+    }
+  }
+  flush();
+}
+
 void ensure_bconst(pg_solver* s, int scheme) {
+  if (td_installed(s)) {               // every step has its own data: combined anew, and counted as changed data
+    td_bconst(s, scheme);
+    s->bconst_scheme = scheme;
+    s->bconst_dirty = false;
+    ++s->bconst_version;
+    return;
+  }
   if (!s->bconst_dirty && s->bconst_scheme == scheme) return;
   hipStream_t st = ctx().stream;
   const i64 n = s->nb.n_own;
@@ -1492,6 +1681,12 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   PG_REQUIRE(s->initial_done, "Solver is not initialized. Call pg_solver_initial_solve first.");
   const pg_krylov_opts o = opts ? *opts : default_opts();
   if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (refuses: a time step is an unsteady system)
+  // time-separable data: this step's row of the coefficient table -- never an older one
+  for (const auto& t : s->td)
+    PG_REQUIRE(t.K == 0 || s->td_cursor < t.nrows,
+               "time-separable data: this step is past the last row of the coefficient table (" + std::to_string(t.nrows) +
+               " rows, all consumed); install a longer table with pg_solver_set_separable");
+  if (td_installed(s)) s->td_row = s->td_cursor++;
   hipStream_t stream = ctx().stream;
   ensure_run_matrix(s, scheme);
   const CsrMatrix& A = run_matrix(s);
@@ -1993,6 +2188,7 @@ int32_t pg_solver_set_source(pg_solver* s, int32_t phase, const double* f_n, con
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(s && phase >= 0 && phase < s->nphase, "pg_solver_set_source: bad arguments");
+  td_clear(s, phase);
   if (f_n) upload_local(s->f_n[phase], f_n, s->slab);
   if (f_np1) upload_local(s->f_np1[phase], f_np1, s->slab);
   s->bconst_dirty = true;
@@ -2004,6 +2200,7 @@ int32_t pg_solver_set_interface_value(pg_solver* s, const double* g_n, const dou
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(s && s->nphase == 1, "pg_solver_set_interface_value: monophasic solver expected");
+  td_clear(s, 2);
   if (g_n) upload_local(s->g_n, g_n, s->slab);
   if (g_np1) upload_local(s->g_np1, g_np1, s->slab);
   s->bconst_dirty = true;
@@ -2015,19 +2212,8 @@ int32_t pg_solver_set_border_values(pg_solver* s, const double* values) {
   PG_API_BEGIN
   require_init();
   PG_REQUIRE(s && values, "pg_solver_set_border_values: NULL argument");
-  pg_mesh* m = s->cap[0]->mesh;
-  mesh_build_border(m);
-  const i64 nb = (i64)m->border_key.size();
-  if (!s->border_cells_lin.p) {
-    std::vector<i64> lin(nb);
-    for (i64 q = 0; q < nb; ++q) {
-      i64 li = 0;
-      for (int d = 0; d < m->N; ++d) li += (m->border_idx[q * m->N + d] - 1) * s->slab.stride[d];
-      lin[q] = li;
-    }
-    s->border_cells_lin.alloc(nb);
-    s->border_cells_lin.upload(lin.data(), nb);
-  }
+  td_clear(s, 3);
+  const i64 nb = ensure_border_cells(s);
   DevBuf<double> dv(nb);
   dv.upload(values, nb);
   hipLaunchKernelGGL(k_set_border_values, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, ctx().stream, nb, s->border_cells_lin.p,
@@ -2036,6 +2222,118 @@ int32_t pg_solver_set_border_values(pg_solver* s, const double* values) {
   PG_HIP(hipStreamSynchronize(ctx().stream));
   s->bconst_dirty = true;
   if (!s->initial_done) build_first_rhs(s);
+  PG_API_END
+}
+
+static int td_slot_of(const pg_solver* s, int32_t which, int32_t phase, const char* entry) {
+  const std::string who = std::string(entry) + ": ";
+  PG_REQUIRE(s, who + "NULL solver");
+  PG_REQUIRE(which == PG_TD_SOURCE || which == PG_TD_INTERFACE || which == PG_TD_BORDER,
+             who + "which must be PG_TD_SOURCE, PG_TD_INTERFACE or PG_TD_BORDER");
+  if (which == PG_TD_SOURCE) {
+    PG_REQUIRE(phase >= 0 && phase < s->nphase, who + "a source belongs to phase 0 (or 1 of a diphasic solver)");
+    return phase;
+  }
+  PG_REQUIRE(phase == 0, who + "phase must be 0 for PG_TD_INTERFACE and PG_TD_BORDER");
+  return which == PG_TD_INTERFACE ? 2 : 3;
+}
+
+int32_t pg_solver_set_separable(pg_solver* s, int32_t which, int32_t phase, int32_t K, const double* modes, int64_t nrows,
+                                const double* coef) {
+  PG_API_BEGIN
+  require_init();
+  const std::string who = "pg_solver_set_separable refused: ";
+  const int slot = td_slot_of(s, which, phase, "pg_solver_set_separable");
+  PG_REQUIRE(K >= 1, who + "K must be at least 1");
+  PG_REQUIRE(K <= PG_TD_MAX_TERMS, who + "more than " + std::to_string((int)PG_TD_MAX_TERMS) + " terms (K = " +
+             std::to_string(K) + ")");
+  PG_REQUIRE(modes && coef && nrows >= 1, who + "modes, coef and at least one table row are needed");
+  PG_REQUIRE(s->scheme_ctor != PG_SCHEME_STEADY, who + "a steady solver has no time loop");
+  PG_REQUIRE(!s->moving && !s->stefan, who + "moving-body and Stefan solvers are one space-time step each");
+  PG_REQUIRE(!(which == PG_TD_INTERFACE && s->nphase == 2),
+             who + "PG_TD_INTERFACE on a diphasic solver (its jump rows carry no time)");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, who + "it runs on one rank only (virtual ranks included)");
+  PG_REQUIRE(s->initial_done, who + "install after pg_solver_initial_solve (the constructor's system takes its data from the host)");
+  hipStream_t st = ctx().stream;
+  const i64 n = s->nb.n_own;
+  pg_solver::TdSlot& t = s->td[slot];
+  td_clear(s, slot);
+  const i64 nb = which == PG_TD_BORDER ? ensure_border_cells(s) : 0;
+  DevBuf<double> field;                        // one spatial part at a time: the padded field does not stay
+  if (which == PG_TD_BORDER) field.alloc(nb > 0 ? nb : 1);
+  for (int k = 0; k < K; ++k) {
+    t.mode[k].alloc(n > 0 ? n : 1);
+    t.mode[k].zero();
+    if (n <= 0) continue;
+    if (which == PG_TD_BORDER) {
+      if (nb <= 0) continue;
+      field.upload(modes + (i64)k * nb, nb);
+      hipLaunchKernelGGL(k_td_border_rows, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, st, nb, s->border_cells_lin.p,
+                         (const double*)field.p, s->slab.first_cell(), s->Mloc, s->nphase, s->nb.red.p, n, s->fixed.p,
+                         t.mode[k].p);
+    } else {
+      upload_local(field, modes + (i64)k * s->M, s->slab);
+      hipLaunchKernelGGL(k_td_mode, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, st, make_params(s, s->scheme_ctor), make_segs(s->nb),
+                         n, s->nb.row_cell.p, (int)which, (int)phase, (const double*)field.p, s->fixed.p, t.mode[k].p);
+    }
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipStreamSynchronize(st));          // (field is overwritten by the next term)
+  }
+  t.coef.assign(coef, coef + (size_t)nrows * 2 * K);
+  t.nrows = nrows;
+  t.K = K;
+  s->td_cursor = 0;
+  s->td_row = -1;
+  s->bconst_dirty = true;                      // td_base: k_bconst without this slot's own data
+  PG_API_END
+}
+
+int32_t pg_solver_clear_separable(pg_solver* s, int32_t which, int32_t phase) {
+  PG_API_BEGIN
+  require_init();
+  td_clear(s, td_slot_of(s, which, phase, "pg_solver_clear_separable"));
+  PG_API_END
+}
+
+int32_t pg_solver_time_data_info(const pg_solver* s, int32_t* terms, int64_t* nrows, int64_t* cursor) {
+  PG_API_BEGIN
+  PG_REQUIRE(s, "pg_solver_time_data_info: NULL solver");
+  i64 rows = 0;
+  for (int q = 0; q < 4; ++q) {
+    if (terms) terms[q] = s->td[q].K;
+    if (s->td[q].K > 0) rows = rows == 0 ? s->td[q].nrows : std::min(rows, s->td[q].nrows);
+  }
+  if (nrows) *nrows = rows;
+  if (cursor) *cursor = s->td_cursor;
+  PG_API_END
+}
+
+// measurement (scripts/bench_time_separable.py): the combine of the last step's table row launched `repeats` times between two
+// events -- the same launches ensure_bconst queues, writing the same bconst again
+int32_t pg_debug_td_combine_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_combine, int32_t* modes,
+                               int64_t* bytes) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && ms_per_combine && repeats >= 1, "pg_debug_td_combine_ms: bad arguments");
+  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
+  PG_REQUIRE(td_installed(s) && s->td_row >= 0, "pg_debug_td_combine_ms: no step has consumed a row of separable data yet");
+  hipStream_t st = ctx().stream;
+  int J = 0;
+  for (const auto& t : s->td) J += t.K;
+  td_bconst(s, scheme);                        // (td_base of this scheme, outside the timed region)
+  s->bconst_scheme = scheme;
+  s->bconst_dirty = false;
+  ++s->bconst_version;
+  EventPair ev;
+  PG_HIP(hipEventRecord(ev.e0, st));
+  for (int r = 0; r < repeats; ++r) td_bconst(s, scheme);
+  PG_HIP(hipEventRecord(ev.e1, st));
+  PG_HIP(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *ms_per_combine = (double)ms / repeats;
+  if (modes) *modes = J;
+  if (bytes) *bytes = (int64_t)(J + 2) * 8 * s->nb.n_own;
   PG_API_END
 }
 
