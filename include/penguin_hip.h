@@ -500,6 +500,41 @@ int32_t pg_solver_time_data_info(const pg_solver* s, int32_t* terms /*4*/, int64
 int32_t pg_debug_td_combine_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_combine, int32_t* modes,
                                int64_t* bytes);
 
+/* Monitors: per-step observables evaluated on the device (DESIGN.md "Monitors").  They replace the post-processing loops over
+   solver.states of the reference's scripts -- the volume-weighted phase means of examples/2D/Diffusion/Heat_2ph.jl (its
+   Sherwood number), the interface flux  sum_i [Id (H' W! G Tw + H' W! H Tg)]_i  the Stefan and species solvers sum per step,
+   the extremum benchmark/Heat3D.jl tracks -- each a linear or weighted-quadratic functional of the state:
+     PG_MON_SUM    sum_i w_i x_i          PG_MON_SUMSQ   sum_i w_i x_i^2
+   weights: K x len, len = 2M (mono) / 4M (diph), the layout of pg_solver_get_state; entries on unknowns that are no row of
+   the system are dropped (the state is 0 there).  Each monitor is stored dense (n_own doubles) or as a sorted (row, weight)
+   list, whichever streams fewer bytes per step.  After EVERY completed solve -- pg_solver_initial_solve, pg_solver_step, and
+   each of them inside pg_solver_run -- one kernel appends one row to a series kept on the device: row 0 is the state after
+   the first solve (states[1] of the reference), row q the state after step q, when the monitors are installed before the
+   first solve.  No atomics; the same run gives the same bits.  Installing monitors clears any earlier series.
+   Refused: K < 1 or K > PG_MON_MAX, an unknown kind, NULL arguments, len != 2M / 4M; steady, moving, Stefan and
+   stream-function - vorticity solvers; more than one rank (virtual ranks included). */
+enum { PG_MON_SUM = 0, PG_MON_SUMSQ = 1 };
+enum { PG_MON_MAX = 8 };
+int32_t pg_solver_set_monitors(pg_solver* s, int32_t K, const int32_t* kinds, const double* weights /* K x len */, int64_t len);
+/* removes the monitors and the series */
+int32_t pg_solver_clear_monitors(pg_solver* s);
+/* K: installed monitors (0: none); rows: rows of the series; per monitor (PG_MON_MAX entries each; any pointer may be NULL):
+   sparse = 1 for a (row, weight) list, 0 for dense; stored = entries of the list / n_own */
+int32_t pg_solver_monitor_info(const pg_solver* s, int32_t* K, int64_t* rows, int32_t* sparse /*[8]*/, int64_t* stored /*[8]*/);
+/* rows row0 .. row0 + nrows - 1 of the series: values nrows x K, times (the solver's time of each row) nrows or NULL.
+   A range past the last row is an error. */
+int32_t pg_solver_get_monitor_series(const pg_solver* s, int64_t row0, int64_t nrows, double* values /* nrows x K */,
+                                     double* times /* nrows or NULL */);
+/* releases the states pg_solver_run kept (save_every > 0) once the caller has fetched them: pg_solver_num_states is 0
+   afterwards.  (The reference keeps every state in solver.states for the life of the solver.) */
+int32_t pg_solver_drop_states(pg_solver* s);
+/* measurement: the evaluation of the installed monitors on the current state, `repeats` launches between two events;
+   bytes = what one evaluation streams (as pg_debug_td_combine_ms) */
+int32_t pg_debug_monitor_ms(pg_solver* s, int32_t repeats, double* ms_per_eval, int64_t* bytes);
+/* test support: the installed monitors evaluated once on the current state (K values), the series untouched; x_form (may be
+   NULL) = 1 when the kernel read the unscaled x (valid after a state download), 0 when it read z and its scaling */
+int32_t pg_debug_monitor_eval(pg_solver* s, double* values /* K */, int32_t* x_form);
+
 /* first solve of solve_DiffusionUnsteadyMono! (diffusion.jl:275): uses the ctor's A, b. */
 int32_t pg_solver_initial_solve(pg_solver* s, const pg_krylov_opts* opts, pg_step_info* info);
 /* one loop iteration (diffusion.jl:286-300): t += Δt; b; border rows; solve. scheme = run scheme. */

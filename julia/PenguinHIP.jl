@@ -26,7 +26,8 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
        MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, spectral_estimate,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
-       set_separable!, clear_separable!, time_data_info, âˆ‡, âˆ‡â‚‹, gmres, bicgstabl, cg
+       set_separable!, clear_separable!, time_data_info, Monitor, VolumeIntegral, InterfaceFlux, Probe, set_monitors!,
+       clear_monitors!, monitor_info, monitor_series, drop_states!, âˆ‡, âˆ‡â‚‹, gmres, bicgstabl, cg
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
 
@@ -390,9 +391,15 @@ mutable struct Solver
     states::Vector{Any}
     handle::Ptr{Cvoid}
     nunk::Int
+    # monitors=[...] of the last unsteady solve: rows x K values (row 1: the first solve), the solver's time of each row, the
+    # monitors' names; state_steps: with save_every=k the step each entry of `states` belongs to ([0, k, 2k, ...])
+    monitor_series::Matrix{Float64}
+    monitor_times::Vector{Float64}
+    monitor_names::Vector{String}
+    state_steps::Union{Vector{Int}, Nothing}
 end
 function _new_solver(tt, pt, et, h::Ptr{Cvoid}, nunk::Int)
-    s = Solver(tt, pt, et, nothing, nothing, nothing, [], [], h, nunk)
+    s = Solver(tt, pt, et, nothing, nothing, nothing, [], [], h, nunk, zeros(0, 0), Float64[], String[], nothing)
     finalizer(x -> ccall((:pg_solver_destroy, libpg), Int32, (Ptr{Cvoid},), x.handle), s)
     s
 end
@@ -468,6 +475,150 @@ function time_data_info(s::Solver)
     check(ccall((:pg_solver_time_data_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ref{Int64}, Ref{Int64}), s.handle, terms, nrows, cursor))
     (terms = Int.(terms), nrows = nrows[], cursor = cursor[])
 end
+# Monitors (include/penguin_hip.h, DESIGN.md "Monitors"): observables Î£ w_i x_i (:sum) / Î£ w_i x_iÂ² (:sumsq) of the state,
+# evaluated on the device after every solve -- what the reference's scripts compute by looping over solver.states
+# (examples/2D/Diffusion/Heat_2ph.jl: volume-weighted phase means; the Stefan and species solvers: the interface flux).
+# `weights(nunk)` gives the nunk = 2M / 4M weights in the layout of solver.x.
+const PG_MON_SUM = Int32(0)
+const PG_MON_SUMSQ = Int32(1)
+const PG_MON_MAX = 8
+struct Monitor
+    weights::Function
+    kind::Int32
+    name::String
+end
+_mon_kind(kind::Symbol) = kind == :sum ? PG_MON_SUM : kind == :sumsq ? PG_MON_SUMSQ : error("unknown monitor kind $kind: :sum or :sumsq")
+Monitor(w::Vector{Float64}; kind::Symbol=:sum, name::String="monitor") = Monitor(nunk -> w, _mon_kind(kind), name)
+# start (0-based) of block (phase, kind) in [TÏ‰, TÎ³] (2M) or [T1Ï‰, T1Î³, T2Ï‰, T2Î³] (4M); phase is 0 or 1 as in the C ABI
+function _block_offset(M::Int, nunk::Int, phase::Int, kind::Symbol)
+    kind in (:omega, :gamma, :Ï‰, :Î³) || error("kind must be :omega or :gamma")
+    (nunk == 2M || nunk == 4M) || error("a solver on this mesh has 2*$M or 4*$M unknowns, not $nunk")
+    (phase == 0 || (phase == 1 && nunk == 4M)) || error("phase $phase: no such phase in this solver")
+    (2 * phase + (kind in (:gamma, :Î³) ? 1 : 0)) * M
+end
+# Î£ V_i T_i over the Ï‰ unknowns of one phase, divided by Î£ V when `mean` (cÌ„ of Heat_2ph.jl); `square`: of T_iÂ²
+function VolumeIntegral(capacity::AbstractCapacity; phase::Int=0, mean::Bool=true, square::Bool=false, name::String="volume_$phase")
+    V = Vector{Float64}(diag(capacity.V))
+    M = length(V)
+    Monitor(square ? PG_MON_SUMSQ : PG_MON_SUM, name) do nunk
+        w = zeros(nunk)
+        off = _block_offset(M, nunk, phase, :omega)
+        w[off+1:off+M] .= mean ? V ./ sum(V) : V
+        w
+    end
+end
+# Î£_i [Id (Háµ€ Wêœ G TÏ‰ + Háµ€ Wêœ H TÎ³)]_i with d = D(C_Ï‰), q = Wêœ H d = âˆ‡(op, (0, d)):  w_Î³ = âˆ‡â‚‹(op, 0, q) = Háµ€q,
+# w_Ï‰ = -âˆ‡â‚‹(op, q, 0) - w_Î³ = Gáµ€q
+function InterfaceFlux(ph::Phase; phase::Int=0, name::String="interface_flux_$phase")
+    Monitor(PG_MON_SUM, name) do nunk
+        op = ph.operator
+        M = prod(op.size)
+        d = evalf0(ph.Diffusion_coeff, ph.capacity.C_Ï‰)
+        q = âˆ‡(op, vcat(zeros(M), d))
+        wÎ³ = âˆ‡â‚‹(op, zeros(length(q)), q)
+        wÏ‰ = -âˆ‡â‚‹(op, q, zeros(length(q))) .- wÎ³
+        w = zeros(nunk)
+        ow, og = _block_offset(M, nunk, phase, :omega), _block_offset(M, nunk, phase, :gamma)
+        w[ow+1:ow+M] .= wÏ‰
+        w[og+1:og+M] .= wÎ³
+        w
+    end
+end
+# unit weight on one unknown: `index` a 1-based CartesianIndex / tuple of the cell, or a point (tuple of Float64) -- the cell
+# whose node interval holds it
+function Probe(mesh::Mesh{N}, point_or_index; kind::Symbol=:omega, phase::Int=0, name::String="probe") where N
+    ext = mesh.dims .+ 1
+    idx = if point_or_index isa CartesianIndex
+        Tuple(point_or_index)
+    elseif all(v -> v isa Integer, point_or_index)
+        Tuple(Int.(collect(point_or_index)))
+    else
+        ntuple(d -> clamp(searchsortedlast(mesh.nodes[d], Float64(point_or_index[d])), 1, mesh.dims[d]), N)
+    end
+    all(1 .<= idx .<= ext) || error("cell $idx is outside the $ext cells of the mesh")
+    lin = LinearIndices(ext)[idx...]
+    M = prod(ext)
+    Monitor(PG_MON_SUM, name) do nunk
+        w = zeros(nunk)
+        w[_block_offset(M, nunk, phase, kind) + lin] = 1.0
+        w
+    end
+end
+function set_monitors!(s::Solver, mons::Vector{Monitor})
+    1 <= length(mons) <= PG_MON_MAX || error("1 .. $PG_MON_MAX monitors per solver, not $(length(mons))")
+    W = zeros(s.nunk, length(mons))                  # one COLUMN per monitor: the C layout K x len
+    for (k, m) in enumerate(mons)
+        w = m.weights(s.nunk)
+        length(w) == s.nunk || error("monitor weights must have the length of solver.x, $(s.nunk), not $(length(w))")
+        W[:, k] .= w
+    end
+    kinds = Int32[m.kind for m in mons]
+    check(ccall((:pg_solver_set_monitors, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}, Ptr{Float64}, Int64),
+                s.handle, length(mons), kinds, W, s.nunk))
+    s.monitor_names = String[m.name for m in mons]
+    s.monitor_series, s.monitor_times = zeros(0, length(mons)), Float64[]
+    nothing
+end
+function clear_monitors!(s::Solver)
+    check(ccall((:pg_solver_clear_monitors, libpg), Int32, (Ptr{Cvoid},), s.handle))
+    s.monitor_names, s.monitor_series, s.monitor_times = String[], zeros(0, 0), Float64[]
+    nothing
+end
+# (K, rows of the series, per monitor: stored as a (row, weight) list?, entries stored)
+function monitor_info(s::Solver)
+    K, rows = Ref{Int32}(0), Ref{Int64}(0)
+    sparse, stored = zeros(Int32, PG_MON_MAX), zeros(Int64, PG_MON_MAX)
+    check(ccall((:pg_solver_monitor_info, libpg), Int32, (Ptr{Cvoid}, Ref{Int32}, Ref{Int64}, Ptr{Int32}, Ptr{Int64}),
+                s.handle, K, rows, sparse, stored))
+    (K = Int(K[]), rows = Int(rows[]), sparse = Bool.(sparse[1:K[]]), stored = Int.(stored[1:K[]]))
+end
+# the whole series: (rows x K values, the solver's time of each row)
+function monitor_series(s::Solver)
+    info = monitor_info(s)
+    vals, times = zeros(info.K, info.rows), zeros(info.rows)       # column q = row q of the C layout rows x K
+    info.K > 0 && info.rows > 0 &&
+        check(ccall((:pg_solver_get_monitor_series, libpg), Int32, (Ptr{Cvoid}, Int64, Int64, Ptr{Float64}, Ptr{Float64}),
+                    s.handle, 0, info.rows, vals, times))
+    (Matrix(vals'), times)
+end
+drop_states!(s::Solver) = check(ccall((:pg_solver_drop_states, libpg), Int32, (Ptr{Cvoid},), s.handle))
+function _kept_state(s::Solver, q::Integer)
+    x = zeros(s.nunk)
+    check(ccall((:pg_solver_get_state, libpg), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int64), s.handle, q, x, s.nunk))
+    x
+end
+# monitors= / save_every= of the unsteady drivers: argument errors first, then this call's monitors (or none)
+function _begin_monitors!(s::Solver, monitors, save_every, log)
+    mons = monitors === nothing ? Monitor[] : Vector{Monitor}(monitors)
+    length(mons) <= PG_MON_MAX || error("at most $PG_MON_MAX monitors per solver, not $(length(mons))")
+    if save_every !== nothing
+        (save_every isa Integer && save_every >= 1) || error("save_every must be an integer >= 1")
+        log && error("save_every keeps the time loop on the device; log needs the per-step branch")
+    end
+    if !isempty(mons)
+        set_monitors!(s, mons)
+    elseif !isempty(s.monitor_names)
+        clear_monitors!(s)
+    end
+    s.state_steps = save_every === nothing ? nothing : Int[0]
+    save_every === nothing || empty!(s.states)        # states and state_steps describe THIS call, entry for entry
+    nothing
+end
+function _end_monitors!(s::Solver)
+    isempty(s.monitor_names) && return nothing
+    s.monitor_series, s.monitor_times = monitor_series(s)
+    nothing
+end
+# after pg_solver_run with save_every = k: the kept states (steps k, 2k, ...) follow the first solve's, the device copies go
+function _fetch_kept_states!(s::Solver, k::Integer)
+    n = Ref{Int64}(0)
+    check(ccall((:pg_solver_num_states, libpg), Int32, (Ptr{Cvoid}, Ref{Int64}), s.handle, n))
+    for q in 0:n[]-1
+        push!(s.states, _kept_state(s, q))
+        push!(s.state_steps, (q + 1) * k)
+    end
+    drop_states!(s)
+end
 function _interface_desc(bc_i::AbstractBoundary, g::Vector{Float64})
     kind = bc_i isa Dirichlet ? Int32(1) : bc_i isa Neumann ? Int32(2) : bc_i isa Robin ? Int32(3) :
            error("unsupported interface condition $(typeof(bc_i))")
@@ -522,12 +673,17 @@ end
 
 # solve_DiffusionUnsteadyMono!(s, phase, Î”t, Tâ‚‘, bc_b, bc, scheme; method=gmres, algorithm=nothing, kwargs...)  diffusion.jl:268-301
 # Extra keywords (not in the reference): `save_states=true`; with `save_states=false` and no function-valued data the
-# whole loop runs on the device (pg_solver_run) and only the last state is fetched.
+# whole loop runs on the device (pg_solver_run) and only the last state is fetched.  `monitors=[...]`: observables evaluated on
+# the device after every solve, in whichever branch runs (s.monitor_series, s.monitor_times, s.monitor_names).  `save_every=k`:
+# the device loop (same conditions on the data) keeps every k-th state; s.states holds the first solve's state and those,
+# s.state_steps = [0, k, 2k, ...].
 function solve_DiffusionUnsteadyMono!(s::Solver, phase::Phase, Î”t::Float64, Tâ‚‘, bc_b::BorderConditions, bc::AbstractBoundary, scheme::String;
-                                      method::Function=gmres, algorithm=nothing, save_states::Bool=true, kwargs...)
+                                      method::Function=gmres, algorithm=nothing, save_states::Bool=true, monitors=nothing,
+                                      save_every=nothing, kwargs...)
     (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
     kw = Dict{Symbol, Any}(kwargs)
     log = get(kw, :log, false)
+    _begin_monitors!(s, monitors, save_every, log)
     opts = Ref(_opts(method, kw))
     info = pg_step_info()
     cap, mesh = phase.capacity, phase.capacity.mesh
@@ -535,14 +691,21 @@ function solve_DiffusionUnsteadyMono!(s::Solver, phase::Phase, Î”t::Float64, Tâ‚
     check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
     _record!(s, info, log)                                                        # states[1]   (:275-277)
     println("Time: ", t); println("Solver Extremum: ", info.extremum)
-    if !save_states && !(bc.value isa Function) && !_has_border_functions(bc_b) && get(kw, :constant_source, false)
+    if (!save_states || save_every !== nothing) && !(bc.value isa Function) && !_has_border_functions(bc_b) && get(kw, :constant_source, false)
         run = pg_run_info()
         check(ccall((:pg_solver_run, libpg), Int32, (Ptr{Cvoid}, Float64, Int32, Ptr{pg_krylov_opts}, Int32, Int64, Int32, Ref{pg_run_info}),
-                    s.handle, Float64(Tâ‚‘), _scheme(scheme), opts, 0, -1, 0, run))
+                    s.handle, Float64(Tâ‚‘), _scheme(scheme), opts, 0, -1, save_every === nothing ? 0 : save_every, run))
         run.unconverged_steps == 0 || @warn "PenguinHIP: $(run.unconverged_steps) of $(run.steps) time-step solves did not converge"
-        s.x = _state(s); s.states[end] = s.x
+        s.x = _state(s)
+        if save_every === nothing
+            s.states[end] = s.x
+        else
+            _fetch_kept_states!(s, save_every)
+        end
+        _end_monitors!(s)
         return s
     end
+    steps = 0
     sent = Dict{Any,Any}()
     while t < Tâ‚‘
         t += Î”t                                                                    # :287
@@ -562,9 +725,18 @@ function solve_DiffusionUnsteadyMono!(s::Solver, phase::Phase, Î”t::Float64, Tâ‚
         end
         check(ccall((:pg_solver_step, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, _scheme(scheme), opts, info))
         _record!(s, info, log)
+        steps += 1
+        _thin_states!(s, save_every, steps)
         println("Solver Extremum: ", info.extremum)
     end
+    _end_monitors!(s)
     s
+end
+# the host-driven loop under save_every = k: the state of a step that is no multiple of k does not stay in s.states
+function _thin_states!(s::Solver, save_every, steps::Int)
+    save_every === nothing && return nothing
+    steps % save_every == 0 ? push!(s.state_steps, steps) : pop!(s.states)
+    nothing
 end
 
 # ---------------------------------------------------------------------------------- DiffusionUnsteadyDiph (diffusion.jl:319-454)
@@ -602,10 +774,11 @@ function DiffusionUnsteadyDiph(phase1::Phase, phase2::Phase, bc_b::BorderConditi
 end
 
 function solve_DiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Phase, Î”t::Float64, Tâ‚‘, bc_b::BorderConditions, ic::InterfaceConditions, scheme::String;
-                                      method::Function=gmres, algorithm=nothing, kwargs...)
+                                      method::Function=gmres, algorithm=nothing, monitors=nothing, save_every=nothing, kwargs...)
     (s.handle == C_NULL) && error("Solver is not initialized. Call a solver constructor first.")
     kw = Dict{Symbol, Any}(kwargs)
     log = get(kw, :log, false)
+    _begin_monitors!(s, monitors, save_every, log)
     opts = Ref(_opts(method, kw))
     info = pg_step_info()
     t = 0.0
@@ -613,7 +786,18 @@ function solve_DiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Phase, Î
     check(ccall((:pg_solver_initial_solve, libpg), Int32, (Ptr{Cvoid}, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, opts, info))
     _record!(s, info, log)
     println("Solver Extremum: ", info.extremum)
+    if save_every !== nothing && get(kw, :constant_source, false)       # (monitors=, save_every=: as the monophasic driver)
+        run = pg_run_info()
+        check(ccall((:pg_solver_run, libpg), Int32, (Ptr{Cvoid}, Float64, Int32, Ptr{pg_krylov_opts}, Int32, Int64, Int32, Ref{pg_run_info}),
+                    s.handle, Float64(Tâ‚‘), _scheme(scheme), opts, 0, -1, save_every, run))
+        run.unconverged_steps == 0 || @warn "PenguinHIP: $(run.unconverged_steps) of $(run.steps) time-step solves did not converge"
+        s.x = _state(s)
+        _fetch_kept_states!(s, save_every)
+        _end_monitors!(s)
+        return s
+    end
     sent = Dict{Any,Any}()
+    steps = 0
     while t < Tâ‚‘
         t += Î”t
         println("Time: ", t)
@@ -624,8 +808,11 @@ function solve_DiffusionUnsteadyDiph!(s::Solver, phase1::Phase, phase2::Phase, Î
         end
         check(ccall((:pg_solver_step, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{pg_krylov_opts}, Ref{pg_step_info}), s.handle, _scheme(scheme), opts, info))
         _record!(s, info, log)
+        steps += 1
+        _thin_states!(s, save_every, steps)
         println("Solver Extremum: ", info.extremum)
     end
+    _end_monitors!(s)
     s
 end
 

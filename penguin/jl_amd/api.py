@@ -724,6 +724,197 @@ def _clear_separable(s: "Solver", nphase: int) -> None:
         L.check(L.lib().pg_solver_clear_separable(s._h, C.c_int32(which), C.c_int32(phase)))
 
 
+# =============================================================================== monitors
+
+
+_MON_KINDS = {"sum": 0, "sumsq": 1}      # PG_MON_SUM, PG_MON_SUMSQ
+MON_MAX = 8                              # PG_MON_MAX
+
+
+def _block_offset(M: int, nunk: int, phase: int, kind: str) -> int:
+    """Where the block (phase, kind) starts in the full unknown vector: [Tω, Tγ] (2M, monophasic) or [T1ω, T1γ, T2ω, T2γ]
+    (4M, diphasic) -- the layout of Solver.x."""
+    if kind not in ("omega", "gamma", "ω", "γ"):
+        raise ValueError(f"kind must be 'omega' or 'gamma', not {kind!r}")
+    if nunk not in (2 * M, 4 * M):
+        raise ValueError(f"a solver on this mesh has 2*{M} or 4*{M} unknowns, not {nunk}")
+    if phase not in (0, 1) or (phase == 1 and nunk == 2 * M):
+        raise ValueError(f"phase {phase}: a {'monophasic' if nunk == 2 * M else 'diphasic'} solver has phase 0"
+                         + ("" if nunk == 2 * M else " and phase 1"))
+    return (2 * phase + (1 if kind in ("gamma", "γ") else 0)) * M
+
+
+class Monitor:
+    """A per-step observable Σ_i w_i x_i (kind="sum") or Σ_i w_i x_i² (kind="sumsq") of the state, evaluated on the device
+    after every solve of an unsteady driver called with monitors=[...] (DESIGN.md "Monitors").  `weights` has the layout of
+    Solver.x: 2M (monophasic) or 4M (diphasic) entries.  The values come back as one column of Solver.monitor_series."""
+
+    def __init__(self, weights, kind: str = "sum", name: Optional[str] = None):
+        if kind not in _MON_KINDS:
+            raise ValueError(f"unknown monitor kind {kind!r}: 'sum' or 'sumsq'")
+        self.kind = kind
+        self.name = name
+        self._w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+
+    def _weights(self, nunk: int) -> np.ndarray:
+        return self._w
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.name or self.kind})"
+
+
+class VolumeIntegral(Monitor):
+    """Σ_i V_i T_i over the bulk (ω) unknowns of one phase -- divided by Σ V when `mean` (the volume-weighted phase mean c̄ of
+    the reference's examples/2D/Diffusion/Heat_2ph.jl); `square`: of T_i² instead."""
+
+    def __init__(self, capacity: "Capacity", phase: int = 0, mean: bool = True, square: bool = False, name: Optional[str] = None):
+        super().__init__(None, "sumsq" if square else "sum", name or f"{'mean' if mean else 'integral'}{'_sq' if square else ''}_{phase}")
+        self.capacity, self.phase, self.mean = capacity, phase, mean
+
+    def _weights(self, nunk: int) -> np.ndarray:
+        V = np.asarray(self.capacity.V, dtype=np.float64)
+        M = V.shape[0]
+        w = np.zeros(nunk)
+        off = _block_offset(M, nunk, self.phase, "omega")
+        w[off:off + M] = V / V.sum() if self.mean else V
+        return w
+
+
+class InterfaceFlux(Monitor):
+    """Σ_i [Id (Hᵀ W! G Tω + Hᵀ W! H Tγ)]_i, Id = diag D(C_ω): the interface flux the reference's Stefan and species solvers sum
+    per step.  With d = D(C_ω) and q = W! H d = ∇(op, (0, d)) the sum is (Gᵀq)·Tω + (Hᵀq)·Tγ; the weights come from the device's
+    own ∇ / ∇₋ once:  w_γ = ∇₋(op, 0, q) = Hᵀq,  w_ω = −∇₋(op, q, 0) − w_γ = Gᵀq."""
+
+    def __init__(self, phase_obj: "Phase", phase: int = 0, name: Optional[str] = None):
+        super().__init__(None, "sum", name or f"interface_flux_{phase}")
+        self.phase_obj, self.phase = phase_obj, phase
+
+    def _weights(self, nunk: int) -> np.ndarray:
+        op = self.phase_obj.operator
+        M = int(np.prod(op.size))
+        off_w, off_g = _block_offset(M, nunk, self.phase, "omega"), _block_offset(M, nunk, self.phase, "gamma")
+        d = _dcoef(self.phase_obj, M)
+        d = np.ones(M) if d is None else np.asarray(d, dtype=np.float64)
+        q = grad(op, np.concatenate([np.zeros(M), d]))
+        zero = np.zeros_like(q)
+        wγ = div(op, zero, q)
+        wω = -div(op, q, zero) - wγ
+        w = np.zeros(nunk)
+        w[off_w:off_w + M] = wω
+        w[off_g:off_g + M] = wγ
+        return w
+
+
+class Probe(Monitor):
+    """The value of one unknown: unit weight on the cell `point_or_index` of block (phase, kind).  An int is the linear
+    index of the cell (0-based, first coordinate fastest, n+1 cells per direction as in Solver.x), a tuple of ints its
+    0-based multi-index, a tuple of floats a point -- the cell whose node interval holds it."""
+
+    def __init__(self, mesh: "Mesh", point_or_index, kind: str = "omega", phase: int = 0, name: Optional[str] = None):
+        super().__init__(None, "sum", name)
+        ext = tuple(int(e) for e in mesh.ext)
+        M = int(np.prod(ext))
+        if isinstance(point_or_index, (int, np.integer)):
+            lin = int(point_or_index)
+        else:
+            p = tuple(point_or_index)
+            if len(p) != len(ext):
+                raise ValueError(f"a point or multi-index of this mesh has {len(ext)} components, not {len(p)}")
+            if all(isinstance(v, (int, np.integer)) for v in p):
+                idx = [int(v) for v in p]
+            else:
+                idx = [int(np.clip(np.searchsorted(mesh.nodes[d], float(p[d]), side="right") - 1, 0, mesh.dims[d] - 1))
+                       for d in range(len(ext))]
+            if any(not 0 <= i < e for i, e in zip(idx, ext)):
+                raise ValueError(f"multi-index {tuple(idx)} is outside the {ext} cells of the mesh")
+            lin, stride = 0, 1
+            for i, e in zip(idx, ext):
+                lin += i * stride
+                stride *= e
+        if not 0 <= lin < M:
+            raise ValueError(f"cell index {lin} is outside 0 .. {M - 1}")
+        _block_offset(M, 4 * M, phase, kind)          # (kind and phase checked here; the solver's phase count later)
+        self.M, self.cell, self.block_kind, self.phase = M, lin, kind, phase
+        if self.name is None:
+            self.name = f"probe_{kind}_{phase}_{lin}"
+
+    def _weights(self, nunk: int) -> np.ndarray:
+        w = np.zeros(nunk)
+        w[_block_offset(self.M, nunk, self.phase, self.block_kind) + self.cell] = 1.0
+        return w
+
+
+def _check_monitor_args(monitors, save_every, verbose: bool, log: bool, nunk: Optional[int] = None):
+    """The argument errors of monitors= / save_every=, raised before any call into the library.  Returns (list of
+    monitors, save_every as an int or None)."""
+    mons = [] if monitors is None else list(monitors)
+    if len(mons) > MON_MAX:
+        raise ValueError(f"at most {MON_MAX} monitors per solver (PG_MON_MAX), not {len(mons)}")
+    for m in mons:
+        if not isinstance(m, Monitor):
+            raise TypeError(f"monitors must be Monitor objects (Monitor, VolumeIntegral, InterfaceFlux, Probe), not {m!r}")
+        if m.kind not in _MON_KINDS:
+            raise ValueError(f"unknown monitor kind {m.kind!r}: 'sum' or 'sumsq'")
+        if nunk is not None and m._w is not None and m._w.shape[0] != nunk:
+            raise ValueError(f"monitor weights must have the length of Solver.x, {nunk}, not {m._w.shape[0]}")
+    if save_every is not None:
+        if isinstance(save_every, bool) or not isinstance(save_every, (int, np.integer)) or save_every < 1:
+            raise ValueError(f"save_every must be an integer >= 1, not {save_every!r}")
+        if verbose or log:
+            raise ValueError("save_every keeps the time loop on the device; verbose / log need the per-step branch: use one or the other")
+        save_every = int(save_every)
+    return mons, save_every
+
+
+def _monitor_weights(mons, nunk: int) -> np.ndarray:
+    """K x nunk, one row per monitor, lengths checked."""
+    W = np.zeros((len(mons), nunk))
+    for k, m in enumerate(mons):
+        w = np.ascontiguousarray(m._weights(nunk), dtype=np.float64).reshape(-1)
+        if w.shape[0] != nunk:
+            raise ValueError(f"monitor weights must have the length of Solver.x, {nunk}, not {w.shape[0]}")
+        W[k] = w
+    return W
+
+
+def _install_monitors(s: "Solver", mons) -> None:
+    """Before the first solve of a driver: this call's monitors (row 0 of the series is then states[1] of the reference), or
+    none -- what an earlier call on the same solver installed goes.  A solver that never had monitors is not touched."""
+    if mons:
+        W = _monitor_weights(mons, s._nunk)
+        kinds = (C.c_int32 * len(mons))(*[_MON_KINDS[m.kind] for m in mons])
+        L.check(L.lib().pg_solver_set_monitors(s._h, C.c_int32(len(mons)), kinds, L.dptr(W), C.c_int64(s._nunk)))
+        s._monitors_installed = True
+    elif s._monitors_installed:
+        L.check(L.lib().pg_solver_clear_monitors(s._h))
+        s._monitors_installed = False
+    s.monitor_names = [m.name or f"monitor_{k}" for k, m in enumerate(mons)]
+    s.monitor_series = np.zeros((0, len(mons)))
+    s.monitor_times = np.zeros(0)
+
+
+def _fetch_monitors(s: "Solver") -> None:
+    if not s._monitors_installed:
+        return
+    K, rows = C.c_int32(0), C.c_int64(0)
+    L.check(L.lib().pg_solver_monitor_info(s._h, C.byref(K), C.byref(rows), None, None))
+    vals, times = np.zeros((rows.value, K.value)), np.zeros(rows.value)
+    if rows.value > 0:
+        L.check(L.lib().pg_solver_get_monitor_series(s._h, C.c_int64(0), rows, L.dptr(vals), L.dptr(times)))
+    s.monitor_series, s.monitor_times = vals, times
+
+
+def _fetch_kept_states(s: "Solver", save_every: int) -> None:
+    """After pg_solver_run with save_every = k: the states it kept on the device (steps k, 2k, ...) follow the first solve's in
+    s.states, s.state_steps says which step each belongs to, and the device copies are released."""
+    n = C.c_int64(0)
+    L.check(L.lib().pg_solver_num_states(s._h, C.byref(n)))
+    for q in range(n.value):
+        s.states.append(s._fetch_state(q))
+        s.state_steps.append((q + 1) * save_every)
+    L.check(L.lib().pg_solver_drop_states(s._h))
+
+
 # =============================================================================== Solver
 
 
@@ -745,6 +936,14 @@ class Solver:
         # and a coefficient table installed once, the loop stays on the device), "host" (closures re-evaluated and uploaded
         # every step), None (no time-dependent data, or no unsteady solve yet)
         self.time_data: Optional[str] = None
+        # monitors=[...] of the last unsteady solve: one row per completed solve (row 0: the first solve), one column per
+        # monitor; the solver's time of each row; the monitors' names.  state_steps: with save_every=k, the step each entry of
+        # `states` belongs to ([0, k, 2k, ...]); None otherwise.
+        self.monitor_series: np.ndarray = np.zeros((0, 0))
+        self.monitor_times: np.ndarray = np.zeros(0)
+        self.monitor_names: list = []
+        self.state_steps: Optional[list] = None
+        self._monitors_installed = False
 
     # reduced system of the constructor (which=0) or of the loop (which=1): (A_csr, b, idx)
     def system(self, which: int = 0):
@@ -1008,16 +1207,24 @@ def _time_dependent(fn, nspace: int, time_independent: bool = False) -> bool:
 def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: float, bc_b: BorderConditions, bc,
                                   scheme: str, method="bicgstab", algorithm=None, save_states: bool = True,
                                   verbose: bool = False, max_steps: Optional[int] = None,
-                                  time_independent: bool = False, **kwargs):
+                                  time_independent: bool = False, monitors=None, save_every: Optional[int] = None, **kwargs):
     """solve_DiffusionUnsteadyMono!(s, phase, Δt, Tₑ, bc_b, bc, scheme; method, algorithm, kwargs...)
     -- src/solver/diffusion.jl:268-301, quirks kept: the first solve uses the constructor's system and is
     states[1]; A is rebuilt once with `scheme`; `while t < Tₑ` with fp64 `t += Δt`; data at t+Δt.
     `time_independent=True` (not in the reference): the caller asserts that no closure depends on t, which lets the
-    loop stay on the device although the closures have a t parameter."""
+    loop stay on the device although the closures have a t parameter.
+    `monitors=[...]` (not in the reference): observables evaluated on the device after every solve, in whichever branch runs
+    (s.monitor_series, s.monitor_times, s.monitor_names).  `save_every=k`: the device loop keeps every k-th state; s.states
+    holds the first solve's state and those, s.state_steps = [0, k, 2k, ...] (refused together with verbose / log)."""
     if s is None or not s._h:
         raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")  # :269-271
-    opts = _krylov_opts(method, kwargs)
     log = bool(kwargs.get("log", False))
+    mons, save_every = _check_monitor_args(monitors, save_every, verbose, log, s._nunk)
+    opts = _krylov_opts(method, kwargs)
+    _install_monitors(s, mons)
+    s.state_steps = [0] if save_every else None
+    if save_every:
+        s.states = []                 # states and state_steps describe THIS call, entry for entry
     cap, mesh, M = phase.capacity, phase.capacity.mesh, s._ctx["M"]
     sch = L.PG_SCHEME[scheme] if scheme in L.PG_SCHEME else L.PG_SCHEME["BE"]
     t = 0.0
@@ -1028,7 +1235,7 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
     if log:
         s.ch.append({"iters": info.iters, "resnorm": info.resnorm, "isconverged": bool(info.converged)})
     s.x = s._fetch_state()
-    if save_states:
+    if save_states or save_every:
         s.states.append(s.x)
     if verbose:
         print("Time: ", t)
@@ -1056,7 +1263,7 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
             if dyn_b:
                 _install_separable(s, _TD_BORDER, 0, border_sep[0], table(border_sep[1]))
     if device or not (dyn_f or dyn_g or dyn_b):
-        if save_states or verbose or log:
+        if (save_states and not save_every) or verbose or log:
             while t < Tₑ:
                 if max_steps is not None and steps >= max_steps:
                     break
@@ -1077,12 +1284,16 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
         else:
             run = L.pg_run_info()
             L.check(L.lib().pg_solver_run(s._h, C.c_double(Tₑ), C.c_int32(sch), C.byref(opts), C.c_int32(0),
-                                          C.c_int64(-1 if max_steps is None else max_steps), C.c_int32(0), C.byref(run)))
+                                          C.c_int64(-1 if max_steps is None else max_steps), C.c_int32(save_every or 0),
+                                          C.byref(run)))
             s._have_run = True
             s.last_run = run
             if run.unconverged_steps:
                 _check_converged(s, False, f"{run.unconverged_steps} of {run.steps} time-step solves", run.worst_relres)
             s.x = s._fetch_state()
+            if save_every:
+                _fetch_kept_states(s, save_every)
+        _fetch_monitors(s)
         return s
     # time-dependent data: host-driven loop, closures evaluated at the reference's points and times
     sent = _UploadCache()
@@ -1115,11 +1326,16 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
         if log:
             s.ch.append({"iters": info.iters, "resnorm": info.resnorm, "isconverged": bool(info.converged)})
         s.x = s._fetch_state()
-        if save_states:
+        steps += 1
+        if save_every:                                   # (the host-driven loop thins what it keeps the same way)
+            if steps % save_every == 0:
+                s.states.append(s.x)
+                s.state_steps.append(steps)
+        elif save_states:
             s.states.append(s.x)
         if verbose:
             print("Solver Extremum: ", info.extremum)
-        steps += 1
+    _fetch_monitors(s)
     return s
 
 
@@ -1162,12 +1378,19 @@ def DiffusionUnsteadyDiph(phase1: Phase, phase2: Phase, bc_b: BorderConditions, 
 def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: float, Tₑ: float,
                                   bc_b: BorderConditions, ic: InterfaceConditions, scheme: str, method="bicgstab",
                                   algorithm=None, save_states: bool = True, verbose: bool = False,
-                                  max_steps: Optional[int] = None, time_independent: bool = False, **kwargs):
+                                  max_steps: Optional[int] = None, time_independent: bool = False, monitors=None,
+                                  save_every: Optional[int] = None, **kwargs):
     """solve_DiffusionUnsteadyDiph!(...) -- src/solver/diffusion.jl:422-454.  Sources with a time parameter are
-    re-evaluated every step (`time_independent=True`: the caller asserts they are constant in time)."""
+    re-evaluated every step (`time_independent=True`: the caller asserts they are constant in time).  `monitors`, `save_every`:
+    as solve_DiffusionUnsteadyMono_b (4M weights; save_every takes the device loop unless a plain closure is among the data)."""
     if s is None or not s._h:
         raise PenguinHipError("Solver is not initialized. Call a solver constructor first.")
+    mons, save_every = _check_monitor_args(monitors, save_every, verbose, bool(kwargs.get("log", False)), s._nunk)
     opts = _krylov_opts(method, kwargs)
+    _install_monitors(s, mons)
+    s.state_steps = [0] if save_every else None
+    if save_every:
+        s.states = []                 # states and state_steps describe THIS call, entry for entry
     M = s._ctx["M"]
     sch = L.PG_SCHEME[scheme] if scheme in L.PG_SCHEME else L.PG_SCHEME["BE"]
     dyn = any(_time_dependent(ph.source, 3, time_independent) for ph in (phase1, phase2))
@@ -1179,7 +1402,7 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
     _step_info_check(s, info, "the first solve")
     s._initial_done = True
     s.x = s._fetch_state()
-    if save_states:
+    if save_states or save_every:
         s.states.append(s.x)
     if verbose:
         print("Solver Extremum: ", info.extremum)
@@ -1194,16 +1417,22 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
             for q, f in dyn_src:
                 _install_separable(s, _TD_SOURCE, q, _separable_fields(f, (phase1, phase2)[q].capacity._cw, 3, M),
                                    _separable_table(f, Δt, Tₑ, max_steps))
-        if not (save_states or verbose or kwargs.get("log", False)):
-            run = L.pg_run_info()
-            L.check(L.lib().pg_solver_run(s._h, C.c_double(Tₑ), C.c_int32(sch), C.byref(opts), C.c_int32(0),
-                                          C.c_int64(-1 if max_steps is None else max_steps), C.c_int32(0), C.byref(run)))
-            s._have_run = True
-            s.last_run = run
-            if run.unconverged_steps:
-                _check_converged(s, False, f"{run.unconverged_steps} of {run.steps} time-step solves", run.worst_relres)
-            s.x = s._fetch_state()
-            return s
+    # the whole loop in one call: separable data without a history asked for, as before; and save_every, whose history the
+    # device keeps, on separable or constant data
+    if (device and not (save_states or verbose or kwargs.get("log", False))) or (save_every and (device or not dyn_src)):
+        run = L.pg_run_info()
+        L.check(L.lib().pg_solver_run(s._h, C.c_double(Tₑ), C.c_int32(sch), C.byref(opts), C.c_int32(0),
+                                      C.c_int64(-1 if max_steps is None else max_steps), C.c_int32(save_every or 0),
+                                      C.byref(run)))
+        s._have_run = True
+        s.last_run = run
+        if run.unconverged_steps:
+            _check_converged(s, False, f"{run.unconverged_steps} of {run.steps} time-step solves", run.worst_relres)
+        s.x = s._fetch_state()
+        if save_every:
+            _fetch_kept_states(s, save_every)
+        _fetch_monitors(s)
+        return s
     sent = _UploadCache()
     while t < Tₑ:
         if max_steps is not None and steps >= max_steps:
@@ -1223,11 +1452,16 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
         _step_info_check(s, info, "a time-step solve")
         s._have_run = True
         s.x = s._fetch_state()
-        if save_states:
+        steps += 1
+        if save_every:
+            if steps % save_every == 0:
+                s.states.append(s.x)
+                s.state_steps.append(steps)
+        elif save_states:
             s.states.append(s.x)
         if verbose:
             print("Solver Extremum: ", info.extremum)
-        steps += 1
+    _fetch_monitors(s)
     return s
 
 

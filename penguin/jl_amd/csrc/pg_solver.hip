@@ -119,7 +119,25 @@ struct pg_solver {
   DevBuf<double> psi_cp[2], psi_cm[2];
   // the Stefan diphasic blocks (pg_solver_create_moving_stefan_diph, liquidmotionsolver/diffusion.jl:445-651)
   bool stefan = false;
+  bool solved_once = false;         // built for one solve and replaced (the vorticity solver of a pg_streamvort step)
   pg_solver* init_from = nullptr;   // constructor only: the previous slab's solver whose state is this one's initial state
+  // monitors (pg_solver_set_monitors): weighted sums Σ w_i x_i / Σ w_i x_i² of the state after every completed solve.  The
+  // weights live in the solver's row numbering, dense (n_own doubles) or as a sorted (row, weight) list, whichever streams
+  // fewer bytes per step (mon_choose_storage).  k_monitor writes one partial per block and monitor straight into `series`
+  // (rows x G x K); the G partials of a row are added in the order of the blocks when the series is read.
+  struct Monitors {
+    int K = 0;                     // 0: none installed -- no launch, no allocation
+    int kind[PG_MON_MAX] = {};
+    bool sparse[PG_MON_MAX] = {};
+    i64 stored[PG_MON_MAX] = {};   // doubles of a dense monitor (n_own), entries of a sparse one
+    DevBuf<double> w[PG_MON_MAX];  // dense: the weight of every row; sparse: the weight of every entry
+    DevBuf<int> row[PG_MON_MAX];   // sparse: the entries' rows, ascending
+    int G = 0;                     // blocks of k_monitor: a function of n_own alone
+    DevBuf<double> series;         // cap x G x K
+    i64 rows = 0, cap = 0;
+    std::vector<double> times;     // s->t of every row
+  };
+  Monitors mon;
 };
 
 namespace {
@@ -1075,6 +1093,95 @@ __global__ __launch_bounds__(256) void k_td_combine(i64 n, const double* base, T
   }
 }
 
+// ---- monitors: weighted sums of the state after every completed solve ------------------------------------------------------
+// One launch per solve evaluates all K monitors.  The state is read where it lives -- x, or z with x = S z (ds != nullptr) --
+// and never written.  Dense monitors share ONE sweep over the rows: block b owns the rows [b·chunk, (b+1)·chunk) (chunk even, so
+// every pair load is 16 bytes wide and aligned), lane l the pairs l, l + 256, ... of that range, one accumulator per monitor in
+// registers.  Sparse monitors follow in the same launch as gathers: entry e belongs to thread e mod (G·256).  Every
+// accumulator is reduced over its wave by shuffles, the block's four waves are added in order through LDS, and the block's K
+// sums go to out[b·K .. b·K + K): no atomics, nothing handed from block to block, an order of summation that depends on
+// (n, chunk, G) alone.  Bytes per launch: 16·n (z and ds; 8·n when x is valid) once if any monitor is dense, 8·n per dense
+// monitor, 12 bytes and two gathered words per sparse entry, G·K·8 written.
+constexpr int MON_ROWS_PER_BLOCK = 2 * BLOCK;   // one pair per lane at the sizes where the launch is all latency
+constexpr int MON_MAX_BLOCKS = 1024;            // 4 blocks per CU: 16-byte loads from 256 K lanes keep HBM busy
+struct MonArgs {
+  const double* w[PG_MON_MAX];
+  const int* row[PG_MON_MAX];     // nullptr: a dense monitor
+  i64 cnt[PG_MON_MAX];            // entries of a sparse monitor
+  int kind[PG_MON_MAX];
+  int dense[PG_MON_MAX];          // the dense monitors, in order
+  int K;
+};
+
+__device__ inline double mon_wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+template <int ND>
+__global__ __launch_bounds__(BLOCK) void k_monitor(i64 n, i64 chunk, const double* __restrict__ x, const double* __restrict__ ds,
+                                                   MonArgs a, double* __restrict__ out) {
+  __shared__ double sh[PG_MON_MAX][BLOCK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (ND > 0) {
+    double acc[ND > 0 ? ND : 1];
+#pragma unroll
+    for (int j = 0; j < ND; ++j) acc[j] = 0.0;
+    const i64 r0 = blockIdx.x * chunk;
+    const i64 r1 = r0 + chunk < n ? r0 + chunk : n;
+    for (i64 i = r0 + 2 * (i64)threadIdx.x; i + 1 < r1; i += 2 * BLOCK) {
+      rd2_t v = *reinterpret_cast<const rd2_t*>(x + i);
+      if (ds) {
+        const rd2_t d = *reinterpret_cast<const rd2_t*>(ds + i);
+        v.x *= d.x;
+        v.y *= d.y;
+      }
+      const rd2_t q = {v.x * v.x, v.y * v.y};
+#pragma unroll
+      for (int j = 0; j < ND; ++j) {
+        const int m = a.dense[j];
+        const rd2_t wv = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(a.w[m] + i));
+        const bool sq = a.kind[m] == PG_MON_SUMSQ;
+        acc[j] += wv.x * (sq ? q.x : v.x);
+        acc[j] += wv.y * (sq ? q.y : v.y);
+      }
+    }
+    if (((r1 - r0) & 1) && r1 > r0 && threadIdx.x == 0) {   // the odd last row (of the last block: chunk is even)
+      const i64 i = r1 - 1;
+      const double v = ds ? ds[i] * x[i] : x[i];
+#pragma unroll
+      for (int j = 0; j < ND; ++j) {
+        const int m = a.dense[j];
+        acc[j] += a.w[m][i] * (a.kind[m] == PG_MON_SUMSQ ? v * v : v);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < ND; ++j) {
+      const double v = mon_wave_sum(acc[j]);
+      if (lane == 0) sh[a.dense[j]][wave] = v;
+    }
+  }
+  for (int m = 0; m < a.K; ++m) {
+    if (!a.row[m]) continue;
+    double acc = 0.0;
+    for (i64 e = blockIdx.x * (i64)BLOCK + threadIdx.x; e < a.cnt[m]; e += (i64)gridDim.x * BLOCK) {
+      const int r = a.row[m][e];
+      const double v = ds ? ds[r] * x[r] : x[r];
+      acc += a.w[m][e] * (a.kind[m] == PG_MON_SUMSQ ? v * v : v);
+    }
+    acc = mon_wave_sum(acc);
+    if (lane == 0) sh[m][wave] = acc;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < a.K) {
+    double v = sh[threadIdx.x][0];
+#pragma unroll
+    for (int wv = 1; wv < BLOCK / 64; ++wv) v += sh[threadIdx.x][wv];
+    out[(i64)blockIdx.x * a.K + threadIdx.x] = v;
+  }
+}
+
 SysParams make_params(const pg_solver* s, int scheme) {
   SysParams P;
   std::memset(&P, 0, sizeof(P));
@@ -1476,6 +1583,90 @@ void keep_state(pg_solver* s) {
   if (s->nb.n_own > 0)
     PG_HIP(hipMemcpyAsync(cp.p, s->x.p, sizeof(double) * s->nb.n_own, hipMemcpyDeviceToDevice, ctx().stream));
   s->states.emplace_back(std::move(cp));
+}
+
+// ---- monitors, host side ---------------------------------------------------------------------------------------------------
+// Storage rule.  Per step a dense monitor streams its n_own weights (8·n bytes) and shares one read of the state (z and ds,
+// 16·n bytes) with every other dense monitor; a sparse entry costs its row and weight (12 bytes) and two gathered words, each
+// counted as a 128-byte line of its own, the unit gfx950's L2 requests from memory (MON_SPARSE_ENTRY_BYTES = 268).  With
+// C = {m : 268·nnz_m > 8·n}, the monitors that are cheaper dense once the state is paid for, the cheapest assignment is: all of
+// C dense when Σ_C (268·nnz_m − 8·n) > 16·n, else every monitor sparse (a subset of C gains less, a monitor outside C loses).
+constexpr i64 MON_SPARSE_ENTRY_BYTES = 12 + 2 * 128;
+
+void mon_choose_storage(i64 n, int K, const i64* nnz, bool* sparse) {
+  i64 gain = 0;
+  for (int m = 0; m < K; ++m)
+    if (MON_SPARSE_ENTRY_BYTES * nnz[m] > 8 * n) gain += MON_SPARSE_ENTRY_BYTES * nnz[m] - 8 * n;
+  const bool any_dense = gain > 16 * n;
+  for (int m = 0; m < K; ++m) sparse[m] = !(any_dense && MON_SPARSE_ENTRY_BYTES * nnz[m] > 8 * n);
+}
+
+void mon_clear(pg_solver* s) {
+  pg_solver::Monitors& M = s->mon;
+  for (int m = 0; m < PG_MON_MAX; ++m) {
+    M.w[m].release();
+    M.row[m].release();
+    M.kind[m] = 0; M.sparse[m] = false; M.stored[m] = 0;
+  }
+  M.series.release();
+  M.times.clear();
+  M.K = 0; M.G = 0; M.rows = 0; M.cap = 0;
+}
+
+// one evaluation of every monitor on the current state: G·K partials to `out`
+void mon_launch(const pg_solver* s, double* out, hipStream_t st) {
+  const pg_solver::Monitors& M = s->mon;
+  const i64 n = s->nb.n_own;
+  MonArgs a{};
+  int nd = 0;
+  for (int m = 0; m < M.K; ++m) {
+    a.w[m] = M.w[m].p;
+    a.row[m] = M.sparse[m] ? M.row[m].p : nullptr;
+    a.cnt[m] = M.sparse[m] ? M.stored[m] : 0;
+    a.kind[m] = M.kind[m];
+    if (!M.sparse[m]) a.dense[nd++] = m;
+  }
+  a.K = M.K;
+  const double* x = s->x_valid ? s->x.p : s->z.p;
+  const double* ds = s->x_valid ? nullptr : s->z_matrix->ds.p;
+  i64 chunk = (n + M.G - 1) / M.G;
+  chunk += chunk & 1;
+  switch (nd) {
+#define PG_MONITOR(NDV) \
+  case NDV: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_monitor<NDV>), dim3(M.G), dim3(BLOCK), 0, st, n, chunk, x, ds, a, out); break;
+    PG_MONITOR(0) PG_MONITOR(1) PG_MONITOR(2) PG_MONITOR(3) PG_MONITOR(4)
+    PG_MONITOR(5) PG_MONITOR(6) PG_MONITOR(7) PG_MONITOR(8)
+#undef PG_MONITOR
+  }
+  PG_HIP(hipGetLastError());
+}
+
+// room for `more` further rows: the buffer grows by doubling (at least), the copy ordered on the same stream.  pg_solver_run
+// reserves its whole loop before the first step, so nothing is allocated, freed or copied between its steps.
+void mon_reserve(pg_solver* s, i64 more) {
+  pg_solver::Monitors& M = s->mon;
+  if (M.K == 0 || M.rows + more <= M.cap) return;
+  hipStream_t st = ctx().stream;
+  const i64 per_row = (i64)M.G * M.K;
+  i64 cap = M.cap > 0 ? 2 * M.cap : 64;
+  while (cap < M.rows + more) cap *= 2;
+  DevBuf<double> grown(cap * per_row);
+  if (M.rows > 0)
+    PG_HIP(hipMemcpyAsync(grown.p, M.series.p, sizeof(double) * (size_t)(M.rows * per_row), hipMemcpyDeviceToDevice, st));
+  M.series = std::move(grown);
+  M.cap = cap;
+}
+
+// after a completed solve: one row of the series
+void mon_record(pg_solver* s) {
+  pg_solver::Monitors& M = s->mon;
+  if (M.K == 0) return;
+  hipStream_t st = ctx().stream;
+  const i64 per_row = (i64)M.G * M.K;
+  mon_reserve(s, 1);
+  mon_launch(s, M.series.p + M.rows * per_row, st);
+  M.times.push_back(s->t);
+  ++M.rows;
 }
 
 pg_krylov_opts default_opts() {
@@ -2047,6 +2238,7 @@ static int32_t create_solver(const SolverSpec& d) {
   }
   s->init_from = d.previous;                // consumed by setup_common after T0: its active unknowns overwrite T0's
   s->A_ctor.want_units = !d.moving && !d.solved_once;
+  s->solved_once = d.solved_once;
   setup_common(s, d.borders, d.nborders, d.T0);
   *d.out = guard.release();
   PG_API_END
@@ -2337,6 +2529,169 @@ int32_t pg_debug_td_combine_ms(pg_solver* s, int32_t scheme, int32_t repeats, do
   PG_API_END
 }
 
+int32_t pg_solver_set_monitors(pg_solver* s, int32_t K, const int32_t* kinds, const double* weights, int64_t len) {
+  PG_API_BEGIN
+  require_init();
+  const std::string who = "pg_solver_set_monitors refused: ";
+  PG_REQUIRE(s, who + "NULL solver");
+  PG_REQUIRE(K >= 1, who + "K must be at least 1");
+  PG_REQUIRE(K <= PG_MON_MAX, who + "more than " + std::to_string((int)PG_MON_MAX) + " monitors (K = " + std::to_string(K) + ")");
+  PG_REQUIRE(kinds && weights, who + "kinds and weights are needed");
+  for (int m = 0; m < K; ++m)
+    PG_REQUIRE(kinds[m] == PG_MON_SUM || kinds[m] == PG_MON_SUMSQ,
+               who + "unknown kind " + std::to_string(kinds[m]) + " (PG_MON_SUM or PG_MON_SUMSQ)");
+  PG_REQUIRE(len == (i64)s->K * s->M, who + "len must be 2M (mono) or 4M (diph), the length of pg_solver_get_state's vector");
+  PG_REQUIRE(s->scheme_ctor != PG_SCHEME_STEADY, who + "a steady solver has no time loop");
+  PG_REQUIRE(!s->moving && !s->stefan, who + "moving-body and Stefan solvers are one space-time step each");
+  PG_REQUIRE(!s->solved_once, who + "the solvers of a stream-function - vorticity step are replaced every step");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm && s->Mloc == s->M, who + "it runs on one rank only (virtual ranks included)");
+  mon_clear(s);
+  const i64 n = s->nb.n_own;
+  // the weights in the solver's row numbering: row r is unknown (kind of r, cell of r) of the full vector, as k_scatter_active
+  // places it -- unknowns that are no row (eliminated: the state is 0 there) drop out
+  std::vector<int> row_cell((size_t)std::max<i64>(n, 1));
+  if (n > 0) s->nb.row_cell.download(row_cell.data(), n);
+  std::vector<std::vector<double>> wr((size_t)K, std::vector<double>((size_t)std::max<i64>(n, 1), 0.0));
+  i64 nnz[PG_MON_MAX] = {};
+  for (int m = 0; m < K; ++m) {
+    const double* w = weights + (i64)m * len;
+    for (int k = 0; k < s->nb.K; ++k) {
+      const i64 r_end = k + 1 < s->nb.K ? s->nb.off_own[k + 1] : n;
+      for (i64 r = s->nb.off_own[k]; r < r_end; ++r) {
+        const double v = w[(i64)k * s->M + row_cell[(size_t)r]];
+        wr[(size_t)m][(size_t)r] = v;
+        if (v != 0.0) ++nnz[m];
+      }
+    }
+  }
+  pg_solver::Monitors& M = s->mon;
+  mon_choose_storage(n, K, nnz, M.sparse);
+  for (int m = 0; m < K; ++m) {
+    M.kind[m] = kinds[m];
+    if (!M.sparse[m]) {
+      M.w[m].alloc(std::max<i64>(n, 1));
+      M.w[m].upload(wr[(size_t)m].data(), n);
+      M.stored[m] = n;
+      continue;
+    }
+    std::vector<int> rows;
+    std::vector<double> vals;
+    for (i64 r = 0; r < n; ++r)
+      if (wr[(size_t)m][(size_t)r] != 0.0) { rows.push_back((int)r); vals.push_back(wr[(size_t)m][(size_t)r]); }
+    M.row[m].alloc(std::max<i64>((i64)rows.size(), 1));
+    M.w[m].alloc(std::max<i64>((i64)rows.size(), 1));
+    M.row[m].upload(rows.data(), (i64)rows.size());
+    M.w[m].upload(vals.data(), (i64)vals.size());
+    M.stored[m] = (i64)rows.size();
+  }
+  M.G = (int)std::min<i64>(MON_MAX_BLOCKS, std::max<i64>(1, (n + MON_ROWS_PER_BLOCK - 1) / MON_ROWS_PER_BLOCK));
+  M.K = K;
+  PG_API_END
+}
+
+int32_t pg_solver_clear_monitors(pg_solver* s) {
+  PG_API_BEGIN
+  PG_REQUIRE(s, "pg_solver_clear_monitors: NULL solver");
+  mon_clear(s);
+  PG_API_END
+}
+
+int32_t pg_solver_monitor_info(const pg_solver* s, int32_t* K, int64_t* rows, int32_t* sparse, int64_t* stored) {
+  PG_API_BEGIN
+  PG_REQUIRE(s, "pg_solver_monitor_info: NULL solver");
+  if (K) *K = s->mon.K;
+  if (rows) *rows = s->mon.rows;
+  for (int m = 0; m < PG_MON_MAX; ++m) {
+    if (sparse) sparse[m] = m < s->mon.K && s->mon.sparse[m] ? 1 : 0;
+    if (stored) stored[m] = m < s->mon.K ? s->mon.stored[m] : 0;
+  }
+  PG_API_END
+}
+
+int32_t pg_solver_get_monitor_series(const pg_solver* s, int64_t row0, int64_t nrows, double* values, double* times) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && values, "pg_solver_get_monitor_series: NULL argument");
+  const pg_solver::Monitors& M = s->mon;
+  PG_REQUIRE(M.K > 0, "pg_solver_get_monitor_series: no monitors are installed");
+  PG_REQUIRE(row0 >= 0 && nrows >= 0 && row0 <= M.rows && nrows <= M.rows - row0,
+             "pg_solver_get_monitor_series: rows " + std::to_string((long long)row0) + " .. " +
+             std::to_string((long long)(row0 + nrows)) + " asked for, the series has " + std::to_string((long long)M.rows));
+  const i64 per_row = (i64)M.G * M.K;
+  std::vector<double> part((size_t)std::max<i64>(nrows * per_row, 1));
+  M.series.download(part.data(), nrows * per_row, row0 * per_row);
+  for (i64 q = 0; q < nrows; ++q)
+    for (int m = 0; m < M.K; ++m) {
+      double v = 0.0;                              // the blocks' partials in the order of the blocks
+      for (int g = 0; g < M.G; ++g) v += part[(size_t)((q * M.G + g) * M.K + m)];
+      values[q * M.K + m] = v;
+    }
+  if (times)
+    for (i64 q = 0; q < nrows; ++q) times[q] = M.times[(size_t)(row0 + q)];
+  PG_API_END
+}
+
+int32_t pg_solver_drop_states(pg_solver* s) {
+  PG_API_BEGIN
+  PG_REQUIRE(s, "pg_solver_drop_states: NULL solver");
+  s->states.clear();
+  PG_API_END
+}
+
+// measurement (scripts/bench_monitors.py): the evaluation of the installed monitors on the current state launched `repeats`
+// times between two events, into a scratch buffer -- the series does not grow
+int32_t pg_debug_monitor_ms(pg_solver* s, int32_t repeats, double* ms_per_eval, int64_t* bytes) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && ms_per_eval && repeats >= 1, "pg_debug_monitor_ms: bad arguments");
+  const pg_solver::Monitors& M = s->mon;
+  PG_REQUIRE(M.K > 0 && s->initial_done, "pg_debug_monitor_ms: monitors and a solved state are needed");
+  hipStream_t st = ctx().stream;
+  DevBuf<double> out((i64)M.G * M.K);
+  mon_launch(s, out.p, st);                    // (outside the timed region)
+  EventPair ev;
+  PG_HIP(hipEventRecord(ev.e0, st));
+  for (int r = 0; r < repeats; ++r) mon_launch(s, out.p, st);
+  PG_HIP(hipEventRecord(ev.e1, st));
+  PG_HIP(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *ms_per_eval = (double)ms / repeats;
+  if (bytes) {
+    const i64 n = s->nb.n_own;
+    i64 b = (i64)M.G * M.K * 8;
+    bool any_dense = false;
+    for (int m = 0; m < M.K; ++m) {
+      if (M.sparse[m]) b += MON_SPARSE_ENTRY_BYTES * M.stored[m];
+      else { b += 8 * n; any_dense = true; }
+    }
+    if (any_dense) b += (s->x_valid ? 8 : 16) * n;
+    *bytes = b;
+  }
+  PG_API_END
+}
+
+// test support: the installed monitors evaluated once on the current state -- x when a state download has made it valid, else z
+// and its scaling -- K values, the blocks' partials added as pg_solver_get_monitor_series adds them; the series is not touched
+int32_t pg_debug_monitor_eval(pg_solver* s, double* values, int32_t* x_form) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && values, "pg_debug_monitor_eval: NULL argument");
+  const pg_solver::Monitors& M = s->mon;
+  PG_REQUIRE(M.K > 0 && s->initial_done, "pg_debug_monitor_eval: monitors and a solved state are needed");
+  DevBuf<double> out((i64)M.G * M.K);
+  mon_launch(s, out.p, ctx().stream);
+  std::vector<double> part((size_t)M.G * M.K);
+  out.download(part.data(), (i64)M.G * M.K);
+  for (int m = 0; m < M.K; ++m) {
+    double v = 0.0;
+    for (int g = 0; g < M.G; ++g) v += part[(size_t)g * M.K + m];
+    values[m] = v;
+  }
+  if (x_form) *x_form = s->x_valid ? 1 : 0;
+  PG_API_END
+}
+
 int32_t pg_solver_initial_solve(pg_solver* s, const pg_krylov_opts* opts, pg_step_info* info) {
   PG_API_BEGIN
   require_init();
@@ -2344,6 +2699,7 @@ int32_t pg_solver_initial_solve(pg_solver* s, const pg_krylov_opts* opts, pg_ste
   SolveStats st;
   std::unique_ptr<AsyncAllocScope> pool(s->moving ? new AsyncAllocScope() : nullptr);   // (work vectors allocated on first use)
   do_initial(s, opts, st);
+  mon_record(s);
   fill_info(s, st, info);
   PG_API_END
 }
@@ -2355,6 +2711,7 @@ int32_t pg_solver_step(pg_solver* s, int32_t scheme, const pg_krylov_opts* opts,
   PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
   SolveStats st;
   do_step(s, scheme, opts, st);
+  mon_record(s);
   fill_info(s, st, info);
   PG_API_END
 }
@@ -2387,9 +2744,16 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
     if (!st.converged) ++unconverged;
     if (st.bnorm > 0.0) worst = std::max(worst, st.resnorm / st.bnorm);
   };
+  if (s->mon.K > 0) {               // the rows this call will record, counted on the loop's own clock (an open-ended run: a
+    const i64 limit = 1 << 16;      // first 65 536, the doubling takes care of the rest)
+    i64 rows = do_initial_flag ? 1 : 0, n = 0;
+    for (double t = s->t; t < Tend && (max_steps < 0 || n < max_steps) && n < limit; t += s->dt) ++n;
+    mon_reserve(s, rows + n);
+  }
   if (do_initial_flag) {
     SolveStats st;
     do_initial(s, opts, st);
+    mon_record(s);
     account(st);
     if (save_every > 0) keep_state(s);
   }
@@ -2399,6 +2763,7 @@ int32_t pg_solver_run(pg_solver* s, double Tend, int32_t scheme, const pg_krylov
     s->hint_more_steps = (s->t + s->dt < Tend) && (max_steps < 0 || steps + 1 < max_steps);   // (another step follows this one)
     struct HintReset { pg_solver* s; ~HintReset() { s->hint_more_steps = false; } } hint_reset{s};
     do_step(s, scheme, opts, st);
+    mon_record(s);
     account(st);
     ++steps;
     if (save_every > 0 && steps % save_every == 0) keep_state(s);
