@@ -57,8 +57,8 @@ enum { PG_SV_PSI = 0, PG_SV_OMEGA = 1, PG_SV_U = 2, PG_SV_V = 3 };   /* fields /
 enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2, PG_METHOD_BICGSTABL = 3 };   /* IterativeSolvers methods
    kept: bicgstab (also serves `\`, and bicgstabl when no l is given), cg, gmres (solve_system!'s default, src/solver.jl:158),
    bicgstabl with l = pg_krylov_opts.restart (BiCGStab(l), DESIGN.md "BiCGStab(l)"): opt-in, one rank, zero initial guess
-   (warm_start is ignored), plain -- refused together with precond = m >= 1, PG_PRECOND_MG, PG_PRECOND_MG_CELL or
-   PG_PRECOND_POLY_EST; with precond = 0 or -1 it runs unpreconditioned.  Its `iters` count BiCG sub-steps, two products each
+   (warm_start is ignored), plain -- refused together with precond = m >= 1, PG_PRECOND_MG, PG_PRECOND_MG_CELL,
+   PG_PRECOND_MG_STEP or PG_PRECOND_POLY_EST; with precond = 0 or -1 it runs unpreconditioned.  Its `iters` count BiCG sub-steps, two products each
    (the unit of BiCGStab's iterations: l = 1 is directly comparable) and maxiter caps that unit (no outer iteration starts at
    iters >= maxiter); products = 2 iters + the products that confirm the true residual before convergence is reported */
 
@@ -112,7 +112,15 @@ typedef struct {
                           the precond = 0 solve and no estimate runs; where it refuses, the first solve on a matrix runs 30
                           Arnoldi steps (pg_solver_spectral_estimate) and the polynomial runs on |z - 1| <= g_ritz + margin when
                           that is < 0.95, the plain iteration otherwise (no error).  One rank, BiCGStab, DiffusionOps, no moving
-                          body: refused with an error that names the failed condition anywhere else */
+                          body: refused with an error that names the failed condition anywhere else;
+                          PG_PRECOND_MG_STEP: the cell-aggregated V-cycle INSIDE the unsteady time loop (DESIGN.md "Multigrid in
+                          the time loop"), meant for steps far above h² where the system approaches the Poisson system --
+                          DiffusionUnsteadyMono (DarcyFlowUnsteady included; Dirichlet, Robin or Neumann interface) and
+                          DiffusionUnsteadyDiph, BE and CN, DiffusionOps, one rank, BiCGStab.  One hierarchy per assembled matrix (pg_solver_mg_step_info); the
+                          iteration runs on the full system, warm-started from the previous state.  Refused with an error that
+                          names the failed condition anywhere else (steady and moving solvers, a ConvectionOps, a
+                          pg_streamvort, CG / GMRES / BiCGStab(l)) and where a coarse diagonal entry is not positive; reports
+                          like the other multigrid solves */
 } pg_krylov_opts;
 enum { PG_PRECOND_MG = -2 };   /* a value of pg_krylov_opts.precond */
 /* a value of pg_krylov_opts.precond: multigrid whose first coarsening merges ALL unknowns, bulk and interface, of a 2 x 2 (x 2)
@@ -124,6 +132,10 @@ enum { PG_PRECOND_MG_CELL = -3 };
    Gershgorin refuses it.  Opt-in; a flag of its own on the matrix: nothing else that Gershgorin's verdict switches on (the
    elimination of rows alone on their diagonal, the compact loop system) starts because of it. */
 enum { PG_PRECOND_POLY_EST = -4 };
+/* a value of pg_krylov_opts.precond: the V-cycle of PG_PRECOND_MG_CELL as right preconditioner of the time steps of an unsteady
+   diffusion solver, monophasic or diphasic.  A name of its own: PG_PRECOND_MG and PG_PRECOND_MG_CELL keep refusing every unsteady system.  Its
+   hierarchies (one for the constructor's system, one for the run system) are its own as well. */
+enum { PG_PRECOND_MG_STEP = -5 };
 /* added to the largest |theta - 1| of the Ritz values before the test against 0.95: twice the largest shortfall of the estimate
    against the true spectrum measured on the oracle's systems (DESIGN.md "Estimated spectral interval" has the table) */
 #define PG_SPECEST_MARGIN 0.0205
@@ -568,6 +580,9 @@ int32_t pg_solver_get_row_scaling(const pg_solver* s, int32_t which, double* ds)
 int32_t pg_solver_mg_info(const pg_solver* s, pg_mg_info* out);
 /* ... and the hierarchy of `precond` = PG_PRECOND_MG (the call above) or PG_PRECOND_MG_CELL */
 int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* out);
+/* the hierarchies of PG_PRECOND_MG_STEP: which = 0 the constructor's system, 1 the run system (levels = 0 while the first
+   solve with the option on that matrix has not run) */
+int32_t pg_solver_mg_step_info(const pg_solver* s, int32_t which, pg_mg_info* out);
 /* The spectral estimate behind PG_PRECOND_POLY_EST of system `which` (0 constructor, 1 run system; + 4: report only).  Runs the
    estimate if it has not run on that matrix (a solve with PG_PRECOND_POLY_EST runs it only where Gershgorin refuses; this call
    runs it on any matrix) and refuses what the option refuses.  With + 4 nothing runs: steps = 0 says no estimate exists. */
@@ -652,7 +667,7 @@ int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const int64_t* n, 
                                    int64_t* n_ghost_out, int64_t* iters_out);
 /* Krylov method (PG_METHOD_*) and GMRES restart length of the virtual-rank runs that follow (default BiCGStab) */
 int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart);
-/* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG and PG_PRECOND_MG_CELL make
+/* pg_krylov_opts.precond of the virtual-rank runs that follow (default 0).  PG_PRECOND_MG, PG_PRECOND_MG_CELL and PG_PRECOND_MG_STEP make
    pg_debug_run_virtual_ranks fail with the multigrid's one-rank refusal before any rank starts, PG_PRECOND_POLY_EST with its own */
 int32_t pg_debug_set_virtual_rank_precond(int32_t precond);
 /* ramp != 0: the virtual-rank runs that follow change the interface value every step, g = interface_value (1 + ramp step)
@@ -689,6 +704,13 @@ int32_t pg_debug_mg_aggregates_for(pg_solver* s, int32_t precond, int32_t level,
 int32_t pg_debug_mg_level_csr_for(pg_solver* s, int32_t precond, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
                                   double* val);
 int32_t pg_debug_mg_apply_for(pg_solver* s, int32_t precond, const double* r, double* z);
+/* the same three on the hierarchies of PG_PRECOND_MG_STEP (tests/test_gpu_mg_step.py): which = 0 the constructor's system, 1 the
+   run system (it must exist: take a step first).  They build the hierarchy when it does not exist yet and refuse what
+   PG_PRECOND_MG_STEP refuses. */
+int32_t pg_debug_mg_step_aggregates(pg_solver* s, int32_t which, int32_t level, int64_t* n, int32_t* agg);
+int32_t pg_debug_mg_step_level_csr(pg_solver* s, int32_t which, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
+                                   double* val);
+int32_t pg_debug_mg_step_apply(pg_solver* s, int32_t which, const double* r, double* z);
 
 /* The Hessenberg matrix of the estimate pg_solver_spectral_estimate(s, which) describes (tests/test_gpu_specest.py compares it
    with the numpy restatement tests/specest_reference.py): (steps + 1) x steps doubles, column major.  Two-call size pattern:

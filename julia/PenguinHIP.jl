@@ -24,7 +24,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        solve_MovingDiffusionUnsteadyMono!, MovingDiffusionUnsteadyDiph, solve_MovingDiffusionUnsteadyDiph!,
        MovingAdvDiffusionUnsteadyMono, solve_MovingAdvDiffusionUnsteadyMono!, MovingAdvDiffusionUnsteadyDiph,
        solve_MovingAdvDiffusionUnsteadyDiph!, MovingLiquidDiffusionUnsteadyMono, solve_MovingLiquidDiffusionUnsteadyMono!,
-       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, spectral_estimate,
+       MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, mg_step_info, spectral_estimate,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
        set_separable!, clear_separable!, time_data_info, Monitor, VolumeIntegral, InterfaceFlux, Probe, set_monitors!,
        clear_monitors!, monitor_info, monitor_series, drop_states!, ∇, ∇₋, gmres, bicgstabl, cg
@@ -104,18 +104,24 @@ end
 # precond = :poly_est (PG_PRECOND_POLY_EST): the polynomial preconditioner of precond = 0, admitted on an estimated spectral disc
 # where Gershgorin refuses it -- diphasic systems and Robin / Neumann interfaces of the unsteady diffusion solvers; one rank,
 # BiCGStab, DiffusionOps, no moving body; the library refuses it anywhere else (spectral_estimate tells what the estimate found).
+# precond = :mg_step (PG_PRECOND_MG_STEP): the cell-aggregated V-cycle inside the time loop of DiffusionUnsteadyMono /
+# DarcyFlowUnsteady (Dirichlet, Robin or Neumann interface) and DiffusionUnsteadyDiph (BE and CN; DiffusionOps, one rank, BiCGStab)
+# for steps far above h²; one hierarchy per assembled matrix (mg_step_info).  The library refuses it on steady and moving solvers, a
+# ConvectionOps, a StreamVorticity, cg / gmres / bicgstabl with l, and where a coarse diagonal entry is not positive.
 const PG_PRECOND_MG = Int32(-2)
 const PG_PRECOND_MG_CELL = Int32(-3)
 const PG_PRECOND_POLY_EST = Int32(-4)
+const PG_PRECOND_MG_STEP = Int32(-5)
 function _precond_id(p)
     p isa Symbol || return Int32(p)
     p === :mg && return PG_PRECOND_MG
     p === :poly_est && return PG_PRECOND_POLY_EST
-    p === :mg_cell || error("precond must be an integer, :mg, :mg_cell or :poly_est, not :$(p)")
+    p === :mg_step && return PG_PRECOND_MG_STEP
+    p === :mg_cell || error("precond must be an integer, :mg, :mg_cell, :mg_step or :poly_est, not :$(p)")
     PG_PRECOND_MG_CELL
 end
 # method = bicgstabl, l = 2 (4, ...): BiCGStab(l) -- one rank, zero initial guess, plain (refused with precond = m >= 1, :mg,
-# :mg_cell, :poly_est; l > 8 is refused).  Its iteration counts are BiCG sub-steps, two products each, the unit maxiter caps;
+# :mg_cell, :mg_step, :poly_est; l > 8 is refused).  Its iteration counts are BiCG sub-steps, two products each, the unit maxiter caps;
 # max_mv_products (IterativeSolvers' spelling) is converted: maxiter = max_mv_products ÷ 2.  Without l the name means BiCGStab.
 function _opts(method, kw; warm_default::Bool=true)
     id = _method_id(method, kw)
@@ -1694,6 +1700,24 @@ function mg_info(s; precond=:mg)
      setup_ms = reinterpret(Float64, buf[34]), bytes = buf[35])
 end
 
+function _mg_info_tuple(buf)
+    levels = Int(buf[1] & 0xffffffff); tail = Int((buf[1] >> 32) & 0xffffffff)
+    (levels = levels, tail_level = tail, rows = buf[2:1 + levels], nnz = buf[18:17 + levels],
+     setup_ms = reinterpret(Float64, buf[34]), bytes = buf[35])
+end
+
+"""
+The hierarchy of `precond = :mg_step` of system `which` (0 constructor, 1 run system; `pg_solver_mg_step_info`), as `mg_info`
+reports it: levels = 0 while no solve with the option has run on that matrix.
+"""
+function mg_step_info(s, which::Integer=0)
+    buf = zeros(Int64, 35)
+    GC.@preserve buf begin
+        check(ccall((:pg_solver_mg_step_info, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}), s.handle, Int32(which), pointer(buf)))
+    end
+    _mg_info_tuple(buf)
+end
+
 """
 The spectral estimate behind `precond = :poly_est` of system `which` (0 constructor, 1 run system; `pg_solver_spectral_estimate`).
 Runs the estimate if it has not run on that matrix; `run = false` only reports (`steps == 0`: none has run).
@@ -1712,7 +1736,7 @@ function spectral_estimate(s, which::Integer=0; run::Bool=true)
      estimate_ms = f(10))
 end
 
-"`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg` and `:mg_cell` make them fail with the one-rank refusal)."
+"`pg_krylov_opts.precond` of the virtual-rank diagnostic runs that follow (`:mg`, `:mg_cell` and `:mg_step` make them fail with the one-rank refusal)."
 set_virtual_rank_precond(p) = check(ccall((:pg_debug_set_virtual_rank_precond, libpg), Int32, (Int32,), _precond_id(p)))
 
 "One application z = M⁻¹ r of the multigrid V-cycle on host vectors (`pg_debug_mg_apply_for`; builds the hierarchy if need be)."
@@ -1741,6 +1765,38 @@ function mg_level_matrix(s, level::Integer)
     check(ccall((:pg_debug_mg_level_csr, libpg), Int32,
                 (Ptr{Cvoid}, Int32, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
                 s.handle, level, n, nnz, rowptr, col, val))
+    rows = [i for i in 1:n[] for _ in rowptr[i] + 1:rowptr[i + 1]]
+    sparse(rows, col[1:nnz[]] .+ 1, val[1:nnz[]], n[], n[])
+end
+
+"One application z = M⁻¹ r of the `:mg_step` V-cycle of system `which` (`pg_debug_mg_step_apply`; builds the hierarchy if need be)."
+function mg_step_apply(s, which::Integer, r::Vector{Float64})
+    z = zeros(Float64, length(r))
+    check(ccall((:pg_debug_mg_step_apply, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}), s.handle, Int32(which), r, z))
+    z
+end
+
+"Aggregate map of `level` of the `:mg_step` hierarchy of system `which` (`pg_debug_mg_step_aggregates`), 0-based rows of level + 1."
+function mg_step_aggregates(s, which::Integer, level::Integer)
+    n = Ref{Int64}(0)
+    check(ccall((:pg_debug_mg_step_aggregates, libpg), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{Int64}, Ptr{Int32}),
+                s.handle, Int32(which), Int32(level), n, C_NULL))
+    agg = zeros(Int32, n[])
+    check(ccall((:pg_debug_mg_step_aggregates, libpg), Int32, (Ptr{Cvoid}, Int32, Int32, Ref{Int64}, Ptr{Int32}),
+                s.handle, Int32(which), Int32(level), n, agg))
+    agg
+end
+
+"The matrix of `level` of the `:mg_step` hierarchy of system `which` (`pg_debug_mg_step_level_csr`) as a SparseMatrixCSC."
+function mg_step_level_matrix(s, which::Integer, level::Integer)
+    n = Ref{Int64}(0); nnz = Ref{Int64}(0)
+    check(ccall((:pg_debug_mg_step_level_csr, libpg), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                s.handle, Int32(which), Int32(level), n, nnz, C_NULL, C_NULL, C_NULL))
+    rowptr = zeros(Int64, n[] + 1); col = zeros(Int64, max(nnz[], 1)); val = zeros(Float64, max(nnz[], 1))
+    check(ccall((:pg_debug_mg_step_level_csr, libpg), Int32,
+                (Ptr{Cvoid}, Int32, Int32, Ref{Int64}, Ref{Int64}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}),
+                s.handle, Int32(which), Int32(level), n, nnz, rowptr, col, val))
     rows = [i for i in 1:n[] for _ in rowptr[i] + 1:rowptr[i + 1]]
     sparse(rows, col[1:nnz[]] .+ 1, val[1:nnz[]], n[], n[])
 end

@@ -36,6 +36,7 @@ PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a 
 PG_PRECOND_MG = -2                   # pg_krylov_opts.precond: the aggregation multigrid V-cycle
 PG_PRECOND_MG_CELL = -3              # ... on the cell-aggregated hierarchy (Dirichlet, Robin and Neumann interfaces)
 PG_PRECOND_POLY_EST = -4             # ... the polynomial of precond = 0, admitted on an estimated spectral disc where Gershgorin refuses
+PG_PRECOND_MG_STEP = -5              # ... the cell-aggregated V-cycle inside the unsteady time loop (large steps)
 PG_SPECEST_MARGIN = 0.0205           # added to the estimate's max |theta - 1| before the test against 0.95
 PG_MG_MAX_LEVELS = 16
 
@@ -271,6 +272,47 @@ def debug_mg_apply(handle, r: np.ndarray, precond: int = PG_PRECOND_MG) -> np.nd
     r = np.ascontiguousarray(r, dtype=np.float64)
     z = np.zeros_like(r)
     check(lib().pg_debug_mg_apply_for(handle, C.c_int32(precond), dptr(r), dptr(z)))
+    return z
+
+
+# ---- the same for the hierarchies of PG_PRECOND_MG_STEP (which: 0 the constructor's system, 1 the run system) -----------------
+def _mg_info_dict(info) -> dict:
+    n = info.levels
+    return {"levels": n, "tail_level": info.tail_level, "rows": list(info.rows[:n]), "nnz": list(info.nnz[:n]),
+            "setup_ms": info.setup_ms, "bytes": info.bytes}
+
+
+def solver_mg_step_info(handle, which: int = 0) -> dict:
+    """pg_solver_mg_step_info: as solver_mg_info, for the hierarchy of system `which`."""
+    info = pg_mg_info()
+    check(lib().pg_solver_mg_step_info(handle, C.c_int32(which), C.byref(info)))
+    return _mg_info_dict(info)
+
+
+def debug_mg_step_aggregates(handle, which: int, level: int) -> np.ndarray:
+    """pg_debug_mg_step_aggregates: the row of level + 1 every row of `level` belongs to."""
+    n = C.c_int64(0)
+    check(lib().pg_debug_mg_step_aggregates(handle, C.c_int32(which), C.c_int32(level), C.byref(n), None))
+    agg = np.zeros(max(n.value, 1), dtype=np.int32)
+    check(lib().pg_debug_mg_step_aggregates(handle, C.c_int32(which), C.c_int32(level), C.byref(n), agg.ctypes.data_as(c_i32_p)))
+    return agg[: n.value]
+
+
+def debug_mg_step_level_csr(handle, which: int, level: int):
+    """pg_debug_mg_step_level_csr: (rowptr, col, val) of the matrix of `level` (0: the Krylov matrix of system `which`)."""
+    n, nnz = C.c_int64(0), C.c_int64(0)
+    w = C.c_int32(which)
+    check(lib().pg_debug_mg_step_level_csr(handle, w, C.c_int32(level), C.byref(n), C.byref(nnz), None, None, None))
+    rowptr, col, val = np.zeros(n.value + 1, dtype=np.int64), np.zeros(max(nnz.value, 1), dtype=np.int64), np.zeros(max(nnz.value, 1))
+    check(lib().pg_debug_mg_step_level_csr(handle, w, C.c_int32(level), C.byref(n), C.byref(nnz), iptr(rowptr), iptr(col), dptr(val)))
+    return rowptr, col[: nnz.value], val[: nnz.value]
+
+
+def debug_mg_step_apply(handle, which: int, r: np.ndarray) -> np.ndarray:
+    """pg_debug_mg_step_apply: z = M⁻¹ r, one application of the V-cycle of system `which` as the time loop runs it."""
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    z = np.zeros_like(r)
+    check(lib().pg_debug_mg_step_apply(handle, C.c_int32(which), dptr(r), dptr(z)))
     return z
 
 

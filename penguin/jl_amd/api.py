@@ -985,6 +985,11 @@ class Solver:
         one hierarchy per value."""
         return L.solver_mg_info(self._h, _precond_value(precond))
 
+    def mg_step_info(self) -> list:
+        """The two hierarchies of precond="mg-step" (pg_solver_mg_step_info): [constructor system, run system], each as mg_info
+        reports (levels = 0 while no solve with the option has run on that matrix)."""
+        return [L.solver_mg_step_info(self._h, which) for which in (0, 1)]
+
     def spectral_estimate(self, which: int = 0, run: bool = True) -> dict:
         """The spectral estimate behind precond="poly-est" of system `which` (0 constructor, 1 run system;
         pg_solver_spectral_estimate): steps, g_ritz, g_used, margin, admitted, gershgorin, gershgorin_admits, the smallest /
@@ -1109,15 +1114,16 @@ def _step_info_check(s: "Solver", info: L.pg_step_info, what: str) -> None:
     _check_converged(s, bool(info.converged), what, info.resnorm / info.bnorm if info.bnorm > 0 else info.resnorm)
 
 
-_PRECOND_NAMES = {"mg": L.PG_PRECOND_MG, "mg-cell": L.PG_PRECOND_MG_CELL, "poly-est": L.PG_PRECOND_POLY_EST}
+_PRECOND_NAMES = {"mg": L.PG_PRECOND_MG, "mg-cell": L.PG_PRECOND_MG_CELL, "poly-est": L.PG_PRECOND_POLY_EST,
+                  "mg-step": L.PG_PRECOND_MG_STEP}
 
 
 def _precond_value(precond) -> int:
     """pg_krylov_opts.precond of a `precond` keyword: an integer as it is, "mg" -> PG_PRECOND_MG, "mg-cell" -> PG_PRECOND_MG_CELL,
-    "poly-est" -> PG_PRECOND_POLY_EST (names in any case)."""
+    "poly-est" -> PG_PRECOND_POLY_EST, "mg-step" -> PG_PRECOND_MG_STEP (names in any case)."""
     if isinstance(precond, str):
         if precond.lower() not in _PRECOND_NAMES:
-            raise ValueError(f'precond must be an integer, "mg", "mg-cell" or "poly-est", not {precond!r}')
+            raise ValueError(f'precond must be an integer, "mg", "mg-cell", "poly-est" or "mg-step", not {precond!r}')
         return _PRECOND_NAMES[precond.lower()]
     return int(precond)
 
@@ -1126,7 +1132,7 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     """method may be "bicgstab" / "cg" / "gmres" or a callable named like IterativeSolvers' (bicgstabl, cg, gmres...).
     gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; bicgstabl WITH the keyword l (l=2, l=4, ..,
     at most 8) -> BiCGStab(l) on the device (DESIGN.md "BiCGStab(l)": one rank, zero initial guess, plain -- the library refuses
-    it together with precond = m >= 1, "mg", "mg-cell" or "poly-est"); `\\`, bicgstabl WITHOUT l and anything else -> BiCGStab.
+    it together with precond = m >= 1, "mg", "mg-cell", "mg-step" or "poly-est"); `\\`, bicgstabl WITHOUT l and anything else -> BiCGStab.
     BiCGStab(l) counts BiCG sub-steps as its iterations, two products each -- the unit of BiCGStab's iterations, and the unit
     maxiter caps (no outer iteration starts at iters >= maxiter); products = 2 iters + the products that confirm the true residual.
     max_mv_products (IterativeSolvers' spelling of the cap) is accepted when maxiter is not given: maxiter = max_mv_products // 2.
@@ -1137,7 +1143,12 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     (steady monophasic diffusion, DarcyFlow included, with a Dirichlet, Robin or Neumann interface), or "poly-est": the
     polynomial preconditioner of precond = 0, admitted on an estimated spectral disc where Gershgorin refuses it (diphasic
     systems, Robin / Neumann interfaces of the unsteady diffusion solvers; one rank, BiCGStab, DiffusionOps, no moving body --
-    refused anywhere else; Solver.spectral_estimate tells what the estimate found)."""
+    refused anywhere else; Solver.spectral_estimate tells what the estimate found), or "mg-step": the cell-aggregated V-cycle
+    inside the time loop of DiffusionUnsteadyMono / DarcyFlowUnsteady (Dirichlet, Robin or Neumann interface) and
+    DiffusionUnsteadyDiph (BE and CN; DiffusionOps, one rank, BiCGStab) for steps far above h² -- one hierarchy per assembled matrix (Solver.mg_step_info), the
+    iteration on the full system, warm-started from the previous state.  The library refuses it on steady and moving
+    solvers, a ConvectionOps, a StreamVorticity, cg / gmres / bicgstabl with l, and where a coarse diagonal entry is not
+    positive (DESIGN.md section 20 has the measured crossover)."""
     name = method if isinstance(method, str) else getattr(method, "__name__", "bicgstab")
     name = name.lower()
     restart = int(kwargs.get("restart", 0))

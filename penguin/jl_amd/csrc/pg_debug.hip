@@ -213,6 +213,8 @@ extern "C" int32_t pg_debug_run_virtual_ranks(int32_t nranks, int32_t N, const i
                                          "(virtual ranks included)");
   PG_REQUIRE(g_precond != PG_PRECOND_MG_CELL, "multigrid preconditioner (precond = PG_PRECOND_MG_CELL) refused: it runs on one rank only "
                                               "(virtual ranks included)");
+  PG_REQUIRE(g_precond != PG_PRECOND_MG_STEP, "multigrid preconditioner (precond = PG_PRECOND_MG_STEP) refused: it runs on one rank only "
+                                              "(virtual ranks included)");
   PG_REQUIRE(g_precond != PG_PRECOND_POLY_EST, "estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST) refused: it runs on "
                                                "one rank only (virtual ranks included)");
   VArgs a{nranks, N, n, L, body_kind, params, nparams, interface_value, border_value, nkeys, keys, dt,

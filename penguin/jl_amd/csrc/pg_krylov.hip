@@ -689,6 +689,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   }
   const int precond = est_opt ? 0 : opts.precond;
   if (opts.method == PG_METHOD_GMRES) {
+    PG_REQUIRE(!mg_is_step(opts.precond), std::string("multigrid preconditioner (precond = PG_PRECOND_MG_STEP) refused: ") +
+                                              krylov_method_refusal(opts.method));
     PG_REQUIRE(!preinit && !x0, "GMRES starts from zero (IterativeSolvers' default)");
     gmres_solve(A, nb, slab, b, x, w, opts, stats);
     return;
@@ -696,8 +698,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   if (opts.method == PG_METHOD_BICGSTABL) {
     // opt-in, plain: every preconditioner of the BiCGStab loop is refused with it rather than dropped without a word
     PG_REQUIRE(!preinit && !x0, "BiCGStab(l) starts from zero (IterativeSolvers' default)");
-    PG_REQUIRE(!mg_is_precond(opts.precond), std::string("multigrid preconditioner (precond = ") + mg_precond_name(mg_rule_of(opts.precond)) +
-                                                 ") refused: " + krylov_method_refusal(opts.method));
+    PG_REQUIRE(!mg_any_precond(opts.precond), std::string("multigrid preconditioner (precond = ") + mg_precond_name_of(opts.precond) +
+                                                  ") refused: " + krylov_method_refusal(opts.method));
     PG_REQUIRE(opts.precond <= 0, "polynomial preconditioner (precond = " + std::to_string(opts.precond) + ") refused: " +
                                       krylov_method_refusal(opts.method) + "; precond = 0 or -1 runs BiCGStab(l) plain");
     w.mg = nullptr;
@@ -750,16 +752,20 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   const bool poly = m > 0;
   MgHierarchy* const mgh = w.mg;
   w.mg = nullptr;
-  const bool mg = mg_is_precond(opts.precond);
+  const bool mg = mg_any_precond(opts.precond);   // (PG_PRECOND_MG_STEP: the same loop from the time loop's prepared start)
   if (mg) {
     PG_REQUIRE(!cg, "multigrid preconditioner refused: the method must be BiCGStab");
     PG_REQUIRE(spmv_supports_preconditioner_product(), "multigrid preconditioner refused: the x-space loop needs the slice kernel (PG_SPMV_VARIANT)");
-    mg_require_one_rank(mg_rule_of(opts.precond));
-    PG_REQUIRE(mgh && !w.scatter && !xg.zbase && n > 0, "multigrid preconditioner refused: this solve has no hierarchy (steady monophasic "
-               "diffusion systems and the stream-function solve only)");
-    PG_REQUIRE(mgh->rule == mg_rule_of(opts.precond),
+    mg_require_one_rank_of(opts.precond);
+    PG_REQUIRE(mgh && !w.scatter && !xg.zbase && n > 0,
+               mg_is_step(opts.precond)
+                   ? "multigrid preconditioner refused: this solve has no hierarchy (the full systems of the unsteady monophasic "
+                     "diffusion time loop only)"
+                   : "multigrid preconditioner refused: this solve has no hierarchy (steady monophasic "
+                     "diffusion systems and the stream-function solve only)");
+    PG_REQUIRE(mgh->rule == mg_rule_of_any(opts.precond) && mgh->matrix == &A,
                std::string("multigrid preconditioner: the hierarchy handed over was not built for precond = ") +
-                   mg_precond_name(mg_rule_of(opts.precond)));
+                   mg_precond_name_of(opts.precond));
   }
   const bool pre = poly || mg;   // right-preconditioned: x moves by α M⁻¹p (k_bicg_s_x) and ω M⁻¹s (k_bicg_xrp)
   stats.poly_degree = m;

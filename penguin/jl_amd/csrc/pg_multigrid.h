@@ -2,6 +2,8 @@
 // driver (pg_krylov.hip) for steady monophasic diffusion systems with a Dirichlet interface (DESIGN.md "Multigrid"), and its
 // cell-aggregated sibling `precond = PG_PRECOND_MG_CELL` for Dirichlet, Robin and Neumann interfaces alike (DESIGN.md
 // "Cell-aggregated multigrid"): the same cycle on a hierarchy whose first coarsening merges the ω and γ unknowns of a cell.
+// `precond = PG_PRECOND_MG_STEP` runs that cell-rule cycle on the systems of the unsteady time loop (DESIGN.md "Multigrid in
+// the time loop"): the same set-up and the same kernels on another matrix, one hierarchy per assembled matrix.
 #pragma once
 #include <memory>
 
@@ -27,6 +29,12 @@ enum MgRule { MG_RULE_KIND = 0, MG_RULE_CELL = 1 };
 inline bool mg_is_precond(int precond) { return precond == PG_PRECOND_MG || precond == PG_PRECOND_MG_CELL; }
 inline MgRule mg_rule_of(int precond) { return precond == PG_PRECOND_MG_CELL ? MG_RULE_CELL : MG_RULE_KIND; }
 inline const char* mg_precond_name(MgRule rule) { return rule == MG_RULE_CELL ? "PG_PRECOND_MG_CELL" : "PG_PRECOND_MG"; }
+// PG_PRECOND_MG_STEP: the cell rule's V-cycle inside the unsteady time loop (DESIGN.md "Multigrid in the time loop").  A value of
+// its own: mg_is_precond stays the test for the two steady values, whose conditions refuse every time step.
+inline bool mg_is_step(int precond) { return precond == PG_PRECOND_MG_STEP; }
+inline bool mg_any_precond(int precond) { return mg_is_precond(precond) || mg_is_step(precond); }
+inline MgRule mg_rule_of_any(int precond) { return mg_is_step(precond) ? MG_RULE_CELL : mg_rule_of(precond); }
+inline const char* mg_precond_name_of(int precond) { return mg_is_step(precond) ? "PG_PRECOND_MG_STEP" : mg_precond_name(mg_rule_of(precond)); }
 
 // One level.  Level 0 borrows the Krylov matrix Â (unit diagonal: dinv == nullptr); coarser levels own their Galerkin product
 // A_{l+1} = P_lᵀ A_l P_l (not equilibrated: the smoother divides by the diagonal).
@@ -60,6 +68,7 @@ struct MgHierarchy {
 
 // the one place the one-rank condition is written (pg_solver.hip mg_conditions, mg_build, krylov_solve)
 void mg_require_one_rank(MgRule rule = MG_RULE_KIND);
+void mg_require_one_rank_of(int precond);   // ... with the name of any of the three values in the message
 // Builds the hierarchy of Â (one rank, no ghosts; a positive diagonal is checked): aggregate maps, coarse
 // numbering (flag + scan) and the Galerkin products on the device, the dense inverse of the last level on the host.
 void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Slab& slab, MgRule rule = MG_RULE_KIND);

@@ -318,12 +318,23 @@ void mg_require_one_rank(MgRule rule) {
                                                           ") refused: it runs on one rank only (virtual ranks included)");
 }
 
+void mg_require_one_rank_of(int precond) {
+  Context& cx = ctx();
+  PG_REQUIRE(cx.nranks == 1 && !cx.comm && !cx.local, std::string("multigrid preconditioner (precond = ") + mg_precond_name_of(precond) +
+                                                          ") refused: it runs on one rank only (virtual ranks included)");
+}
+
 void mg_build(MgHierarchy& H, const CsrMatrix& A, const Numbering& nb, const Slab& slab, MgRule rule) {
   Context& cx = ctx();
   hipStream_t st = cx.stream;
   mg_require_one_rank(rule);
   PG_REQUIRE(nb.n_ghost == 0 && slab.s0 == 0 && slab.Mloc() == slab.M, "multigrid set-up: the numbering of one rank (no ghosts, every plane) is expected");
-  PG_REQUIRE(nb.K == 2, "multigrid preconditioner refused: a monophasic system (two kinds of unknowns) is expected");
+  // (the cell rule merges whatever kinds a cell has: the child table between levels 0 and 1 is 8 K wide, K = 4 on a diphasic
+  //  system -- slot = cell parity + 8 kind -- and every kernel reads the width from the level.  The callers decide which systems
+  //  come here: pg_solver.hip mg_conditions keeps diphasic systems away from PG_PRECOND_MG and PG_PRECOND_MG_CELL.)
+  PG_REQUIRE(nb.K == 2 || (rule == MG_RULE_CELL && nb.K == 4),
+             "multigrid preconditioner refused: a monophasic system (two kinds of unknowns) is expected");
+  static_assert(8 * MAX_KINDS <= 255, "k_mg_key0 keeps 8 * kind in a byte");
   PG_REQUIRE(A.n > 0 && A.n == nb.n_own, "multigrid preconditioner refused: empty system");
   PG_REQUIRE((i64)nb.K * slab.M < (i64)2000000000, "multigrid preconditioner: grid too large for 32-bit cell keys");
   PG_HIP(hipStreamSynchronize(st));

@@ -138,6 +138,9 @@ struct pg_solver {
     std::vector<double> times;     // s->t of every row
   };
   Monitors mon;
+  // the two hierarchies of PG_PRECOND_MG_STEP, one per assembled matrix of the time loop: [0] A_ctor, [1] A_run (dropped with
+  // it); slots of their own, beside mg / mg_cell above.  (At the end: every field the default loop touches keeps its offset.)
+  MgHierarchy mg_step[2];
 };
 
 namespace {
@@ -1544,6 +1547,7 @@ void ensure_run_matrix(pg_solver* s, int scheme) {
   s->spec_y_valid = false;          // (a product queued ahead with the matrix that is about to be replaced)
   s->elim_run = GammaElim();        // (belongs to the matrix that is about to be replaced)
   s->diag_run = DiagElim();
+  if (!s->mg_step[1].lev.empty()) s->mg_step[1] = MgHierarchy();
   if (s->blk_cache_matrix == &s->A_run) s->blk_cache_matrix = nullptr;
   assemble_csr_like(P, s->slab, s->nb, s->A_ctor, s->A_run);
   s->A_run.scheme = scheme;
@@ -1718,6 +1722,37 @@ void mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
   s->work.mg = &mg_ensure(s, rule);
 }
 
+// opts.precond = PG_PRECOND_MG_STEP: the cell rule's V-cycle inside the unsteady time loop.  Served on the systems of
+// DiffusionUnsteadyMono (Dirichlet, Robin or Neumann interface) and DiffusionUnsteadyDiph, BE and CN; refused with the failed
+// condition anywhere else.
+void mg_step_conditions(const pg_solver* s, int method) {
+  const std::string who = "multigrid preconditioner (precond = PG_PRECOND_MG_STEP) refused: ";
+  mg_require_one_rank_of(PG_PRECOND_MG_STEP);
+  PG_REQUIRE(s->scheme_ctor != PG_SCHEME_STEADY,
+             who + "the system is a steady one (the time loop of the unsteady monophasic diffusion solver only; steady solves are "
+                   "served by PG_PRECOND_MG and PG_PRECOND_MG_CELL)");
+  PG_REQUIRE(!s->moving, who + "a moving-body solver (every space-time slab is a new matrix that is solved once)");
+  PG_REQUIRE(!s->solved_once, who + "the vorticity solver of a pg_streamvort step (a new matrix every step, solved once)");
+  PG_REQUIRE(!s->advdiff && !s->convection && !(s->ops[0] && s->ops[0]->has_velocity),
+             who + "the operator is a ConvectionOps (DiffusionOps only)");
+  // (diphasic systems are served: the cell rule merges the four kinds of unknowns of a cell as it merges two -- mg_build)
+  PG_REQUIRE(method == PG_METHOD_BICGSTAB, who + krylov_method_refusal(method));
+}
+
+// the hierarchy of A (&s->A_ctor or &s->A_run), built on first use and kept for the life of the matrix.  A set-up that fails (a
+// coarse diagonal entry that is not positive) is the refusal of this solve: nothing is kept, nothing else runs in its place.
+MgHierarchy& mg_step_ensure(pg_solver* s, const CsrMatrix& A) {
+  MgHierarchy& H = s->mg_step[&A == &s->A_ctor ? 0 : 1];
+  if (H.matrix == &A && !H.lev.empty()) return H;
+  try {
+    mg_build(H, A, s->nb, s->slab, MG_RULE_CELL);
+  } catch (...) {
+    H = MgHierarchy();
+    throw;
+  }
+  return H;
+}
+
 // opts.precond = PG_PRECOND_POLY_EST: what it is refused on (with the condition that failed, as the multigrid does), then --
 // before every krylov_solve on A that takes the caller's options, and only where Gershgorin refuses A -- the spectral estimate of
 // A (pg_specest.hip), once per assembled matrix.  Where Gershgorin admits A nothing runs: the solve is the precond = 0 solve.
@@ -1739,6 +1774,10 @@ void specest_prepare(pg_solver* s, const CsrMatrix& A, const pg_krylov_opts& o) 
 void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
   mg_prepare(s, o);
+  if (mg_is_step(o.precond)) {
+    mg_step_conditions(s, o.method);
+    s->work.mg = &mg_step_ensure(s, s->A_ctor);
+  }
   specest_prepare(s, s->A_ctor, o);
   // solve_system!(s) with the constructor's A and b (diffusion.jl:275)
   const i64 n = s->nb.n_own;
@@ -1872,6 +1911,14 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   PG_REQUIRE(s->initial_done, "Solver is not initialized. Call pg_solver_initial_solve first.");
   const pg_krylov_opts o = opts ? *opts : default_opts();
   if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (refuses: a time step is an unsteady system)
+  // PG_PRECOND_MG_STEP: its conditions and the hierarchy of this step's matrix before the step consumes anything (time, a row of
+  // the coefficient table) -- a refusal, the set-up's included, leaves the solver where it was
+  const bool mgs = mg_is_step(o.precond);
+  if (mgs) {
+    mg_step_conditions(s, o.method);
+    ensure_run_matrix(s, scheme);
+    mg_step_ensure(s, run_matrix(s));
+  }
   // time-separable data: this step's row of the coefficient table -- never an older one
   for (const auto& t : s->td)
     PG_REQUIRE(t.K == 0 || s->td_cursor < t.nrows,
@@ -1924,8 +1971,9 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     KrylovWork& w = s->work;
     // rows alone on their diagonal (interface AND border identity rows) left out, compact vectors (pg_reduce.hip, DiagElim)
     DiagElim& DE = (&A == &s->A_ctor) ? s->diag_ctor : s->diag_run;
-    if (!DE.tried) build_diag_elim(A, s->nb, s->slab, DE);
-    if (DE.active && krylov_uses_polynomial(DE.A, o)) {
+    // (PG_PRECOND_MG_STEP iterates on the full system: neither the compact system nor the γ elimination starts)
+    if (!mgs && !DE.tried) build_diag_elim(A, s->nb, s->slab, DE);
+    if (!mgs && DE.active && krylov_uses_polynomial(DE.A, o)) {
       // r = r̂ = p of the remaining rows go straight to the compact vectors; the other rows are solved in the same pass
       const int stamp = (int)((s->steps_done % 2000000000) + 1);   // marks E.flag when a diagonal row moved in THIS step
       // quiet: the previous step ran this path with the same constant data, so every diagonal row already holds its solution
@@ -2042,14 +2090,15 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     }
     // Dirichlet interface: the γ rows are rows of the identity -- solved here, the iteration runs on Â_ωω (pg_reduce.hip)
     GammaElim& E = (&A == &s->A_ctor) ? s->elim_ctor : s->elim_run;
-    if (!E.tried) build_gamma_elim(A, s->nb, E);
+    if (!mgs && !E.tried) build_gamma_elim(A, s->nb, E);
+    const bool e_active = !mgs && E.active;
     // The plain warm path (no row left out: diphasic systems, interfaces with Robin / Neumann conditions and no border rows)
     // takes the extrapolated start as well, on one rank: the kept products are products of whole states whatever the data do,
     // so steps with changing data qualify too.
     const bool single = ctx().nranks == 1 && !ctx().comm;
     const int which = (&A == &s->A_ctor) ? 0 : 1;
-    if (single && !E.active) guess_policy(s->plain_guess_on[which], s->plain_last_products[which], (double)A.spmv_bytes);
-    const GuessPlan gp = guess_prepare(s, &A, single && !E.active && s->plain_guess_on[which], s->plain_last_products[which], stream);
+    if (single && !e_active) guess_policy(s->plain_guess_on[which], s->plain_last_products[which], (double)A.spmv_bytes);
+    const GuessPlan gp = guess_prepare(s, &A, single && !e_active && s->plain_guess_on[which], s->plain_last_products[which], stream);
 #define PG_RHS_INIT(KHV)                                                                                                          \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, s->nb.n_vec(), scheme, s->z.p,     \
                      s->y.p, A.ds.p, s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, s->b.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, \
@@ -2064,7 +2113,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
 #undef PG_RHS_INIT
     PG_HIP(hipGetLastError());
     guess_after_rhs(s, gp, n, nullptr, (const double*)A.ds.p, (const double*)w.rhat.p, true, w, stream);
-    if (E.active) {
+    if (e_active) {
       gamma_fix(E, s->z.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, w.grid, stream);
       // the sub-matrix carries Gershgorin's verdict on Â but no spectral estimate: PG_PRECOND_POLY_EST is precond = 0 here (the
       // polynomial where Gershgorin admits, the plain loop where it refuses -- DESIGN.md section 16)
@@ -2073,6 +2122,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       krylov_solve(E.A, E.nb, s->slab, s->b.p, s->z.p, w, oe, st, nullptr, nullptr, true);
     } else {
       // y0 = z (in place), r0 = b̂ - ŷ: same solution as a zero start, fewer iterations
+      if (mgs) w.mg = &mg_step_ensure(s, A);
       krylov_solve(A, s->nb, s->slab, s->b.p, s->z.p, w, o, st, nullptr, nullptr, true);
       s->plain_last_products[which] = (double)st.products;
       guess_commit(s, gp, &A);
@@ -2099,6 +2149,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
                            s->bconst.p, s->fixed.p, s->b.p);
       PG_HIP(hipGetLastError());
     }
+    if (mgs) s->work.mg = &mg_step_ensure(s, A);
     krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
     std::swap(s->z.p, s->ysol.p);
     s->z_matrix = &A;
@@ -2998,6 +3049,40 @@ int32_t pg_solver_stefan_terms(const pg_solver* s, double* out) {
   PG_API_END
 }
 
+static void fill_mg_info(const MgHierarchy& H, pg_mg_info* out) {
+  out->levels = (int32_t)H.lev.size();
+  out->tail_level = H.tail0;
+  for (size_t l = 0; l < H.lev.size() && l < PG_MG_MAX_LEVELS; ++l) {
+    out->rows[l] = H.lev[l]->n;
+    out->nnz[l] = H.lev[l]->nnz;
+  }
+  out->setup_ms = H.setup_ms;
+  out->bytes = H.bytes;
+}
+
+// one level of a hierarchy to the host (two-call size pattern: NULL arrays are skipped)
+static void download_mg_level(const MgLevel& v, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col, double* val) {
+  if (n) *n = v.n;
+  if (nnz) *nnz = v.nnz;
+  hipStream_t st = ctx().stream;
+  if (rowptr) {
+    std::vector<int> h(v.n + 1);
+    PG_HIP(hipMemcpyAsync(h.data(), v.rowptr, sizeof(int) * (size_t)(v.n + 1), hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    for (i64 i = 0; i <= v.n; ++i) rowptr[i] = h[i];
+  }
+  if (col && v.nnz > 0) {
+    std::vector<int> h(v.nnz);
+    PG_HIP(hipMemcpyAsync(h.data(), v.col, sizeof(int) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+    for (i64 i = 0; i < v.nnz; ++i) col[i] = h[i];
+  }
+  if (val && v.nnz > 0) {
+    PG_HIP(hipMemcpyAsync(val, v.val, sizeof(double) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
+    PG_HIP(hipStreamSynchronize(st));
+  }
+}
+
 static MgRule debug_mg_rule(int32_t precond) {
   PG_REQUIRE(mg_is_precond(precond), "multigrid diagnostics: precond must be PG_PRECOND_MG or PG_PRECOND_MG_CELL");
   return mg_rule_of(precond);
@@ -3011,14 +3096,7 @@ int32_t pg_solver_mg_info_for(const pg_solver* s, int32_t precond, pg_mg_info* o
   std::memset(out, 0, sizeof(*out));
   const MgHierarchy& H = debug_mg_rule(precond) == MG_RULE_CELL ? s->mg_cell : s->mg;
   if (H.matrix != &s->A_ctor) return 0;
-  out->levels = (int32_t)H.lev.size();
-  out->tail_level = H.tail0;
-  for (size_t l = 0; l < H.lev.size() && l < PG_MG_MAX_LEVELS; ++l) {
-    out->rows[l] = H.lev[l]->n;
-    out->nnz[l] = H.lev[l]->nnz;
-  }
-  out->setup_ms = H.setup_ms;
-  out->bytes = H.bytes;
+  fill_mg_info(H, out);
   PG_API_END
 }
 
@@ -3095,26 +3173,7 @@ int32_t pg_debug_mg_level_csr_for(pg_solver* s, int32_t precond, int32_t level, 
   PG_API_BEGIN
   MgHierarchy& H = debug_mg(s, precond);
   PG_REQUIRE(level >= 0 && level < (int)H.lev.size(), "pg_debug_mg_level_csr: no such level");
-  const MgLevel& v = *H.lev[level];
-  if (n) *n = v.n;
-  if (nnz) *nnz = v.nnz;
-  hipStream_t st = ctx().stream;
-  if (rowptr) {
-    std::vector<int> h(v.n + 1);
-    PG_HIP(hipMemcpyAsync(h.data(), v.rowptr, sizeof(int) * (size_t)(v.n + 1), hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
-    for (i64 i = 0; i <= v.n; ++i) rowptr[i] = h[i];
-  }
-  if (col && v.nnz > 0) {
-    std::vector<int> h(v.nnz);
-    PG_HIP(hipMemcpyAsync(h.data(), v.col, sizeof(int) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
-    for (i64 i = 0; i < v.nnz; ++i) col[i] = h[i];
-  }
-  if (val && v.nnz > 0) {
-    PG_HIP(hipMemcpyAsync(val, v.val, sizeof(double) * (size_t)v.nnz, hipMemcpyDeviceToHost, st));
-    PG_HIP(hipStreamSynchronize(st));
-  }
+  download_mg_level(*H.lev[level], n, nnz, rowptr, col, val);
   PG_API_END
 }
 
@@ -3128,6 +3187,66 @@ int32_t pg_debug_mg_apply_for(pg_solver* s, int32_t precond, const double* r, do
   dout.zero();
   din.upload(r, n);
   mg_apply(H, s->A_ctor, s->nb, s->slab, din.p, dout.p, nullptr, ctx().stream);
+  dout.download(z, n);
+  PG_API_END
+}
+
+// ---- PG_PRECOND_MG_STEP: the same report and diagnostics per assembled matrix (which = 0 constructor system, 1 run system)
+int32_t pg_solver_mg_step_info(const pg_solver* s, int32_t which, pg_mg_info* out) {
+  PG_API_BEGIN
+  PG_REQUIRE(s && out, "pg_solver_mg_step_info: NULL argument");
+  PG_REQUIRE(which == 0 || which == 1, "pg_solver_mg_step_info: which = 0 (constructor system) or 1 (run system)");
+  std::memset(out, 0, sizeof(*out));
+  const MgHierarchy& H = s->mg_step[which];
+  if (H.lev.empty() || H.matrix != (which == 0 ? &s->A_ctor : &s->A_run)) return 0;
+  fill_mg_info(H, out);
+  PG_API_END
+}
+
+// the matrix `which` names and its PG_PRECOND_MG_STEP hierarchy, built if need be
+static MgHierarchy& debug_mg_step(pg_solver* s, int32_t which, const CsrMatrix** A) {
+  require_init();
+  PG_REQUIRE(s, "multigrid diagnostics: NULL solver");
+  PG_REQUIRE(which == 0 || which == 1, "multigrid diagnostics: which = 0 (constructor system) or 1 (run system)");
+  mg_step_conditions(s, PG_METHOD_BICGSTAB);
+  PG_REQUIRE(which == 0 || (s->have_run && &run_matrix(s) == &s->A_run),
+             "multigrid diagnostics: the solver has no run system of its own (take a step in the other scheme first)");
+  *A = which == 0 ? &s->A_ctor : &s->A_run;
+  return mg_step_ensure(s, **A);
+}
+
+int32_t pg_debug_mg_step_aggregates(pg_solver* s, int32_t which, int32_t level, int64_t* n, int32_t* agg) {
+  PG_API_BEGIN
+  const CsrMatrix* A = nullptr;
+  MgHierarchy& H = debug_mg_step(s, which, &A);
+  PG_REQUIRE(level >= 0 && level + 1 < (int)H.lev.size(), "pg_debug_mg_step_aggregates: level has no aggregates (0 <= level < levels - 1)");
+  const MgLevel& v = *H.lev[level];
+  if (n) *n = v.n;
+  if (agg) v.agg.download(agg, v.n);
+  PG_API_END
+}
+
+int32_t pg_debug_mg_step_level_csr(pg_solver* s, int32_t which, int32_t level, int64_t* n, int64_t* nnz, int64_t* rowptr, int64_t* col,
+                                   double* val) {
+  PG_API_BEGIN
+  const CsrMatrix* A = nullptr;
+  MgHierarchy& H = debug_mg_step(s, which, &A);
+  PG_REQUIRE(level >= 0 && level < (int)H.lev.size(), "pg_debug_mg_step_level_csr: no such level");
+  download_mg_level(*H.lev[level], n, nnz, rowptr, col, val);
+  PG_API_END
+}
+
+int32_t pg_debug_mg_step_apply(pg_solver* s, int32_t which, const double* r, double* z) {
+  PG_API_BEGIN
+  const CsrMatrix* A = nullptr;
+  MgHierarchy& H = debug_mg_step(s, which, &A);
+  PG_REQUIRE(r && z, "pg_debug_mg_step_apply: NULL argument");
+  const i64 n = s->nb.n_own, nv = s->nb.n_vec();
+  DevBuf<double> din(nv), dout(nv);
+  din.zero();
+  dout.zero();
+  din.upload(r, n);
+  mg_apply(H, *A, s->nb, s->slab, din.p, dout.p, nullptr, ctx().stream);
   dout.download(z, n);
   PG_API_END
 }
@@ -3495,6 +3614,7 @@ void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st
   }
   const pg_krylov_opts o = opts ? *opts : default_opts();
   mg_prepare(s, o);
+  if (mg_is_step(o.precond)) mg_step_conditions(s, o.method);   // (refuses: a steady system)
   specest_prepare(s, s->A_ctor, o);
   hipStream_t stream = ctx().stream;
   const i64 n = s->nb.n_own;
@@ -3558,6 +3678,7 @@ static void refine_once(pg_solver* s, const pg_krylov_opts& o, SolveStats& st) {
 void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
   const pg_krylov_opts o = opts ? *opts : default_opts();
   if (mg_is_precond(o.precond)) mg_conditions(s, o.method, mg_rule_of(o.precond));   // (a solver built for one time step: refused)
+  if (mg_is_step(o.precond)) mg_step_conditions(s, o.method);                        // (likewise)
   specest_prepare(s, s->A_ctor, o);
   const i64 n = s->nb.n_own;
   if (!(o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) || s->initial_done) {

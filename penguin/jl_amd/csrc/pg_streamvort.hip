@@ -108,6 +108,9 @@ void solve_stream(pg_streamvort* sv, const pg_krylov_opts* opts, SolveStats& st,
   PG_REQUIRE(!(opts && opts->precond == PG_PRECOND_MG_CELL),
              "multigrid preconditioner (precond = PG_PRECOND_MG_CELL) refused: a StreamVorticity solver -- its stream-function solve "
              "has a Dirichlet interface and is served by PG_PRECOND_MG");
+  PG_REQUIRE(!(opts && opts->precond == PG_PRECOND_MG_STEP),
+             "multigrid preconditioner (precond = PG_PRECOND_MG_STEP) refused: a StreamVorticity solver -- its stream-function solve "
+             "is a steady system (served by PG_PRECOND_MG) and its vorticity solve a new ConvectionOps matrix every step");
   PG_REQUIRE(!(opts && opts->precond == PG_PRECOND_POLY_EST),
              "estimated polynomial preconditioner (precond = PG_PRECOND_POLY_EST) refused: a StreamVorticity solver -- one set of options "
              "serves both of its solves, and the operator of the vorticity solve is a ConvectionOps (DiffusionOps only); the "
