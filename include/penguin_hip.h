@@ -54,13 +54,21 @@ enum { PG_KEY_LEFT = 0 /* dim2 = 1 */, PG_KEY_RIGHT = 1 /* dim2 = n2 */, PG_KEY_
 enum { PG_SCHEME_BE = 0, PG_SCHEME_CN = 1,                   /* "BE" / "CN" strings of the reference */
        PG_SCHEME_STEADY = 2 };                                /* internal: the steady constructors */
 enum { PG_SV_PSI = 0, PG_SV_OMEGA = 1, PG_SV_U = 2, PG_SV_V = 3 };   /* fields / systems of a pg_streamvort */
-enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2, PG_METHOD_BICGSTABL = 3 };   /* IterativeSolvers methods
-   kept: bicgstab (also serves `\`, and bicgstabl when no l is given), cg, gmres (solve_system!'s default, src/solver.jl:158),
+enum { PG_METHOD_BICGSTAB = 0, PG_METHOD_CG = 1, PG_METHOD_GMRES = 2, PG_METHOD_BICGSTABL = 3,
+       PG_METHOD_IDRS = 4 };   /* IterativeSolvers methods
+   kept: bicgstab (also serves `\`, bicgstabl when no l is given and idrs when no s is given), cg, gmres (solve_system!'s default,
+   src/solver.jl:158),
    bicgstabl with l = pg_krylov_opts.restart (BiCGStab(l), DESIGN.md "BiCGStab(l)"): opt-in, one rank, zero initial guess
    (warm_start is ignored), plain -- refused together with precond = m >= 1, PG_PRECOND_MG, PG_PRECOND_MG_CELL,
    PG_PRECOND_MG_STEP or PG_PRECOND_POLY_EST; with precond = 0 or -1 it runs unpreconditioned.  Its `iters` count BiCG sub-steps, two products each
    (the unit of BiCGStab's iterations: l = 1 is directly comparable) and maxiter caps that unit (no outer iteration starts at
-   iters >= maxiter); products = 2 iters + the products that confirm the true residual before convergence is reported */
+   iters >= maxiter); products = 2 iters + the products that confirm the true residual before convergence is reported;
+   idrs with s = pg_krylov_opts.restart (IDR(s) with biorthogonalisation, DESIGN.md "IDR(s)"; replaces `idrs` of IterativeSolvers
+   passed through solve_system!, src/solver.jl:158-188): s <= 0 means 8 (IterativeSolvers' default), s > 8 is refused; opt-in, one
+   rank, plain -- refused together with precond = m >= 1, PG_PRECOND_MG, PG_PRECOND_MG_CELL, PG_PRECOND_MG_STEP or
+   PG_PRECOND_POLY_EST; with precond = 0 or -1 it runs unpreconditioned.  With warm_start != 0 a steady re-solve and a time
+   step start from the previous state.  Its `iters` count updates of x, one product each, and maxiter caps exactly that unit
+   (<= 0: 200000); products = iters + restarts + confirmations of the true residual (+ 1 for the product of a warm start) */
 
 /* ---- plain structs ------------------------------------------------------------------- */
 typedef struct {

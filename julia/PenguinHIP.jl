@@ -27,7 +27,7 @@ export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace,
        MovingLiquidDiffusionUnsteadyDiph, solve_MovingLiquidDiffusionUnsteadyDiph!, config_string, guess_info, mg_info, mg_step_info, spectral_estimate,
        StreamVorticity, solve_StreamVorticity!, step_StreamVorticity!, run_StreamVorticity!, run_until_StreamVorticity!,
        set_separable!, clear_separable!, time_data_info, Monitor, VolumeIntegral, InterfaceFlux, Probe, set_monitors!,
-       clear_monitors!, monitor_info, monitor_series, drop_states!, ∇, ∇₋, gmres, bicgstabl, cg
+       clear_monitors!, monitor_info, monitor_series, drop_states!, ∇, ∇₋, gmres, bicgstabl, cg, idrs
 
 const libpg = get(ENV, "PENGUIN_HIP_LIB", joinpath(@__DIR__, "..", "penguin", "jl_amd", "lib", "libpenguin_hip.so"))
 
@@ -48,13 +48,16 @@ function init(device::Integer=0)
     nothing
 end
 
-# Markers with IterativeSolvers' names: `method = gmres` (the default of solve_system!, src/solver.jl:158), `bicgstabl`, `cg`.
+# Markers with IterativeSolvers' names: `method = gmres` (the default of solve_system!, src/solver.jl:158), `bicgstabl`, `cg`,
+# `idrs`.
 # Passing the real IterativeSolvers functions works too: only the NAME of the function is looked at.
 function gmres end
 function bicgstabl end
 function cg end
+function idrs end
 # method -> PG_METHOD_*: cg -> 1, gmres -> 2 (restarted GMRES on the device), bicgstabl WITH the keyword l -> 3 (BiCGStab(l),
-# l = 1 .. 8, DESIGN.md "BiCGStab(l)"), everything else (`\`, bicgstabl without l) -> 0 = BiCGStab
+# l = 1 .. 8, DESIGN.md "BiCGStab(l)"), idrs WITH the keyword s -> 4 (IDR(s), s = 1 .. 8, DESIGN.md "IDR(s)"), everything else
+# (`\`, bicgstabl without l, idrs without s) -> 0 = BiCGStab
 function _method_name(m)
     m isa Symbol ? String(m) : (m isa Function ? String(nameof(m)) : "")
 end
@@ -62,6 +65,7 @@ function _method_id(m, kw = NamedTuple())
     n = _method_name(m)
     n == "cg" && return Int32(1)
     n == "gmres" && return Int32(2)
+    (n == "idrs" && haskey(kw, :s)) && return Int32(4)
     (n == "bicgstabl" && haskey(kw, :l)) ? Int32(3) : Int32(0)
 end
 
@@ -123,11 +127,14 @@ end
 # method = bicgstabl, l = 2 (4, ...): BiCGStab(l) -- one rank, zero initial guess, plain (refused with precond = m >= 1, :mg,
 # :mg_cell, :mg_step, :poly_est; l > 8 is refused).  Its iteration counts are BiCG sub-steps, two products each, the unit maxiter caps;
 # max_mv_products (IterativeSolvers' spelling) is converted: maxiter = max_mv_products ÷ 2.  Without l the name means BiCGStab.
+# method = idrs, s = 4 (8, ...): IDR(s) -- one rank, plain (refused with the same preconditioners; s > 8 is refused, s <= 0 means
+# 8); s travels in `restart`.  Its iteration counts are updates of x, one product each: maxiter is passed unchanged and caps that
+# unit.  With warm_start a steady re-solve and a time step start from the previous state.  Without s the name means BiCGStab.
 function _opts(method, kw; warm_default::Bool=true)
     id = _method_id(method, kw)
     maxiter = haskey(kw, :maxiter) ? Int32(kw[:maxiter]) :
-              (haskey(kw, :max_mv_products) ? Int32(max(1, Int(kw[:max_mv_products]) ÷ 2)) : Int32(0))
-    restart = id == Int32(3) ? Int32(kw[:l]) : Int32(get(kw, :restart, 0))
+              ((id != Int32(4) && haskey(kw, :max_mv_products)) ? Int32(max(1, Int(kw[:max_mv_products]) ÷ 2)) : Int32(0))
+    restart = id == Int32(3) ? Int32(kw[:l]) : (id == Int32(4) ? Int32(kw[:s]) : Int32(get(kw, :restart, 0)))
     pg_krylov_opts(id, Float64(get(kw, :reltol, 1e-12)), Float64(get(kw, :abstol, 0.0)),
                    maxiter, Int32(4), Int32(get(kw, :warm_start, warm_default) ? 1 : 0),
                    restart, _precond_id(get(kw, :precond, 0)))

@@ -32,6 +32,7 @@ PG_BC_NONE, PG_BC_DIRICHLET, PG_BC_NEUMANN, PG_BC_ROBIN, PG_BC_PERIODIC = 0, 1, 
 PG_KEY = {"left": 0, "right": 1, "bottom": 2, "top": 3, "backward": 4, "forward": 5}
 PG_SCHEME = {"BE": 0, "CN": 1, "STEADY": 2}
 PG_METHOD = {"bicgstab": 0, "cg": 1, "gmres": 2, "bicgstabl": 3}   # "bicgstabl": BiCGStab(l), chosen by api._krylov_opts when l is given
+PG_METHOD_IDRS = 4                   # IDR(s), chosen by api._krylov_opts when nshadow is given; not in PG_METHOD: the bare name "idrs" stays BiCGStab
 PG_SV_PSI, PG_SV_OMEGA, PG_SV_U, PG_SV_V = 0, 1, 2, 3   # fields / systems of a pg_streamvort
 PG_PRECOND_MG = -2                   # pg_krylov_opts.precond: the aggregation multigrid V-cycle
 PG_PRECOND_MG_CELL = -3              # ... on the cell-aggregated hierarchy (Dirichlet, Robin and Neumann interfaces)

@@ -1136,6 +1136,12 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     BiCGStab(l) counts BiCG sub-steps as its iterations, two products each -- the unit of BiCGStab's iterations, and the unit
     maxiter caps (no outer iteration starts at iters >= maxiter); products = 2 iters + the products that confirm the true residual.
     max_mv_products (IterativeSolvers' spelling of the cap) is accepted when maxiter is not given: maxiter = max_mv_products // 2.
+    idrs WITH the keyword nshadow (nshadow=4, nshadow=8, .., at most 8; 0 means 8) -> IDR(s) on the device with s = nshadow shadow
+    vectors (DESIGN.md "IDR(s)": one rank, plain -- refused with the same preconditioners as BiCGStab(l); with warm_start a steady
+    re-solve and a time step start from the previous state); idrs WITHOUT nshadow -> BiCGStab.  IterativeSolvers spells the keyword
+    `s`; it cannot be spelled that way here because the drivers' first positional parameter is `s` (the solver).  IDR(s) counts
+    updates of x as its iterations, one product each; maxiter is passed unchanged and caps exactly that unit;
+    products = iters + restarts + confirmations of the true residual (+ 1 for the product of a start from a previous state).
     reltol defaults to 1e-12: the parity target is the direct-solve path.
     precond: an integer as pg_krylov_opts.precond takes it (0 automatic, -1 off, m >= 1 the polynomial's degree), or "mg":
     the aggregation multigrid V-cycle (steady monophasic diffusion with a Dirichlet interface and the ψ solve of a
@@ -1158,11 +1164,14 @@ def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
             m, restart = L.PG_METHOD["bicgstabl"], int(kwargs["l"])
         else:
             m = L.PG_METHOD["bicgstab"]
+    elif name == "idrs" and kwargs.get("nshadow") is not None:
+        # likewise: the bare name keeps meaning BiCGStab; the keyword nshadow opts in and travels in `restart`
+        m, restart = L.PG_METHOD_IDRS, int(kwargs["nshadow"])
     else:
         m = L.PG_METHOD.get(name, L.PG_METHOD["bicgstab"])
     precond = _precond_value(kwargs.get("precond", 0))
     maxiter = int(kwargs.get("maxiter", 0))
-    if "maxiter" not in kwargs and kwargs.get("max_mv_products") is not None:
+    if m != L.PG_METHOD_IDRS and "maxiter" not in kwargs and kwargs.get("max_mv_products") is not None:
         maxiter = max(1, int(kwargs["max_mv_products"]) // 2)
     return L.pg_krylov_opts(m, float(kwargs.get("reltol", 1e-12)), float(kwargs.get("abstol", 0.0)),
                             maxiter, int(kwargs.get("check_every", 4)),

@@ -156,6 +156,7 @@ void rank_main(const VArgs& a, int rank, LocalComm* lc, int device, std::string*
 extern "C" int32_t pg_debug_set_virtual_rank_method(int32_t method, int32_t restart) {
   PG_API_BEGIN
   PG_REQUIRE(method != PG_METHOD_BICGSTABL, "BiCGStab(l) refused: the solve runs on several ranks (one rank only; virtual ranks count)");
+  PG_REQUIRE(method != PG_METHOD_IDRS, "IDR(s) refused: the solve runs on several ranks (one rank only; virtual ranks count)");
   PG_REQUIRE(method == PG_METHOD_BICGSTAB || method == PG_METHOD_CG || method == PG_METHOD_GMRES, "unknown Krylov method");
   g_method = method;
   g_restart = restart;

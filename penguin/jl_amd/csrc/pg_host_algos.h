@@ -661,6 +661,43 @@ PGHOST_HD inline int bicgstabl_small_solve(const double* G, int l, double* gamma
   return 0;
 }
 
+// ---- scalars of IDR(s) (pg_idrs.hip; tests/idrs_host.cpp) --------------------------------------------------------------------
+// The shadow vectors are never stored: p_k[i] is a pure integer function of the row number i and k, the splitmix64 finaliser of
+// i + (k + 1) 0x9E3779B97F4A7C15 mapped to (z >> 11) 2^-52 - 1 in [-1, 1) -- 53 bits times a power of two less one: exact in fp64,
+// bit-identical here, on the device and in numpy (tests/idrs_reference.py shadow).
+constexpr int IDR_MAX_S = 8;
+constexpr double IDR_PIV_TOL = 1e-15;   // ~ 9 eps.  |M_kk| <= IDR_PIV_TOL |p_k| |G_k|: the pivot is the rounding of its own dot product
+constexpr double IDR_KAPPA = 0.7;       // ω is enlarged when the angle between t = Âr and r has a cosine below it
+constexpr uint64_t IDR_GOLDEN = 0x9E3779B97F4A7C15ull;
+
+PGHOST_HD inline double idr_shadow_mixed(uint64_t z) {   // z = i + (k + 1) IDR_GOLDEN
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return (double)(z >> 11) * 2.220446049250313e-16 - 1.0;
+}
+
+PGHOST_HD inline double idr_shadow(uint64_t i, int k) { return idr_shadow_mixed(i + (uint64_t)(k + 1) * IDR_GOLDEN); }
+
+// Forward substitution on the lower triangle of M (s x s, row major, leading dimension IDR_MAX_S):
+//   M[lo..hi, lo..hi] out[lo..hi] = rhs[lo..hi],  0 <= lo <= hi <= s;  out = 0 outside [lo, hi).
+// Used with (k, s) for c and with (0, k) for α.  False -- and out all zero -- when s is not in 1 .. IDR_MAX_S, the range is
+// not inside it, or an entry of the solution is not finite (a zero or non-finite pivot included): the caller restarts.
+PGHOST_HD inline bool idr_lower_solve(const double* M, int s, int lo, int hi, const double* rhs, double* out) {
+  for (int i = 0; i < IDR_MAX_S; ++i) out[i] = 0.0;
+  if (s < 1 || s > IDR_MAX_S || lo < 0 || hi > s || lo > hi) return false;
+  bool ok = true;
+  for (int i = lo; i < hi; ++i) {
+    double v = rhs[i];
+    for (int j = lo; j < i; ++j) v -= M[i * IDR_MAX_S + j] * out[j];
+    out[i] = v / M[i * IDR_MAX_S + i];
+    if (!bl_finite(out[i])) ok = false;
+  }
+  if (!ok)
+    for (int i = 0; i < IDR_MAX_S; ++i) out[i] = 0.0;
+  return ok;
+}
+
 // ---- schedule of the mixed-precision Horner chain (pg_krylov.hip) ------------------------------------------
 // The chain applies the m factors (I - Â/λ_k), λ_k the Chebyshev nodes of [1 - g, 1 + g] (index 0 = the largest), in m - 1
 // launches: the first applied root is folded into the first launch's coefficients, launch i = 0 .. m-2 applies root

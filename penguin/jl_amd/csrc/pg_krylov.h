@@ -1,4 +1,4 @@
-// pg_krylov.h -- K11: Krylov solve of the reduced system on one slab (BiCGStab / CG / GMRES / BiCGStab(l)).
+// pg_krylov.h -- K11: Krylov solve of the reduced system on one slab (BiCGStab / CG / GMRES / BiCGStab(l) / IDR(s)).
 #pragma once
 #include <functional>
 
@@ -77,6 +77,11 @@ struct KrylovWork {
   DevBuf<double> bl_vecs, bl, bl_partials;
   int bl_l = -1;
   i64 bl_stride = 0;
+  // IDR(s) only, allocated on first use (pg_idrs.hip): G[0..s), U[0..s), r and t in one block (id_stride apart), the method's
+  // device scalars (M, f, c, α, β, ω), per-block partial sums of its kernels
+  DevBuf<double> id_vecs, id, id_partials;
+  int id_s = -1;
+  i64 id_stride = 0;
   // Set by the caller around one krylov_solve: work to queue right AFTER the first batch of iterations and the copy of the
   // scalars, BEFORE the host waits for that copy -- the next time step's first product, speculatively: the device then
   // has something to run while the host wakes up, reads the scalars and queues the next step (the wait is on an event
@@ -119,7 +124,7 @@ void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st);
 // halo exchange of x (when the matrix needs one) overlapped with y[0..n) = A * x
 void spmv_halo(const CsrMatrix& A, const Numbering& nb, const Slab& slab, double* x, double* y, hipStream_t st);
 // x (n_vec, overwritten) = A^{-1} b.  x0 == nullptr: zero initial guess; else start from x0 with Ax0 = A*x0 given
-// (BiCGStab only).  x0 may be x itself (the iteration continues from the iterate x holds).
+// (BiCGStab and IDR(s) only).  x0 may be x itself (the iteration continues from the iterate x holds).
 // preinit (BiCGStab only): the caller has already written x, w.r = w.rhat = w.p = r0 and the partial sums of (r0,r0)
 // / (b,b) in slots 0 / 1 of w.partials with a w.grid-block launch (pg_solver.hip fuses that with the right-hand side).
 void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x,
@@ -142,6 +147,11 @@ void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, cons
 // one rank; stats.iters counts BiCG sub-steps (two products each), stats.products = 2 iters + true-residual confirmations
 void bicgstabl_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,
                      const pg_krylov_opts& opts, SolveStats& stats);
+// IDR(s), s = opts.restart (<= 0: 8, > 8 refused) (pg_idrs.hip): x (n_vec, overwritten) = A^{-1} b from zero or from x0 with
+// Ax0 = A*x0 given (x0 may be x); one rank; stats.iters counts updates of x (one product each: the unit maxiter caps),
+// stats.products = iters + restarts + true-residual confirmations (+ 1 from an x0: the caller's product with it)
+void idrs_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,
+                const pg_krylov_opts& opts, SolveStats& stats, const double* x0 = nullptr, const double* Ax0 = nullptr);
 // "the method is CG (BiCGStab only)" and its kin: the refusal texts of what serves BiCGStab alone
 const char* krylov_method_refusal(int method);
 

@@ -551,7 +551,8 @@ void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st) {
 
 const char* krylov_method_refusal(int method) {
   return method == PG_METHOD_CG ? "the method is CG (BiCGStab only)"
-         : method == PG_METHOD_BICGSTABL ? "the method is BiCGStab(l) (BiCGStab only)" : "the method is GMRES (BiCGStab only)";
+         : method == PG_METHOD_BICGSTABL ? "the method is BiCGStab(l) (BiCGStab only)"
+         : method == PG_METHOD_IDRS ? "the method is IDR(s) (BiCGStab only)" : "the method is GMRES (BiCGStab only)";
 }
 
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts) {
@@ -671,7 +672,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   const i64 n = A.n, nvec = nb.n_vec();
   PG_REQUIRE(w.n >= n && w.nvec >= nvec, "krylov workspace too small");   // (a reduced system works on prefixes, pg_reduce.hip)
   PG_REQUIRE(opts.method == PG_METHOD_BICGSTAB || opts.method == PG_METHOD_CG || opts.method == PG_METHOD_GMRES ||
-                 opts.method == PG_METHOD_BICGSTABL,
+                 opts.method == PG_METHOD_BICGSTABL || opts.method == PG_METHOD_IDRS,
              "unknown Krylov method");
   // PG_PRECOND_POLY_EST: precond = 0 wherever Gershgorin admits the matrix; where it refuses, the verdict of the spectral
   // estimate the caller has run on this matrix (CsrMatrix::est, pg_specest.hip) -- a flag of its own, poly_ok stays false
@@ -708,6 +709,21 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     w.moved_flag = nullptr;
     w.after_first_batch = nullptr;
     bicgstabl_solve(A, nb, slab, b, x, w, opts, stats);
+    return;
+  }
+  if (opts.method == PG_METHOD_IDRS) {
+    // opt-in, plain, as BiCGStab(l); it honours x0 / Ax0 (no prepared start: that is the BiCGStab loop's own)
+    PG_REQUIRE(!preinit, "IDR(s) refused: a prepared start (preinit) is the BiCGStab loop's alone; pass x0 and Ax0");
+    PG_REQUIRE(!mg_any_precond(opts.precond), std::string("multigrid preconditioner (precond = ") + mg_precond_name_of(opts.precond) +
+                                                  ") refused: " + krylov_method_refusal(opts.method));
+    PG_REQUIRE(opts.precond <= 0, "polynomial preconditioner (precond = " + std::to_string(opts.precond) + ") refused: " +
+                                      krylov_method_refusal(opts.method) + "; precond = 0 or -1 runs IDR(s) plain");
+    w.mg = nullptr;
+    w.xguess = XGuess();
+    w.p_in_rhat = w.start_folded = false;
+    w.moved_flag = nullptr;
+    w.after_first_batch = nullptr;
+    idrs_solve(A, nb, slab, b, x, w, opts, stats, x0, Ax0);
     return;
   }
   const int G = w.grid;

@@ -2132,8 +2132,10 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     // cold start / CG: the reference's zero initial guess, on the unscaled state
     s->hist_cnt = 0;
     materialize_x(s);
+    // IDR(s) starts from the previous state here too (krylov_solve's x0 / Ax0): the scaled state and one product, which CN takes anyway
+    const bool idr_warm = o.warm_start != 0 && o.method == PG_METHOD_IDRS && n > 0;
     if (n > 0) {
-      if (scheme == PG_SCHEME_CN) {
+      if (scheme == PG_SCHEME_CN || idr_warm) {
         hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, A.ds.p, s->x.p, s->z.p, 1);
         spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
       }
@@ -2150,7 +2152,8 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
       PG_HIP(hipGetLastError());
     }
     if (mgs) s->work.mg = &mg_step_ensure(s, A);
-    krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
+    if (idr_warm) krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
+    else krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
     std::swap(s->z.p, s->ysol.p);
     s->z_matrix = &A;
     s->x_valid = false;
@@ -3620,7 +3623,7 @@ void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st
   const i64 n = s->nb.n_own;
   ensure_bconst(s, PG_SCHEME_STEADY);
   if (n > 0) apply_left(s->A_ctor, s->bconst.p, s->b.p, stream);      // b̂ = B⁻¹ S b
-  if (o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
+  if (o.warm_start != 0 && (o.method == PG_METHOD_BICGSTAB || o.method == PG_METHOD_IDRS) && n > 0) {
     spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);       // z: the previous solution, scaled by this matrix's S
     PG_HIP(hipGetLastError());
     krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
