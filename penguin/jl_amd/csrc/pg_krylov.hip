@@ -1059,7 +1059,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   w.last_iters = stats.iters;
   stats.converged = w.h_sc[S_DONE] == 1.0 ? 1 : 0;
   stats.half_exit = w.h_sc[S_HALF] != 0.0 ? 1 : 0;
-  stats.resnorm = std::sqrt(cg ? w.h_sc[S_RRW] : w.h_sc[S_RR]);   // the weighted norms of the convergence test
+  // the weighted norms of the convergence test (S_HELD: the rows a folded start left where they were, pg_solver.hip)
+  stats.resnorm = std::sqrt((cg ? w.h_sc[S_RRW] : w.h_sc[S_RR]) + w.h_sc[S_HELD]);
   stats.bnorm = std::sqrt(w.h_sc[S_BB]);
   timer.collect(stats, stats.iters, w.h_sc[S_HALF] != 0.0);
   stats.products = (i64)(2 * stats.iters - stats.half_exit) * (m >= 2 ? m : 1);

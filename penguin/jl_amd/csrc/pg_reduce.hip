@@ -499,7 +499,8 @@ void build_diag_elim(const CsrMatrix& A, const Numbering& nb, const Slab& slab, 
             (long long)A.nnz, n_wg, nnz_g, (long long)A.rows_g, (long long)R.rows_g);
 }
 
-// (the rows themselves were solved by k_rhs_init_c: x += δ, δ kept in E.delta, E.flag = stamp if any δ != 0)
+// (the rows themselves were solved by k_rhs_init_c: x += δ, δ kept in E.delta, E.flag = stamp if any δ != 0 -- any at all:
+// a δ below the noise threshold of the steps without this call is coupled in here like every other)
 // force: the data of the right-hand side changed since the last step, so rows may have moved on ANY rank: the owners'
 // deltas travel to the neighbours (one halo exchange of a full-layout vector), coupling and start sums are redone
 // unconditionally.  One rank never forces: its own flag says whether anything moved.

@@ -524,12 +524,27 @@ __global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const d
                                                       double* __restrict__ delta, int* __restrict__ flag, int stamp,
                                                       double* __restrict__ rhat, double* __restrict__ partials,
                                                       unsigned* __restrict__ ticket, double* __restrict__ sc, double reltol2,
-                                                      double abstol2, GuessArgs g) {
+                                                      double abstol2, int coupled, GuessArgs g) {
   // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovWork::p_in_rhat)
+  // coupled != 0: diag_fix follows (the data changed): every δ != 0 moves its row, raises the flag and is coupled into the
+  // residual of the rows that reference it.  coupled == 0: no coupling launch follows (unchanged data); only a δ beyond the
+  // noise threshold raises the flag, and the step is then finished on the full system.  Several ranks with unchanged data
+  // take this branch WITHOUT a ticket (their start phase goes through an all-reduce): there a δ within the threshold still
+  // moves its row with neither coupling nor S_HELD, and the residual reported can miss the state's by up to ||S Â_RE δ|| --
+  // the one-rank remedy below needs the held sum in that all-reduce and is not carried over yet.
   // ticket != NULL: the solver's start phase (scalar reset, start sums, PH_INIT) by the last block of this launch -- the
-  // caller knows that nothing will touch the start sums afterwards (no diagonal row can move: diag_fix is not launched)
+  // caller knows that nothing will touch the start sums afterwards (diag_fix is not launched).  A row alone on its diagonal
+  // whose δ is within the noise threshold then STAYS where it is: moving it would leave the start residual of the rows coupled
+  // to it -- formed from ŷ = Âz with the row at its old place -- short of Â_RE δ, and with it every residual the solve reports
+  // afterwards.  (With a Dirichlet interface and CN such a row reads x_new = 2 g - x_old: what the first solve left on it, a
+  // fraction of its tolerance, changes sign every step and never dies out.)  What the rows that stay lack is their own
+  // residual, constant through the solve and on rows of their own: its weighted square goes to S_HELD, the tolerance of the
+  // iteration is lowered by it and the residual reported has it added (pg_krylov.hip) -- the solve is accepted on, and
+  // reports, the residual of the whole state.  Where that square is half the tolerance's or more the step is finished on the
+  // full system, as if a row had moved.
   __shared__ double s_red[BLOCK / 64];
-  double acc = 0.0, accb = 0.0, accw = 0.0;
+  double acc = 0.0, accb = 0.0, accw = 0.0, acch = 0.0;
+  const bool hold = ticket != nullptr;
   double cj[KH > 0 ? KH : 1];
   const double* zo[KH > 0 ? KH : 1];
   const double* yo[KH > 0 ? KH : 1];
@@ -569,13 +584,18 @@ __global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const d
       acc += ri * ri;
       accw += (d * ri) * (d * ri);
     } else {
-      // a row alone on its diagonal: solved here, x += δ = r / a_ii (δ = 0 once the row's datum has stopped changing);
-      // δ is what the rows coupled to it need (diag_fix), the flag says whether any δ of this step is non-zero
+      // a row alone on its diagonal: solved here, x += δ = r / a_ii (δ = 0 once the row's datum has stopped changing, up to
+      // the rows that stay on a folded start); δ is what the rows coupled to it need (diag_fix), the flag says whether any row moved
       const int e = -1 - c;
-      const double dl = ri / gdiag[e];
+      double dl = ri / gdiag[e];
+      const bool beyond = fabs(dl) > 1e-12 * fabs(zi);
+      if (hold && !beyond) {
+        acch += (d * ri) * (d * ri);
+        dl = 0.0;
+      }
       delta[e] = dl;
       if (KH > 0 || dl != 0.0) zw[i] = zi + dl;
-      if (fabs(dl) > 1e-12 * fabs(zi)) moved = 1;
+      if (coupled ? dl != 0.0 : beyond) moved = 1;
     }
   };
   // two rows per lane, 16-byte loads of the seven input streams (as k_rhs_init); the compact stores are 8-byte
@@ -644,11 +664,13 @@ __global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const d
     pg::store_partial(partials + gridDim.x + blockIdx.x, tb);
     pg::store_partial(partials + 2 * (size_t)gridDim.x + blockIdx.x, tw);
   }
+  const double th = block_sum(acch, s_red);
+  if (threadIdx.x == 0) pg::store_partial(partials + 3 * (size_t)gridDim.x + blockIdx.x, th);
   if (!pg::last_block_arrives(ticket, gridDim.x, s_red)) return;
   // (k_start's work, in its order of summation)
   if (threadIdx.x < pg::S_COUNT) sc[threadIdx.x] = threadIdx.x == pg::S_RELTOL2 ? reltol2 : (threadIdx.x == pg::S_ABSTOL2 ? abstol2 : 0.0);
   __syncthreads();
-  for (int sl = 0; sl < 3; ++sl) {
+  for (int sl = 0; sl < 4; ++sl) {      // (slot 3: the rows that stayed)
     double a = 0.0;
     for (int i = threadIdx.x; i < (int)gridDim.x; i += BLOCK) a += pg::load_partial(partials + (size_t)sl * gridDim.x + i);
     const double sum = block_sum(a, s_red);
@@ -658,6 +680,15 @@ __global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const d
     pg::derive(pg::PH_INIT, sc);
     // (every block's atomicMax on the flag was drained before it drew its ticket)
     sc[pg::S_MOVED] = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == stamp ? 1.0 : 0.0;
+    const double held = sc[pg::S_RED0 + 3];
+    if (held > 0.0) {
+      if (2.0 * held >= sc[pg::S_TOL2]) sc[pg::S_MOVED] = 1.0;
+      else {
+        sc[pg::S_HELD] = held;
+        sc[pg::S_TOL2] -= held;
+        sc[pg::S_DONE] = sc[pg::S_RR] <= sc[pg::S_TOL2] ? 1.0 : 0.0;
+      }
+    }
     if (KH > 0) g.coef[13] += (double)ku;
   }
 }
@@ -2005,7 +2036,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p,   \
                      s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, DE.cmap.p, s->b.p, (const double*)DE.gdiag.p, DE.delta.p,     \
                      DE.flag.p, stamp, w.rhat.p, w.partials.p, quiet ? w.ticket.p : nullptr, w.sc.p, o.reltol * o.reltol,          \
-                     o.abstol * o.abstol, ga)
+                     o.abstol * o.abstol, same_data ? 0 : 1, ga)
       switch (KH) {
         case 1: PG_RHS_INIT_C(1); break;
         case 2: PG_RHS_INIT_C(2); break;
