@@ -520,6 +520,58 @@ int32_t pg_solver_time_data_info(const pg_solver* s, int32_t* terms /*4*/, int64
 int32_t pg_debug_td_combine_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_combine, int32_t* modes,
                                int64_t* bytes);
 
+/* Device functions: a scalar expression in (x0, x1, x2, t) shipped once as a small postfix program and evaluated on the device
+   every step at the points where the reference evaluates the closure (DESIGN.md "Device functions").  pg_program is a POD of
+   fixed size, handed BY VALUE to the kernel that runs it: no upload, no read-back.
+   Instruction q is (op[q], arg[q]); arg is read by PG_OP_CONST (index into konst, < n_const) and PG_OP_VAR (0, 1, 2: the
+   coordinates of the point, missing ones 0.0; 3: t) only.  Unary operations replace the top of the operand stack, binary ones
+   (a below b) pop two and push one, the comparisons give 1.0 / 0.0, PG_OP_SELECT pops (c, a, b) and pushes a if c != 0 else b.
+   A valid program never underflows the stack, never holds more than PG_PROG_MAX_STACK values and ends with exactly one. */
+enum { PG_PROG_MAX_OPS = 96, PG_PROG_MAX_CONST = 32, PG_PROG_MAX_STACK = 16 };
+enum {
+  PG_OP_CONST = 0, PG_OP_VAR = 1, PG_OP_ADD = 2, PG_OP_SUB = 3, PG_OP_MUL = 4, PG_OP_DIV = 5, PG_OP_NEG = 6, PG_OP_ABS = 7,
+  PG_OP_SQRT = 8, PG_OP_EXP = 9, PG_OP_LOG = 10, PG_OP_SIN = 11, PG_OP_COS = 12, PG_OP_TANH = 13, PG_OP_POW = 14,
+  PG_OP_ATAN2 = 15, PG_OP_ERF = 16, PG_OP_ERFC = 17, PG_OP_MIN = 18, PG_OP_MAX = 19, PG_OP_LT = 20, PG_OP_LE = 21,
+  PG_OP_GT = 22, PG_OP_GE = 23, PG_OP_SELECT = 24, PG_OP_COUNT = 25
+};
+typedef struct pg_program {
+  int32_t n_ops;                       /* 1 .. PG_PROG_MAX_OPS */
+  int32_t n_const;                     /* 0 .. PG_PROG_MAX_CONST */
+  uint8_t op[PG_PROG_MAX_OPS];
+  uint8_t arg[PG_PROG_MAX_OPS];
+  double konst[PG_PROG_MAX_CONST];
+} pg_program;
+/* 0 when the program is valid; otherwise 1 and the reason in pg_last_error.  Host only, needs no device. */
+int32_t pg_program_validate(const pg_program* prog);
+/* the host interpreter: out[i] = P(xyz[3i], xyz[3i+1], xyz[3i+2], t).  Validates first; needs no device. */
+int32_t pg_program_eval_host(const pg_program* prog, int64_t npts, const double* xyz /* npts x 3 */, double t, double* out);
+/* A program in a slot of time-dependent data, with the which / phase values of pg_solver_set_separable.  A slot holds separable
+   terms OR programs: installing one clears the other, and pg_solver_clear_separable, pg_solver_set_source / _interface_value /
+   _border_values clear a program slot as they clear a separable one.  times: 2 x nrows, row q = the "t" and "t + dt" of step q
+   (the two times at which the host-driven loop evaluates its closures for that step).  Table discipline as above: one row per
+   step, installing rewinds the cursor, a step past the last row fails.  At install one kernel lists the rows that carry the
+   slot's data with their weights and points (source: bulk rows of the phase that are not fixed, V, C_omega; interface: interface
+   rows, Gamma, C_gamma; border: the fixed rows of the border cells, 1, the cell centres); every step one kernel adds
+   weight * (c0 P(p, t) + c1 P(p, t + dt)) to the right-hand side of those rows, c0 and c1 being the scheme's factors of
+   separable data.  PG_TD_BORDER gives every border cell the program's value; pg_solver_set_border_program gives it to the
+   cells of one border key (PG_KEY_*) and leaves the others what pg_solver_set_border_values set -- at most one program per key.
+   Refused: what pg_solver_set_separable refuses, an invalid program, a capacity without C_gamma (PG_TD_INTERFACE). */
+int32_t pg_solver_set_program(pg_solver* s, int32_t which, int32_t phase, const pg_program* prog, int64_t nrows,
+                              const double* times /* 2 x nrows */);
+int32_t pg_solver_set_border_program(pg_solver* s, int32_t key, const pg_program* prog, int64_t nrows,
+                                     const double* times /* 2 x nrows */);
+/* programs: 4 counts of installed programs per slot (as `terms` of pg_solver_time_data_info; the border slot: one per key or 1);
+   entries: 4 counts of listed rows; nrows / cursor as pg_solver_time_data_info, over separable and program slots together */
+int32_t pg_solver_program_info(const pg_solver* s, int32_t* programs /*4*/, int64_t* entries /*4*/, int64_t* nrows,
+                               int64_t* cursor);
+/* test support: the kernel-side evaluator (same instantiation and stack layout as the per-step kernel) on caller-supplied
+   points: out[i] = P(xyz[3i .. 3i+2], t) */
+int32_t pg_debug_program_eval(const pg_program* prog, int64_t npts, const double* xyz /* npts x 3 */, double t, double* out);
+/* measurement: the per-step evaluation of every installed program at the last consumed row, `repeats` times between two
+   events; entries = listed rows summed over the programs, instructions = entries x n_ops x evaluations summed likewise */
+int32_t pg_debug_td_eval_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_eval, int64_t* entries,
+                            int64_t* instructions);
+
 /* Monitors: per-step observables evaluated on the device (DESIGN.md "Monitors").  They replace the post-processing loops over
    solver.states of the reference's scripts -- the volume-weighted phase means of examples/2D/Diffusion/Heat_2ph.jl (its
    Sherwood number), the interface flux  sum_i [Id (H' W! G Tw + H' W! H Tg)]_i  the Stefan and species solvers sum per step,

@@ -488,6 +488,176 @@ function time_data_info(s::Solver)
     check(ccall((:pg_solver_time_data_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ref{Int64}, Ref{Int64}), s.handle, terms, nrows, cursor))
     (terms = Int.(terms), nrows = nrows[], cursor = cursor[])
 end
+# Device functions (include/penguin_hip.h, DESIGN.md "Device functions"): a scalar closure of (coordinates..., t) traced ONCE
+# into a postfix program that a kernel evaluates every step at the reference's points.  DeviceFunction(f) calls f with Sym
+# operands -- a Number type whose arithmetic, comparisons and elementary functions record themselves -- and keeps f: the object
+# is callable and forwards to the ORIGINAL closure, so constructors and the host-driven loop use it as a plain closure.
+# dev_select / dev_erf / dev_erfc / dev_atan2 work on Sym and on numbers alike.  What cannot be traced (a branch on a Sym, a
+# function without an opcode, more than 96 instructions) is an error naming the operation: nothing falls back silently.
+const PG_PROG_MAX_OPS = 96
+const PG_PROG_MAX_CONST = 32
+const PG_PROG_MAX_STACK = 16
+const PG_OP_CONST = UInt8(0)
+const PG_OP_VAR = UInt8(1)
+const PG_OP_ADD = UInt8(2)
+const PG_OP_SUB = UInt8(3)
+const PG_OP_MUL = UInt8(4)
+const PG_OP_DIV = UInt8(5)
+const PG_OP_NEG = UInt8(6)
+const PG_OP_ABS = UInt8(7)
+const PG_OP_SQRT = UInt8(8)
+const PG_OP_EXP = UInt8(9)
+const PG_OP_LOG = UInt8(10)
+const PG_OP_SIN = UInt8(11)
+const PG_OP_COS = UInt8(12)
+const PG_OP_TANH = UInt8(13)
+const PG_OP_POW = UInt8(14)
+const PG_OP_ATAN2 = UInt8(15)
+const PG_OP_ERF = UInt8(16)
+const PG_OP_ERFC = UInt8(17)
+const PG_OP_MIN = UInt8(18)
+const PG_OP_MAX = UInt8(19)
+const PG_OP_LT = UInt8(20)
+const PG_OP_LE = UInt8(21)
+const PG_OP_GT = UInt8(22)
+const PG_OP_GE = UInt8(23)
+const PG_OP_SELECT = UInt8(24)
+struct Sym <: Real
+    op::UInt8
+    args::Vector{Sym}
+    value::Float64      # PG_OP_CONST: the constant; PG_OP_VAR: the index 0 .. 3
+end
+Sym(v::Real) = Sym(PG_OP_CONST, Sym[], Float64(v))
+_symvar(i::Integer) = Sym(PG_OP_VAR, Sym[], Float64(i))
+_sym(op::UInt8, args...) = Sym(op, Sym[a isa Sym ? a : Sym(a) for a in args], 0.0)
+Base.promote_rule(::Type{Sym}, ::Type{<:Real}) = Sym
+Base.convert(::Type{Sym}, v::Real) = Sym(v)
+Base.convert(::Type{Sym}, v::Sym) = v
+Base.:+(a::Sym, b::Sym) = _sym(PG_OP_ADD, a, b)
+Base.:-(a::Sym, b::Sym) = _sym(PG_OP_SUB, a, b)
+Base.:*(a::Sym, b::Sym) = _sym(PG_OP_MUL, a, b)
+Base.:/(a::Sym, b::Sym) = _sym(PG_OP_DIV, a, b)
+Base.:-(a::Sym) = _sym(PG_OP_NEG, a)
+Base.:+(a::Sym) = a
+Base.abs(a::Sym) = _sym(PG_OP_ABS, a)
+Base.sqrt(a::Sym) = _sym(PG_OP_SQRT, a)
+Base.exp(a::Sym) = _sym(PG_OP_EXP, a)
+Base.log(a::Sym) = _sym(PG_OP_LOG, a)
+Base.sin(a::Sym) = _sym(PG_OP_SIN, a)
+Base.cos(a::Sym) = _sym(PG_OP_COS, a)
+Base.tanh(a::Sym) = _sym(PG_OP_TANH, a)
+Base.min(a::Sym, b::Sym) = _sym(PG_OP_MIN, a, b)
+Base.max(a::Sym, b::Sym) = _sym(PG_OP_MAX, a, b)
+Base.atan(a::Sym, b::Sym) = _sym(PG_OP_ATAN2, a, b)
+Base.:^(a::Sym, b::Sym) = _sym(PG_OP_POW, a, b)
+# x^k, k = 0 .. 4 an integer: multiplications; anything else: POW
+function Base.:^(a::Sym, k::Integer)
+    (0 <= k <= 4) || return _sym(PG_OP_POW, a, k)
+    k == 0 && return Sym(1.0)
+    out = a
+    for _ in 2:k
+        out = _sym(PG_OP_MUL, out, a)
+    end
+    out
+end
+# the comparisons give a Sym worth 1.0 / 0.0 -- not a Bool: `if x < y` on traced values fails in the `if`, by design
+Base.:<(a::Sym, b::Sym) = _sym(PG_OP_LT, a, b)
+Base.:<=(a::Sym, b::Sym) = _sym(PG_OP_LE, a, b)
+Base.:<(a::Sym, b::Real) = _sym(PG_OP_LT, a, b)
+Base.:<(a::Real, b::Sym) = _sym(PG_OP_LT, a, b)
+Base.:<=(a::Sym, b::Real) = _sym(PG_OP_LE, a, b)
+Base.:<=(a::Real, b::Sym) = _sym(PG_OP_LE, a, b)
+dev_gt(a, b) = _sym(PG_OP_GT, a, b)
+dev_ge(a, b) = _sym(PG_OP_GE, a, b)
+_traced(args...) = any(a -> a isa Sym, args)
+dev_select(c, a, b) = _traced(c, a, b) ? _sym(PG_OP_SELECT, c, a, b) : (c != 0 ? a : b)
+dev_erf(x) = _traced(x) ? _sym(PG_OP_ERF, x) : error("dev_erf of a number: use SpecialFunctions.erf")
+dev_erfc(x) = _traced(x) ? _sym(PG_OP_ERFC, x) : error("dev_erfc of a number: use SpecialFunctions.erfc")
+dev_atan2(y, x) = _traced(y, x) ? _sym(PG_OP_ATAN2, y, x) : atan(y, x)
+Base.Float64(::Sym) = error("DeviceFunction: cannot trace a conversion of a traced value to Float64 (a function without an opcode?)")
+Base.Bool(::Sym) = error("DeviceFunction: cannot trace a branch on a traced value; use dev_select(cond, a, b), min or max")
+
+# the bytes of a pg_program: n_ops::Int32, n_const::Int32, op[96]::UInt8, arg[96]::UInt8, konst[32]::Float64
+const PG_PROGRAM_BYTES = 8 + 2 * PG_PROG_MAX_OPS + 8 * PG_PROG_MAX_CONST
+function _compile_program(root::Sym)
+    ops, args, consts = UInt8[], UInt8[], Float64[]
+    deepest = Ref(0)
+    function emit(node::Sym, depth::Int)            # operands left to right, then the operation; returns the depth after it
+        if node.op == PG_OP_CONST
+            k = findfirst(c -> reinterpret(UInt64, c) == reinterpret(UInt64, node.value), consts)
+            if k === nothing
+                length(consts) == PG_PROG_MAX_CONST && error("DeviceFunction: more than $PG_PROG_MAX_CONST distinct constants")
+                push!(consts, node.value)
+                k = length(consts)
+            end
+            push!(ops, PG_OP_CONST); push!(args, UInt8(k - 1))
+            depth += 1
+        elseif node.op == PG_OP_VAR
+            push!(ops, PG_OP_VAR); push!(args, UInt8(node.value))
+            depth += 1
+        else
+            d = depth
+            for a in node.args
+                d = emit(a, d)
+            end
+            push!(ops, node.op); push!(args, 0x00)
+            depth += 1
+        end
+        length(ops) > PG_PROG_MAX_OPS && error("DeviceFunction: more than $PG_PROG_MAX_OPS instructions")
+        deepest[] = max(deepest[], depth)
+        depth
+    end
+    emit(root, 0)
+    deepest[] > PG_PROG_MAX_STACK && error("DeviceFunction: an operand stack of $(deepest[]) values, more than $PG_PROG_MAX_STACK")
+    buf = zeros(UInt8, PG_PROGRAM_BYTES)
+    buf[1:4] .= reinterpret(UInt8, Int32[length(ops)])
+    buf[5:8] .= reinterpret(UInt8, Int32[length(consts)])
+    buf[9:8 + length(ops)] .= ops
+    buf[9 + PG_PROG_MAX_OPS:8 + PG_PROG_MAX_OPS + length(args)] .= args
+    kb = reinterpret(UInt8, consts)
+    buf[9 + 2 * PG_PROG_MAX_OPS:8 + 2 * PG_PROG_MAX_OPS + length(kb)] .= kb
+    check(ccall((:pg_program_validate, libpg), Int32, (Ptr{Cvoid},), buf))
+    buf
+end
+struct DeviceFunction <: Function
+    f::Function
+    programs::Dict{Int,Vector{UInt8}}      # by the number of space coordinates the closure is called with
+end
+DeviceFunction(f::Function) = DeviceFunction(f, Dict{Int,Vector{UInt8}}())
+(df::DeviceFunction)(args...) = df.f(args...)
+function program(df::DeviceFunction, nspace::Integer = 3)
+    get!(df.programs, Int(nspace)) do
+        out = df.f((_symvar(d) for d in 0:nspace - 1)..., _symvar(3))
+        _compile_program(out isa Sym ? out : Sym(out))
+    end
+end
+# the host interpreter of the library on the rows of xyz (3 x npts, one point per COLUMN: the C layout npts x 3)
+function evaluate_program(df::DeviceFunction, xyz::Matrix{Float64}, t::Real; nspace::Integer = 3)
+    size(xyz, 1) == 3 || error("evaluate_program: xyz must be 3 x npts")
+    out = zeros(size(xyz, 2))
+    check(ccall((:pg_program_eval_host, libpg), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Float64}),
+                program(df, nspace), size(xyz, 2), xyz, t, out))
+    out
+end
+# times: 2 x nrows, times[1, q] = step q's "t", times[2, q] = its "t + Δt" (column-major: the C layout nrows x 2)
+function set_program!(s::Solver, which::Integer, phase::Integer, df::DeviceFunction, times::Matrix{Float64}; nspace::Integer = 3)
+    size(times, 1) == 2 || error("set_program!: times must be 2 x nrows")
+    check(ccall((:pg_solver_set_program, libpg), Int32, (Ptr{Cvoid}, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Float64}),
+                s.handle, which, phase, program(df, nspace), size(times, 2), times))
+end
+function set_border_program!(s::Solver, key::Integer, df::DeviceFunction, times::Matrix{Float64}, nspace::Integer)
+    size(times, 1) == 2 || error("set_border_program!: times must be 2 x nrows")
+    check(ccall((:pg_solver_set_border_program, libpg), Int32, (Ptr{Cvoid}, Int32, Ptr{Cvoid}, Int64, Ptr{Float64}),
+                s.handle, key, program(df, nspace), size(times, 2), times))
+end
+# (programs and listed rows per slot; table rows over separable and program slots together; the next step's row)
+function program_info(s::Solver)
+    programs, entries = zeros(Int32, 4), zeros(Int64, 4)
+    nrows, cursor = Ref{Int64}(0), Ref{Int64}(0)
+    check(ccall((:pg_solver_program_info, libpg), Int32, (Ptr{Cvoid}, Ptr{Int32}, Ptr{Int64}, Ref{Int64}, Ref{Int64}),
+                s.handle, programs, entries, nrows, cursor))
+    (programs = Int.(programs), entries = Int.(entries), nrows = nrows[], cursor = cursor[])
+end
 # Monitors (include/penguin_hip.h, DESIGN.md "Monitors"): observables Σ w_i x_i (:sum) / Σ w_i x_i² (:sumsq) of the state,
 # evaluated on the device after every solve -- what the reference's scripts compute by looping over solver.states
 # (examples/2D/Diffusion/Heat_2ph.jl: volume-weighted phase means; the Stefan and species solvers: the interface flux).

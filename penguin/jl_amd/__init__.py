@@ -16,6 +16,7 @@ from .api import (  # noqa: F401
     check_convergence, check_convergence_diph, div, grad, lp_norm, nC, solve_DarcyFlow_b, solve_DarcyFlowUnsteady_b, solve_darcy_velocity, solve_DiffusionSteadyDiph_b, solve_DiffusionSteadyMono_b,
     solve_DiffusionUnsteadyDiph_b, solve_DiffusionUnsteadyMono_b, TimeSeparable,
     InterfaceFlux, Monitor, Probe, VolumeIntegral,
+    DeviceFunction, dev,
 )
 from .utils import (  # noqa: F401,E402
     cfl_restriction, initialize_poiseuille_velocity_field, initialize_radial_velocity_field,

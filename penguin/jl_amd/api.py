@@ -22,6 +22,8 @@ import numpy as np
 
 from . import _lib as L
 from ._lib import PenguinHipError
+from . import devfn as dev  # noqa: F401
+from .devfn import DeviceFunction
 
 Number = Union[int, float]
 
@@ -724,6 +726,41 @@ def _clear_separable(s: "Solver", nphase: int) -> None:
         L.check(L.lib().pg_solver_clear_separable(s._h, C.c_int32(which), C.c_int32(phase)))
 
 
+# =============================================================================== device functions
+
+
+def _program_times(Δt: float, Tₑ: float, max_steps: Optional[int]) -> np.ndarray:
+    """rows x 2: the two times of every step, from the one walk of the loop's clock (_separable_table with a(t) = t)."""
+    tab = _separable_table([lambda t: t], Δt, Tₑ, max_steps)
+    return np.ascontiguousarray(tab.reshape(tab.shape[0], 2))
+
+
+def _install_program(s: "Solver", which: int, phase: int, df: DeviceFunction, nspace: int, times: np.ndarray,
+                     key: Optional[int] = None) -> None:
+    prog = df.program_for(nspace)
+    times = np.ascontiguousarray(times, dtype=np.float64)
+    if key is None:
+        L.check(L.lib().pg_solver_set_program(s._h, C.c_int32(which), C.c_int32(phase), C.byref(prog), C.c_int64(times.shape[0]),
+                                              L.dptr(times)))
+    else:
+        L.check(L.lib().pg_solver_set_border_program(s._h, C.c_int32(key), C.byref(prog), C.c_int64(times.shape[0]),
+                                                     L.dptr(times)))
+
+
+def _program_border(bc_b: "BorderConditions", mesh: "Mesh", time_independent: bool):
+    """Border values with DeviceFunction conditions as (values of every border cell without them -- constants and closures
+    without a time parameter, 0 on the cells of a DeviceFunction --, [(key, DeviceFunction), ...]): one program per border key,
+    applied to that key's cells."""
+    progs: list = []
+    static = _border_values(bc_b, mesh, 0.0, programs=progs, time_independent=time_independent)
+    return static, progs
+
+
+def _device_data(values) -> bool:
+    """Can these time-dependent data stay on the device?  Every one a TimeSeparable or a DeviceFunction."""
+    return bool(values) and all(isinstance(v, (TimeSeparable, DeviceFunction)) for v in values)
+
+
 # =============================================================================== monitors
 
 
@@ -932,9 +969,10 @@ class Solver:
         self._initial_done = False
         self.last_run: Optional[L.pg_run_info] = None
         self.unconverged = 0          # solves that ended without meeting the tolerance (see _check_converged)
-        # where the last unsteady solve took its time-dependent data from: "device" (every one a TimeSeparable: spatial parts
-        # and a coefficient table installed once, the loop stays on the device), "host" (closures re-evaluated and uploaded
-        # every step), None (no time-dependent data, or no unsteady solve yet)
+        # where the last unsteady solve took its time-dependent data from: "device" (every one a TimeSeparable or a
+        # DeviceFunction: spatial parts and a coefficient table, or a program and a table of times, installed once, the loop
+        # stays on the device), "host" (closures re-evaluated and uploaded every step), None (no time-dependent data, or no
+        # unsteady solve yet)
         self.time_data: Optional[str] = None
         # monitors=[...] of the last unsteady solve: one row per completed solve (row 0: the first solve), one column per
         # monitor; the solver's time of each row; the monitors' names.  state_steps: with save_every=k, the step each entry of
@@ -1063,9 +1101,11 @@ def _border_descs(bc_b: BorderConditions, mesh: Mesh, t: Optional[float]):
     return arr, len(descs), values
 
 
-def _border_values(bc_b: BorderConditions, mesh: Mesh, t: Optional[float]) -> np.ndarray:
+def _border_values(bc_b: BorderConditions, mesh: Mesh, t: Optional[float], programs: Optional[list] = None,
+                   time_independent: bool = False) -> np.ndarray:
     """eval_bc_value at every border cell (src/solver.jl:441-448): value(pos..., t) with the N unpadded
-    coordinates of mesh.centers."""
+    coordinates of mesh.centers.  With a list `programs`, a key whose value is a time-dependent DeviceFunction is not
+    evaluated: its cells stay 0 and (key, DeviceFunction) is appended to the list."""
     idx, pos, key = mesh._border_arrays()
     out = np.zeros(len(key))
     inv = {v: k for k, v in L.PG_KEY.items()}
@@ -1075,7 +1115,9 @@ def _border_values(bc_b: BorderConditions, mesh: Mesh, t: Optional[float]) -> np
             continue
         sel = key == kval
         v = getattr(cond, "value", 0.0)
-        if callable(v):
+        if programs is not None and isinstance(v, DeviceFunction) and _time_dependent(v, mesh.N, time_independent):
+            programs.append((int(kval), v))
+        elif callable(v):
             out[sel] = _eval(v, pos[sel], t, mesh.N)
         elif v is not None:
             out[sel] = float(v)
@@ -1270,18 +1312,35 @@ def solve_DiffusionUnsteadyMono_b(s: Solver, phase: Phase, Δt: float, Tₑ: flo
     _clear_separable(s, 1)
     dyn_data = ([phase.source] if dyn_f else []) + ([bc.value] if dyn_g else []) + \
         [c.value for c in bc_b.borders.values() if _time_dependent(getattr(c, "value", None), mesh.N, time_independent)]
-    border_sep = _separable_border(bc_b, mesh) if dyn_b and all(isinstance(v, TimeSeparable) for v in dyn_data) else None
-    device = bool(dyn_data) and all(isinstance(v, TimeSeparable) for v in dyn_data) and (not dyn_b or border_sep is not None)
+    # ... or a DeviceFunction: its program goes once, and a kernel evaluates it every step.  One kind per slot; the border slot
+    # takes TimeSeparable values or DeviceFunctions, not both.
+    dyn_bv = dyn_data[int(dyn_f) + int(dyn_g):]
+    border_sep = border_prog = None
+    if dyn_b and _device_data(dyn_data):
+        if all(isinstance(v, TimeSeparable) for v in dyn_bv):
+            border_sep = _separable_border(bc_b, mesh)
+        elif all(isinstance(v, DeviceFunction) for v in dyn_bv):
+            border_prog = _program_border(bc_b, mesh, time_independent)
+    device = _device_data(dyn_data) and (not dyn_b or border_sep is not None or border_prog is not None)
     s.time_data = "device" if device else ("host" if dyn_data else None)
     if device:
         table = lambda coefs: _separable_table(coefs, Δt, Tₑ, max_steps)
         if len(table([])) > 0:
-            if dyn_f:
+            times = _program_times(Δt, Tₑ, max_steps)
+            if dyn_f and isinstance(phase.source, DeviceFunction):
+                _install_program(s, _TD_SOURCE, 0, phase.source, 3, times)
+            elif dyn_f:
                 _install_separable(s, _TD_SOURCE, 0, _separable_fields(phase.source, cap._cw, 3, M), table(phase.source))
-            if dyn_g:
+            if dyn_g and isinstance(bc.value, DeviceFunction):
+                _install_program(s, _TD_INTERFACE, 0, bc.value, 3, times)
+            elif dyn_g:
                 _install_separable(s, _TD_INTERFACE, 0, _separable_fields(bc.value, cap._cg, 3, M), table(bc.value))
-            if dyn_b:
+            if border_sep is not None:
                 _install_separable(s, _TD_BORDER, 0, border_sep[0], table(border_sep[1]))
+            elif border_prog is not None:
+                L.check(L.lib().pg_solver_set_border_values(s._h, L.dptr(border_prog[0])))
+                for kval, df in border_prog[1]:
+                    _install_program(s, _TD_BORDER, 0, df, mesh.N, times, key=kval)
     if device or not (dyn_f or dyn_g or dyn_b):
         if (save_states and not save_every) or verbose or log:
             while t < Tₑ:
@@ -1430,13 +1489,16 @@ def solve_DiffusionUnsteadyDiph_b(s: Solver, phase1: Phase, phase2: Phase, Δt: 
     # every time-dependent source a TimeSeparable: installed once, and no pg_solver_set_source inside the loop
     _clear_separable(s, 2)
     dyn_src = [(q, ph.source) for q, ph in enumerate((phase1, phase2)) if _time_dependent(ph.source, 3, time_independent)]
-    device = bool(dyn_src) and all(isinstance(f, TimeSeparable) for _, f in dyn_src)
+    device = _device_data([f for _, f in dyn_src])
     s.time_data = "device" if device else ("host" if dyn_src else None)
     if device:
         if len(_separable_table([], Δt, Tₑ, max_steps)) > 0:
             for q, f in dyn_src:
-                _install_separable(s, _TD_SOURCE, q, _separable_fields(f, (phase1, phase2)[q].capacity._cw, 3, M),
-                                   _separable_table(f, Δt, Tₑ, max_steps))
+                if isinstance(f, DeviceFunction):
+                    _install_program(s, _TD_SOURCE, q, f, 3, _program_times(Δt, Tₑ, max_steps))
+                else:
+                    _install_separable(s, _TD_SOURCE, q, _separable_fields(f, (phase1, phase2)[q].capacity._cw, 3, M),
+                                       _separable_table(f, Δt, Tₑ, max_steps))
     # the whole loop in one call: separable data without a history asked for, as before; and save_every, whose history the
     # device keeps, on separable or constant data
     if (device and not (save_states or verbose or kwargs.get("log", False))) or (save_every and (device or not dyn_src)):

@@ -16,6 +16,8 @@
 #include "pg_krylov.h"
 #include "pg_reduce.h"
 #include "pg_multigrid.h"
+#include "pg_program.h"
+#include "pg_scan.h"
 #include "pg_solver_internal.h"
 #include "pg_spmv.h"
 #include "pg_specest.h"
@@ -66,6 +68,20 @@ struct pg_solver {
     i64 nrows = 0;
     DevBuf<double> mode[PG_TD_MAX_TERMS];
     std::vector<double> coef;      // nrows x 2 x K
+    // ... or device functions (pg_solver_set_program; K == 0 then): each a program, the compact list of the rows that carry its
+    // data -- (row, weight, point) in SoA form, built once by k_td_points_* -- and the two times of every step.  One program in
+    // a source or interface slot; in the border slot one for every border cell (key -1) or one per border key.
+    struct Prog {
+      pg_program prog;
+      int key = -1;
+      i64 n = 0;                   // listed rows (0: nothing is launched)
+      DevBuf<int> row;
+      DevBuf<double> w, p[3];
+      i64 nrows = 0;
+      std::vector<double> times;   // nrows x 2
+    };
+    std::vector<Prog> progs;
+    bool empty() const { return K == 0 && progs.empty(); }
   };
   TdSlot td[4];                    // source of phase 0, source of phase 1, mono interface value, border values
   DevBuf<double> td_base;
@@ -1097,6 +1113,66 @@ __global__ void k_td_border_rows(i64 nb, const i64* cells_global, const double* 
   }
 }
 
+// ---- device functions: the list of the rows that carry a slot's data (built once per installed program) --------------------
+// item i of a source / interface slot is row i; item i of the border slot is (border cell i / nbulk, phase i % nbulk)
+struct TdPointsArgs {
+  int which, phase, nbulk, N;
+  i64 n_items, n_own, first_cell, Mloc;
+  const int* row_cell;
+  const int* red;
+  const unsigned char* fixed;
+  const i64* cells_global;         // border: global linear index of each border cell
+  const unsigned char* selected;   // border: 1 for the cells of the program's key(s)
+  const double* weight;            // V (source) / Γ (interface) by local cell; border: none (1)
+  const double* pos[3];            // C_ω / C_γ by local cell (source / interface), the cell centres by border cell (border)
+};
+
+// the row of item i, or -1 when the item carries no data of the slot -- the rows and weights of k_td_mode and k_td_border_rows
+__device__ inline i64 td_item_row(const TdPointsArgs& a, const RowSegs& seg, i64 i, i64* src) {
+  if (a.which == PG_TD_BORDER) {
+    const i64 q = i / a.nbulk;
+    const int ph = (int)(i % a.nbulk);
+    *src = q;
+    if (!a.selected[q]) return -1;
+    const i64 lc = a.cells_global[q] - a.first_cell;
+    if (lc < 0 || lc >= a.Mloc) return -1;
+    const int r = a.red[(i64)(2 * ph) * a.Mloc + lc];
+    return (r >= 0 && r < a.n_own && a.fixed[r]) ? r : -1;
+  }
+  const int k = seg_kind(seg, i);
+  *src = a.row_cell[i];
+  if (a.which == PG_TD_SOURCE) return ((k & 1) == 0 && (k >> 1) == a.phase && !a.fixed[i]) ? i : -1;
+  return (k & 1) == 1 ? i : -1;
+}
+
+__global__ void k_td_points_flag(TdPointsArgs a, RowSegs seg, unsigned char* __restrict__ flag) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < a.n_items; i += (i64)gridDim.x * blockDim.x) {
+    i64 src;
+    flag[i] = td_item_row(a, seg, i, &src) >= 0 ? 1 : 0;
+  }
+}
+
+// k_td_points: the flagged items in their order, compact: (row, weight, p0, p1, p2), coordinates the problem lacks as 0.0
+__global__ void k_td_points(TdPointsArgs a, RowSegs seg, const int* __restrict__ where, i64 n_list, int* __restrict__ row,
+                            double* __restrict__ w, double* __restrict__ p0, double* __restrict__ p1, double* __restrict__ p2) {
+  for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < a.n_items; i += (i64)gridDim.x * blockDim.x) {
+    i64 src;
+    const i64 r = td_item_row(a, seg, i, &src);
+    if (r < 0) continue;
+    const i64 e = where[i];
+    if (e < 0 || e >= n_list) continue;        // (cannot happen: the list has the scan's total)
+    row[e] = (int)r;
+    w[e] = a.weight ? a.weight[src] : 1.0;
+    p0[e] = a.pos[0] ? a.pos[0][src] : 0.0;
+    p1[e] = a.pos[1] ? a.pos[1][src] : 0.0;
+    p2[e] = a.pos[2] ? a.pos[2][src] : 0.0;
+  }
+}
+
+__global__ void k_td_zero_rows(i64 n, const int* __restrict__ row, double* __restrict__ out) {
+  for (i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x; e < n; e += (i64)gridDim.x * blockDim.x) out[row[e]] = 0.0;
+}
+
 struct TdTerms {
   const double* m[PG_TD_MAX_TERMS];
   double c[PG_TD_MAX_TERMS];
@@ -1322,14 +1398,15 @@ SrcView src_view(const pg_solver* s) {
 
 bool td_installed(const pg_solver* s) {
   for (const auto& t : s->td)
-    if (t.K > 0) return true;
+    if (!t.empty()) return true;
   return false;
 }
 
 void td_clear(pg_solver* s, int slot) {
   pg_solver::TdSlot& t = s->td[slot];
-  if (t.K == 0) return;
+  if (t.empty()) return;
   for (auto& m : t.mode) m.release();
+  t.progs.clear();
   t.K = 0;
   t.nrows = 0;
   t.coef.clear();
@@ -1372,8 +1449,8 @@ void td_bconst(pg_solver* s, int scheme) {
     if (s->td_base.n != n) s->td_base.alloc(n);
     SrcView v = src_view(s);
     for (int q = 0; q < 2; ++q)
-      if (s->td[q].K > 0) v.f_n[q] = v.f_np1[q] = nullptr;
-    if (s->td[2].K > 0) { v.g_n = v.g_np1 = nullptr; v.g_const = 0.0; }
+      if (!s->td[q].empty()) v.f_n[q] = v.f_np1[q] = nullptr;
+    if (!s->td[2].empty()) { v.g_n = v.g_np1 = nullptr; v.g_const = 0.0; }
     hipLaunchKernelGGL(k_bconst, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, st, make_params(s, scheme), make_segs(s->nb), n,
                        s->nb.row_cell.p, v, scheme, s->dt, s->fixed.p, s->bcv.p, s->td_base.p, 0);
     PG_HIP(hipGetLastError());
@@ -1383,6 +1460,11 @@ void td_bconst(pg_solver* s, int scheme) {
         hipLaunchKernelGGL(k_td_border_rows, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, st, nb, s->border_cells_lin.p,
                            (const double*)nullptr, s->slab.first_cell(), s->Mloc, s->nphase, s->nb.red.p, n, s->fixed.p,
                            s->td_base.p);
+      PG_HIP(hipGetLastError());
+    }
+    for (const auto& pr : s->td[3].progs) {      // a border program's rows: its value alone, the others keep what bcv holds
+      if (pr.n <= 0) continue;
+      hipLaunchKernelGGL(k_td_zero_rows, dim3(grid_for(pr.n, BLOCK)), dim3(BLOCK), 0, st, pr.n, pr.row.p, s->td_base.p);
       PG_HIP(hipGetLastError());
     }
   }
@@ -1422,6 +1504,23 @@ void td_bconst(pg_solver* s, int scheme) {
     }
   }
   flush();
+  // device functions: bconst = base (+ separable terms), then every program adds its own rows, slot after slot
+  bool any_prog = false;
+  for (const auto& t : s->td) any_prog = any_prog || !t.progs.empty();
+  if (!any_prog) return;
+  if (base != s->bconst.p && n > 0)
+    PG_HIP(hipMemcpyAsync(s->bconst.p, s->td_base.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, st));
+  for (int slot = 0; slot < 4; ++slot)
+    for (const auto& pr : s->td[slot].progs) {
+      PG_REQUIRE(s->td_row >= 0 && s->td_row < pr.nrows, "device function: no table row for this right-hand side");
+      const double t0 = pr.times[(size_t)2 * s->td_row], t1 = pr.times[(size_t)2 * s->td_row + 1];
+      double c0, c1;
+      if (slot == 3) { c0 = 0.0; c1 = 1.0; }
+      else if (cn) c0 = c1 = s->dt / 2;
+      else { c0 = 0.0; c1 = slot == 2 ? 1.0 : s->dt; }
+      td_eval_launch(pr.prog, pr.n, pr.row.p, pr.w.p, pr.p[0].p, pr.p[1].p, pr.p[2].p, c0, c1, t0, slot == 3 ? t0 : t1,
+                     s->bconst.p, st);
+    }
 }
 
 void ensure_bconst(pg_solver* s, int scheme) {
@@ -1951,10 +2050,15 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     mg_step_ensure(s, run_matrix(s));
   }
   // time-separable data: this step's row of the coefficient table -- never an older one
-  for (const auto& t : s->td)
+  for (const auto& t : s->td) {
     PG_REQUIRE(t.K == 0 || s->td_cursor < t.nrows,
                "time-separable data: this step is past the last row of the coefficient table (" + std::to_string(t.nrows) +
                " rows, all consumed); install a longer table with pg_solver_set_separable");
+    for (const auto& pr : t.progs)
+      PG_REQUIRE(s->td_cursor < pr.nrows,
+                 "device function: this step is past the last row of the table of times (" + std::to_string(pr.nrows) +
+                 " rows, all consumed); install a longer table with pg_solver_set_program");
+  }
   if (td_installed(s)) s->td_row = s->td_cursor++;
   hipStream_t stream = ctx().stream;
   ensure_run_matrix(s, scheme);
@@ -2562,6 +2666,163 @@ int32_t pg_solver_set_separable(pg_solver* s, int32_t which, int32_t phase, int3
   s->td_cursor = 0;
   s->td_row = -1;
   s->bconst_dirty = true;                      // td_base: k_bconst without this slot's own data
+  PG_API_END
+}
+
+// a program into slot `slot` (border: for the cells of `key`, -1 every one): refusals, the list of its rows, the table
+static void td_install_program(pg_solver* s, const std::string& who, int which, int phase, int slot, int key,
+                               const pg_program* prog, int64_t nrows, const double* times) {
+  std::string why;
+  PG_REQUIRE(pgprog::program_validate(prog, &why), who + "invalid program: " + why);
+  PG_REQUIRE(times && nrows >= 1, who + "times and at least one table row are needed");
+  PG_REQUIRE(s->scheme_ctor != PG_SCHEME_STEADY, who + "a steady solver has no time loop");
+  PG_REQUIRE(!s->moving && !s->stefan, who + "moving-body and Stefan solvers are one space-time step each");
+  PG_REQUIRE(!(which == PG_TD_INTERFACE && s->nphase == 2),
+             who + "PG_TD_INTERFACE on a diphasic solver (its jump rows carry no time)");
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm, who + "it runs on one rank only (virtual ranks included)");
+  PG_REQUIRE(s->initial_done, who + "install after pg_solver_initial_solve (the constructor's system takes its data from the host)");
+  const pg_capacity* cap = s->cap[which == PG_TD_SOURCE ? phase : 0];
+  PG_REQUIRE(which != PG_TD_INTERFACE || cap->has_cg, who + "the capacity was built without C_gamma (PG_FLAG_NO_CENTROIDS)");
+  const i64 n = s->nb.n_own;
+  const i64 nb = which == PG_TD_BORDER ? ensure_border_cells(s) : 0;
+  const i64 n_items = which == PG_TD_BORDER ? nb * s->nphase : n;
+  PG_REQUIRE(n_items < ((i64)1 << 31), who + "more rows than the list's 32-bit positions hold");
+  hipStream_t st = ctx().stream;                                        // (every refusal is above: what was installed stays until here)
+  pg_solver::TdSlot& t = s->td[slot];
+  if (t.K > 0 || which != PG_TD_BORDER || key < 0) td_clear(s, slot);   // separable terms, or the slot's one program, go
+  for (size_t j = 0; j < t.progs.size(); ++j)                            // (border: the program of the same key, or of every key)
+    if (t.progs[j].key == key || t.progs[j].key < 0) { t.progs.erase(t.progs.begin() + j); --j; }
+  pg_solver::TdSlot::Prog pr;
+  pr.prog = *prog;
+  pr.key = key;
+  const pg_mesh* m = s->cap[0]->mesh;
+  const int N = m->N;
+  const SysParams P = make_params(s, s->scheme_ctor);
+  TdPointsArgs a{};
+  a.which = which; a.phase = phase; a.nbulk = s->nphase; a.N = N;
+  a.n_own = n; a.first_cell = s->slab.first_cell(); a.Mloc = s->Mloc;
+  a.row_cell = s->nb.row_cell.p; a.red = s->nb.red.p; a.fixed = s->fixed.p;
+  DevBuf<unsigned char> selected;
+  DevBuf<double> centres;
+  if (which == PG_TD_BORDER) {
+    a.n_items = n_items;
+    if (nb > 0) {
+      std::vector<unsigned char> sel(nb);
+      std::vector<double> pos((size_t)N * nb);
+      for (i64 q = 0; q < nb; ++q) {
+        sel[q] = key < 0 || m->border_key[q] == key;
+        for (int d = 0; d < N; ++d) pos[(size_t)d * nb + q] = m->border_pos[q * N + d];
+      }
+      selected.alloc(nb); selected.upload(sel.data(), nb);
+      centres.alloc((i64)N * nb); centres.upload(pos.data(), (i64)N * nb);
+      for (int d = 0; d < N; ++d) a.pos[d] = centres.p + (i64)d * nb;
+    }
+    a.cells_global = s->border_cells_lin.p;
+    a.selected = selected.p;
+  } else {
+    a.n_items = n_items;
+    a.weight = which == PG_TD_SOURCE ? P.cap[phase].V : P.cap[0].G;
+    for (int d = 0; d < N; ++d) a.pos[d] = which == PG_TD_SOURCE ? cap->Cw[d].p : cap->Cg[d].p;
+  }
+  if (a.n_items > 0) {
+    DevBuf<unsigned char> flag(a.n_items);
+    DevBuf<int> where(a.n_items), total(1);
+    const RowSegs seg = make_segs(s->nb);
+    hipLaunchKernelGGL(k_td_points_flag, dim3(grid_for(a.n_items, BLOCK)), dim3(BLOCK), 0, st, a, seg, flag.p);
+    PG_HIP(hipGetLastError());
+    scan_exclusive<unsigned char>(flag.p, where.p, a.n_items, total.p, st);
+    int cnt = 0;
+    total.download(&cnt, 1);
+    pr.n = cnt;
+    if (cnt > 0) {
+      pr.row.alloc(cnt); pr.w.alloc(cnt);
+      for (auto& p : pr.p) p.alloc(cnt);
+      hipLaunchKernelGGL(k_td_points, dim3(grid_for(a.n_items, BLOCK)), dim3(BLOCK), 0, st, a, seg, (const int*)where.p, (i64)cnt,
+                         pr.row.p, pr.w.p, pr.p[0].p, pr.p[1].p, pr.p[2].p);
+      PG_HIP(hipGetLastError());
+    }
+    PG_HIP(hipStreamSynchronize(st));          // (flag, where, selected and centres go with this scope)
+  }
+  pr.times.assign(times, times + (size_t)nrows * 2);
+  pr.nrows = nrows;
+  t.progs.push_back(std::move(pr));
+  s->td_cursor = 0;
+  s->td_row = -1;
+  s->bconst_dirty = true;                      // td_base: k_bconst without this slot's own data
+}
+
+int32_t pg_solver_set_program(pg_solver* s, int32_t which, int32_t phase, const pg_program* prog, int64_t nrows,
+                              const double* times) {
+  PG_API_BEGIN
+  require_init();
+  const int slot = td_slot_of(s, which, phase, "pg_solver_set_program");
+  td_install_program(s, "pg_solver_set_program refused: ", which, phase, slot, -1, prog, nrows, times);
+  PG_API_END
+}
+
+int32_t pg_solver_set_border_program(pg_solver* s, int32_t key, const pg_program* prog, int64_t nrows, const double* times) {
+  PG_API_BEGIN
+  require_init();
+  const std::string who = "pg_solver_set_border_program refused: ";
+  PG_REQUIRE(s, who + "NULL solver");
+  PG_REQUIRE(key >= 0 && key < 6, who + "key must be one of PG_KEY_*");
+  td_install_program(s, who, PG_TD_BORDER, 0, 3, key, prog, nrows, times);
+  PG_API_END
+}
+
+int32_t pg_solver_program_info(const pg_solver* s, int32_t* programs, int64_t* entries, int64_t* nrows, int64_t* cursor) {
+  PG_API_BEGIN
+  PG_REQUIRE(s, "pg_solver_program_info: NULL solver");
+  i64 rows = 0;
+  auto take = [&](i64 r) { rows = rows == 0 ? r : std::min(rows, r); };
+  for (int q = 0; q < 4; ++q) {
+    i64 e = 0;
+    if (s->td[q].K > 0) take(s->td[q].nrows);
+    for (const auto& pr : s->td[q].progs) { e += pr.n; take(pr.nrows); }
+    if (programs) programs[q] = (int32_t)s->td[q].progs.size();
+    if (entries) entries[q] = e;
+  }
+  if (nrows) *nrows = rows;
+  if (cursor) *cursor = s->td_cursor;
+  PG_API_END
+}
+
+// measurement (scripts/bench_device_function.py): the evaluation of every installed program at the last step's times launched
+// `repeats` times between two events.  It adds to a scratch vector, not to bconst: the solver's data stay what they were.
+int32_t pg_debug_td_eval_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_eval, int64_t* entries,
+                            int64_t* instructions) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && ms_per_eval && repeats >= 1, "pg_debug_td_eval_ms: bad arguments");
+  PG_REQUIRE(scheme == PG_SCHEME_BE || scheme == PG_SCHEME_CN, "scheme must be BE or CN");
+  PG_REQUIRE(s->td_row >= 0, "pg_debug_td_eval_ms: no step has consumed a row of the table yet");
+  hipStream_t st = ctx().stream;
+  const bool cn = scheme == PG_SCHEME_CN;
+  DevBuf<double> sink(s->nb.n_own > 0 ? s->nb.n_own : 1);
+  sink.zero();
+  i64 ne = 0, ni = 0;
+  auto once = [&](bool count) {
+    for (int slot = 0; slot < 4; ++slot)
+      for (const auto& pr : s->td[slot].progs) {
+        PG_REQUIRE(s->td_row < pr.nrows, "pg_debug_td_eval_ms: no table row");
+        const double t0 = pr.times[(size_t)2 * s->td_row], t1 = pr.times[(size_t)2 * s->td_row + 1];
+        const double c0 = (slot != 3 && cn) ? s->dt / 2 : 0.0, c1 = slot == 3 ? 1.0 : cn ? s->dt / 2 : slot == 2 ? 1.0 : s->dt;
+        td_eval_launch(pr.prog, pr.n, pr.row.p, pr.w.p, pr.p[0].p, pr.p[1].p, pr.p[2].p, c0, c1, t0, slot == 3 ? t0 : t1, sink.p, st);
+        if (count) { ne += pr.n; ni += pr.n * pr.prog.n_ops * (c0 != 0.0 ? 2 : 1); }
+      }
+  };
+  once(true);
+  PG_REQUIRE(ne > 0, "pg_debug_td_eval_ms: no program with listed rows is installed");
+  EventPair ev;
+  PG_HIP(hipEventRecord(ev.e0, st));
+  for (int r = 0; r < repeats; ++r) once(false);
+  PG_HIP(hipEventRecord(ev.e1, st));
+  PG_HIP(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *ms_per_eval = (double)ms / repeats;
+  if (entries) *entries = ne;
+  if (instructions) *instructions = ni;
   PG_API_END
 }
 

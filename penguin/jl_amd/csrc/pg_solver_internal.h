@@ -31,4 +31,10 @@ void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, Sol
 void solver_state_padded(pg_solver* s, double* padded /* K * Mloc, device */);
 void solver_step_info(pg_solver* s, const SolveStats& st, double time, pg_step_info* info);
 
+// device functions (pg_program.hip): entry e of a list: out[row_e] += w_e (c0 P(p_e, t0) + c1 P(p_e, t1)), c0 == 0 skipping
+// the first evaluation; n == 0 launches nothing.  row == nullptr: out[e] = the sum itself.
+constexpr int TD_EVAL_BLOCK = 256;
+void td_eval_launch(const pg_program& P, i64 n, const int* row, const double* w, const double* p0, const double* p1,
+                    const double* p2, double c0, double c1, double t0, double t1, double* out, hipStream_t st);
+
 }  // namespace pg
