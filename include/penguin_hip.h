@@ -38,6 +38,7 @@ typedef struct pg_streamvort pg_streamvort; /* Penguin.StreamVorticity{2} src/so
 
 /* ---- enums --------------------------------------------------------------------------- */
 enum { PG_BODY_BALL = 1, PG_BODY_MULTIBALL = 2, PG_BODY_HALFSPACE = 3, PG_BODY_ELLIPSOID = 4, PG_BODY_PLANE = 5 }; /* closed-form level sets evaluated in-kernel */
+enum { PG_BODY_PROGRAM = 6 };                     /* a traced level set: pg_capacity_create_program */
 enum { PG_FLAG_COMPLEMENT = 1, PG_FLAG_NO_CENTROIDS = 2 };
 /* capacity fields for pg_capacity_get (d = dimension for A,B,W,C_omega,C_gamma) */
 enum { PG_CAP_V = 0, PG_CAP_GAMMA = 1, PG_CAP_CELL_TYPES = 2, PG_CAP_A = 3, PG_CAP_B = 4,
@@ -331,6 +332,10 @@ int32_t pg_capacity_destroy(pg_capacity* c);
    the rest are left untouched) */
 int32_t pg_capacity_get(const pg_capacity* c, int32_t field, int32_t d, double* out, int64_t len);
 int32_t pg_capacity_kernel_ms(const pg_capacity* c, double* ms); /* device time of K1-K5 for the bench */
+/* the same per kernel, each between its own pair of events: ms[0..4] = classification, cut cells, sections, staggered volumes,
+   cut staggered boxes; 0 where an empty work list launched nothing.  Zeros for capacities not built by pg_capacity_create_levelset
+   or pg_capacity_create_program. */
+int32_t pg_capacity_kernel_ms_parts(const pg_capacity* c, double* ms /* 5 */);
 
 /* ---- DiffusionOps                         replaces DiffusionOps(capacity), operators.jl:127-178 */
 int32_t pg_diffops_create(pg_capacity* c, pg_diffops** out);
@@ -567,6 +572,20 @@ int32_t pg_solver_program_info(const pg_solver* s, int32_t* programs /*4*/, int6
 /* test support: the kernel-side evaluator (same instantiation and stack layout as the per-step kernel) on caller-supplied
    points: out[i] = P(xyz[3i .. 3i+2], t) */
 int32_t pg_debug_program_eval(const pg_program* prog, int64_t npts, const double* xyz /* npts x 3 */, double t, double* out);
+/* Capacity(body, mesh) of an ARBITRARY level set (PG_BODY_PROGRAM): phi(x_1 .. x_N) as a program and the N programs of its
+   partial derivatives d phi / d x_d (grad[0 .. N-1]); fluid where phi <= 0, PG_FLAG_COMPLEMENT: -phi and -grad phi,
+   PG_FLAG_NO_CENTROIDS as for the closed-form kinds.  1-D and 2-D.  The kernels of pg_capacity_create_levelset run with the
+   body evaluated to rounding where the geometry needs it: a cell is classified on a lattice of 9 samples per edge and its centre
+   (a feature of the body narrower than h / 8 is not seen), the roots of phi along cell edges and quadrature lines are found
+   to an ulp of their coordinate, cut cells are integrated with 16 Gauss-Legendre nodes per smooth piece.
+   Refused before anything is allocated, each with its own message: an invalid program; a program that reads t (PG_OP_VAR 3) or
+   a coordinate >= N; a 3-D mesh; grad == NULL; more than one rank or a communicator; a gradient that disagrees with central
+   differences of phi (step 1e-6 h) by more than 1e-4 max(|grad phi|, 1) at the centres of up to 64 cells spread over the mesh
+   (evaluated on the host with pg_program_eval_host's interpreter: it catches a wrong derivative, not rounding).
+   The programs of the capacity under construction sit in one __constant__ table per process: concurrent calls from several
+   host threads are serialised by a mutex inside, each holding it until its last kernel has run. */
+int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */, int32_t flags,
+                                   pg_capacity** out);
 /* measurement: the per-step evaluation of every installed program at the last consumed row, `repeats` times between two
    events; entries = listed rows summed over the programs, instructions = entries x n_ops x evaluations summed likewise */
 int32_t pg_debug_td_eval_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_eval, int64_t* entries,

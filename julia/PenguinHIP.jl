@@ -303,7 +303,8 @@ end
 # (`Penguin.Capacity(body, penguin_mesh)`, the libvofi path) and hand its arrays over with capacity_from_arrays.
 function Capacity(body::Function, mesh::Mesh{N}; kwargs...) where N
     error("PenguinHIP.Capacity: arbitrary level-set closures cannot run on the GPU; pass a Sphere / MultiSphere / " *
-          "Ellipsoid / HalfSpace / Plane, or build the capacity with Penguin.Capacity and call PenguinHIP.capacity_from_arrays(cap, mesh)")
+          "Ellipsoid / HalfSpace / Plane, wrap the closure in DeviceFunction (1-D and 2-D: it is traced and evaluated in the " *
+          "kernels), or build the capacity with Penguin.Capacity and call PenguinHIP.capacity_from_arrays(cap, mesh)")
 end
 """
     capacity_from_arrays(cap, mesh::Mesh{N})
@@ -638,6 +639,94 @@ function evaluate_program(df::DeviceFunction, xyz::Matrix{Float64}, t::Real; nsp
     check(ccall((:pg_program_eval_host, libpg), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Float64, Ptr{Float64}),
                 program(df, nspace), size(xyz, 2), xyz, t, out))
     out
+end
+# ---- DeviceFunction as the BODY of a Capacity (1-D, 2-D): the closure of the coordinates alone is traced, differentiated rule
+# by rule (the twin of penguin/jl_amd/devfn.py `differentiate`) and evaluated inside the capacity kernels; fluid where it is <= 0
+_isk(s::Sym) = s.op == PG_OP_CONST
+_isk(s::Sym, v) = s.op == PG_OP_CONST && s.value == v
+_dadd(a::Sym, b::Sym) = _isk(a) && _isk(b) ? Sym(a.value + b.value) : _isk(a, 0.0) ? b : _isk(b, 0.0) ? a : _sym(PG_OP_ADD, a, b)
+_dneg(a::Sym) = _isk(a) ? Sym(-a.value) : a.op == PG_OP_NEG ? a.args[1] : _sym(PG_OP_NEG, a)
+_dsub(a::Sym, b::Sym) = _isk(a) && _isk(b) ? Sym(a.value - b.value) : _isk(b, 0.0) ? a : _isk(a, 0.0) ? _dneg(b) : _sym(PG_OP_SUB, a, b)
+function _dmul(a::Sym, b::Sym)
+    _isk(a) && _isk(b) && return Sym(a.value * b.value)
+    (_isk(a, 0.0) || _isk(b, 0.0)) && return Sym(0.0)
+    _isk(a, 1.0) && return b
+    _isk(b, 1.0) && return a
+    _isk(a, -1.0) && return _dneg(b)
+    _isk(b, -1.0) && return _dneg(a)
+    _sym(PG_OP_MUL, a, b)
+end
+_ddiv(a::Sym, b::Sym) = _isk(a, 0.0) ? Sym(0.0) : _isk(b, 1.0) ? a : (_isk(a) && _isk(b) && b.value != 0.0) ? Sym(a.value / b.value) : _sym(PG_OP_DIV, a, b)
+_dsel(c::Sym, a::Sym, b::Sym) = (_isk(a) && _isk(b) && a.value == b.value) ? a : _sym(PG_OP_SELECT, c, a, b)
+function differentiate(node::Sym, var::Int)
+    op, a = node.op, node.args
+    op == PG_OP_CONST && return Sym(0.0)
+    op == PG_OP_VAR && return Sym(Int(node.value) == var ? 1.0 : 0.0)
+    op in (PG_OP_LT, PG_OP_LE, PG_OP_GT, PG_OP_GE) && return Sym(0.0)
+    d = [differentiate(x, var) for x in a]
+    op == PG_OP_SELECT && return _dsel(a[1], d[2], d[3])
+    op == PG_OP_ADD && return _dadd(d[1], d[2])
+    op == PG_OP_SUB && return _dsub(d[1], d[2])
+    op == PG_OP_NEG && return _dneg(d[1])
+    op == PG_OP_MUL && return _dadd(_dmul(d[1], a[2]), _dmul(a[1], d[2]))
+    if op == PG_OP_DIV
+        _isk(d[2], 0.0) && return _ddiv(d[1], a[2])
+        return _ddiv(_dsub(_dmul(d[1], a[2]), _dmul(a[1], d[2])), _dmul(a[2], a[2]))
+    end
+    op == PG_OP_MIN && return _dsel(_sym(PG_OP_LE, a[1], a[2]), d[1], d[2])
+    op == PG_OP_MAX && return _dsel(_sym(PG_OP_GE, a[1], a[2]), d[1], d[2])
+    if op == PG_OP_POW
+        if _isk(a[2])
+            e = a[2].value
+            return _dmul(_dmul(Sym(e), _sym(PG_OP_POW, a[1], Sym(e - 1.0))), d[1])
+        end
+        out = _dmul(_dmul(node, _sym(PG_OP_LOG, a[1])), d[2])
+        _isk(d[1], 0.0) || (out = _dadd(out, _dmul(node, _ddiv(_dmul(a[2], d[1]), a[1]))))
+        return out
+    end
+    op == PG_OP_ATAN2 && return _ddiv(_dsub(_dmul(a[2], d[1]), _dmul(a[1], d[2])), _dadd(_dmul(a[1], a[1]), _dmul(a[2], a[2])))
+    u, du = a[1], d[1]
+    _isk(du, 0.0) && return Sym(0.0)
+    op == PG_OP_ABS && return _dsel(_sym(PG_OP_GE, u, Sym(0.0)), du, _dneg(du))
+    op == PG_OP_SQRT && return _ddiv(du, _dmul(Sym(2.0), node))
+    op == PG_OP_EXP && return _dmul(node, du)
+    op == PG_OP_LOG && return _ddiv(du, u)
+    op == PG_OP_SIN && return _dmul(_sym(PG_OP_COS, u), du)
+    op == PG_OP_COS && return _dneg(_dmul(_sym(PG_OP_SIN, u), du))
+    op == PG_OP_TANH && return _dmul(_dsub(Sym(1.0), _dmul(node, node)), du)
+    if op == PG_OP_ERF || op == PG_OP_ERFC
+        g = _dmul(Sym((op == PG_OP_ERF ? 2.0 : -2.0) / sqrt(pi)), _sym(PG_OP_EXP, _dneg(_dmul(u, u))))
+        return _dmul(g, du)
+    end
+    error("DeviceFunction: no derivative rule for opcode $op")
+end
+function _body_trace(df::DeviceFunction, N::Integer)
+    out = df.f((_symvar(d) for d in 0:N - 1)...)
+    out isa Sym ? out : Sym(out)
+end
+body_program(df::DeviceFunction, N::Integer) = _compile_program(_body_trace(df, N))
+function gradient_programs(df::DeviceFunction, N::Integer)
+    root = _body_trace(df, N)
+    out = Vector{Vector{UInt8}}()
+    for d in 0:N - 1
+        try
+            push!(out, _compile_program(differentiate(root, d)))
+        catch e
+            error("DeviceFunction: the derivative along coordinate $d of the body $(df.f) does not fit: $(sprint(showerror, e))")
+        end
+    end
+    out
+end
+function Capacity(body::DeviceFunction, mesh::Mesh{N}; method::String="VOFI", compute_centroids::Bool=true, complement::Bool=false) where N
+    N == 3 && error("PenguinHIP.Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D)")
+    init()
+    phi = body_program(body, N)
+    grad = reduce(vcat, gradient_programs(body, N))          # N programs, contiguous as the C array
+    flags = Int32((complement ? 1 : 0) | (compute_centroids ? 0 : 2))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pg_capacity_create_program, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                mesh.handle, phi, grad, flags, h))
+    _wrap_capacity(h[], mesh, body, compute_centroids)
 end
 # times: 2 x nrows, times[1, q] = step q's "t", times[2, q] = its "t + Δt" (column-major: the C layout nrows x 2)
 function set_program!(s::Solver, which::Integer, phase::Integer, df::DeviceFunction, times::Matrix{Float64}; nspace::Integer = 3)

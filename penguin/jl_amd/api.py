@@ -23,7 +23,7 @@ import numpy as np
 from . import _lib as L
 from ._lib import PenguinHipError
 from . import devfn as dev  # noqa: F401
-from .devfn import DeviceFunction
+from .devfn import DeviceFunction, pg_program
 
 Number = Union[int, float]
 
@@ -228,20 +228,42 @@ class Capacity:
 
     Fields A, B, W (N-tuples), V, Γ are the DIAGONALS of the reference's diagonal matrices (length
     M = prod(n_d+1)); C_ω, C_γ are (M,N) arrays; cell_types is the Float64 vector.  They are fetched
-    from the GPU on first access.  `body` must be a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace /
-    Plane); an arbitrary callable needs precomputed arrays: Capacity.from_arrays(...)."""
+    from the GPU on first access.  `body` is a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace / Plane) or, in 1-D
+    and 2-D, any level set wrapped in DeviceFunction: `Capacity(DeviceFunction(lambda x, y: ...), mesh)` traces the closure and
+    its derivatives and evaluates them inside the capacity kernels (fluid where it is <= 0; `complement=True`: where it is
+    >= 0, the other phase; `cap.body` stays callable as the closure, negated for the complement).  A plain callable needs DeviceFunction or precomputed arrays: Capacity.from_arrays(...)."""
 
-    def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True):
+    def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True, complement: bool = False):
         if method not in ("VOFI", "ImplicitIntegration"):
             raise ValueError('method must be "VOFI" or "ImplicitIntegration"')
-        if not hasattr(body, "_abi"):
+        if complement:
+            # the keyword of the Julia twin: the other phase of a DeviceFunction body (tagged bodies carry their own flag)
+            if not isinstance(body, DeviceFunction):
+                raise PenguinHipError("Capacity(complement=True) is for DeviceFunction bodies; tagged bodies take complement=True themselves")
+            body = DeviceFunction(body, complement=True)
+        program_body = isinstance(body, DeviceFunction)
+        if not program_body and not hasattr(body, "_abi"):
             raise PenguinHipError(
                 "Capacity: arbitrary level-set callables cannot be evaluated on the GPU; pass a tagged body "
-                "(Sphere, MultiSphere, Ellipsoid, HalfSpace, Plane) or use Capacity.from_arrays with precomputed capacities")
+                "(Sphere, MultiSphere, Ellipsoid, HalfSpace, Plane), wrap the closure in DeviceFunction (1-D and 2-D: it is "
+                "traced and evaluated in the kernels) or use Capacity.from_arrays with precomputed capacities")
+        if program_body and mesh.N == 3:
+            raise PenguinHipError("Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D)")
         L.init()
         self.mesh = mesh
         self.body = body
         self.compute_centroids = compute_centroids
+        if program_body:
+            # fluid where body(x_1 .. x_N) <= 0; the N derivative programs come from the trace (devfn.differentiate)
+            phi = body.body_program(mesh.N)
+            grad = (pg_program * mesh.N)(*body.gradient_programs(mesh.N))
+            self._h = C.c_void_p()
+            L.check(L.lib().pg_capacity_create_program(mesh._h, C.byref(phi), grad,
+                                                       C.c_int32((0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
+                                                                 | (L.PG_FLAG_COMPLEMENT if body.complement else 0)),
+                                                       C.byref(self._h)))
+            self._cache = {}
+            return
         kind, params, flags = body._abi(mesh.N)
         if not compute_centroids:
             flags |= L.PG_FLAG_NO_CENTROIDS
@@ -346,6 +368,13 @@ class Capacity:
         ms = C.c_double()
         L.check(L.lib().pg_capacity_kernel_ms(self._h, C.byref(ms)))
         return ms.value
+
+    @property
+    def kernel_ms_parts(self) -> Dict[str, float]:
+        """device time of each capacity kernel between its own events (0.0: an empty work list launched nothing)"""
+        ms = (C.c_double * 5)()
+        L.check(L.lib().pg_capacity_kernel_ms_parts(self._h, ms))
+        return dict(zip(("classify", "cut_cells", "sections", "stagger", "stagger_cut"), (float(v) for v in ms)))
 
     def __del__(self):
         try:

@@ -14,6 +14,7 @@ struct pg_capacity {
   pg::DevBuf<double> V, G, ct;
   pg::DevBuf<double> A[3], B[3], W[3], Cw[3], Cg[3];
   double kernel_ms = 0.0;
+  double kernel_ms_parts[5] = {0, 0, 0, 0, 0};   // k_classify, k_cut_cells, k_sections, k_stagger, k_stagger_cut (0: not launched)
   pg::i64 n_cut_local = 0;
   // space-time capacity of ONE time slab [t0, t1] (pg_spacetime.hip): V, A, B, W, Γ above are the time-integrated
   // measures of the first time layer of the reference's (N+1)-D capacity; Vt = A_(N+1) at the two time faces

@@ -12,15 +12,20 @@
 // compacted work list and processed by a dense second kernel so that no wave idles on a lone cut
 // cell.  Compiled with -ffp-contract=off: classification must match the oracle bit for bit.
 #include "pg_capacity.h"
+#include "pg_geom_program.h"
 
 #include <algorithm>
 #include <cmath>
 #include <memory>
+#include <mutex>
 
 using namespace pg;
 using namespace pggeom;
 
 __constant__ GLTable c_gl;
+// the programs of the traced level set under construction: phi, d phi / dx, d phi / dy.  (Not in the unnamed namespace: a
+// variable with internal linkage that no device code writes is folded to its zero initialiser.)
+__constant__ pg_program c_prog[3];
 
 namespace {
 
@@ -61,10 +66,54 @@ __device__ inline void cell_box(const GeoView& g, const i64* idx, double* lo, do
   }
 }
 
+// The kernels below reach the body through pick_ball, box_measure and section_measure only, and are templates over the kernel
+// argument the body travels in: BallArg for the closed-form kinds (a BallSet by value, the code the project always had) and
+// ProgArg for a traced level set (pg_geom_program.h).
+struct BallArg : BallSet {
+  static constexpr int MAX_BLOCK = 1024;        // (HIP's default: the closed-form instantiations compile as they always did)
+};
+__device__ __forceinline__ const BallSet& kernel_body(const BallArg& a) { return a; }
+
+// A traced level set.  The programs live in __constant__ memory (c_prog, 1368 bytes for phi and two derivatives), written
+// before the launches of one capacity.  The evaluator is one function per kernel, called and not inlined (pg_geom_program.h
+// says why); the program index is a literal at every call, so it is read into a scalar register and the instruction fetches
+// are scalar loads.  The operand stack of lane l is column l of stack[PG_PROG_MAX_STACK][256] in LDS, as in k_td_eval
+// (pg_program.hip): consecutive lanes hit consecutive banks, no lane reads another's column, so there is no barrier.
+constexpr int PROG_BLOCK = 256;
+
+struct ProgArg {
+  static constexpr int MAX_BLOCK = PROG_BLOCK;
+  int N;
+  double sgn;
+};
+
+struct ProgStack {
+  double* col;
+  __device__ double get(int d) const { return col[d * PROG_BLOCK]; }
+  __device__ void set(int d, double x) { col[d * PROG_BLOCK] = x; }
+};
+
+__device__ __noinline__ double prog_value(int which, double* col, double x, double y) {
+  ProgStack S{col};
+  return pgprog::prog_eval(c_prog[__builtin_amdgcn_readfirstlane(which)], x, y, 0.0, 0.0, S);
+}
+
+struct DevEval {
+  double* col;
+  __device__ double value(int which, double x, double y) const { return prog_value(which, col, x, y); }
+};
+
+__device__ __forceinline__ ProgBody<DevEval> kernel_body(const ProgArg& a) {
+  __shared__ double stack[PG_PROG_MAX_STACK * PROG_BLOCK];
+  return ProgBody<DevEval>{a.N, 0, a.sgn, DevEval{stack + threadIdx.x}};
+}
+
 // K1 (cheap part): classify every stored cell; full/empty cells are finished here.
-__global__ void k_classify(GeoView g, BallSet bs, i64 Mloc, double* V, double* G, double* ct, double* Cw0,
-                           double* Cw1, double* Cw2, double* Cg0, double* Cg1, double* Cg2, int* cut_list,
-                           int* cut_count) {
+template <class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_classify(GeoView g, BodyArg ba, i64 Mloc, double* V, double* G, double* ct,
+                                                                 double* Cw0, double* Cw1, double* Cw2, double* Cg0, double* Cg1,
+                                                                 double* Cg2, int* cut_list, int* cut_count) {
+  const auto& bs = kernel_body(ba);
   double* Cw[3] = {Cw0, Cw1, Cw2};
   double* Cg[3] = {Cg0, Cg1, Cg2};
   for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < Mloc; lc += (i64)gridDim.x * blockDim.x) {
@@ -124,9 +173,11 @@ struct LaneGroup {
 };
 
 // K1/K5 (expensive part): LANES lanes per cut cell of the compacted list.
-template <int LANES>
-__global__ void k_cut_cells(GeoView g, BallSet bs, const int* cut_list, int ncut, double* V, double* G,
-                            double* Cw0, double* Cw1, double* Cw2, double* Cg0, double* Cg1, double* Cg2) {
+template <int LANES, class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_cut_cells(GeoView g, BodyArg ba, const int* cut_list, int ncut, double* V,
+                                                                  double* G, double* Cw0, double* Cw1, double* Cw2, double* Cg0,
+                                                                  double* Cg1, double* Cg2) {
+  const auto& bs = kernel_body(ba);
   double* Cw[3] = {Cw0, Cw1, Cw2};
   double* Cg[3] = {Cg0, Cg1, Cg2};
   const i64 gt = blockIdx.x * (i64)blockDim.x + threadIdx.x;
@@ -153,9 +204,11 @@ __global__ void k_cut_cells(GeoView g, BallSet bs, const int* cut_list, int ncut
 // A face or a centroid section of cell i lies inside the closed cell: if the cell is FULL (EMPTY) the section is FULL
 // (EMPTY) by the same monotone far / near tests that classified the cell, with the same value prod_ext(...) (0) the
 // geometric path returns -- so only cut cells (and the padding faces next to them) evaluate geometry: 17 -> 3 ms at 512^3.
-__global__ void k_sections(GeoView g, BallSet bs, i64 Mloc, const double* ct, const double* Cw0, const double* Cw1,
-                           const double* Cw2, double* A0, double* A1, double* A2, double* B0, double* B1,
-                           double* B2) {
+template <class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_sections(GeoView g, BodyArg ba, i64 Mloc, const double* ct, const double* Cw0,
+                                                                 const double* Cw1, const double* Cw2, double* A0, double* A1,
+                                                                 double* A2, double* B0, double* B1, double* B2) {
+  const auto& bs = kernel_body(ba);
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* A[3] = {A0, A1, A2};
   double* B[3] = {B0, B1, B2};
@@ -200,8 +253,11 @@ __global__ void k_sections(GeoView g, BallSet bs, i64 Mloc, const double* ct, co
 }
 
 // K3 (cheap part): W_d between the centroids of i-e_d and i; cut boxes go to the work list.
-__global__ void k_stagger(GeoView g, BallSet bs, i64 Mloc, const double* ct, const double* Cw0, const double* Cw1,
-                          const double* Cw2, double* W0, double* W1, double* W2, int* wlist, int* wcount, int wcap) {
+template <class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_stagger(GeoView g, BodyArg ba, i64 Mloc, const double* ct, const double* Cw0,
+                                                                const double* Cw1, const double* Cw2, double* W0, double* W1,
+                                                                double* W2, int* wlist, int* wcount, int wcap) {
+  const auto& bs = kernel_body(ba);
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* W[3] = {W0, W1, W2};
   for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < Mloc; lc += (i64)gridDim.x * blockDim.x) {
@@ -254,9 +310,11 @@ __global__ void k_stagger(GeoView g, BallSet bs, i64 Mloc, const double* ct, con
   }
 }
 
-template <int LANES>
-__global__ void k_stagger_cut(GeoView g, BallSet bs, const int* wlist, int nw, const double* Cw0,
-                              const double* Cw1, const double* Cw2, double* W0, double* W1, double* W2) {
+template <int LANES, class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_stagger_cut(GeoView g, BodyArg ba, const int* wlist, int nw, const double* Cw0,
+                                                                    const double* Cw1, const double* Cw2, double* W0, double* W1,
+                                                                    double* W2) {
+  const auto& bs = kernel_body(ba);
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* W[3] = {W0, W1, W2};
   const i64 gt = blockIdx.x * (i64)blockDim.x + threadIdx.x;
@@ -652,6 +710,78 @@ void ensure_gl() {
   g_gl_uploaded = true;
 }
 
+// K1 .. K5 on the stored slab of c for the body in `ba`; LANES lanes share a cut box.  An empty work list launches nothing.
+template <int LANES, class BodyArg>
+void run_static_kernels(pg_capacity* c, pg_mesh* m, const BodyArg& ba, hipStream_t st) {
+  const int N = c->N;
+  alloc_fields(c);
+  const Slab& s = c->slab;
+  const i64 Ml = s.Mloc();
+  GeoView g = geo_view(m, s);
+  DevBuf<int> cut_list(Ml), counters(2);
+  DevBuf<int> wlist;
+  counters.zero();
+  EventPair ev, part[5];                        // the whole sequence, and each kernel alone (pg_capacity_kernel_ms_parts)
+  bool ran[5] = {true, false, true, true, false};
+  PG_HIP(hipEventRecord(ev.e0, st));
+  const int gr = grid_for(Ml, 256, 256 * 16);
+  PG_HIP(hipEventRecord(part[0].e0, st));
+  hipLaunchKernelGGL(k_classify<BodyArg>, dim3(gr), dim3(256), 0, st, g, ba, Ml, c->V.p, c->G.p, c->ct.p, c->Cw[0].p,
+                     c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p, cut_list.p, counters.p);
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipEventRecord(part[0].e1, st));
+  int hc[2];
+  counters.download(hc, 2);
+  const int ncut = hc[0];
+  c->n_cut_local = ncut;
+  if (ncut > 0) {
+    ran[1] = true;
+    PG_HIP(hipEventRecord(part[1].e0, st));
+    hipLaunchKernelGGL((k_cut_cells<LANES, BodyArg>), dim3((unsigned)(((i64)ncut * LANES + 255) / 256)), dim3(256), 0, st, g, ba,
+                       cut_list.p, ncut, c->V.p, c->G.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipEventRecord(part[1].e1, st));
+  }
+  PG_HIP(hipEventRecord(part[2].e0, st));
+  hipLaunchKernelGGL(k_sections<BodyArg>, dim3(gr), dim3(256), 0, st, g, ba, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
+                     c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipEventRecord(part[2].e1, st));
+  // W work list: at most N entries per cut-adjacent cell; bound by 2*N*ncut + slack
+  const i64 wcap = std::min<i64>((i64)N * Ml, (i64)4 * N * (i64)ncut + 1024);
+  wlist.alloc(2 * wcap);
+  PG_HIP(hipEventRecord(part[3].e0, st));
+  hipLaunchKernelGGL(k_stagger<BodyArg>, dim3(gr), dim3(256), 0, st, g, ba, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
+                     c->W[0].p, c->W[1].p, c->W[2].p, wlist.p, counters.p + 1, (int)wcap);
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipEventRecord(part[3].e1, st));
+  counters.download(hc, 2);
+  const int nw = hc[1];
+  PG_REQUIRE(nw <= wcap, "internal: staggered-volume work list overflow");
+  if (nw > 0) {
+    ran[4] = true;
+    PG_HIP(hipEventRecord(part[4].e0, st));
+    hipLaunchKernelGGL((k_stagger_cut<LANES, BodyArg>), dim3((unsigned)(((i64)nw * LANES + 255) / 256)), dim3(256), 0, st, g, ba,
+                       wlist.p, nw, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->W[0].p, c->W[1].p, c->W[2].p);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipEventRecord(part[4].e1, st));
+  }
+  PG_HIP(hipEventRecord(ev.e1, st));
+  PG_HIP(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  c->kernel_ms = ms;
+  for (int k = 0; k < 5; ++k) {
+    c->kernel_ms_parts[k] = 0.0;
+    if (!ran[k]) continue;                      // an empty work list: nothing was launched
+    PG_HIP(hipEventElapsedTime(&ms, part[k].e0, part[k].e1));
+    c->kernel_ms_parts[k] = ms;
+  }
+}
+
+// c_prog is one table per process: two host threads building program capacities at once take turns
+std::mutex g_prog_mutex;
+
 }  // namespace
 
 namespace pg {
@@ -773,58 +903,48 @@ int32_t pg_capacity_create_levelset(pg_mesh* m, int32_t body_kind, const double*
     c->slab.set_own(bounds[cx.rank], bounds[cx.rank + 1]);
   }
 
-  alloc_fields(c);
-  const Slab& s = c->slab;
-  const i64 Ml = s.Mloc();
-  GeoView g = geo_view(m, s);
-  DevBuf<int> cut_list(Ml), counters(2);
-  DevBuf<int> wlist;
-  counters.zero();
-  hipEvent_t e0, e1;
-  PG_HIP(hipEventCreate(&e0));
-  PG_HIP(hipEventCreate(&e1));
-  PG_HIP(hipEventRecord(e0, st));
-  const int gr = grid_for(Ml, 256, 256 * 16);
-  const bool plane_lanes = bs.kind == BODY_PLANE;
-  const int lanes = plane_lanes ? PG_PLANE_CUT_LANES : CUT_LANES;
-  hipLaunchKernelGGL(k_classify, dim3(gr), dim3(256), 0, st, g, bs, Ml, c->V.p, c->G.p, c->ct.p, c->Cw[0].p,
-                     c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p, cut_list.p, counters.p);
-  PG_HIP(hipGetLastError());
-  int hc[2];
-  counters.download(hc, 2);
-  const int ncut = hc[0];
-  c->n_cut_local = ncut;
-  if (ncut > 0) {
-    auto* const kern = plane_lanes ? k_cut_cells<PG_PLANE_CUT_LANES> : k_cut_cells<CUT_LANES>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(((i64)ncut * lanes + 255) / 256)), dim3(256), 0, st, g, bs, cut_list.p, ncut, c->V.p, c->G.p,
-                       c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->Cg[0].p, c->Cg[1].p, c->Cg[2].p);
-    PG_HIP(hipGetLastError());
+  BallArg ba;
+  static_cast<BallSet&>(ba) = bs;
+  if (bs.kind == BODY_PLANE) run_static_kernels<PG_PLANE_CUT_LANES>(c, m, ba, st);
+  else run_static_kernels<CUT_LANES>(c, m, ba, st);
+  *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_program* grad, int32_t flags, pg_capacity** out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(m && phi && out, "pg_capacity_create_program: NULL argument");
+  Context& cx = ctx();
+  PG_REQUIRE(cx.nranks == 1 && !cx.comm, "pg_capacity_create_program: single rank only (program bodies on slabs are not supported yet)");
+  const int N = m->N;
+  {
+    i64 n[3];
+    const double* nodes[3];
+    for (int d = 0; d < N; ++d) { n[d] = m->n[d]; nodes[d] = m->nodes[d].data(); }
+    std::string why;
+    PG_REQUIRE(program_body_check(N, n, nodes, phi, grad, &why), "pg_capacity_create_program refused: " + why);
   }
-  hipLaunchKernelGGL(k_sections, dim3(gr), dim3(256), 0, st, g, bs, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->A[0].p,
-                     c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
-  PG_HIP(hipGetLastError());
-  // W work list: at most N entries per cut-adjacent cell; bound by 2*N*ncut + slack
-  const i64 wcap = std::min<i64>((i64)N * Ml, (i64)4 * N * (i64)ncut + 1024);
-  wlist.alloc(2 * wcap);
-  hipLaunchKernelGGL(k_stagger, dim3(gr), dim3(256), 0, st, g, bs, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
-                     c->W[0].p, c->W[1].p, c->W[2].p, wlist.p, counters.p + 1, (int)wcap);
-  PG_HIP(hipGetLastError());
-  counters.download(hc, 2);
-  const int nw = hc[1];
-  PG_REQUIRE(nw <= wcap, "internal: staggered-volume work list overflow");
-  if (nw > 0) {
-    auto* const kern = plane_lanes ? k_stagger_cut<PG_PLANE_CUT_LANES> : k_stagger_cut<CUT_LANES>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(((i64)nw * lanes + 255) / 256)), dim3(256), 0, st, g, bs, wlist.p, nw, c->Cw[0].p, c->Cw[1].p,
-                       c->Cw[2].p, c->W[0].p, c->W[1].p, c->W[2].p);
-    PG_HIP(hipGetLastError());
-  }
-  PG_HIP(hipEventRecord(e1, st));
-  PG_HIP(hipEventSynchronize(e1));
-  float ms = 0.f;
-  PG_HIP(hipEventElapsedTime(&ms, e0, e1));
-  c->kernel_ms = ms;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
+  auto* c = new pg_capacity();
+  std::unique_ptr<pg_capacity> guard(c);
+  c->mesh = m;
+  c->N = N;
+  c->from_body = true;
+  c->has_cg = !(flags & PG_FLAG_NO_CENTROIDS);
+  std::memset(&c->body, 0, sizeof(c->body));     // (not a BallSet: nothing reads it)
+  c->slab = m->base_slab();
+  ensure_gl();
+  pg_program progs[3];
+  std::memset(progs, 0, sizeof(progs));
+  progs[0] = *phi;
+  for (int d = 0; d < N; ++d) progs[1 + d] = grad[d];
+  std::lock_guard<std::mutex> table(g_prog_mutex);   // held until the last kernel of this capacity has run
+  PG_HIP(hipStreamSynchronize(cx.stream));       // (no earlier launch may still read the table)
+  PG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_prog), progs, sizeof(progs)));
+  ProgArg pa;
+  pa.N = N;
+  pa.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
+  run_static_kernels<CUT_LANES>(c, m, pa, cx.stream);
   *out = guard.release();
   PG_API_END
 }
@@ -1056,6 +1176,13 @@ int32_t pg_capacity_kernel_ms(const pg_capacity* c, double* ms) {
   PG_API_BEGIN
   PG_REQUIRE(c && ms, "pg_capacity_kernel_ms: NULL argument");
   *ms = c->kernel_ms;
+  PG_API_END
+}
+
+int32_t pg_capacity_kernel_ms_parts(const pg_capacity* c, double* ms) {
+  PG_API_BEGIN
+  PG_REQUIRE(c && ms, "pg_capacity_kernel_ms_parts: NULL argument");
+  for (int k = 0; k < 5; ++k) ms[k] = c->kernel_ms_parts[k];
   PG_API_END
 }
 

@@ -230,6 +230,143 @@ def _compile(root: Sym, what: str) -> pg_program:
     return p
 
 
+# ---- derivatives of a trace (the level-set bodies: Capacity(DeviceFunction(...), mesh)) ----------------------------------------
+
+def _const(s: Sym) -> Optional[float]:
+    return s.args[0] if s.op == "CONST" else None
+
+
+def _k(v: float) -> Sym:
+    return Sym("CONST", float(v))
+
+
+# the four operations with the folds that keep a derivative short: 0 * x, 1 * x, x + 0, x - 0, 0 / x, x / 1, and constants
+def _add(a: Sym, b: Sym) -> Sym:
+    ca, cb = _const(a), _const(b)
+    if ca is not None and cb is not None:
+        return _k(ca + cb)
+    if ca == 0.0:
+        return b
+    if cb == 0.0:
+        return a
+    return Sym("ADD", a, b)
+
+
+def _neg(a: Sym) -> Sym:
+    if _const(a) is not None:
+        return _k(-_const(a))
+    if a.op == "NEG":
+        return a.args[0]
+    return Sym("NEG", a)
+
+
+def _sub(a: Sym, b: Sym) -> Sym:
+    ca, cb = _const(a), _const(b)
+    if ca is not None and cb is not None:
+        return _k(ca - cb)
+    if cb == 0.0:
+        return a
+    if ca == 0.0:
+        return _neg(b)
+    return Sym("SUB", a, b)
+
+
+def _mul(a: Sym, b: Sym) -> Sym:
+    ca, cb = _const(a), _const(b)
+    if ca is not None and cb is not None:
+        return _k(ca * cb)
+    if ca == 0.0 or cb == 0.0:
+        return _k(0.0)
+    if ca == 1.0:
+        return b
+    if cb == 1.0:
+        return a
+    if ca == -1.0:
+        return _neg(b)
+    if cb == -1.0:
+        return _neg(a)
+    return Sym("MUL", a, b)
+
+
+def _div(a: Sym, b: Sym) -> Sym:
+    ca, cb = _const(a), _const(b)
+    if ca == 0.0:
+        return _k(0.0)
+    if cb == 1.0:
+        return a
+    if ca is not None and cb is not None and cb != 0.0:
+        return _k(ca / cb)
+    return Sym("DIV", a, b)
+
+
+def _select(c: Sym, a: Sym, b: Sym) -> Sym:
+    if _const(a) is not None and _const(a) == _const(b):
+        return a
+    return Sym("SELECT", c, a, b)
+
+
+def differentiate(node: Sym, var: int) -> Sym:
+    """d node / d x_var as a trace: one rule per opcode.  ABS, MIN, MAX and SELECT are piecewise through SELECT (the derivative of
+    the branch the value comes from), comparisons have derivative 0, POW with a constant exponent has its own rule."""
+    op, a = node.op, node.args
+    if op == "CONST":
+        return _k(0.0)
+    if op == "VAR":
+        return _k(1.0 if a[0] == var else 0.0)
+    if op in ("LT", "LE", "GT", "GE"):
+        return _k(0.0)
+    d = [differentiate(x, var) for x in a]
+    if op == "SELECT":
+        return _select(a[0], d[1], d[2])
+    if op == "ADD":
+        return _add(d[0], d[1])
+    if op == "SUB":
+        return _sub(d[0], d[1])
+    if op == "NEG":
+        return _neg(d[0])
+    if op == "MUL":
+        return _add(_mul(d[0], a[1]), _mul(a[0], d[1]))
+    if op == "DIV":
+        if _const(d[1]) == 0.0:
+            return _div(d[0], a[1])
+        return _div(_sub(_mul(d[0], a[1]), _mul(a[0], d[1])), _mul(a[1], a[1]))
+    if op == "MIN":
+        return _select(Sym("LE", a[0], a[1]), d[0], d[1])
+    if op == "MAX":
+        return _select(Sym("GE", a[0], a[1]), d[0], d[1])
+    if op == "POW":
+        e = _const(a[1])
+        if e is not None:                        # u ** e: e u ** (e - 1) u'
+            return _mul(_mul(_k(e), Sym("POW", a[0], _k(e - 1.0))), d[0])
+        out = _mul(_mul(node, Sym("LOG", a[0])), d[1])          # u ** v: u ** v (v' log u + v u' / u)
+        if _const(d[0]) != 0.0:
+            out = _add(out, _mul(node, _div(_mul(a[1], d[0]), a[0])))
+        return out
+    if op == "ATAN2":                            # atan2(y, x): (x y' - y x') / (x x + y y)
+        return _div(_sub(_mul(a[1], d[0]), _mul(a[0], d[1])), _add(_mul(a[0], a[0]), _mul(a[1], a[1])))
+    u, du = a[0], d[0]
+    if _const(du) == 0.0:
+        return _k(0.0)
+    if op == "ABS":
+        return _select(Sym("GE", u, _k(0.0)), du, _neg(du))
+    if op == "SQRT":
+        return _div(du, _mul(_k(2.0), node))
+    if op == "EXP":
+        return _mul(node, du)
+    if op == "LOG":
+        return _div(du, u)
+    if op == "SIN":
+        return _mul(Sym("COS", u), du)
+    if op == "COS":
+        return _neg(_mul(Sym("SIN", u), du))
+    if op == "TANH":
+        return _mul(_sub(_k(1.0), _mul(node, node)), du)
+    if op in ("ERF", "ERFC"):
+        g = _mul(_k((2.0 if op == "ERF" else -2.0) / math.sqrt(math.pi)), Sym("EXP", _neg(_mul(u, u))))
+        return _mul(g, du)
+    raise PenguinHipError(f"DeviceFunction: no derivative rule for {op}")
+
+
 def program_listing(p: pg_program) -> List[str]:
     out = []
     for q in range(p.n_ops):
@@ -278,15 +415,24 @@ def interpret(p: pg_program, coords, t, dtype=np.float64, erf_fn=None, erfc_fn=N
 class DeviceFunction:
     """DeviceFunction(fn): fn(x, y, z, t) for sources and interface values (three coordinates, the missing ones of a 1-D / 2-D
     problem 0.0, as the constructors call every closure), fn(x_1 .. x_N, t) for the value of a border condition.  Traced per
-    use site: `.program` is the three-coordinate trace, `program_for(nspace)` the one of another arity."""
+    use site: `.program` is the three-coordinate trace, `program_for(nspace)` the one of another arity.
 
-    def __init__(self, fn):
+    As the body of a Capacity, fn(x_1 .. x_N) is a level set with the fluid where it is <= 0: `body_program(N)` is its trace
+    and `gradient_programs(N)` the N traces of its partial derivatives, differentiated rule by rule from that trace.
+    `complement=True` is the body -fn (the other phase of a two-phase problem; `Capacity(body, mesh, complement=True)` sets it):
+    calls return -fn, the body programs stay fn's and the capacity kernels negate.  Such an object is a body only: `program_for`
+    (time-dependent data) refuses it."""
+
+    def __init__(self, fn, complement: bool = False):
         if isinstance(fn, DeviceFunction):
+            complement = complement != fn.complement
             fn = fn.fn
+        self.complement = bool(complement)       # as a BODY: -fn (the traces stay those of fn, the kernels negate)
         if not callable(fn):
             raise TypeError(f"DeviceFunction takes a callable, not {fn!r}")
         self.fn = fn
         self._programs: Dict[int, pg_program] = {}
+        self._bodies: Dict[int, Sym] = {}
         self.__signature__ = None
         try:
             import inspect
@@ -295,13 +441,16 @@ class DeviceFunction:
             pass
 
     def __call__(self, *args):
-        return self.fn(*args)
+        return -self.fn(*args) if self.complement else self.fn(*args)
 
     def __repr__(self):
-        return f"DeviceFunction({self.fn!r})"
+        return f"DeviceFunction({self.fn!r}, complement=True)" if self.complement else f"DeviceFunction({self.fn!r})"
 
     def program_for(self, nspace: int) -> pg_program:
         """The program of fn(x_1 .. x_nspace, t), traced on first use."""
+        if self.complement:
+            raise PenguinHipError(f"{self!r}: complement=True makes a BODY (the other phase of a Capacity); as a source, an interface "
+                                  "value or a border value the program would be fn's while calls give -fn: write the sign into the closure")
         if nspace not in self._programs:
             what = f"{self.fn!r} with {nspace} coordinates and t"
             args = [Sym("VAR", d) for d in range(nspace)] + [Sym("VAR", 3)]
@@ -321,6 +470,32 @@ class DeviceFunction:
     @property
     def program(self) -> pg_program:
         return self.program_for(3)
+
+    # ---- a level-set body: fn(x_1 .. x_N), no t
+    def _body_trace(self, N: int) -> Sym:
+        if N not in self._bodies:
+            what = f"the body {self.fn!r} with {N} coordinates"
+            try:
+                out = self.fn(*[Sym("VAR", d) for d in range(N)])
+            except PenguinHipError:
+                raise
+            except Exception as e:
+                raise PenguinHipError(f"DeviceFunction: cannot trace {what}: {type(e).__name__}: {e}") from e
+            if isinstance(out, (list, tuple)) or (isinstance(out, np.ndarray) and out.ndim > 0):
+                raise PenguinHipError(f"DeviceFunction: {what} returned {type(out).__name__}, not a scalar")
+            if isinstance(out, np.ndarray) and out.dtype == object:
+                out = out.item()
+            self._bodies[N] = Sym.wrap(out, "the returned value")
+        return self._bodies[N]
+
+    def body_program(self, N: int) -> pg_program:
+        """The program of the level set fn(x_1 .. x_N)."""
+        return _compile(self._body_trace(N), f"the body {self.fn!r} with {N} coordinates")
+
+    def gradient_programs(self, N: int) -> List[pg_program]:
+        """The N programs of the partial derivatives of fn(x_1 .. x_N), differentiated from its trace."""
+        root = self._body_trace(N)
+        return [_compile(differentiate(root, d), f"the derivative along coordinate {d} of the body {self.fn!r}") for d in range(N)]
 
     def evaluate_program(self, coords, t, nspace: Optional[int] = None, dtype=np.float64, **kw) -> np.ndarray:
         """The bytecode interpreted with numpy at the rows of coords; nspace (default: 3, the arity of sources and interface
