@@ -586,6 +586,31 @@ int32_t pg_debug_program_eval(const pg_program* prog, int64_t npts, const double
    host threads are serialised by a mutex inside, each holding it until its last kernel has run. */
 int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */, int32_t flags,
                                    pg_capacity** out);
+/* Capacity(body, SpaceTimeMesh(mesh, [t0, t1])) of an ARBITRARY moving level set phi(x_1 .. x_N, t) (t: PG_OP_VAR 3): phi, the N
+   programs of d phi / d x_d and the program of d phi / dt; fluid where phi <= 0, flags as pg_capacity_create_program.  The
+   space-time kernels of pg_capacity_create_spacetime run with "the body at time node k" = phi(., tau_k) measured by the
+   primitives of pg_capacity_create_program, with the conventions of the closed-form moving kinds: every first-layer capacity is
+   the composite-rule time integral sum_k w_k (spatial measure at tau_k), V_t0 / V_t1 are the spatial volumes at the two faces,
+   a cell is FULL / EMPTY only if it is so at every node and both faces, Gamma = sum_k w_k Gamma(tau_k) sqrt(1 + v_n^2) with
+   v_n = - d_t phi / |grad phi| at (C_gamma(tau_k), tau_k) (0 where |grad phi| is zero or not finite).  The cheap pass finishes a
+   cell only if its sample lattice (9 points in 1-D, 33 in 2-D) has one strict sign at t0, mid time and t1 and min |phi| over
+   those samples exceeds (t1 - t0) max |d phi / dt| over them: a body that crosses a whole cell AND comes back within half a slab,
+   or a feature narrower than h / 8, is not seen.  tau_w: nq rows (tau_k, w_k), t0 < tau_k < t1.
+   1-D+t and 2-D+t.  Refused before anything is allocated, each with its own message: N not 1 or 2; a NULL mesh or out; a NULL
+   phi, grad, dphidt or tau_w (each named); an invalid
+   program; a program reading a coordinate >= N; nq outside 1 .. 4096; t1 <= t0; a node outside (t0, t1); weights that do not add
+   up to t1 - t0 within 1e-12 (t1 - t0); more than one rank or a communicator; a spatial or time derivative that disagrees with
+   central differences of phi (pg_capacity_create_program's rule and tolerance at t0, mid time and t1; the time step is
+   1e-6 (t1 - t0)).  *out is NULL after a refusal.  The __constant__ table and its mutex are pg_capacity_create_program's. */
+int32_t pg_capacity_create_spacetime_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */,
+                                             const pg_program* dphidt, int32_t flags, double t0, double t1, int32_t nq,
+                                             const double* tau_w /* nq x 2 */, pg_capacity** out);
+/* measurement, off by default: while on, pg_capacity_create_spacetime_program brackets each of its six kernels with events */
+int32_t pg_debug_spacetime_kernel_timing(int32_t on);
+/* capacities of pg_capacity_create_spacetime_program: the number of cells the cheap pass left to the list and, when built with
+   the timing on, ms of k_st_classify, k_st_cells, k_st_sections, k_st_sections_cut, k_st_stagger, k_st_stagger_cut (0: not
+   launched, or not timed) */
+int32_t pg_debug_capacity_spacetime_ms_parts(const pg_capacity* c, double* ms /*6*/, int64_t* n_listed);
 /* measurement: the per-step evaluation of every installed program at the last consumed row, `repeats` times between two
    events; entries = listed rows summed over the programs, instructions = entries x n_ops x evaluations summed likewise */
 int32_t pg_debug_td_eval_ms(pg_solver* s, int32_t scheme, int32_t repeats, double* ms_per_eval, int64_t* entries,

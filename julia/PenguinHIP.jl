@@ -623,8 +623,10 @@ end
 struct DeviceFunction <: Function
     f::Function
     programs::Dict{Int,Vector{UInt8}}      # by the number of space coordinates the closure is called with
+    # as a MOVING body f(x_1 .. x_N, t), by N: (phi, the N spatial derivative programs then d/dt, contiguous as the C arrays)
+    moving::Dict{Int,Tuple{Vector{UInt8},Vector{UInt8}}}
 end
-DeviceFunction(f::Function) = DeviceFunction(f, Dict{Int,Vector{UInt8}}())
+DeviceFunction(f::Function) = DeviceFunction(f, Dict{Int,Vector{UInt8}}(), Dict{Int,Tuple{Vector{UInt8},Vector{UInt8}}}())
 (df::DeviceFunction)(args...) = df.f(args...)
 function program(df::DeviceFunction, nspace::Integer = 3)
     get!(df.programs, Int(nspace)) do
@@ -1329,6 +1331,73 @@ function Capacity(body::MovingBody, mesh::SpaceTimeMesh; method::String="VOFI", 
                          _field(hnd[], PG_CAP_ST_CT_OMEGA, 0, M), compute_centroids ? _field(hnd[], PG_CAP_ST_CT_GAMMA, 0, M) : Float64[],
                          mesh, body)
 end
+
+# A moving body of any shape: body = DeviceFunction((x, y, t) -> ...), the reference's `body = (x, y, t) -> ...` traced once.
+# phi, its N spatial derivatives and d phi / dt are evaluated inside the space-time kernels
+# (pg_capacity_create_spacetime_program); the programs are cached in the DeviceFunction (`moving`, by N), so a solve
+# compiles them once, not once per slab.  The other phase of a two-phase problem: body_c = MovingComplement(body).
+function _moving_trace(df::DeviceFunction, N::Integer)
+    out = df.f((_symvar(d) for d in 0:N - 1)..., _symvar(3))
+    out isa Sym ? out : Sym(out)
+end
+function _moving_programs(df::DeviceFunction, N::Integer)
+    get!(df.moving, Int(N)) do
+        root = _moving_trace(df, N)
+        derivs = UInt8[]
+        for (var, name) in [((d, "coordinate $d") for d in 0:N - 1)..., (3, "t")]
+            try
+                append!(derivs, _compile_program(differentiate(root, var)))
+            catch e
+                error("DeviceFunction: the derivative along $name of the moving body $(df.f) does not fit: $(sprint(showerror, e))")
+            end
+        end
+        (_compile_program(root), derivs)
+    end
+end
+moving_body_program(df::DeviceFunction, N::Integer) = _moving_programs(df, N)[1]
+"N + 1 programs, contiguous as the C arrays: the N spatial partial derivatives, then d/dt"
+moving_gradient_programs(df::DeviceFunction, N::Integer) = _moving_programs(df, N)[2]
+struct MovingComplement <: Function
+    body::DeviceFunction
+end
+(b::MovingComplement)(xt...) = -b.body.f(xt...)
+function Capacity(body::DeviceFunction, mesh::SpaceTimeMesh; method::String="VOFI", compute_centroids::Bool=true,
+                  time_panels::Int=16, time_order::Int=4, complement::Bool=false, reported_body::Function=body)
+    init()
+    sp = mesh.space
+    N = length(sp.dims)
+    t0, t1 = mesh.nodes[end][1], mesh.nodes[end][2]
+    gx, gw = _gauss(time_order)
+    edges = range(t0, t1; length=time_panels + 1)
+    nq = time_panels * time_order
+    tau_w = zeros(2, nq)                               # column k = {tau, w}: the C layout nq x 2
+    k = 0
+    for p in 1:time_panels, i in 1:time_order
+        k += 1
+        a, b = edges[p], edges[p + 1]
+        tau_w[1, k], tau_w[2, k] = (a + b) / 2 + (b - a) / 2 * gx[i], (b - a) / 2 * gw[i]
+    end
+    tau_w[2, :] .*= (t1 - t0) / sum(tau_w[2, :])
+    flags = Int32((complement ? 1 : 0) | (compute_centroids ? 0 : 2))
+    hnd = Ref{Ptr{Cvoid}}(C_NULL)
+    if N == 1 || N == 2
+        phi, derivs = moving_body_program(body, N), moving_gradient_programs(body, N)
+        np = length(phi)                               # bytes of one program
+        GC.@preserve derivs begin
+            check(ccall((:pg_capacity_create_spacetime_program, libpg), Int32,
+                        (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Float64, Float64, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                        sp.handle, phi, pointer(derivs), pointer(derivs) + N * np, flags, t0, t1, Int32(nq), tau_w, hnd))
+        end
+    else
+        error("space-time capacities: 1-D+t and 2-D+t (the reference's 3-D+t blocks drop the z direction)")
+    end
+    layer = _wrap_capacity(hnd[], sp, reported_body, compute_centroids)
+    M = prod(sp.dims .+ 1)
+    SpaceTimeCapacity{N}(layer, _field(hnd[], PG_CAP_ST_V0, 0, M), _field(hnd[], PG_CAP_ST_V1, 0, M),
+                         _field(hnd[], PG_CAP_ST_CT_OMEGA, 0, M), compute_centroids ? _field(hnd[], PG_CAP_ST_CT_GAMMA, 0, M) : Float64[],
+                         mesh, reported_body)
+end
+Capacity(b::MovingComplement, mesh::SpaceTimeMesh; kwargs...) = Capacity(b.body, mesh; complement=true, reported_body=b, kwargs...)
 DiffusionOps(cap::SpaceTimeCapacity) = DiffusionOps(cap.layer)
 
 # ConvectionOps(capacity, uₒ, uᵧ) of a space-time capacity (2-D+t), as the moving advection-diffusion blocks slice it

@@ -22,6 +22,9 @@ struct pg_capacity {
   bool spacetime = false;
   double t0 = 0.0, t1 = 0.0;
   pg::DevBuf<double> Vt[2], Ctw, Ctg;
+  // program bodies only, and only while pg_debug_spacetime_kernel_timing is on: k_st_classify, k_st_cells, k_st_sections, k_st_sections_cut,
+  // k_st_stagger, k_st_stagger_cut (0: not launched); n_cut_local is then the number of cells the cheap pass left to the list
+  double st_ms_parts[6] = {0, 0, 0, 0, 0, 0};
 };
 
 struct pg_diffops {

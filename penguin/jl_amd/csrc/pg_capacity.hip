@@ -23,9 +23,9 @@ using namespace pg;
 using namespace pggeom;
 
 __constant__ GLTable c_gl;
-// the programs of the traced level set under construction: phi, d phi / dx, d phi / dy.  (Not in the unnamed namespace: a
-// variable with internal linkage that no device code writes is folded to its zero initialiser.)
-__constant__ pg_program c_prog[3];
+// the programs of the traced level set under construction: phi, d phi / dx, d phi / dy, d phi / dt (moving bodies).  (Not in
+// the unnamed namespace: a variable with internal linkage that no device code writes is folded to its zero initialiser.)
+__constant__ pg_program c_prog[4];
 
 namespace {
 
@@ -74,7 +74,7 @@ struct BallArg : BallSet {
 };
 __device__ __forceinline__ const BallSet& kernel_body(const BallArg& a) { return a; }
 
-// A traced level set.  The programs live in __constant__ memory (c_prog, 1368 bytes for phi and two derivatives), written
+// A traced level set.  The programs live in __constant__ memory (c_prog, 1824 bytes for phi and three derivatives), written
 // before the launches of one capacity.  The evaluator is one function per kernel, called and not inlined (pg_geom_program.h
 // says why); the program index is a literal at every call, so it is read into a scalar register and the instruction fetches
 // are scalar loads.  The operand stack of lane l is column l of stack[PG_PROG_MAX_STACK][256] in LDS, as in k_td_eval
@@ -93,14 +93,14 @@ struct ProgStack {
   __device__ void set(int d, double x) { col[d * PROG_BLOCK] = x; }
 };
 
-__device__ __noinline__ double prog_value(int which, double* col, double x, double y) {
+__device__ __noinline__ double prog_value(int which, double* col, double x, double y, double t) {
   ProgStack S{col};
-  return pgprog::prog_eval(c_prog[__builtin_amdgcn_readfirstlane(which)], x, y, 0.0, 0.0, S);
+  return pgprog::prog_eval(c_prog[__builtin_amdgcn_readfirstlane(which)], x, y, 0.0, t, S);
 }
 
 struct DevEval {
   double* col;
-  __device__ double value(int which, double x, double y) const { return prog_value(which, col, x, y); }
+  __device__ double value(int which, double x, double y, double t) const { return prog_value(which, col, x, y, t); }
 };
 
 __device__ __forceinline__ ProgBody<DevEval> kernel_body(const ProgArg& a) {
@@ -394,6 +394,72 @@ struct MotionView {
   const BallSet* bodies;
 };
 
+// The k_st_* kernels that look at the body are templates over how "the body at node k / at a time face" is obtained, as the
+// static kernels are templates over BallArg / ProgArg: StBall reads the BallSet table the host built (the code the project
+// always had), StProg evaluates the traced level set phi(x, t) at tau[k], t0, t1 (ProgBody with its time set).  Slot k of
+// st_body: k < nq the time node k, nq the face t0, nq + 1 the face t1.  (k_st_sections and k_st_stagger, the cheap passes that
+// only read the cell types, never touch the body and serve both.)
+struct StBall {
+  static constexpr int MAX_BLOCK = 1024;        // (HIP's default: the closed-form instantiations compile as they always did)
+};
+struct StBallBase {};
+__device__ __forceinline__ StBallBase st_base(const StBall&) { return StBallBase(); }
+
+struct StProg : ProgArg {};
+__device__ __forceinline__ ProgBody<DevEval> st_base(const StProg& a) { return kernel_body(a); }
+
+__device__ __forceinline__ const BallSet& st_body(const StBallBase&, const MotionView& mv, int k) { return mv.bodies[k]; }
+__device__ __forceinline__ ProgBody<DevEval> st_body(ProgBody<DevEval> b, const MotionView& mv, int k) {
+  b.t = k < mv.nq ? mv.q[k].tau : k == mv.nq ? mv.t0 : mv.t1;
+  return b;
+}
+
+// the cheap test of a cell: 1 inside every body the rule sees, -1 outside every one, 0 near
+__device__ inline int st_far(const StBallBase&, const GeoView& g, const MotionView& mv, const double* lo, const double* hi) {
+  int far = 0;
+  if (mv.kind == BODY_HALFSPACE) {
+    const double pl = mv.mid.c[0] - mv.reach, ph = mv.mid.c[0] + mv.reach;
+    if (hi[mv.axis] <= pl) far = mv.sgn > 0.0 ? 1 : -1;
+    else if (lo[mv.axis] >= ph) far = mv.sgn > 0.0 ? -1 : 1;
+  } else {
+    if (mv.mid.r - mv.reach > 0.0 && ball_box_type(mv.mid.c, mv.mid.r - mv.reach, lo, hi, g.N) == PG_FULL) far = 1;
+    else if (ball_box_type(mv.mid.c, mv.mid.r + mv.reach, lo, hi, g.N) == PG_EMPTY) far = -1;
+  }
+  return far;
+}
+// a traced level set has no `reach`: the sample lattice at t0, mid time and t1 with a margin from d phi / dt (prog_st_far)
+__device__ inline int st_far(const ProgBody<DevEval>& b, const GeoView&, const MotionView& mv, const double* lo, const double* hi) {
+  return prog_st_far(b, lo, hi, mv.t0, mv.t1);
+}
+
+// the spatial volume at a time face.  Program bodies: a face that is FULL gets the measure the full cells get (from h, see
+// full_measure), so that V(t1) of one slab and V(t0) of the next are the same bits whichever of the two slabs cuts the cell;
+// the closed-form kinds keep the box's own product of node differences, as they always had
+__device__ __forceinline__ double st_face_volume(const StBallBase&, const GeoView&, const BoxMeasure& m) { return m.vol; }
+__device__ __forceinline__ double st_face_volume(const ProgBody<DevEval>&, const GeoView& g, const BoxMeasure& m) {
+  return m.type == PG_FULL ? full_measure(g, -1) : m.vol;
+}
+
+// the normal speed of the interface at the spatial interface centroid cg of time node q
+__device__ inline double st_normal_speed(const BallSet&, const MotionView& mv, const MotionNode& q, const double* cg, int N) {
+  double vn;
+  if (mv.kind == BODY_HALFSPACE) vn = q.dc[0];
+  else {
+    double nn = 0.0, dot = 0.0;
+    for (int d = 0; d < N; ++d) {
+      const double e = cg[d] - q.c[d];
+      nn += e * e;
+      dot += e * q.dc[d];
+    }
+    vn = q.dr + (nn > 0.0 ? dot / sqrt(nn) : 0.0);
+  }
+  return vn;
+}
+// - d_t phi / |grad phi| at (cg, tau) -- the body carries tau
+__device__ inline double st_normal_speed(const ProgBody<DevEval>& b, const MotionView&, const MotionNode&, const double* cg, int N) {
+  return b.normal_speed(cg[0], N > 1 ? cg[1] : 0.0);
+}
+
 // Work is split as in the static kernels: a cheap pass over all cells finishes the ones that need no quadrature and
 // lists the others; a second kernel gives every listed item one WAVE whose lanes take the time nodes (a box / section
 // measure is a few thousand fp64 instructions with square roots and arc tangents: 64 of them in one lane, for the few
@@ -425,7 +491,10 @@ __device__ inline void st_store_plain(const GeoView& g, const MotionView& mv, co
 }
 
 // pass 1 of V, C_ω, Γ, C_γ, type, V(t0), V(t1): cells far from the interface during the whole slab are finished here
-__global__ void k_st_classify(GeoView g, MotionView mv, i64 Mloc, StOut o, int* list, int* count) {
+template <class St>
+__global__ __launch_bounds__(St::MAX_BLOCK) void k_st_classify(GeoView g, MotionView mv, St sa, i64 Mloc, StOut o, int* list,
+                                                               int* count) {
+  const auto base = st_base(sa);
   for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < Mloc; lc += (i64)gridDim.x * blockDim.x) {
     i64 idx[3];
     decode_cell(g.N, g.ext, g.plane, g.s0, lc, idx);
@@ -434,15 +503,7 @@ __global__ void k_st_classify(GeoView g, MotionView mv, i64 Mloc, StOut o, int* 
     int far = -1;   // 1: inside every body the rule sees, -1: outside every one, 0: near
     if (real) {
       cell_box(g, idx, lo, hi);
-      far = 0;
-      if (mv.kind == BODY_HALFSPACE) {
-        const double pl = mv.mid.c[0] - mv.reach, ph = mv.mid.c[0] + mv.reach;
-        if (hi[mv.axis] <= pl) far = mv.sgn > 0.0 ? 1 : -1;
-        else if (lo[mv.axis] >= ph) far = mv.sgn > 0.0 ? -1 : 1;
-      } else {
-        if (mv.mid.r - mv.reach > 0.0 && ball_box_type(mv.mid.c, mv.mid.r - mv.reach, lo, hi, g.N) == PG_FULL) far = 1;
-        else if (ball_box_type(mv.mid.c, mv.mid.r + mv.reach, lo, hi, g.N) == PG_EMPTY) far = -1;
-      }
+      far = st_far(base, g, mv, lo, hi);
     }
     if (far != 0) st_store_plain(g, mv, o, lc, lo, hi, real, (far == 1) != (mv.complement != 0));
     else list[atomicAdd(count, 1)] = (int)lc;
@@ -450,7 +511,10 @@ __global__ void k_st_classify(GeoView g, MotionView mv, i64 Mloc, StOut o, int* 
 }
 
 // pass 2: one wave per listed cell, lanes over the time nodes (+ lanes 0 / 1: the two time faces)
-__global__ void k_st_cells(GeoView g, MotionView mv, const int* __restrict__ list, int nlist, StOut o) {
+template <class St>
+__global__ __launch_bounds__(St::MAX_BLOCK) void k_st_cells(GeoView g, MotionView mv, St sa, const int* __restrict__ list, int nlist,
+                                                            StOut o) {
+  const auto base = st_base(sa);
   const int lane = threadIdx.x & 63;
   const i64 item = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;
   if (item >= nlist) return;
@@ -463,14 +527,16 @@ __global__ void k_st_cells(GeoView g, MotionView mv, const int* __restrict__ lis
   double mom[3] = {0.0, 0.0, 0.0}, gm[3] = {0.0, 0.0, 0.0};
   bool full = true, empty = true;
   if (lane < 2) {
-    const BoxMeasure m = box_measure(mv.bodies[mv.nq + lane], lo, hi, false, c_gl);
-    vend = m.vol;
+    const auto& face = st_body(base, mv, mv.nq + lane);
+    const BoxMeasure m = box_measure(face, lo, hi, false, c_gl);
+    vend = st_face_volume(base, g, m);
     full = m.type == PG_FULL;
     empty = m.type == PG_EMPTY;
   }
   for (int k = lane; k < mv.nq; k += 64) {
     const MotionNode q = mv.q[k];
-    const BoxMeasure m = box_measure(mv.bodies[k], lo, hi, true, c_gl);
+    const auto& body = st_body(base, mv, k);
+    const BoxMeasure m = box_measure(body, lo, hi, true, c_gl);
     full = full && m.type == PG_FULL;
     empty = empty && m.type == PG_EMPTY;
     const double wv = q.w * m.vol;
@@ -478,17 +544,7 @@ __global__ void k_st_cells(GeoView g, MotionView mv, const int* __restrict__ lis
     momt += wv * q.tau;
     for (int d = 0; d < g.N; ++d) mom[d] += wv * m.cen[d];
     if (m.gamma > 0.0) {
-      double vn;
-      if (mv.kind == BODY_HALFSPACE) vn = q.dc[0];
-      else {
-        double nn = 0.0, dot = 0.0;
-        for (int d = 0; d < g.N; ++d) {
-          const double e = m.cg[d] - q.c[d];
-          nn += e * e;
-          dot += e * q.dc[d];
-        }
-        vn = q.dr + (nn > 0.0 ? dot / sqrt(nn) : 0.0);
-      }
+      const double vn = st_normal_speed(body, mv, q, m.cg, g.N);
       const double ws = q.w * m.gamma * sqrt(1.0 + vn * vn);
       gam += ws;
       gmt += ws * q.tau;
@@ -555,9 +611,12 @@ __global__ void k_st_sections(GeoView g, MotionView mv, i64 Mloc, const double* 
   }
 }
 
-__global__ void k_st_sections_cut(GeoView g, MotionView mv, const int* __restrict__ list, int nlist, const double* Cw0,
-                                  const double* Cw1, const double* Cw2, double* A0, double* A1, double* A2, double* B0,
-                                  double* B1, double* B2) {
+template <class St>
+__global__ __launch_bounds__(St::MAX_BLOCK) void k_st_sections_cut(GeoView g, MotionView mv, St src, const int* __restrict__ list,
+                                                                   int nlist, const double* Cw0, const double* Cw1, const double* Cw2,
+                                                                   double* A0, double* A1, double* A2, double* B0, double* B1,
+                                                                   double* B2) {
+  const auto base = st_base(src);
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* A[3] = {A0, A1, A2};
   double* B[3] = {B0, B1, B2};
@@ -580,11 +639,12 @@ __global__ void k_st_sections_cut(GeoView g, MotionView mv, const int* __restric
   bool a_full = true, b_full = real;
   for (int k = lane; k < mv.nq; k += 64) {
     const double wq = mv.q[k].w;
-    const double sa = section_measure(mv.bodies[k], d, g.nodes[d][idx[d]], lo, hi, fm);
+    const auto& body = st_body(base, mv, k);
+    const double sa = section_measure(body, d, g.nodes[d][idx[d]], lo, hi, fm);
     a += wq * sa;
     a_full = a_full && sa == fm;
     if (real) {
-      const double sb = section_measure(mv.bodies[k], d, Cw[d][lc], lo, hi, fm);
+      const double sb = section_measure(body, d, Cw[d][lc], lo, hi, fm);
       b += wq * sb;
       b_full = b_full && sb == fm;
     }
@@ -639,8 +699,11 @@ __global__ void k_st_stagger(GeoView g, MotionView mv, i64 Mloc, const double* c
   }
 }
 
-__global__ void k_st_stagger_cut(GeoView g, MotionView mv, const int* __restrict__ list, int nlist, const double* Cw0,
-                                 const double* Cw1, const double* Cw2, double* W0, double* W1, double* W2) {
+template <class St>
+__global__ __launch_bounds__(St::MAX_BLOCK) void k_st_stagger_cut(GeoView g, MotionView mv, St sa, const int* __restrict__ list,
+                                                                  int nlist, const double* Cw0, const double* Cw1, const double* Cw2,
+                                                                  double* W0, double* W1, double* W2) {
+  const auto base = st_base(sa);
   const double* Cw[3] = {Cw0, Cw1, Cw2};
   double* W[3] = {W0, W1, W2};
   const int lane = threadIdx.x & 63;
@@ -663,7 +726,10 @@ __global__ void k_st_stagger_cut(GeoView g, MotionView mv, const int* __restrict
   lo[d] = Cw[d][lp];
   hi[d] = Cw[d][ln];
   double w = 0.0;
-  for (int k = lane; k < mv.nq; k += 64) w += mv.q[k].w * box_measure(mv.bodies[k], lo, hi, false, c_gl).vol;
+  for (int k = lane; k < mv.nq; k += 64) {
+    const auto& body = st_body(base, mv, k);
+    w += mv.q[k].w * box_measure(body, lo, hi, false, c_gl).vol;
+  }
   w = wave_add(w);
   if (lane == 0) W[d][lc] = w;
 }
@@ -779,8 +845,93 @@ void run_static_kernels(pg_capacity* c, pg_mesh* m, const BodyArg& ba, hipStream
   }
 }
 
+// The six space-time kernels on the whole mesh for the body `sa` reaches (mv: the time rule on the device, and for StBall the
+// bodies).  parts (may be NULL): the time of each kernel alone, 0 for one an empty list did not launch.
+template <class St>
+void run_spacetime_kernels(pg_capacity* c, pg_mesh* m, const MotionView& mv, const St& sa, hipStream_t st, double* parts) {
+  const int N = c->N;
+  alloc_fields(c);
+  const i64 Ml = c->slab.Mloc();
+  c->Vt[0].alloc(Ml); c->Vt[1].alloc(Ml); c->Ctw.alloc(Ml); c->Ctg.alloc(Ml);
+  GeoView g = geo_view(m, c->slab);
+  EventPair ev;
+  std::unique_ptr<EventPair[]> part(parts ? new EventPair[6] : nullptr);
+  bool ran[6] = {true, false, true, false, true, false};
+  auto t_begin = [&](int k) { if (parts) PG_HIP(hipEventRecord(part[k].e0, st)); };
+  auto t_end = [&](int k) { if (parts) PG_HIP(hipEventRecord(part[k].e1, st)); };
+  PG_HIP(hipEventRecord(ev.e0, st));
+  const int gr = grid_for(Ml, 256, 256 * 16);
+  StOut so;
+  so.V = c->V.p; so.G = c->G.p; so.ct = c->ct.p; so.Vt0 = c->Vt[0].p; so.Vt1 = c->Vt[1].p; so.Ctw = c->Ctw.p; so.Ctg = c->Ctg.p;
+  for (int d = 0; d < 3; ++d) { so.Cw[d] = c->Cw[d].p; so.Cg[d] = c->Cg[d].p; }
+  DevBuf<int> near_list(Ml), counters(3);
+  counters.zero();
+  t_begin(0);
+  hipLaunchKernelGGL(k_st_classify<St>, dim3(gr), dim3(256), 0, st, g, mv, sa, Ml, so, near_list.p, counters.p);
+  PG_HIP(hipGetLastError());
+  t_end(0);
+  int hc[3];
+  counters.download(hc, 3);
+  const int nnear = hc[0];
+  c->n_cut_local = nnear;
+  auto waves = [](i64 items) { return dim3((unsigned)((items * 64 + 255) / 256)); };
+  if (nnear > 0) {
+    ran[1] = true;
+    t_begin(1);
+    hipLaunchKernelGGL(k_st_cells<St>, waves(nnear), dim3(256), 0, st, g, mv, sa, near_list.p, nnear, so);
+    PG_HIP(hipGetLastError());
+    t_end(1);
+  }
+  // at most N faces / staggered volumes per near cell and per neighbour of one (1-D: every face is evaluated)
+  const i64 cap = std::min<i64>((i64)N * Ml, (N == 1 ? (i64)Ml : (i64)6 * N * (i64)nnear) + 1024);
+  DevBuf<int> list2(2 * cap);
+  t_begin(2);
+  hipLaunchKernelGGL(k_st_sections, dim3(gr), dim3(256), 0, st, g, mv, Ml, c->ct.p, c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p,
+                     c->B[1].p, c->B[2].p, list2.p, counters.p + 1, (int)cap);
+  PG_HIP(hipGetLastError());
+  t_end(2);
+  counters.download(hc, 3);
+  PG_REQUIRE(hc[1] <= cap, "internal: space-time section work list overflow");
+  if (hc[1] > 0) {
+    ran[3] = true;
+    t_begin(3);
+    hipLaunchKernelGGL(k_st_sections_cut<St>, waves(hc[1]), dim3(256), 0, st, g, mv, sa, list2.p, hc[1], c->Cw[0].p, c->Cw[1].p,
+                       c->Cw[2].p, c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
+    PG_HIP(hipGetLastError());
+    t_end(3);
+  }
+  t_begin(4);
+  hipLaunchKernelGGL(k_st_stagger, dim3(gr), dim3(256), 0, st, g, mv, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->W[0].p,
+                     c->W[1].p, c->W[2].p, list2.p, counters.p + 2, (int)cap);
+  PG_HIP(hipGetLastError());
+  t_end(4);
+  counters.download(hc, 3);
+  PG_REQUIRE(hc[2] <= cap, "internal: space-time staggered-volume work list overflow");
+  if (hc[2] > 0) {
+    ran[5] = true;
+    t_begin(5);
+    hipLaunchKernelGGL(k_st_stagger_cut<St>, waves(hc[2]), dim3(256), 0, st, g, mv, sa, list2.p, hc[2], c->Cw[0].p, c->Cw[1].p,
+                       c->Cw[2].p, c->W[0].p, c->W[1].p, c->W[2].p);
+    PG_HIP(hipGetLastError());
+    t_end(5);
+  }
+  PG_HIP(hipEventRecord(ev.e1, st));
+  PG_HIP(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  c->kernel_ms = ms;
+  for (int k = 0; parts && k < 6; ++k) {
+    parts[k] = 0.0;
+    if (!ran[k]) continue;
+    PG_HIP(hipEventElapsedTime(&ms, part[k].e0, part[k].e1));
+    parts[k] = ms;
+  }
+}
+
 // c_prog is one table per process: two host threads building program capacities at once take turns
 std::mutex g_prog_mutex;
+// measurement only (pg_debug_spacetime_kernel_timing): each of the six kernels of a program body between its own events
+bool g_st_timing = false;
 
 }  // namespace
 
@@ -1066,59 +1217,87 @@ int32_t pg_capacity_create_spacetime(pg_mesh* m, const pg_motion_desc* mo, pg_ca
   c->t1 = mo->t1;
   c->slab = m->base_slab();
   ensure_gl();
-  alloc_fields(c);
-  const i64 Ml = c->slab.Mloc();
-  c->Vt[0].alloc(Ml); c->Vt[1].alloc(Ml); c->Ctw.alloc(Ml); c->Ctg.alloc(Ml);
-  hipStream_t st = ctx().stream;
-  GeoView g = geo_view(m, c->slab);
-  EventPair ev;
-  PG_HIP(hipEventRecord(ev.e0, st));
-  const int gr = grid_for(Ml, 256, 256 * 16);
-  StOut so;
-  so.V = c->V.p; so.G = c->G.p; so.ct = c->ct.p; so.Vt0 = c->Vt[0].p; so.Vt1 = c->Vt[1].p; so.Ctw = c->Ctw.p; so.Ctg = c->Ctg.p;
-  for (int d = 0; d < 3; ++d) { so.Cw[d] = c->Cw[d].p; so.Cg[d] = c->Cg[d].p; }
-  DevBuf<int> near_list(Ml), counters(3);
-  counters.zero();
-  hipLaunchKernelGGL(k_st_classify, dim3(gr), dim3(256), 0, st, g, mv, Ml, so, near_list.p, counters.p);
-  PG_HIP(hipGetLastError());
-  int hc[3];
-  counters.download(hc, 3);
-  const int nnear = hc[0];
-  c->n_cut_local = nnear;
-  auto waves = [](i64 items) { return dim3((unsigned)((items * 64 + 255) / 256)); };
-  if (nnear > 0) {
-    hipLaunchKernelGGL(k_st_cells, waves(nnear), dim3(256), 0, st, g, mv, near_list.p, nnear, so);
-    PG_HIP(hipGetLastError());
-  }
-  // at most N faces / staggered volumes per near cell and per neighbour of one (1-D: every face is evaluated)
-  const i64 cap = std::min<i64>((i64)N * Ml, (N == 1 ? (i64)Ml : (i64)6 * N * (i64)nnear) + 1024);
-  DevBuf<int> list2(2 * cap);
-  hipLaunchKernelGGL(k_st_sections, dim3(gr), dim3(256), 0, st, g, mv, Ml, c->ct.p, c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p,
-                     c->B[1].p, c->B[2].p, list2.p, counters.p + 1, (int)cap);
-  PG_HIP(hipGetLastError());
-  counters.download(hc, 3);
-  PG_REQUIRE(hc[1] <= cap, "internal: space-time section work list overflow");
-  if (hc[1] > 0) {
-    hipLaunchKernelGGL(k_st_sections_cut, waves(hc[1]), dim3(256), 0, st, g, mv, list2.p, hc[1], c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
-                       c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
-    PG_HIP(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_st_stagger, dim3(gr), dim3(256), 0, st, g, mv, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->W[0].p,
-                     c->W[1].p, c->W[2].p, list2.p, counters.p + 2, (int)cap);
-  PG_HIP(hipGetLastError());
-  counters.download(hc, 3);
-  PG_REQUIRE(hc[2] <= cap, "internal: space-time staggered-volume work list overflow");
-  if (hc[2] > 0) {
-    hipLaunchKernelGGL(k_st_stagger_cut, waves(hc[2]), dim3(256), 0, st, g, mv, list2.p, hc[2], c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
-                       c->W[0].p, c->W[1].p, c->W[2].p);
-    PG_HIP(hipGetLastError());
-  }
-  PG_HIP(hipEventRecord(ev.e1, st));
-  PG_HIP(hipEventSynchronize(ev.e1));
-  float ms = 0.f;
-  PG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  c->kernel_ms = ms;
+  run_spacetime_kernels(c, m, mv, StBall(), ctx().stream, nullptr);
   *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_capacity_create_spacetime_program(pg_mesh* m, const pg_program* phi, const pg_program* grad, const pg_program* dphidt,
+                                             int32_t flags, double t0, double t1, int32_t nq, const double* tau_w,
+                                             pg_capacity** out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(m && out, "pg_capacity_create_spacetime_program: NULL argument");
+  *out = nullptr;                                // (a missing program or rule is named by spacetime_program_check below)
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm,
+             "pg_capacity_create_spacetime_program: single rank only (program bodies on slabs are not supported yet)");
+  const int N = m->N;
+  {
+    i64 n[3];
+    const double* nodes[3];
+    for (int d = 0; d < N; ++d) { n[d] = m->n[d]; nodes[d] = m->nodes[d].data(); }
+    std::string why;
+    PG_REQUIRE(spacetime_program_check(N, n, nodes, phi, grad, dphidt, t0, t1, nq, tau_w, &why),
+               N == 1 || N == 2 ? "pg_capacity_create_spacetime_program refused: " + why : why);
+  }
+  AsyncAllocScope pool;   // one capacity per time slab: the stream-ordered allocator (pg_common.h)
+  MotionView mv;
+  std::memset(&mv, 0, sizeof(mv));
+  mv.kind = BODY_BALLS;          // (not read: the body is the program)
+  mv.sgn = 1.0;
+  mv.nq = nq;
+  mv.t0 = t0;
+  mv.t1 = t1;
+  std::vector<MotionNode> hq(nq);
+  for (int k = 0; k < nq; ++k) {
+    std::memset(&hq[k], 0, sizeof(MotionNode));
+    hq[k].tau = tau_w[2 * k];
+    hq[k].w = tau_w[2 * k + 1];
+  }
+  DevBuf<MotionNode> dq(nq);
+  dq.upload(hq.data(), nq);
+  mv.q = dq.p;
+
+  auto* c = new pg_capacity();
+  std::unique_ptr<pg_capacity> guard(c);
+  c->mesh = m;
+  c->N = N;
+  c->from_body = false;
+  c->has_cg = !(flags & PG_FLAG_NO_CENTROIDS);
+  std::memset(&c->body, 0, sizeof(c->body));     // (not a BallSet: nothing reads it)
+  c->spacetime = true;
+  c->t0 = t0;
+  c->t1 = t1;
+  c->slab = m->base_slab();
+  ensure_gl();
+  pg_program progs[4];
+  std::memset(progs, 0, sizeof(progs));
+  progs[0] = *phi;
+  for (int d = 0; d < N; ++d) progs[1 + d] = grad[d];
+  progs[3] = *dphidt;
+  std::lock_guard<std::mutex> table(g_prog_mutex);   // held until the last kernel of this capacity has run
+  PG_HIP(hipStreamSynchronize(ctx().stream));    // (no earlier launch may still read the table)
+  PG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_prog), progs, sizeof(progs)));
+  StProg sp;
+  sp.N = N;
+  sp.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
+  run_spacetime_kernels(c, m, mv, sp, ctx().stream, g_st_timing ? c->st_ms_parts : nullptr);
+  *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_debug_spacetime_kernel_timing(int32_t on) {
+  PG_API_BEGIN
+  g_st_timing = on != 0;
+  PG_API_END
+}
+
+int32_t pg_debug_capacity_spacetime_ms_parts(const pg_capacity* c, double* ms, int64_t* n_listed) {
+  PG_API_BEGIN
+  PG_REQUIRE(c && ms && n_listed, "pg_debug_capacity_spacetime_ms_parts: NULL argument");
+  PG_REQUIRE(c->spacetime, "pg_debug_capacity_spacetime_ms_parts: not a space-time capacity");
+  for (int k = 0; k < 6; ++k) ms[k] = c->st_ms_parts[k];
+  *n_listed = c->n_cut_local;
   PG_API_END
 }
 

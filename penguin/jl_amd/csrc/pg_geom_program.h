@@ -2,7 +2,8 @@
 // (pick_ball, box_measure, section_measure of pg_geom.h) for a body given as a pg_program phi(x_1 .. x_N) and the N programs of
 // its partial derivatives.  Fluid is where phi <= 0.  1-D and 2-D.  Usable from HIP kernels and from a host (g++) build, like
 // pg_geom.h; compile with -ffp-contract=off.  The operand stack of the evaluator is a template parameter as in prog_eval: a
-// plain array on the host, a column of LDS in the kernels.
+// plain array on the host, a column of LDS in the kernels.  A body carries a time t (VAR 3 of its programs): a static body
+// passes 0, a moving one phi(x, t) is the static body "phi at t" for every primitive here, and a fourth program gives d phi / dt.
 //
 // Conventions (the test-side arbiters restate them):
 //   samples     a segment [a, b] is looked at in NS + 1 = 9 points a + (b - a) (k / 8), k = 0 .. 7, and b itself
@@ -28,7 +29,7 @@ namespace pggeom {
 constexpr int LS_NS = 8;        // sample intervals per segment
 constexpr int LS_ITMAX = 64;    // root refinement cap
 
-// Eval: value(which, x, y) runs program `which` (0: phi, 1 + d: d phi / d x_d) at a point.  `which` is a literal at every
+// Eval: value(which, x, y, t) runs program `which` (0: phi, 1 + d: d phi / d x_d, 3: d phi / dt) at a point.  `which` is a literal at every
 // call: in a kernel the evaluator is ONE function that is called, not inlined (dozens of inlined interpreters, each with its
 // own exp, pow, erf ..., do not fit the register file), and it fetches the instructions with scalar loads, which needs the
 // program to be the same for all lanes of the wave.
@@ -38,13 +39,23 @@ struct ProgBody {
   int complement;               // always 0: the sign lives in sgn, the kernels' own complement flip must not apply
   double sgn;                   // -1: PG_FLAG_COMPLEMENT (-phi, -grad phi)
   Eval ev;
+  double t = 0.0;               // the time every evaluation runs at (a static body: 0, its programs read no t)
   PG_HD double f(double x, double y) const {
-    const double v = sgn * ev.value(0, x, y);
+    const double v = sgn * ev.value(0, x, y, t);
     return v == v ? v : 1.0;
   }
   PG_HD void grad(double x, double y, double& g0, double& g1) const {
-    g0 = sgn * ev.value(1, x, y);
-    g1 = N > 1 ? sgn * ev.value(2, x, y) : 0.0;
+    g0 = sgn * ev.value(1, x, y, t);
+    g1 = N > 1 ? sgn * ev.value(2, x, y, t) : 0.0;
+  }
+  PG_HD double dfdt(double x, double y) const { return sgn * ev.value(3, x, y, t); }   // moving bodies only
+  // the normal speed of the interface at a point, - d_t phi / |grad phi|; a zero or non-finite |grad phi| gives 0
+  PG_HD double normal_speed(double x, double y) const {
+    double g0, g1;
+    grad(x, y, g0, g1);
+    const double gn = sqrt(g0 * g0 + g1 * g1);
+    if (!(gn > 0.0 && gn < 1e300)) return 0.0;
+    return -dfdt(x, y) / gn;
   }
 };
 
@@ -53,8 +64,9 @@ struct HostEval {
   const pg_program* phi;
   const pg_program* grad;       // N programs
   pgprog::HostStack* S;
-  double value(int which, double x, double y) const {
-    return pgprog::prog_eval(which == 0 ? *phi : grad[which - 1], x, y, 0.0, 0.0, *S);
+  const pg_program* dt = nullptr;   // d phi / dt of a moving body
+  double value(int which, double x, double y, double t) const {
+    return pgprog::prog_eval(which == 0 ? *phi : which == 3 ? *dt : grad[which - 1], x, y, 0.0, t, *S);
   }
 };
 
@@ -187,6 +199,46 @@ template <class Eval>
 PG_HD int pick_ball(const ProgBody<Eval>& bs, const double* lo, const double* hi, int& type) {
   type = prog_box_type(bs, lo, hi);
   return 0;
+}
+
+// The cheap test of a space-time cell (box) x [t0, t1] of a MOVING body: +1 the box is fluid during the whole slab, -1 solid,
+// 0 not decided here.  Decided only if, at t0, mid time and t1, the sample lattice of prog_box_type (9 points in 1-D, 33 in 2-D)
+// has ONE strict sign, and the smallest |phi| over those samples exceeds (t1 - t0) max |d phi / dt| over the same samples:
+// twice the first-order change of phi over half a slab, the farthest any time is from one of the three.  A NaN of d phi / dt
+// decides nothing.  What is not decided goes to the all-nodes rule, so the margin costs time and never a type.
+template <class Eval>
+PG_HD int prog_st_far(ProgBody<Eval> bs, const double* lo, const double* hi, double t0, double t1) {
+  bool in = true, out = true, ok = true;
+  double amin = 1e300, rate = 0.0;
+  auto look = [&](double x, double y) {
+    const double v = bs.f(x, y), r = fabs(bs.dfdt(x, y));
+    in = in && v < 0.0;
+    out = out && v > 0.0;
+    amin = dmin(amin, fabs(v));
+    ok = ok && r == r;
+    rate = dmax(rate, r);
+  };
+  for (int e = 0; e < 3 && (in || out) && ok; ++e) {
+    bs.t = e == 0 ? t0 : e == 1 ? 0.5 * (t0 + t1) : t1;
+    if (bs.N == 1) {
+      for (int k = 0; k <= LS_NS && (in || out); ++k) look(ls_sample(lo[0], hi[0], k), 0.0);
+    } else {
+      for (int k = 0; k <= LS_NS && (in || out); ++k) {
+        const double x = ls_sample(lo[0], hi[0], k);
+        look(x, lo[1]);
+        look(x, hi[1]);
+      }
+      for (int k = 1; k < LS_NS && (in || out); ++k) {
+        const double y = ls_sample(lo[1], hi[1], k);
+        look(lo[0], y);
+        look(hi[0], y);
+      }
+      if (in || out) look(0.5 * (lo[0] + hi[0]), 0.5 * (lo[1] + hi[1]));
+    }
+  }
+  if (!(in || out) || !ok) return 0;
+  if (!(amin > (t1 - t0) * rate)) return 0;
+  return in ? 1 : -1;
 }
 
 // qlane / qstride: as ball_box_moments -- this caller takes the Gauss-Legendre nodes qlane, qlane + qstride, ... of every piece
@@ -354,6 +406,82 @@ inline bool program_body_check(int N, const int64_t* n, const double* const* nod
         return fail("gradient program " + std::to_string(d) + " gives " + std::to_string(g[d]) + " at (" + std::to_string(x[0]) +
                     (N > 1 ? ", " + std::to_string(x[1]) : std::string()) + ") where central differences of the level set give " +
                     std::to_string(fd[d]));
+  }
+  return true;
+}
+
+// Host only: what pg_capacity_create_spacetime_program refuses before it allocates anything (the mesh, the output pointer and
+// the ranks are the caller's to check).  The derivative rule is program_body_check's, with its tolerances, taken at t0, mid time
+// and t1, and d phi / dt against central differences of phi in time with the step 1e-6 (t1 - t0).
+inline bool spacetime_program_check(int N, const int64_t* n, const double* const* nodes /* n_d + 1 each */, const pg_program* phi,
+                                    const pg_program* grad, const pg_program* dphidt, double t0, double t1, int nq,
+                                    const double* tau_w /* nq x 2 */, std::string* why) {
+  auto fail = [&](const std::string& m) {
+    if (why) *why = m;
+    return false;
+  };
+  if (N != 1 && N != 2) return fail("space-time capacities: 1-D+t and 2-D+t (the reference's 3-D+t blocks drop the z direction)");
+  if (!phi) return fail("NULL level-set program");
+  if (!grad) return fail("grad == NULL: the N programs of d phi / d x_d are needed (DeviceFunction.moving_gradient_programs builds them)");
+  if (!dphidt) return fail("dphidt == NULL: the program of d phi / dt is needed (DeviceFunction.moving_gradient_programs builds it)");
+  if (!tau_w) return fail("tau_w == NULL: the time nodes and weights are needed");
+  for (int k = 0; k <= N + 1; ++k) {
+    const pg_program* p = k == 0 ? phi : k <= N ? grad + (k - 1) : dphidt;
+    const std::string name = k == 0 ? std::string("the level-set program")
+                             : k <= N ? "gradient program " + std::to_string(k - 1) : std::string("the time-derivative program");
+    std::string w;
+    if (!pgprog::program_validate(p, &w)) return fail(name + " is invalid: " + w);
+    for (int q = 0; q < p->n_ops; ++q)
+      if (p->op[q] == PG_OP_VAR && p->arg[q] != 3 && p->arg[q] >= N)
+        return fail(name + " reads coordinate " + std::to_string((int)p->arg[q]) + " (instruction " + std::to_string(q) + ") on a " +
+                    std::to_string(N) + "-D mesh");
+  }
+  if (nq < 1 || nq > 4096) return fail("1 .. 4096 time nodes");
+  if (!(t1 > t0)) return fail("empty time slab");
+  double wsum = 0.0;
+  for (int k = 0; k < nq; ++k) {
+    if (!(tau_w[2 * k] > t0 && tau_w[2 * k] < t1)) return fail("time nodes must lie inside (t0, t1)");
+    wsum += tau_w[2 * k + 1];
+  }
+  if (!(fabs(wsum - (t1 - t0)) <= 1e-12 * (t1 - t0))) return fail("time weights must add up to t1 - t0");
+  int64_t M = 1;
+  for (int d = 0; d < N; ++d) M *= n[d];
+  const int64_t npts = M < 64 ? M : 64;
+  pgprog::HostStack S;
+  const double et = 1e-6 * (t1 - t0);
+  for (int e = 0; e < 3; ++e) {
+    const double t = e == 0 ? t0 : e == 1 ? 0.5 * (t0 + t1) : t1;
+    for (int64_t k = 0; k < npts; ++k) {
+      int64_t cell = npts > 1 ? (k * (M - 1)) / (npts - 1) : 0;
+      double x[2] = {0.0, 0.0};
+      double h[2] = {1.0, 1.0};
+      for (int d = 0; d < N; ++d) {
+        const int64_t j = cell % n[d];
+        x[d] = 0.5 * (nodes[d][j] + nodes[d][j + 1]);
+        h[d] = (nodes[d][n[d]] - nodes[d][0]) / (double)n[d];
+        cell /= n[d];
+      }
+      double g[3] = {0.0, 0.0, 0.0}, fd[3] = {0.0, 0.0, 0.0}, gn = 0.0;
+      for (int d = 0; d < N; ++d) {
+        const double e1 = 1e-6 * h[d];
+        double xp[2] = {x[0], x[1]}, xm[2] = {x[0], x[1]};
+        xp[d] += e1; xm[d] -= e1;
+        fd[d] = (pgprog::prog_eval(*phi, xp[0], xp[1], 0.0, t, S) - pgprog::prog_eval(*phi, xm[0], xm[1], 0.0, t, S)) / (xp[d] - xm[d]);
+        g[d] = pgprog::prog_eval(grad[d], x[0], x[1], 0.0, t, S);
+        gn += g[d] * g[d];
+      }
+      const double tp = t + et, tm = t - et;
+      fd[2] = (pgprog::prog_eval(*phi, x[0], x[1], 0.0, tp, S) - pgprog::prog_eval(*phi, x[0], x[1], 0.0, tm, S)) / (tp - tm);
+      g[2] = pgprog::prog_eval(*dphidt, x[0], x[1], 0.0, t, S);
+      const double tol = 1e-4 * dmax(sqrt(gn), 1.0);
+      const std::string at = " at (" + std::to_string(x[0]) + (N > 1 ? ", " + std::to_string(x[1]) : std::string()) + "), t = " +
+                             std::to_string(t) + " where central differences of the level set give ";
+      for (int d = 0; d < N; ++d)
+        if (fabs(g[d] - fd[d]) > tol)                 // (false for a NaN)
+          return fail("gradient program " + std::to_string(d) + " gives " + std::to_string(g[d]) + at + std::to_string(fd[d]));
+      if (fabs(g[2] - fd[2]) > tol)
+        return fail("the time-derivative program gives " + std::to_string(g[2]) + at + std::to_string(fd[2]));
+    }
   }
   return true;
 }

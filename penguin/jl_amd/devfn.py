@@ -421,7 +421,10 @@ class DeviceFunction:
     and `gradient_programs(N)` the N traces of its partial derivatives, differentiated rule by rule from that trace.
     `complement=True` is the body -fn (the other phase of a two-phase problem; `Capacity(body, mesh, complement=True)` sets it):
     calls return -fn, the body programs stay fn's and the capacity kernels negate.  Such an object is a body only: `program_for`
-    (time-dependent data) refuses it."""
+    (time-dependent data) refuses it.
+
+    As the body of a space-time Capacity (the prescribed-motion solvers), fn(x_1 .. x_N, t) is a moving level set:
+    `moving_body_program(N)` and `moving_gradient_programs(N)` (the N spatial derivatives, then d/dt)."""
 
     def __init__(self, fn, complement: bool = False):
         if isinstance(fn, DeviceFunction):
@@ -496,6 +499,44 @@ class DeviceFunction:
         """The N programs of the partial derivatives of fn(x_1 .. x_N), differentiated from its trace."""
         root = self._body_trace(N)
         return [_compile(differentiate(root, d), f"the derivative along coordinate {d} of the body {self.fn!r}") for d in range(N)]
+
+    # ---- a moving level-set body: fn(x_1 .. x_N, t)
+    def _moving_trace(self, N: int) -> Sym:
+        key = -N                                 # (the static traces of the same object sit under N)
+        if key not in self._bodies:
+            what = f"the moving body {self.fn!r} with {N} coordinates and t"
+            try:
+                out = self.fn(*([Sym("VAR", d) for d in range(N)] + [Sym("VAR", 3)]))
+            except PenguinHipError:
+                raise
+            except Exception as e:
+                raise PenguinHipError(f"DeviceFunction: cannot trace {what}: {type(e).__name__}: {e}") from e
+            if isinstance(out, (list, tuple)) or (isinstance(out, np.ndarray) and out.ndim > 0):
+                raise PenguinHipError(f"DeviceFunction: {what} returned {type(out).__name__}, not a scalar")
+            if isinstance(out, np.ndarray) and out.dtype == object:
+                out = out.item()
+            self._bodies[key] = Sym.wrap(out, "the returned value")
+        return self._bodies[key]
+
+    def moving_body_program(self, N: int) -> pg_program:
+        """The program of the moving level set fn(x_1 .. x_N, t): coordinates VAR 0 .. N-1, t VAR 3.  Compiled once per object
+        and N (a solve asks for it on every slab)."""
+        key = ("moving body", N)
+        if key not in self._programs:
+            self._programs[key] = _compile(self._moving_trace(N), f"the moving body {self.fn!r} with {N} coordinates and t")
+        return self._programs[key]
+
+    def moving_gradient_programs(self, N: int) -> List[pg_program]:
+        """N + 1 programs: the N spatial partial derivatives of fn(x_1 .. x_N, t), then d/dt, differentiated from its trace and
+        folded like the static ones (a closure that does not read t gives the constant 0).  Compiled once per object and N."""
+        key = ("moving derivatives", N)
+        if key not in self._programs:
+            root = self._moving_trace(N)
+            body = f"the moving body {self.fn!r}"
+            progs = [_compile(differentiate(root, d), f"the derivative along coordinate {d} of {body}") for d in range(N)]
+            progs.append(_compile(differentiate(root, 3), f"the derivative along t of {body}"))
+            self._programs[key] = tuple(progs)
+        return list(self._programs[key])
 
     def evaluate_program(self, coords, t, nspace: Optional[int] = None, dtype=np.float64, **kw) -> np.ndarray:
         """The bytecode interpreted with numpy at the rows of coords; nspace (default: 3, the arity of sources and interface

@@ -11,7 +11,10 @@ src/mesh.jl:129-146 (SpaceTimeMesh), with the same names and argument order.
 Every time slab builds a new space-time capacity on the GPU (pg_capacity_create_spacetime), assembles the moving blocks
 there (pg_solver_create_moving_mono) and solves; the host only evaluates the motion at the time-quadrature nodes and the
 user's closures.  The level set of the reference is an arbitrary `body(x..., t)`; here it is a tagged moving body, as for
-static capacities (an arbitrary one: integrate it yourself and use SpaceTimeCapacity.from_arrays).
+static capacities, or any closure wrapped in DeviceFunction: `Capacity(DeviceFunction(lambda x, y, t: ...), STmesh)` traces it
+once and evaluates phi, its gradient and d phi / dt inside the space-time kernels (pg_capacity_create_spacetime_program,
+DESIGN.md section 24); the drivers take it as `body`, and `DeviceFunction(fn, complement=True)` as `body_c`.  A plain callable
+is refused (integrate it yourself and use SpaceTimeCapacity.from_arrays).
 1-D and 2-D in space: the reference's 3-D+t selection `[1:end÷2]` drops the z direction."""
 from __future__ import annotations
 
@@ -23,6 +26,7 @@ import numpy as np
 from . import _lib as L
 from . import api
 from ._lib import PenguinHipError
+from .devfn import DeviceFunction, pg_program
 
 
 class SpaceTimeMesh:
@@ -124,7 +128,14 @@ class SpaceTimeCapacity(api.Capacity):
     time_panels x time_order: the composite Gauss-Legendre rule in time (space is exact)."""
 
     def __init__(self, body, mesh: SpaceTimeMesh, method: str = "VOFI", compute_centroids: bool = True,
-                 time_panels: int = 16, time_order: int = 4):
+                 time_panels: int = 16, time_order: int = 4, complement: bool = False):
+        if complement:
+            if not isinstance(body, DeviceFunction):
+                raise PenguinHipError("Capacity(complement=True) is for DeviceFunction bodies; tagged bodies take complement=True themselves")
+            body = DeviceFunction(body, complement=True)
+        if isinstance(body, DeviceFunction):
+            self._init_program(body, mesh, compute_centroids, time_panels, time_order)
+            return
         if not hasattr(body, "_state"):
             raise PenguinHipError("Capacity(body, SpaceTimeMesh): pass a MovingSphere / MovingHalfSpace (an arbitrary moving "
                                   "level set needs SpaceTimeCapacity.from_arrays)")
@@ -151,6 +162,40 @@ class SpaceTimeCapacity(api.Capacity):
         self._h = C.c_void_p()
         L.check(L.lib().pg_capacity_create_spacetime(self.mesh._h, C.byref(desc), C.byref(self._h)))
         self._cache = {}
+
+    def _init_program(self, body: DeviceFunction, mesh: SpaceTimeMesh, compute_centroids: bool, time_panels: int, time_order: int):
+        """body(x_1 .. x_N, t) traced: phi, its N spatial derivatives and d phi / dt are evaluated inside the space-time kernels
+        (pg_capacity_create_spacetime_program).  The programs are compiled once per DeviceFunction, not once per slab."""
+        L.init()
+        self.stmesh, self.mesh, self.body, self.compute_centroids = mesh, mesh.space, body, compute_centroids
+        N = self.mesh.N
+        t0, t1 = mesh.time
+        tau, wt = time_rule(t0, t1, time_panels, time_order)
+        self._nodes = np.ascontiguousarray(np.column_stack([tau, wt]))
+        self._h = C.c_void_p()
+        self._cache = {}
+        if N not in (1, 2):
+            # (3-D+t: the entry's own refusal, in its words -- nothing is traced for it)
+            z = pg_program()
+            L.check(L.lib().pg_capacity_create_spacetime_program(self.mesh._h, C.byref(z), C.byref(z), C.byref(z), C.c_int32(0),
+                                                                 C.c_double(t0), C.c_double(t1), C.c_int32(len(tau)),
+                                                                 L.dptr(self._nodes), C.byref(self._h)))
+        phi = body.moving_body_program(N)
+        derivs = body.moving_gradient_programs(N)
+        grad = (pg_program * N)(*derivs[:N])
+        flags = (L.PG_FLAG_COMPLEMENT if body.complement else 0) | (0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
+        L.check(L.lib().pg_capacity_create_spacetime_program(self.mesh._h, C.byref(phi), grad, C.byref(derivs[N]), C.c_int32(flags),
+                                                             C.c_double(t0), C.c_double(t1), C.c_int32(len(tau)),
+                                                             L.dptr(self._nodes), C.byref(self._h)))
+
+    @property
+    def spacetime_kernel_ms(self):
+        """measurement, program bodies: ({kernel: ms}, cells the cheap pass left to the list).  The times are those of this slab's
+        six kernels when the capacity was built under `spacetime_kernel_timing(True)`, 0 otherwise and for a kernel not launched."""
+        ms, n = (C.c_double * 6)(), C.c_int64(0)
+        L.check(L.lib().pg_debug_capacity_spacetime_ms_parts(self._h, ms, C.byref(n)))
+        names = ("k_st_classify", "k_st_cells", "k_st_sections", "k_st_sections_cut", "k_st_stagger", "k_st_stagger_cut")
+        return dict(zip(names, (float(v) for v in ms))), int(n.value)
 
     @classmethod
     def from_arrays(cls, stmesh: SpaceTimeMesh, V, A, B, W, Gamma, C_omega, C_gamma, cell_types, Vn_1, Vn, body=None):
@@ -200,6 +245,12 @@ class SpaceTimeCapacity(api.Capacity):
 
     def _cg(self):
         return self.C_γ_st
+
+
+def spacetime_kernel_timing(on: bool) -> None:
+    """measurement, off by default: bracket each of the six kernels of later program-body space-time capacities with events"""
+    L.init()
+    L.check(L.lib().pg_debug_spacetime_kernel_timing(C.c_int32(1 if on else 0)))
 
 
 def _capacity_new(cls, body=None, mesh=None, *args, **kwargs):
