@@ -1201,8 +1201,9 @@ def _precond_value(precond) -> int:
 
 def _krylov_opts(method, kwargs) -> L.pg_krylov_opts:
     """method may be "bicgstab" / "cg" / "gmres" or a callable named like IterativeSolvers' (bicgstabl, cg, gmres...).
-    gmres -> restarted GMRES on the device (restart kwarg, default 20); cg -> CG; bicgstabl WITH the keyword l (l=2, l=4, ..,
-    at most 8) -> BiCGStab(l) on the device (DESIGN.md "BiCGStab(l)": one rank, zero initial guess, plain -- the library refuses
+    gmres -> restarted GMRES on the device (restart kwarg, default 20; its iterations are Arnoldi steps, one product each, and that
+    is the unit maxiter caps: a cycle that ends early is charged the steps it ran, the solve ends at iters >= maxiter); cg -> CG;
+    bicgstabl WITH the keyword l (l=2, l=4, .., at most 8) -> BiCGStab(l) on the device (DESIGN.md "BiCGStab(l)": one rank, zero initial guess, plain -- the library refuses
     it together with precond = m >= 1, "mg", "mg-cell", "mg-step" or "poly-est"); `\\`, bicgstabl WITHOUT l and anything else -> BiCGStab.
     BiCGStab(l) counts BiCG sub-steps as its iterations, two products each -- the unit of BiCGStab's iterations, and the unit
     maxiter caps (no outer iteration starts at iters >= maxiter); products = 2 iters + the products that confirm the true residual.

@@ -24,6 +24,7 @@
 // It iterates on the same preconditioned system  Â = B⁻¹SAS  as BiCGStab / CG (pg_precond.hip), so the residual it
 // minimises is the preconditioned one.  Not on the benchmark path (BiCGStab needs 18 vector passes per two SpMVs, GMRES
 // ~4j + 6 per SpMV); it is here so that `method = gmres` means GMRES.
+#include "pg_host_algos.h"
 #include "pg_krylov.h"
 #include "pg_spmv.h"
 #include "pg_specest.h"
@@ -34,20 +35,14 @@ namespace {
 
 constexpr int GRP = GM_GRP;   // basis vectors handled per launch of the dot / update kernels
 
-// device scalar block of GMRES (KrylovWork::gm), after the H / cs / sn / g / y / h arrays
-struct GmLayout {
-  int m;
-  __host__ __device__ int H(int i, int j) const { return (m + 1) * j + i; }        // (m+1) x m, column major
-  __host__ __device__ int cs(int i) const { return (m + 1) * m + i; }
-  __host__ __device__ int sn(int i) const { return (m + 1) * m + m + i; }
-  __host__ __device__ int g(int i) const { return (m + 1) * m + 2 * m + i; }       // m + 1
-  __host__ __device__ int y(int i) const { return (m + 1) * m + 3 * m + 1 + i; }   // m
-  __host__ __device__ int h1(int i) const { return (m + 1) * m + 4 * m + 1 + i; }  // m + 2: first-pass coefficients
-  __host__ __device__ int h2(int i) const { return (m + 1) * m + 5 * m + 3 + i; }  // m + 2: second pass, then ||w||^2
-  __host__ __device__ int J() const { return (m + 1) * m + 6 * m + 5; }            // columns of the current cycle
-  __host__ __device__ int invn() const { return J() + 1; }                          // 1 / norm of the vector to scale
-  __host__ __device__ int size() const { return J() + 2; }
-};
+// device scalar block of GMRES (KrylovWork::gm): the layout and the three one-thread steps are pg_host_algos.h's -- the code the
+// CPU suite runs under sanitizers (tests/gmres_host.cpp)
+using pghost::GmLayout;
+
+// the steps' scalars in the S_* block: S_RHAT2 holds the weighted tolerance here, S_RRW (b,b), S_FORCE the not-finite mark
+constexpr pghost::GmSlots gm_slots() {
+  return pghost::GmSlots{S_BB, S_RR, S_RRW, S_ITERS, S_RELTOL2, S_ABSTOL2, S_TOL2, S_RHAT2, S_DONE, S_FORCE};
+}
 
 // v = b - Ax (Ax == nullptr: v = b), ghosts zeroed; partial slot 0 = (v,v), slot 1 = (v,v)_W (weights ds^2)
 __global__ __launch_bounds__(BLOCK) void k_gm_resid(i64 n, i64 nvec, const double* __restrict__ b, const double* __restrict__ Ax,
@@ -93,34 +88,9 @@ __global__ __launch_bounds__(BLOCK) void k_gm_reduce(int nslots, int grid, const
 
 namespace {
 
-// start of a restart cycle (and verdict on the one before): rr = (r,r), rrw = (r,r)_W of the TRUE residual; beta = ||r||.
-// Inner tolerance (Givens estimate) from the first residual (zero initial guess: ||r0|| = ||b||), lowered when the estimate
-// was met and the weighted test was not; acceptance on the weighted norm.  S_RHAT2 holds the weighted tolerance here.
+// start of a restart cycle (and verdict on the one before): pghost::gm_begin
 __global__ void k_gm_begin(GmLayout L, double* __restrict__ gm, double* __restrict__ sc, int first) {
-  const double rr = gm[L.h2(0)], rrw = gm[L.h2(1)];
-  if (first) {
-    sc[S_BB] = rrw;
-    sc[S_RRW] = rr;          // (b,b): the inner tolerance's reference
-    sc[S_ITERS] = 0.0;
-    const double t2 = sc[S_RELTOL2] * rr;
-    sc[S_TOL2] = t2 > sc[S_ABSTOL2] ? t2 : sc[S_ABSTOL2];
-    const double tw = sc[S_RELTOL2] * rrw;
-    sc[S_RHAT2] = tw > sc[S_ABSTOL2] ? tw : sc[S_ABSTOL2];
-  }
-  sc[S_RR] = rrw;
-  const double beta = sqrt(rr > 0.0 ? rr : 0.0);
-  for (int i = 0; i <= L.m; ++i) gm[L.g(i)] = 0.0;
-  gm[L.g(0)] = beta;
-  gm[L.J()] = 0.0;
-  gm[L.invn()] = beta > 0.0 ? 1.0 / beta : 0.0;
-  if (sc[S_DONE] == 2.0) return;   // singular (k_gm_hess): stays
-  const bool ok = rrw <= sc[S_RHAT2] || beta == 0.0;
-  sc[S_DONE] = ok ? 1.0 : 0.0;
-  if (!ok && !first && rrw > 0.0) {
-    // the estimate may already be below the inner tolerance: aim the next cycle at the weighted test
-    const double aim = 0.25 * rr * (sc[S_RHAT2] / rrw);
-    if (aim < sc[S_TOL2]) sc[S_TOL2] = aim;
-  }
+  pghost::gm_begin(L, gm_slots(), gm, sc, first);
 }
 
 }  // namespace
@@ -190,52 +160,13 @@ __global__ __launch_bounds__(BLOCK) void k_gm_update(i64 n, i64 stride, int k0, 
 
 namespace {
 
-// column j of the Hessenberg matrix: h = h1 + h2 (CGS2), previous rotations, new rotation, residual estimate
+// column j of the Hessenberg matrix: pghost::gm_hess
 __global__ void k_gm_hess(GmLayout L, int j, double* __restrict__ gm, double* __restrict__ sc) {
-  if (sc[S_DONE] != 0.0) return;
-  for (int i = 0; i <= j; ++i) gm[L.H(i, j)] = gm[L.h1(i)] + gm[L.h2(i)];
-  const double nn = gm[L.h2(j + 1)];
-  const double hn = sqrt(nn > 0.0 ? nn : 0.0);
-  gm[L.H(j + 1, j)] = hn;
-  for (int i = 0; i < j; ++i) {
-    const double c = gm[L.cs(i)], s = gm[L.sn(i)];
-    const double a = gm[L.H(i, j)], b = gm[L.H(i + 1, j)];
-    gm[L.H(i, j)] = c * a + s * b;
-    gm[L.H(i + 1, j)] = -s * a + c * b;
-  }
-  const double a = gm[L.H(j, j)];
-  const double d = hypot(a, hn);
-  sc[S_ITERS] += 1.0;
-  gm[L.J()] = (double)(j + 1);
-  if (d == 0.0) {   // A v_j = 0: singular system; keep the previous columns only
-    gm[L.J()] = (double)j;
-    sc[S_DONE] = 2.0;
-    return;
-  }
-  const double c = a / d, s = hn / d;
-  gm[L.cs(j)] = c;
-  gm[L.sn(j)] = s;
-  gm[L.H(j, j)] = d;
-  gm[L.H(j + 1, j)] = 0.0;
-  const double gj = gm[L.g(j)];
-  gm[L.g(j)] = c * gj;
-  gm[L.g(j + 1)] = -s * gj;
-  const double rr = gm[L.g(j + 1)] * gm[L.g(j + 1)];
-  gm[L.invn()] = hn > 0.0 ? 1.0 / hn : 0.0;
-  // the cycle ends here (3: not a verdict -- the true weighted residual at the restart decides, k_gm_begin);
-  // hn == 0: the Krylov space is exhausted (exact solution)
-  if (rr <= sc[S_TOL2] || hn == 0.0) sc[S_DONE] = 3.0;
+  pghost::gm_hess(L, gm_slots(), j, gm, sc);
 }
 
-// y = H(0:J,0:J)^-1 g(0:J)   (back substitution on the rotated, upper-triangular H)
-__global__ void k_gm_solve_y(GmLayout L, double* __restrict__ gm) {
-  const int J = (int)gm[L.J()];
-  for (int i = J - 1; i >= 0; --i) {
-    double s = gm[L.g(i)];
-    for (int k = i + 1; k < J; ++k) s -= gm[L.H(i, k)] * gm[L.y(k)];
-    gm[L.y(i)] = s / gm[L.H(i, i)];
-  }
-}
+// y = H(0:J,0:J)^-1 g(0:J): pghost::gm_solve_y
+__global__ void k_gm_solve_y(GmLayout L, double* __restrict__ gm) { pghost::gm_solve_y(L, gm); }
 
 // x += sum_{i<J} y_i V_i
 __global__ __launch_bounds__(BLOCK) void k_gm_xupdate(i64 n, i64 stride, GmLayout L, const double* __restrict__ gm,
@@ -290,7 +221,7 @@ void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, cons
     if (multi) comm_allreduce_sum_f64(out, nslots, st);   // identical sums, hence identical control flow, on every rank
   };
 
-  int launched = 0;
+  int iters = 0;   // Arnoldi steps that ran (S_ITERS): the unit maxiter caps -- a cycle the estimate ends early is charged what it ran
   bool done = false;
   // r = b - Â x  ->  v_0 = r / ||r||, with the verdict on x (k_gm_begin): at the start, and after every cycle
   auto restart = [&](bool first) {
@@ -307,7 +238,7 @@ void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, cons
   };
   restart(true);
   while (!done) {
-    const int steps = std::max(0, std::min(m, maxiter - launched));
+    const int steps = std::max(0, std::min(m, maxiter - iters));
     for (int j = 0; j < steps; ++j) {
       double* vj = V + (size_t)j * stride;
       double* wv = V + (size_t)(j + 1) * stride;
@@ -329,7 +260,6 @@ void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, cons
       hipLaunchKernelGGL(k_gm_hess, dim3(1), dim3(1), 0, st, L, j, gm, w.sc.p);
       hipLaunchKernelGGL(k_gm_scale, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, gm, L.invn(), wv);
     }
-    launched += steps;
     // end of the cycle (or convergence inside it): x += V y
     hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, st, L, gm);
     hipLaunchKernelGGL(k_gm_xupdate, dim3(G), dim3(BLOCK), 0, st, n, stride, L, (const double*)gm, (const double*)V, x);
@@ -337,12 +267,18 @@ void gmres_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, cons
     PG_HIP(hipGetLastError());
     PG_HIP(hipMemcpyAsync(w.h_sc, w.sc.p, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost, st));
     PG_HIP(hipStreamSynchronize(st));
-    if (w.h_sc[S_DONE] == 1.0 || w.h_sc[S_DONE] == 2.0 || launched >= maxiter || steps == 0) done = true;
+    iters = (int)w.h_sc[S_ITERS];
+    if (w.h_sc[S_DONE] == 1.0 || w.h_sc[S_DONE] == 2.0 || iters >= maxiter || steps == 0) done = true;
   }
   stats.iters = (int)w.h_sc[S_ITERS];
   stats.converged = w.h_sc[S_DONE] == 1.0 ? 1 : 0;
   stats.resnorm = std::sqrt(w.h_sc[S_RR]);
   stats.bnorm = std::sqrt(w.h_sc[S_BB]);
+  if (w.h_sc[S_FORCE] != 0.0) {
+    // a norm that is not finite (gm_begin / gm_hess stopped the solve): the state is not handed back, as in BiCGStab(l)
+    PG_HIP(hipMemsetAsync(x, 0, sizeof(double) * (size_t)nvec, st));
+    stats.resnorm = stats.bnorm;
+  }
 }
 
 }  // namespace pg

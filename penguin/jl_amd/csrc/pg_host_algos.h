@@ -2,7 +2,8 @@
 // AddressSanitizer + UndefinedBehaviorSanitizer (tests/host_asan.cpp): the slab partition of the
 // planes and the planning of the SpMV's marching units (index arithmetic over run descriptors: the place where an
 // off-by-one reads outside a vector on the GPU), the host side of the multigrid set-up (tests/mg_host_asan.cpp) and the
-// eigenvalues of the spectral estimate's Hessenberg matrix (tests/specest_host.cpp).  Included by pg_context.hip, pg_spmv.hip,
+// eigenvalues of the spectral estimate's Hessenberg matrix (tests/specest_host.cpp), and the one-thread scalar steps of BiCGStab(l),
+// IDR(s) and GMRES, compiled for the device too (tests/bicgstabl_host.cpp, idrs_host.cpp, gmres_host.cpp).  Included by pg_context.hip, pg_spmv.hip,
 // pg_multigrid.hip and pg_specest.hip.
 #pragma once
 #include <algorithm>
@@ -696,6 +697,126 @@ PGHOST_HD inline bool idr_lower_solve(const double* M, int s, int lo, int hi, co
   if (!ok)
     for (int i = 0; i < IDR_MAX_S; ++i) out[i] = 0.0;
   return ok;
+}
+
+// ---- scalars of restarted GMRES (pg_gmres.hip; tests/gmres_host.cpp) ---------------------------------------------------------
+// The scalar block `gm` of a solve with restart length m -- H, cs, sn, g, y and the two coefficient arrays the reductions write --
+// and the three one-thread steps that work on it: the verdict at a restart, one column of the Hessenberg matrix, the back
+// substitution.  The kernels of pg_gmres.hip are one-line wrappers of these; tests/gmres_reference.py GmScalars restates them.
+struct GmLayout {
+  int m;
+  PGHOST_HD int H(int i, int j) const { return (m + 1) * j + i; }        // (m+1) x m, column major
+  PGHOST_HD int cs(int i) const { return (m + 1) * m + i; }
+  PGHOST_HD int sn(int i) const { return (m + 1) * m + m + i; }
+  PGHOST_HD int g(int i) const { return (m + 1) * m + 2 * m + i; }       // m + 1
+  PGHOST_HD int y(int i) const { return (m + 1) * m + 3 * m + 1 + i; }   // m
+  PGHOST_HD int h1(int i) const { return (m + 1) * m + 4 * m + 1 + i; }  // m + 2: first-pass coefficients
+  PGHOST_HD int h2(int i) const { return (m + 1) * m + 5 * m + 3 + i; }  // m + 2: second pass, then ||w||^2
+  PGHOST_HD int J() const { return (m + 1) * m + 6 * m + 5; }            // columns of the current cycle
+  PGHOST_HD int invn() const { return J() + 1; }                          // 1 / norm of the vector to scale
+  PGHOST_HD int size() const { return J() + 2; }
+};
+
+// where the steps find their scalars in `sc` (the device: the S_* slots of pg_spmv.h, pg_gmres.hip gm_slots)
+struct GmSlots {
+  int bb, rr, rr0, iters, reltol2, abstol2, tol2, tolw2, done, notfinite;
+  // bb: (b,b)_W    rr: (r,r)_W of the last true residual    rr0: (b,b), the inner tolerance's reference    tol2: the inner tolerance
+  // (Givens estimate)    tolw2: the weighted one (acceptance)    notfinite: set with done = 2 when a norm was NaN or Inf
+};
+// done: 0 the cycle runs; 1 converged; 2 stopped, unconverged (singular, or not finite); 3 the cycle has ended, no verdict yet
+constexpr double GM_RUNS = 0.0, GM_CONVERGED = 1.0, GM_STOPPED = 2.0, GM_CYCLE_ENDED = 3.0;
+
+// start of a restart cycle (and verdict on the one before): gm[h2(0)] = (r,r), gm[h2(1)] = (r,r)_W of the TRUE residual.
+// Inner tolerance from the first residual (zero initial guess: ||r0|| = ||b||), lowered when the estimate was met and the weighted
+// test was not; acceptance on the weighted norm.  A norm that is not finite stops the solve: never converged.
+PGHOST_HD inline void gm_begin(GmLayout L, GmSlots S, double* gm, double* sc, int first) {
+  const double rr = gm[L.h2(0)], rrw = gm[L.h2(1)];
+  if (first) {
+    sc[S.bb] = rrw;
+    sc[S.rr0] = rr;
+    sc[S.iters] = 0.0;
+    const double t2 = sc[S.reltol2] * rr;
+    sc[S.tol2] = t2 > sc[S.abstol2] ? t2 : sc[S.abstol2];
+    const double tw = sc[S.reltol2] * rrw;
+    sc[S.tolw2] = tw > sc[S.abstol2] ? tw : sc[S.abstol2];
+  }
+  sc[S.rr] = rrw;
+  const bool finite = bl_finite(rr) && bl_finite(rrw);
+  const double beta = finite && rr > 0.0 ? sqrt(rr) : 0.0;
+  for (int i = 0; i <= L.m; ++i) gm[L.g(i)] = 0.0;
+  gm[L.g(0)] = beta;
+  gm[L.J()] = 0.0;
+  gm[L.invn()] = beta > 0.0 ? 1.0 / beta : 0.0;
+  if (!finite) {
+    sc[S.done] = GM_STOPPED;
+    sc[S.notfinite] = 1.0;
+    return;
+  }
+  if (sc[S.done] == GM_STOPPED) return;   // singular (gm_hess): stays
+  const bool ok = rrw <= sc[S.tolw2] || beta == 0.0;
+  sc[S.done] = ok ? GM_CONVERGED : GM_RUNS;
+  if (!ok && !first && rrw > 0.0) {
+    // the estimate may already be below the inner tolerance: aim the next cycle at the weighted test
+    const double aim = 0.25 * rr * (sc[S.tolw2] / rrw);
+    if (aim < sc[S.tol2]) sc[S.tol2] = aim;
+  }
+}
+
+// column j of the Hessenberg matrix: h = h1 + h2 (CGS2), previous rotations, new rotation, residual estimate
+PGHOST_HD inline void gm_hess(GmLayout L, GmSlots S, int j, double* gm, double* sc) {
+  if (sc[S.done] != GM_RUNS) return;
+  const double nn = gm[L.h2(j + 1)];
+  bool finite = bl_finite(nn);
+  for (int i = 0; i <= j; ++i) {
+    gm[L.H(i, j)] = gm[L.h1(i)] + gm[L.h2(i)];
+    finite = finite && bl_finite(gm[L.H(i, j)]);
+  }
+  const double hn = nn > 0.0 ? sqrt(nn) : 0.0;
+  gm[L.H(j + 1, j)] = hn;
+  sc[S.iters] += 1.0;
+  if (!finite) {   // keep the previous columns only; the caller does not hand the state back
+    gm[L.J()] = (double)j;
+    sc[S.done] = GM_STOPPED;
+    sc[S.notfinite] = 1.0;
+    return;
+  }
+  for (int i = 0; i < j; ++i) {
+    const double c = gm[L.cs(i)], s = gm[L.sn(i)];
+    const double a = gm[L.H(i, j)], b = gm[L.H(i + 1, j)];
+    gm[L.H(i, j)] = c * a + s * b;
+    gm[L.H(i + 1, j)] = -s * a + c * b;
+  }
+  const double a = gm[L.H(j, j)];
+  const double d = hypot(a, hn);
+  gm[L.J()] = (double)(j + 1);
+  if (d == 0.0) {   // A v_j = 0: singular system; keep the previous columns only
+    gm[L.J()] = (double)j;
+    sc[S.done] = GM_STOPPED;
+    return;
+  }
+  const double c = a / d, s = hn / d;
+  gm[L.cs(j)] = c;
+  gm[L.sn(j)] = s;
+  gm[L.H(j, j)] = d;
+  gm[L.H(j + 1, j)] = 0.0;
+  const double gj = gm[L.g(j)];
+  gm[L.g(j)] = c * gj;
+  gm[L.g(j + 1)] = -s * gj;
+  const double rr = gm[L.g(j + 1)] * gm[L.g(j + 1)];
+  gm[L.invn()] = hn > 0.0 ? 1.0 / hn : 0.0;
+  // the cycle ends here (not a verdict -- the true weighted residual at the restart decides, gm_begin);
+  // hn == 0: the Krylov space is exhausted (exact solution)
+  if (rr <= sc[S.tol2] || hn == 0.0) sc[S.done] = GM_CYCLE_ENDED;
+}
+
+// y = H(0:J,0:J)^-1 g(0:J)   (back substitution on the rotated, upper-triangular H)
+PGHOST_HD inline void gm_solve_y(GmLayout L, double* gm) {
+  const int J = (int)gm[L.J()];
+  for (int i = J - 1; i >= 0; --i) {
+    double s = gm[L.g(i)];
+    for (int k = i + 1; k < J; ++k) s -= gm[L.H(i, k)] * gm[L.y(k)];
+    gm[L.y(i)] = s / gm[L.H(i, i)];
+  }
 }
 
 // ---- schedule of the mixed-precision Horner chain (pg_krylov.hip) ------------------------------------------
