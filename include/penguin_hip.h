@@ -39,6 +39,7 @@ typedef struct pg_streamvort pg_streamvort; /* Penguin.StreamVorticity{2} src/so
 /* ---- enums --------------------------------------------------------------------------- */
 enum { PG_BODY_BALL = 1, PG_BODY_MULTIBALL = 2, PG_BODY_HALFSPACE = 3, PG_BODY_ELLIPSOID = 4, PG_BODY_PLANE = 5 }; /* closed-form level sets evaluated in-kernel */
 enum { PG_BODY_PROGRAM = 6 };                     /* a traced level set: pg_capacity_create_program */
+enum { PG_BODY_POLYGON = 7 };                     /* a closed polygon of markers: pg_capacity_create_polygon */
 enum { PG_FLAG_COMPLEMENT = 1, PG_FLAG_NO_CENTROIDS = 2 };
 /* capacity fields for pg_capacity_get (d = dimension for A,B,W,C_omega,C_gamma) */
 enum { PG_CAP_V = 0, PG_CAP_GAMMA = 1, PG_CAP_CELL_TYPES = 2, PG_CAP_A = 3, PG_CAP_B = 4,
@@ -586,6 +587,19 @@ int32_t pg_debug_program_eval(const pg_program* prog, int64_t npts, const double
    host threads are serialised by a mutex inside, each holding it until its last kernel has run. */
 int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */, int32_t flags,
                                    pg_capacity** out);
+/* Capacity(front::FrontTracker, mesh) (PG_BODY_POLYGON): a simple closed polygon of M >= 3 markers in 2-D, xy = x0 y0 x1 y1 ...;
+   fluid is the interior (the reference's get_fluid_polygon), PG_FLAG_COMPLEMENT: the exterior, PG_FLAG_NO_CENTROIDS as for the
+   other kinds.  A closing duplicate of the first marker is dropped and the orientation is normalised to counter-clockwise.  The
+   kernels of pg_capacity_create_levelset run with the polygon itself as the body (csrc/pg_geom_polygon.h states the crossing,
+   touching and half-open rules): no transcendental, every capacity a finite sum of polynomial terms, a
+   corner inside a cell exact.  An edge lookup (the edges of every column, row and cell, ascending) is built on the device
+   first; its time is entry 5 of pg_capacity_polygon_ms_parts, outside the five of pg_capacity_kernel_ms_parts.  Results are
+   bitwise repeatable.  Refused before anything is allocated, each with its own message: a mesh that is not 2-D; more than one
+   rank or a communicator; M < 3; a non-finite coordinate; a zero-length edge; zero signed area; a polygon that intersects
+   itself (an O(M^2) test on the host).  *out is NULL after a refusal. */
+int32_t pg_capacity_create_polygon(pg_mesh* m, const double* xy /* 2 M */, int64_t M, int32_t flags, pg_capacity** out);
+/* the five kernel times of pg_capacity_kernel_ms_parts and, in ms[5], the time of the edge lookup (count, scan, fill, order) */
+int32_t pg_capacity_polygon_ms_parts(const pg_capacity* c, double* ms /* 6 */);
 /* Capacity(body, SpaceTimeMesh(mesh, [t0, t1])) of an ARBITRARY moving level set phi(x_1 .. x_N, t) (t: PG_OP_VAR 3): phi, the N
    programs of d phi / d x_d and the program of d phi / dt; fluid where phi <= 0, flags as pg_capacity_create_program.  The
    space-time kernels of pg_capacity_create_spacetime run with "the body at time node k" = phi(., tau_k) measured by the

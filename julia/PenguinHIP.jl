@@ -13,6 +13,7 @@ module PenguinHIP
 
 using SparseArrays, StaticArrays, LinearAlgebra, Libdl
 
+export FrontTracker, get_markers, set_markers!, add_marker!, create_circle!, create_ellipse!, create_crystal!, is_point_inside, sdf
 export Mesh, nC, Capacity, capacity_from_arrays, Sphere, MultiSphere, HalfSpace, Ellipsoid, Plane, plane_through, DiffusionOps, Phase,
        Dirichlet, Neumann, Robin, Periodic, ScalarJump, FluxJump, BorderConditions, InterfaceConditions, Solver,
        DiffusionUnsteadyMono, solve_DiffusionUnsteadyMono!, DiffusionUnsteadyDiph, solve_DiffusionUnsteadyDiph!,
@@ -729,6 +730,88 @@ function Capacity(body::DeviceFunction, mesh::Mesh{N}; method::String="VOFI", co
     check(ccall((:pg_capacity_create_program, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
                 mesh.handle, phi, grad, flags, h))
     _wrap_capacity(h[], mesh, body, compute_centroids)
+end
+# ---- FrontTracker (src/front_tracking.jl:5-266): a closed polyline of markers whose interior is the fluid.  Capacity(front, mesh)
+# sends the markers to pg_capacity_create_polygon; the capacity kernels measure the polygon itself (csrc/pg_geom_polygon.h).
+mutable struct FrontTracker <: Function      # (callable as its signed distance, negative inside: cap.body behaves like the other bodies)
+    markers::Vector{Tuple{Float64, Float64}}
+    is_closed::Bool
+end
+function _polygon(ft::FrontTracker)
+    p = ft.markers
+    length(p) >= 2 && p[1] == p[end] ? p[1:end-1] : p
+end
+"even-odd with the kernels' crossing rule: (p_y <= y) != (q_y <= y), the crossing at or left of x"
+function is_point_inside(ft::FrontTracker, x::Real, y::Real)
+    p = _polygon(ft)
+    M = length(p)
+    M < 3 && return false
+    below = 0
+    for k in 1:M
+        (px, py), (qx, qy) = p[k], p[mod1(k + 1, M)]
+        (py <= y) != (qy <= y) || continue
+        c = clamp(px + (y - py) * (qx - px) / (qy - py), min(px, qx), max(px, qx))
+        c <= x && (below += 1)
+    end
+    isodd(below)
+end
+function sdf(ft::FrontTracker, x::Real, y::Real)
+    p = _polygon(ft)
+    M = length(p)
+    M < 3 && return Inf
+    dist = Inf
+    for k in 1:(ft.is_closed ? M : M - 1)
+        (px, py), (qx, qy) = p[k], p[mod1(k + 1, M)]
+        ex, ey = qx - px, qy - py
+        ee = ex * ex + ey * ey
+        t = ee > 0 ? clamp(((x - px) * ex + (y - py) * ey) / ee, 0.0, 1.0) : 0.0
+        dist = min(dist, hypot(x - (px + t * ex), y - (py + t * ey)))
+    end
+    is_point_inside(ft, x, y) ? -dist : dist
+end
+(ft::FrontTracker)(x, y, _...) = sdf(ft, x, y)
+FrontTracker() = FrontTracker(Tuple{Float64, Float64}[], true)
+FrontTracker(markers::AbstractVector) = FrontTracker(convert(Vector{Tuple{Float64, Float64}}, markers), true)
+get_markers(ft::FrontTracker) = ft.markers
+function set_markers!(ft::FrontTracker, markers::AbstractVector, is_closed = nothing)
+    ft.markers = convert(Vector{Tuple{Float64, Float64}}, markers)
+    is_closed === nothing || (ft.is_closed = is_closed)
+    ft
+end
+add_marker!(ft::FrontTracker, x::Real, y::Real) = (push!(ft.markers, (Float64(x), Float64(y))); ft)
+function create_circle!(ft::FrontTracker, center_x::Real, center_y::Real, radius::Real, n_markers::Integer = 100)
+    set_markers!(ft, [(center_x + radius * cos(2.0 * π * (i / n_markers)), center_y + radius * sin(2.0 * π * (i / n_markers)))
+                      for i in 0:n_markers-1], true)
+end
+function create_ellipse!(ft::FrontTracker, center_x::Real, center_y::Real, radius_x::Real, radius_y::Real, n_markers::Integer = 100)
+    theta = range(0, 2π, length = n_markers + 1)[1:end-1]
+    set_markers!(ft, [(center_x + radius_x * cos(t), center_y + radius_y * sin(t)) for t in theta], true)
+end
+function create_crystal!(ft::FrontTracker, center_x::Real, center_y::Real, base_radius::Real, n_lobes::Integer = 6,
+                         amplitude::Real = 0.2, n_markers::Integer = 100)
+    markers = Vector{Tuple{Float64, Float64}}(undef, n_markers + 1)
+    for i in 1:n_markers
+        θ = 2.0 * π * (i - 1) / n_markers
+        r = base_radius * (1.0 + amplitude * cos(n_lobes * θ))
+        markers[i] = (center_x + r * cos(θ), center_y + r * sin(θ))
+    end
+    markers[n_markers + 1] = markers[1]
+    set_markers!(ft, markers, true)
+end
+function Capacity(front::FrontTracker, mesh::Mesh{N}; method::String="VOFI", compute_centroids::Bool=true, complement::Bool=false) where N
+    front.is_closed || error("PenguinHIP.Capacity(FrontTracker): is_closed=false is not supported (the reference substitutes the " *
+                             "convex hull of the markers for an open front; close the front or pass the hull's markers)")
+    pts = front.markers
+    length(pts) >= 2 && pts[1] == pts[end] && (pts = pts[1:end-1])
+    length(pts) >= 3 || error("PenguinHIP.Capacity(FrontTracker): a polygon needs at least 3 markers (got $(length(pts)))")
+    N == 2 || error("PenguinHIP.Capacity(FrontTracker): a marker polygon is a 2-D body, the mesh is $(N)-D")
+    init()
+    xy = Float64[p[k] for p in pts for k in 1:2]              # x0 y0 x1 y1 ...
+    flags = Int32((complement ? 1 : 0) | (compute_centroids ? 0 : 2))
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pg_capacity_create_polygon, libpg), Int32, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Ptr{Ptr{Cvoid}}),
+                mesh.handle, xy, length(pts), flags, h))
+    _wrap_capacity(h[], mesh, front, compute_centroids)
 end
 # times: 2 x nrows, times[1, q] = step q's "t", times[2, q] = its "t + Δt" (column-major: the C layout nrows x 2)
 function set_program!(s::Solver, which::Integer, phase::Integer, df::DeviceFunction, times::Matrix{Float64}; nspace::Integer = 3)

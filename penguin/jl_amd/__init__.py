@@ -18,6 +18,10 @@ from .api import (  # noqa: F401
     InterfaceFlux, Monitor, Probe, VolumeIntegral,
     DeviceFunction, dev,
 )
+from .front import (  # noqa: F401,E402
+    FrontTracker, add_marker_b, create_circle_b, create_crystal_b, create_ellipse_b, create_rectangle_b, get_markers,
+    is_point_inside, sdf, set_markers_b,
+)
 from .utils import (  # noqa: F401,E402
     cfl_restriction, initialize_poiseuille_velocity_field, initialize_radial_velocity_field,
     initialize_rotating_velocity_field, initialize_temperature_circle_b, initialize_temperature_function_b,

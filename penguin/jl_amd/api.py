@@ -24,6 +24,7 @@ from . import _lib as L
 from ._lib import PenguinHipError
 from . import devfn as dev  # noqa: F401
 from .devfn import DeviceFunction, pg_program
+from .front import FrontTracker
 
 Number = Union[int, float]
 
@@ -223,6 +224,20 @@ class Ellipsoid:
 Ellipse = Ellipsoid
 
 
+def check_front_body(front: FrontTracker, mesh) -> None:
+    """what Capacity(front, mesh) refuses before it touches the device"""
+    if not hasattr(mesh, "_h"):
+        raise PenguinHipError("Capacity(FrontTracker, SpaceTimeMesh): space-time capacities of a moving front "
+                              "(compute_spacetime_capacities) are not supported; pass the spatial Mesh")
+    if not front.is_closed:
+        raise PenguinHipError("Capacity(FrontTracker): is_closed=False is not supported (the reference substitutes the convex hull "
+                              "of the markers for an open front; close the front or pass the hull's markers)")
+    if len(front.polygon()) < 3:
+        raise PenguinHipError(f"Capacity(FrontTracker): a polygon needs at least 3 markers (got {len(front.polygon())})")
+    if mesh.N != 2:
+        raise PenguinHipError(f"Capacity(FrontTracker): a marker polygon is a 2-D body, the mesh is {mesh.N}-D")
+
+
 class Capacity:
     """Capacity(body, mesh; method="VOFI", compute_centroids=true) -- src/capacity.jl:51-123.
 
@@ -231,11 +246,16 @@ class Capacity:
     from the GPU on first access.  `body` is a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace / Plane) or, in 1-D
     and 2-D, any level set wrapped in DeviceFunction: `Capacity(DeviceFunction(lambda x, y: ...), mesh)` traces the closure and
     its derivatives and evaluates them inside the capacity kernels (fluid where it is <= 0; `complement=True`: where it is
-    >= 0, the other phase; `cap.body` stays callable as the closure, negated for the complement).  A plain callable needs DeviceFunction or precomputed arrays: Capacity.from_arrays(...)."""
+    >= 0, the other phase; `cap.body` stays callable as the closure, negated for the complement).  A plain callable needs DeviceFunction or precomputed arrays: Capacity.from_arrays(...).
+    `Capacity(front, mesh)` with a FrontTracker (2-D): the closed polygon of its markers, interior fluid, measured by the same
+    kernels (src/capacity.jl:472-598); `complement=True`: the exterior."""
 
     def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True, complement: bool = False):
         if method not in ("VOFI", "ImplicitIntegration"):
             raise ValueError('method must be "VOFI" or "ImplicitIntegration"')
+        if isinstance(body, FrontTracker):
+            self._init_front(body, mesh, compute_centroids, complement)
+            return
         if complement:
             # the keyword of the Julia twin: the other phase of a DeviceFunction body (tagged bodies carry their own flag)
             if not isinstance(body, DeviceFunction):
@@ -272,6 +292,21 @@ class Capacity:
         L.check(L.lib().pg_capacity_create_levelset(mesh._h, C.c_int32(kind), L.dptr(params), C.c_int32(len(params)),
                                                     C.c_int32(flags), C.byref(self._h)))
         self._cache: Dict = {}
+
+    def _init_front(self, front: FrontTracker, mesh: Mesh, compute_centroids: bool, complement: bool):
+        """Capacity(front::FrontTracker, mesh) -- src/capacity.jl:472-598: the polygon of the markers is the body, its interior
+        the fluid (complement=True: the exterior); cap.body is the front, callable as its signed distance"""
+        check_front_body(front, mesh)
+        L.init()
+        self.mesh, self.body, self.compute_centroids = mesh, front, compute_centroids
+        self.complement = bool(complement)
+        xy = np.ascontiguousarray(front.polygon().reshape(-1), dtype=np.float64)
+        self._h = C.c_void_p()
+        L.check(L.lib().pg_capacity_create_polygon(mesh._h, L.dptr(xy), C.c_int64(len(xy) // 2),
+                                                   C.c_int32((0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
+                                                             | (L.PG_FLAG_COMPLEMENT if complement else 0)),
+                                                   C.byref(self._h)))
+        self._cache = {}
 
     @classmethod
     def from_arrays(cls, mesh: Mesh, V, A, B, W, Gamma, C_omega, C_gamma, cell_types, body=None):
@@ -375,6 +410,13 @@ class Capacity:
         ms = (C.c_double * 5)()
         L.check(L.lib().pg_capacity_kernel_ms_parts(self._h, ms))
         return dict(zip(("classify", "cut_cells", "sections", "stagger", "stagger_cut"), (float(v) for v in ms)))
+
+    @property
+    def polygon_ms_parts(self) -> Dict[str, float]:
+        """a FrontTracker capacity: the five kernel times and the time of the edge lookup (`binning`), each between its own events"""
+        ms = (C.c_double * 6)()
+        L.check(L.lib().pg_capacity_polygon_ms_parts(self._h, ms))
+        return dict(zip(("classify", "cut_cells", "sections", "stagger", "stagger_cut", "binning"), (float(v) for v in ms)))
 
     def __del__(self):
         try:

@@ -16,6 +16,7 @@ struct pg_capacity {
   double kernel_ms = 0.0;
   double kernel_ms_parts[5] = {0, 0, 0, 0, 0};   // k_classify, k_cut_cells, k_sections, k_stagger, k_stagger_cut (0: not launched)
   pg::i64 n_cut_local = 0;
+  double poly_bin_ms = 0.0;                      // polygon bodies: the edge lookup (count, scan, fill, order), outside the five
   // space-time capacity of ONE time slab [t0, t1] (pg_spacetime.hip): V, A, B, W, Γ above are the time-integrated
   // measures of the first time layer of the reference's (N+1)-D capacity; Vt = A_(N+1) at the two time faces
   // (V(t0), V(t1)), Ctw / Ctg = the time components of the space-time centroids C_ω / C_γ

@@ -13,6 +13,8 @@
 // cell.  Compiled with -ffp-contract=off: classification must match the oracle bit for bit.
 #include "pg_capacity.h"
 #include "pg_geom_program.h"
+#include "pg_geom_polygon.h"
+#include "pg_scan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -68,9 +70,12 @@ __device__ inline void cell_box(const GeoView& g, const i64* idx, double* lo, do
 
 // The kernels below reach the body through pick_ball, box_measure and section_measure only, and are templates over the kernel
 // argument the body travels in: BallArg for the closed-form kinds (a BallSet by value, the code the project always had) and
-// ProgArg for a traced level set (pg_geom_program.h).
+// ProgArg for a traced level set (pg_geom_program.h), PolyArg for a marker polygon (pg_geom_polygon.h).  LISTS_TOUCHING: a cell
+// that is not CUT may still own a piece of the front (an edge along its lower or left face); only PolyArg has such cells, and
+// for the other kinds the constant folds the branches away: they compile to the code they always compiled to.
 struct BallArg : BallSet {
   static constexpr int MAX_BLOCK = 1024;        // (HIP's default: the closed-form instantiations compile as they always did)
+  static constexpr bool LISTS_TOUCHING = false;
 };
 __device__ __forceinline__ const BallSet& kernel_body(const BallArg& a) { return a; }
 
@@ -83,6 +88,7 @@ constexpr int PROG_BLOCK = 256;
 
 struct ProgArg {
   static constexpr int MAX_BLOCK = PROG_BLOCK;
+  static constexpr bool LISTS_TOUCHING = false;
   int N;
   double sgn;
 };
@@ -108,6 +114,43 @@ __device__ __forceinline__ ProgBody<DevEval> kernel_body(const ProgArg& a) {
   return ProgBody<DevEval>{a.N, 0, a.sgn, DevEval{stack + threadIdx.x}};
 }
 
+// A marker polygon: the body is the struct itself (markers, mesh nodes and the edge lookup, all in device memory).
+struct PolyArg : PolyBody {
+  static constexpr int MAX_BLOCK = 256;
+  static constexpr bool LISTS_TOUCHING = true;
+};
+__device__ __forceinline__ const PolyBody& kernel_body(const PolyArg& a) { return a; }
+
+// ---- the edge lookup of a polygon (pg_geom_polygon.h): count, scan (pg_scan.h), fill, order.  One thread per edge walks its
+// bins (poly_edge_bins: at most 2 (n0 + n1) + 3 n0 + n1 visits, whatever the markers are; an edge outside the mesh visits none);
+// the integer atomics fix only WHERE in its bin an edge lands, and k_poly_order then puts every bin in ascending edge order,
+// so the lists, and every sum taken along them, are the same in every run.
+__global__ void k_poly_count(PolyBody b, int* __restrict__ count) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= b.M) return;
+  poly_edge_bins(b, k, [&](int bin) { atomicAdd(&count[bin], 1); });
+}
+__global__ void k_poly_fill(PolyBody b, const int* __restrict__ ptr, int* __restrict__ cursor, int* __restrict__ tmp_edge,
+                            int* __restrict__ tmp_bin) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= b.M) return;
+  poly_edge_bins(b, k, [&](int bin) {
+    const int pos = ptr[bin] + atomicAdd(&cursor[bin], 1);
+    tmp_edge[pos] = k;
+    tmp_bin[pos] = bin;
+  });
+}
+// entry e of bin b goes to the place its rank among the bin's edge ids gives it (an edge is in a bin once: the ranks differ)
+__global__ void k_poly_order(const int* __restrict__ ptr, const int* __restrict__ tmp_edge, const int* __restrict__ tmp_bin, int total,
+                             int* __restrict__ idx) {
+  for (i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x; e < total; e += (i64)gridDim.x * blockDim.x) {
+    const int bin = tmp_bin[e], id = tmp_edge[e];
+    int rank = 0;
+    for (int q = ptr[bin]; q < ptr[bin + 1]; ++q) rank += tmp_edge[q] < id ? 1 : 0;
+    idx[ptr[bin] + rank] = id;
+  }
+}
+
 // K1 (cheap part): classify every stored cell; full/empty cells are finished here.
 template <class BodyArg>
 __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_classify(GeoView g, BodyArg ba, i64 Mloc, double* V, double* G, double* ct,
@@ -125,11 +168,16 @@ __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_classify(GeoView g, Body
       double lo[3], hi[3];
       cell_box(g, idx, lo, hi);
       int type;
-      pick_ball(bs, lo, hi, type);
+      bool listed;
+      if constexpr (BodyArg::LISTS_TOUCHING) listed = pick_ball(bs, lo, hi, type) != 0 || type == PG_CUT;
+      else {
+        pick_ball(bs, lo, hi, type);
+        listed = type == PG_CUT;
+      }
       if (type != PG_CUT && bs.complement) type = 1 - type;
       for (int d = 0; d < g.N; ++d) cw[d] = 0.5 * (lo[d] + hi[d]);
       if (type == PG_FULL) v = full_measure(g, -1);
-      if (type == PG_CUT) {
+      if (listed) {
         const int slot = atomicAdd(cut_count, 1);
         cut_list[slot] = (int)lc;
       }
@@ -192,6 +240,14 @@ __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_cut_cells(GeoView g, Bod
   cell_box(g, idx, lo, hi);
   const BoxMeasure m = box_measure(bs, lo, hi, true, c_gl, ql, LANES, LaneGroup<LANES>());
   if (!live || ql != 0) return;
+  if constexpr (BodyArg::LISTS_TOUCHING) {
+    if (m.type != PG_CUT) {           // listed for the piece of the front it owns: its type, volume and centroid stand
+      G[lc] = m.gamma;
+      for (int d = 0; d < g.N; ++d)
+        if (Cg[d]) Cg[d][lc] = m.cg[d];
+      return;
+    }
+  }
   V[lc] = m.vol;
   G[lc] = m.gamma;
   for (int d = 0; d < g.N; ++d) {
@@ -1097,6 +1153,85 @@ int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_p
   pa.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
   run_static_kernels<CUT_LANES>(c, m, pa, cx.stream);
   *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_capacity_create_polygon(pg_mesh* m, const double* xy, int64_t M, int32_t flags, pg_capacity** out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(m && out, "pg_capacity_create_polygon: NULL argument");
+  *out = nullptr;
+  Context& cx = ctx();
+  PG_REQUIRE(m->N == 2, "pg_capacity_create_polygon: a marker polygon is a 2-D body, the mesh is " + std::to_string(m->N) + "-D");
+  PG_REQUIRE(cx.nranks == 1 && !cx.comm, "pg_capacity_create_polygon: single rank only (polygon bodies on slabs are not supported yet)");
+  M = polygon_open_count(xy, M);
+  {
+    std::string why;
+    PG_REQUIRE(polygon_body_check(xy, M, &why), "pg_capacity_create_polygon refused: " + why);
+  }
+  PG_REQUIRE(m->n[0] < (i64)1 << 30 && m->n[1] < (i64)1 << 30 && m->n[0] + m->n[1] + m->n[0] * m->n[1] < (i64)2147483647 - 1,
+             "pg_capacity_create_polygon: the edge lookup exceeds 2^31 bins");
+  const std::vector<double> ccw = polygon_normalise(xy, M);
+  auto* c = new pg_capacity();
+  std::unique_ptr<pg_capacity> guard(c);
+  c->mesh = m;
+  c->N = 2;
+  c->from_body = true;
+  c->has_cg = !(flags & PG_FLAG_NO_CENTROIDS);
+  std::memset(&c->body, 0, sizeof(c->body));     // (not a BallSet: nothing reads it)
+  c->slab = m->base_slab();
+  ensure_gl();
+  hipStream_t st = cx.stream;
+  const GeoView g = geo_view(m, c->slab);
+  DevBuf<double> dxy(2 * M);
+  dxy.upload(ccw.data(), 2 * M);
+  PolyArg pa;
+  pa.N = 2;
+  pa.complement = 0;
+  pa.flip = (flags & PG_FLAG_COMPLEMENT) ? 1 : 0;
+  pa.M = (int)M;
+  pa.xy = dxy.p;
+  for (int d = 0; d < 2; ++d) { pa.n[d] = (int)m->n[d]; pa.nodes[d] = g.nodes[d]; }
+  pa.ptr = nullptr;
+  pa.idx = nullptr;
+  // ---- the edge lookup: count, scan, fill, order
+  const i64 nbins = m->n[0] + m->n[1] + m->n[0] * m->n[1];
+  DevBuf<int> count(nbins + 1), ptr(nbins + 1), cursor(nbins), d_total(1);
+  count.zero();
+  cursor.zero();
+  EventPair bin_ev;
+  PG_HIP(hipEventRecord(bin_ev.e0, st));
+  const dim3 per_edge((unsigned)((M + 255) / 256));
+  hipLaunchKernelGGL(k_poly_count, per_edge, dim3(256), 0, st, static_cast<const PolyBody&>(pa), count.p);
+  PG_HIP(hipGetLastError());
+  scan_exclusive<int>(count.p, ptr.p, nbins + 1, d_total.p, st);          // ptr[nbins] = the total
+  int total = 0;
+  d_total.download(&total, 1);
+  PG_REQUIRE(total >= 0, "pg_capacity_create_polygon: the edge lookup exceeds 2^31 entries");
+  DevBuf<int> tmp_edge(total > 0 ? total : 1), tmp_bin(total > 0 ? total : 1), idx(total > 0 ? total : 1);
+  idx.zero();
+  if (total > 0) {                               // (a polygon wholly outside the mesh: no list, nothing to launch)
+    hipLaunchKernelGGL(k_poly_fill, per_edge, dim3(256), 0, st, static_cast<const PolyBody&>(pa), ptr.p, cursor.p, tmp_edge.p, tmp_bin.p);
+    PG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_poly_order, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, st, ptr.p, tmp_edge.p, tmp_bin.p, total, idx.p);
+    PG_HIP(hipGetLastError());
+  }
+  PG_HIP(hipEventRecord(bin_ev.e1, st));
+  pa.ptr = ptr.p;
+  pa.idx = idx.p;
+  run_static_kernels<CUT_LANES>(c, m, pa, st);   // (waits for its last kernel: the lists above outlive every launch)
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, bin_ev.e0, bin_ev.e1));
+  c->poly_bin_ms = ms;
+  *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_capacity_polygon_ms_parts(const pg_capacity* c, double* ms) {
+  PG_API_BEGIN
+  PG_REQUIRE(c && ms, "pg_capacity_polygon_ms_parts: NULL argument");
+  for (int k = 0; k < 5; ++k) ms[k] = c->kernel_ms_parts[k];
+  ms[5] = c->poly_bin_ms;
   PG_API_END
 }
 

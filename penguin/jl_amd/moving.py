@@ -129,6 +129,8 @@ class SpaceTimeCapacity(api.Capacity):
 
     def __init__(self, body, mesh: SpaceTimeMesh, method: str = "VOFI", compute_centroids: bool = True,
                  time_panels: int = 16, time_order: int = 4, complement: bool = False):
+        if isinstance(body, api.FrontTracker):
+            api.check_front_body(body, mesh)
         if complement:
             if not isinstance(body, DeviceFunction):
                 raise PenguinHipError("Capacity(complement=True) is for DeviceFunction bodies; tagged bodies take complement=True themselves")
