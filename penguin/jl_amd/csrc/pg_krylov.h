@@ -34,29 +34,6 @@ struct KrylovWork {
   int fail_deg = 0, good_deg = 0;       // log of start residual / tolerance it fell short at) and the last that sufficed
   double fail_L = 0.0;
   int fail_wait = 0, fail_backoff = 1;  // solves left before that degree may be tried again; doubles when it falls short again
-  // set by the caller around one krylov_solve: the system is a compact image of the caller's (pg_reduce.hip, DiagElim) and
-  // x is the caller's FULL vector -- the updates x += α M⁻¹p, x += ω M⁻¹s land at x[scatter[i]].  Needs the polynomial path.
-  const int* scatter = nullptr;
-  // set by the caller around one krylov_solve with opts.precond = PG_PRECOND_MG: the multigrid hierarchy of THIS matrix (the
-  // caller has checked that the system admits it, pg_solver.hip mg_prepare).  Reset by krylov_solve.
-  MgHierarchy* mg = nullptr;
-  // set by the caller of a compact solve whose start was extrapolated from older states (pg_solver.hip, GuessArgs) and who left
-  // the extrapolated state unformed: the FIRST update of x then writes  x[map] = z_g[map] + α M⁻¹p,  z_g = zbase + Σ c_j (zr[o_j] -
-  // zbase)  (coef: [0..3] c_j, [4] how many, [5..8] which of zr), instead of adding to x.  Reset by krylov_solve.
-  XGuess xguess;
-  // set by the caller of a prepared start that wrote r̂ only: p = r = r̂ at the start, so the first iteration reads r̂
-  // wherever it needs p or r (k_bicg_s writes r = s, k_bicg_xrp writes p, as always) and the start kernel writes two
-  // vectors less.  Reset by krylov_solve.
-  bool p_in_rhat = false;
-  // set by the caller whose start kernel has already reset the scalars, summed the start sums and derived PH_INIT
-  // (k_rhs_init_c with a ticket): krylov_solve launches no start kernel.  Reset by krylov_solve.
-  bool start_folded = false;
-  // set by the caller of a prepared start on SEVERAL ranks that has not looked at the rows alone on their diagonal (a compact
-  // step with unchanged data, pg_solver.hip): *moved_flag == moved_stamp says that one of them moved on this rank all the
-  // same.  The verdict rides as a fourth slot in the start phase's all-reduce and every rank finds the same S_MOVED in the
-  // scalars of the solve.  Reset by krylov_solve.
-  const int* moved_flag = nullptr;
-  int moved_stamp = 0;
   // polynomial right preconditioner (pg_krylov.hip), n_vec each, on first use: ya = M⁻¹p, yb = M⁻¹s of the running
   // iteration (the updates of x read them) and the two work vectors the Horner chain alternates between
   DevBuf<double> ya, yb, wa, wb;
@@ -82,14 +59,49 @@ struct KrylovWork {
   DevBuf<double> id_vecs, id, id_partials;
   int id_s = -1;
   i64 id_stride = 0;
-  // Set by the caller around one krylov_solve: work to queue right AFTER the first batch of iterations and the copy of the
-  // scalars, BEFORE the host waits for that copy -- the next time step's first product, speculatively: the device then
-  // has something to run while the host wakes up, reads the scalars and queues the next step (the wait is on an event
-  // recorded behind the copy, not on the stream).  Called at most once per solve; reset by krylov_solve.
-  std::function<void()> after_first_batch;
+  // the event recorded behind the first poll's copy of the scalars when the call carries KrylovCall::after_first_batch
   hipEvent_t ev_poll = nullptr;
   void init(i64 n_own, i64 n_vec);
   ~KrylovWork();
+};
+
+// What ONE krylov_solve is asked to do, beyond the system, the options and the workspace: a value the caller builds next to the
+// solve that uses it.  krylov_solve reads it and never writes it; nothing of it outlives the solve.  Everything below `preinit`
+// belongs to a prepared start of the BiCGStab loop and is refused, not dropped, on any other solve.
+struct KrylovCall {
+  // x0 == nullptr: zero initial guess; else start from x0 with Ax0 = A*x0 given (BiCGStab and IDR(s) only).  x0 may be x itself
+  // (the iteration continues from the iterate x holds).
+  const double* x0 = nullptr;
+  const double* Ax0 = nullptr;
+  // (BiCGStab only) the caller has already written x, w.r = w.rhat = w.p = r0 and the partial sums of (r0,r0) / (b,b) in slots
+  // 0 / 1 of w.partials with a w.grid-block launch (pg_solver.hip fuses that with the right-hand side).
+  bool preinit = false;
+  // a prepared start that wrote r̂ only: p = r = r̂ at the start, so the first iteration reads r̂ wherever it needs p or r
+  // (k_bicg_s writes r = s, k_bicg_xrp writes p, as always) and the start kernel writes two vectors less.
+  bool p_in_rhat = false;
+  // the caller's start kernel has already reset the scalars, summed the start sums and derived PH_INIT (k_rhs_init_c with a
+  // ticket): krylov_solve launches no start kernel.
+  bool start_folded = false;
+  // the system is a compact image of the caller's (pg_reduce.hip, DiagElim) and x is the caller's FULL vector -- the updates
+  // x += α M⁻¹p, x += ω M⁻¹s land at x[scatter[i]].  Needs the polynomial path.
+  const int* scatter = nullptr;
+  // with opts.precond = PG_PRECOND_MG and its kin: the multigrid hierarchy of THIS matrix (the caller has checked that the
+  // system admits it, pg_solver.hip mg_prepare); refused without such a precond.
+  MgHierarchy* mg = nullptr;
+  // a compact solve whose start was extrapolated from older states (pg_solver.hip, GuessArgs) and whose caller left the
+  // extrapolated state unformed: the FIRST update of x then writes  x[map] = z_g[map] + α M⁻¹p,  z_g = zbase + Σ c_j (zr[o_j] -
+  // zbase)  (coef: [0..3] c_j, [4] how many, [5..8] which of zr), instead of adding to x.
+  XGuess xguess;
+  // a prepared start on SEVERAL ranks that has not looked at the rows alone on their diagonal (a compact step with unchanged
+  // data, pg_solver.hip): *moved_flag == moved_stamp says that one of them moved on this rank all the same.  The verdict rides
+  // as a fourth slot in the start phase's all-reduce and every rank finds the same S_MOVED in the scalars of the solve.
+  const int* moved_flag = nullptr;
+  int moved_stamp = 0;
+  // work to queue right AFTER the first batch of iterations and the copy of the scalars, BEFORE the host waits for that copy
+  // -- the next time step's first product, speculatively: the device then has something to run while the host wakes up, reads
+  // the scalars and queues the next step (the wait is on an event recorded behind the copy, not on the stream).  Called at
+  // most once per solve.
+  std::function<void()> after_first_batch;
 };
 
 struct SolveStats {
@@ -123,16 +135,13 @@ void halo_end(hipStream_t st);
 void spmv(const CsrMatrix& A, const double* x, double* y, hipStream_t st);
 // halo exchange of x (when the matrix needs one) overlapped with y[0..n) = A * x
 void spmv_halo(const CsrMatrix& A, const Numbering& nb, const Slab& slab, double* x, double* y, hipStream_t st);
-// x (n_vec, overwritten) = A^{-1} b.  x0 == nullptr: zero initial guess; else start from x0 with Ax0 = A*x0 given
-// (BiCGStab and IDR(s) only).  x0 may be x itself (the iteration continues from the iterate x holds).
-// preinit (BiCGStab only): the caller has already written x, w.r = w.rhat = w.p = r0 and the partial sums of (r0,r0)
-// / (b,b) in slots 0 / 1 of w.partials with a w.grid-block launch (pg_solver.hip fuses that with the right-hand side).
+// x (n_vec, overwritten) = A^{-1} b, started and instructed as `call` says (the default: from zero, nothing prepared).  A call
+// that the method of opts cannot honour is refused.  w is workspace and what one solve leaves for the next, never an input.
 void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x,
-                  KrylovWork& w, const pg_krylov_opts& opts, SolveStats& stats, const double* x0 = nullptr,
-                  const double* Ax0 = nullptr, bool preinit = false);
+                  KrylovWork& w, const pg_krylov_opts& opts, SolveStats& stats, const KrylovCall& call = {});
 
 // will krylov_solve(A, ..., opts) run BiCGStab right-preconditioned with the polynomial?  (Only that loop can solve a
-// compact system: it updates x through KrylovWork::scatter.)
+// compact system: it updates x through KrylovCall::scatter.)
 bool krylov_uses_polynomial(const CsrMatrix& A, const pg_krylov_opts& opts);
 
 // iterations after which a polynomial-preconditioned solve that has not converged is given up as stagnated; 0: the built-in

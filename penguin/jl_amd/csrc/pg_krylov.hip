@@ -386,7 +386,7 @@ __global__ void k_derive(int phase, double* sc, int check_done) {
   derive(phase, sc);
 }
 
-// The start phase of a prepared start on several ranks that carries KrylovWork::moved_flag: k_finalize's sums of the three
+// The start phase of a prepared start on several ranks that carries KrylovCall::moved_flag: k_finalize's sums of the three
 // start slots, and S_RED3 = 1 when a row alone on its diagonal moved on this rank (0 otherwise) ...
 __global__ __launch_bounds__(BLOCK) void k_start_sums_moved(int grid, const double* __restrict__ partials, double* __restrict__ sc,
                                                             const int* __restrict__ flag, int stamp) {
@@ -666,7 +666,9 @@ void choose_next_degree(const CsrMatrix& A, const SolveStats& stats, int m, bool
 }  // namespace
 
 void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, const double* b, double* x, KrylovWork& w,
-                  const pg_krylov_opts& opts, SolveStats& stats, const double* x0, const double* Ax0, bool preinit) {
+                  const pg_krylov_opts& opts, SolveStats& stats, const KrylovCall& call) {
+  const double *const x0 = call.x0, *const Ax0 = call.Ax0;
+  const bool preinit = call.preinit;
   Context& cx = ctx();
   hipStream_t st = cx.stream;
   const i64 n = A.n, nvec = nb.n_vec();
@@ -689,6 +691,12 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
                "has run on this matrix (specest_run before krylov_solve)");
   }
   const int precond = est_opt ? 0 : opts.precond;
+  // the one place that decides what a method accepts of a call: what it cannot honour is refused, never dropped
+  PG_REQUIRE((preinit && opts.method == PG_METHOD_BICGSTAB) ||
+                 !(call.p_in_rhat || call.start_folded || call.xguess.zbase || call.scatter || call.moved_flag || call.after_first_batch),
+             "krylov_solve: p_in_rhat, start_folded, xguess, scatter, moved_flag and after_first_batch belong to a prepared start "
+             "(preinit) of the BiCGStab loop");
+  PG_REQUIRE(!call.mg || mg_any_precond(opts.precond), "krylov_solve: a multigrid hierarchy was handed over without a multigrid precond");
   if (opts.method == PG_METHOD_GMRES) {
     PG_REQUIRE(!mg_is_step(opts.precond), std::string("multigrid preconditioner (precond = PG_PRECOND_MG_STEP) refused: ") +
                                               krylov_method_refusal(opts.method));
@@ -703,11 +711,6 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
                                                   ") refused: " + krylov_method_refusal(opts.method));
     PG_REQUIRE(opts.precond <= 0, "polynomial preconditioner (precond = " + std::to_string(opts.precond) + ") refused: " +
                                       krylov_method_refusal(opts.method) + "; precond = 0 or -1 runs BiCGStab(l) plain");
-    w.mg = nullptr;
-    w.xguess = XGuess();
-    w.p_in_rhat = w.start_folded = false;
-    w.moved_flag = nullptr;
-    w.after_first_batch = nullptr;
     bicgstabl_solve(A, nb, slab, b, x, w, opts, stats);
     return;
   }
@@ -718,11 +721,6 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
                                                   ") refused: " + krylov_method_refusal(opts.method));
     PG_REQUIRE(opts.precond <= 0, "polynomial preconditioner (precond = " + std::to_string(opts.precond) + ") refused: " +
                                       krylov_method_refusal(opts.method) + "; precond = 0 or -1 runs IDR(s) plain");
-    w.mg = nullptr;
-    w.xguess = XGuess();
-    w.p_in_rhat = w.start_folded = false;
-    w.moved_flag = nullptr;
-    w.after_first_batch = nullptr;
     idrs_solve(A, nb, slab, b, x, w, opts, stats, x0, Ax0);
     return;
   }
@@ -734,16 +732,9 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     maxiter = 100000;
   }
   // tolerances -> device scalars (a one-thread kernel: a host-to-device copy out of pageable memory stalls the stream)
-  struct HookReset { KrylovWork& w; ~HookReset() { w.after_first_batch = nullptr; } } hook_reset{w};   // (every exit path)
-  const bool p_in_rhat = w.p_in_rhat && preinit && opts.method == PG_METHOD_BICGSTAB;
-  w.p_in_rhat = false;
-  const XGuess xg = w.xguess;      // (first update of x out of place: see KrylovWork::xguess)
-  w.xguess = XGuess();
-  const bool start_folded = w.start_folded && preinit && opts.method == PG_METHOD_BICGSTAB;
-  w.start_folded = false;
-  const int* moved_flag = w.moved_flag;
-  const int moved_stamp = w.moved_stamp;
-  w.moved_flag = nullptr;
+  const bool p_in_rhat = call.p_in_rhat, start_folded = call.start_folded;
+  const XGuess& xg = call.xguess;      // (first update of x out of place: see KrylovCall::xguess)
+  const int* const scatter = call.scatter;
   const bool fused_start = !start_folded && preinit && opts.method == PG_METHOD_BICGSTAB && cx.nranks == 1 && !cx.comm;   // k_start below
   if (!fused_start && !start_folded)
     hipLaunchKernelGGL(k_sc_reset, dim3(1), dim3(S_COUNT), 0, st, w.sc.p, opts.reltol * opts.reltol, opts.abstol * opts.abstol);
@@ -766,14 +757,13 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   if (adaptive && w.adapt_matrix == &A && w.adapt_m >= 2) { m = w.adapt_m; expect_halves = w.adapt_h; }
   if (m < 2) m = 0;
   const bool poly = m > 0;
-  MgHierarchy* const mgh = w.mg;
-  w.mg = nullptr;
+  MgHierarchy* const mgh = call.mg;
   const bool mg = mg_any_precond(opts.precond);   // (PG_PRECOND_MG_STEP: the same loop from the time loop's prepared start)
   if (mg) {
     PG_REQUIRE(!cg, "multigrid preconditioner refused: the method must be BiCGStab");
     PG_REQUIRE(spmv_supports_preconditioner_product(), "multigrid preconditioner refused: the x-space loop needs the slice kernel (PG_SPMV_VARIANT)");
     mg_require_one_rank_of(opts.precond);
-    PG_REQUIRE(mgh && !w.scatter && !xg.zbase && n > 0,
+    PG_REQUIRE(mgh && !scatter && !xg.zbase && n > 0,
                mg_is_step(opts.precond)
                    ? "multigrid preconditioner refused: this solve has no hierarchy (the full systems of the unsteady monophasic "
                      "diffusion time loop only)"
@@ -786,7 +776,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   const bool pre = poly || mg;   // right-preconditioned: x moves by α M⁻¹p (k_bicg_s_x) and ω M⁻¹s (k_bicg_xrp)
   stats.poly_degree = m;
   stats.poly_xspace = poly ? 1 : 0;
-  PG_REQUIRE(!w.scatter || (poly && preinit), "a compact system needs the polynomial path and a prepared start");
+  PG_REQUIRE(!scatter || (poly && preinit), "a compact system needs the polynomial path and a prepared start");
   double tau[MAX_POLY_DEGREE];
   if (poly) {
     // 1 / Chebyshev nodes of [1 - g, 1 + g], the largest and the smallest remaining root in turn
@@ -832,7 +822,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   // convergence is also tested after the first half of an iteration when a half costs several products (the test itself
   // costs two small launches)
   const bool half_test = m >= 3 || mg;
-  PG_REQUIRE(!xg.zbase || (poly && p_in_rhat && w.scatter), "an unformed extrapolated state needs the polynomial loop on a compact system");
+  PG_REQUIRE(!xg.zbase || (poly && p_in_rhat && scatter), "an unformed extrapolated state needs the polynomial loop on a compact system");
   PG_REQUIRE(!preinit || !cg, "preinit is a BiCGStab path");
   if (!cg) {
     if (!preinit)
@@ -843,10 +833,10 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     } else if (fused_start)
       hipLaunchKernelGGL(k_start, dim3(1), dim3(BLOCK), 0, st, (int)PH_INIT, 3, w.grid, (const double*)w.partials.p, w.sc.p,
                          opts.reltol * opts.reltol, opts.abstol * opts.abstol);
-    else if (moved_flag && preinit && !(cx.nranks == 1 && !cx.comm)) {
+    else if (call.moved_flag && !(cx.nranks == 1 && !cx.comm)) {
       // finalize(PH_INIT) with one more slot in the same all-reduce: did a row alone on its diagonal move on ANY rank?
-      hipLaunchKernelGGL(k_start_sums_moved, dim3(1), dim3(BLOCK), 0, st, w.grid, (const double*)w.partials.p, w.sc.p, moved_flag,
-                         moved_stamp);
+      hipLaunchKernelGGL(k_start_sums_moved, dim3(1), dim3(BLOCK), 0, st, w.grid, (const double*)w.partials.p, w.sc.p, call.moved_flag,
+                         call.moved_stamp);
       comm_allreduce_sum_f64(w.sc.p + S_RED0, 4, st);
       hipLaunchKernelGGL(k_derive_start_moved, dim3(1), dim3(1), 0, st, w.sc.p);
     } else
@@ -962,7 +952,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     // iteration the sums of slot 4 are simply not looked at
     if (pre)
       hipLaunchKernelGGL(k_bicg_s_x, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.v.p, w.rhat.p, w.r.p, w.partials.p, (const double*)A.ds.p, tk,
-                         p_in_rhat ? 1 : 0, (const double*)w.ya.p, x, w.scatter, xg, itn == 0 ? 1 : 0);
+                         p_in_rhat ? 1 : 0, (const double*)w.ya.p, x, scatter, xg, itn == 0 ? 1 : 0);
     else
       hipLaunchKernelGGL(k_bicg_s, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.v.p, w.rhat.p, w.r.p, w.partials.p, (const double*)A.ds.p, tk,
                          p_in_rhat ? 1 : 0);
@@ -971,7 +961,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   auto second_half = [&](int itn) {
     apply(w.r.p, w.t.p, PH_BICG_2, 5, itn);     // t = C s (r holds s), (t,s), (t,t), (r̂,t); then ω, ρ, β / restart
     hipLaunchKernelGGL(k_bicg_xrp, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.t.p, w.v.p, x, w.r.p, w.p.p, w.rhat.p, w.partials.p,
-                       (const double*)A.ds.p, p_in_rhat ? 1 : 0, pre ? (const double*)w.yb.p : nullptr, w.scatter);
+                       (const double*)A.ds.p, p_in_rhat ? 1 : 0, pre ? (const double*)w.yb.p : nullptr, scatter);
   };
   while (!done) {
     int want = check_every;
@@ -1014,13 +1004,11 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
       std::chrono::steady_clock::time_point t0;
       ~WaitClock() { g_host_wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
     } wait_clock{t_wait0};
-    if (w.after_first_batch && polls == 1) {
+    if (call.after_first_batch && polls == 1) {
       // the caller's speculative work goes behind the copy; the host waits for the COPY only
       if (!w.ev_poll) PG_HIP(hipEventCreateWithFlags(&w.ev_poll, hipEventDisableTiming));
       PG_HIP(hipEventRecord(w.ev_poll, st));
-      std::function<void()> hook;
-      hook.swap(w.after_first_batch);
-      hook();
+      call.after_first_batch();
       PG_HIP(hipEventSynchronize(w.ev_poll));
     } else {
       PG_HIP(hipStreamSynchronize(st));   // (spinning on hipStreamQuery instead: no measurable difference)
@@ -1032,11 +1020,9 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     if (!done && poly && launched >= poly_give_up) { poly_failed = true; done = true; }
   }
   if (poly_failed) {                        // x is the iterate reached
-    const_cast<CsrMatrix&>(A).poly_ok = false;
-    const_cast<CsrMatrix&>(A).est.admitted = false;
-    const_cast<CsrMatrix&>(A).poly_gave_up = true;
+    poly_record_stagnation(A);
     timer.collect(stats, launched, false);
-    if (w.scatter) {                        // (the caller solves again on its full system, which has a right-hand side vector)
+    if (scatter) {                          // (the caller solves again on its full system, which has a right-hand side vector)
       stats.iters = launched;
       stats.converged = 0;
       stats.poly_degree = -1;
@@ -1045,7 +1031,9 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     if (cfg.debug) fprintf(stderr, "[pg_krylov] polynomial preconditioner (m = %d) stagnated after %d iterations: plain iteration\n", m, launched);
     spmv_with_halo(0, A, nb, slab, x, w.t.p, nullptr, nullptr, nullptr, G, st);   // Â x of the iterate reached
     SolveStats rest;
-    krylov_solve(A, nb, slab, b, x, w, opts, rest, x, w.t.p, false);
+    KrylovCall finish;      // (a fresh call: nothing of the prepared start carries over)
+    finish.x0 = x; finish.Ax0 = w.t.p;
+    krylov_solve(A, nb, slab, b, x, w, opts, rest, finish);
     stats = rest;
     stats.iters += launched;
     return;

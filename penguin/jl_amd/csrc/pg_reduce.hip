@@ -258,7 +258,7 @@ __global__ void k_c_couple(i64 n_wg, const int* __restrict__ wg_rows, const int*
     }
     if (s != 0.0) {
       const int c = cmap[wg_rows[q]];
-      rhat[c] -= s;   // (r and p are not stored at the start: KrylovWork::p_in_rhat)
+      rhat[c] -= s;   // (r and p are not stored at the start: KrylovCall::p_in_rhat)
     }
   }
 }

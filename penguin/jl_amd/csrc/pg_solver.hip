@@ -108,7 +108,7 @@ struct pg_solver {
   MgHierarchy mg;
   // ... and the one of the cell rule (PG_PRECOND_MG_CELL): one hierarchy per rule, neither reuses or disturbs the other's
   MgHierarchy mg_cell;
-  // ŷ = Â z of the NEXT step, queued speculatively behind the previous solve's first batch (KrylovWork::after_first_batch):
+  // ŷ = Â z of the NEXT step, queued speculatively behind the previous solve's first batch (KrylovCall::after_first_batch):
   // valid when that solve ended inside the batch (nothing moved z afterwards) and the next step runs on the same matrix
   bool spec_y_valid = false, spec_pending = false, hint_more_steps = false;
   const CsrMatrix* spec_matrix = nullptr;
@@ -396,7 +396,7 @@ struct GuessArgs {
   double* coef;             // [0..3] c_j, [4] how many, [5..8] their ring indices o_j - 1   (k_guess_fit); [13] += the number of
                             // older states this launch read (a running total for the bench's byte count)
   int defer;                // 1: z_g is NOT formed here -- the older states are not read for it and znew gets the rows alone on
-                            // their diagonal only; the solve's first update of x writes z_g + α M⁻¹p (KrylovWork::xguess) from
+                            // their diagonal only; the solve's first update of x writes z_g + α M⁻¹p (KrylovCall::xguess) from
                             // the copy of [0..8] this launch leaves at coef[GUESS_USED ..] (the fit rewrites [0..8] meanwhile)
 };
 constexpr int GUESS_USED = 64;
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const d
                                                       double* __restrict__ rhat, double* __restrict__ partials,
                                                       unsigned* __restrict__ ticket, double* __restrict__ sc, double reltol2,
                                                       double abstol2, int coupled, GuessArgs g) {
-  // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovWork::p_in_rhat)
+  // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovCall::p_in_rhat)
   // coupled != 0: diag_fix follows (the data changed): every δ != 0 moves its row, raises the flag and is coupled into the
   // residual of the rows that reference it.  coupled == 0: no coupling launch follows (unchanged data); only a δ beyond the
   // noise threshold raises the flag, and the step is then finished on the full system.  Several ranks with unchanged data
@@ -1844,12 +1844,12 @@ MgHierarchy& mg_ensure(pg_solver* s, MgRule rule = MG_RULE_KIND) {
   return H;
 }
 
-// before every krylov_solve on A_ctor that takes the caller's options
-void mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
-  if (!mg_is_precond(o.precond)) return;
+// before every krylov_solve on A_ctor that takes the caller's options: the hierarchy for that solve's KrylovCall (null: none asked for)
+MgHierarchy* mg_prepare(pg_solver* s, const pg_krylov_opts& o) {
+  if (!mg_is_precond(o.precond)) return nullptr;
   const MgRule rule = mg_rule_of(o.precond);
   mg_conditions(s, o.method, rule);
-  s->work.mg = &mg_ensure(s, rule);
+  return &mg_ensure(s, rule);
 }
 
 // opts.precond = PG_PRECOND_MG_STEP: the cell rule's V-cycle inside the unsteady time loop.  Served on the systems of
@@ -1901,34 +1901,45 @@ void specest_prepare(pg_solver* s, const CsrMatrix& A, const pg_krylov_opts& o) 
   specest_run(const_cast<CsrMatrix&>(A), s->nb, s->slab);
 }
 
-void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
-  const pg_krylov_opts o = opts ? *opts : default_opts();
-  mg_prepare(s, o);
-  if (mg_is_step(o.precond)) {
-    mg_step_conditions(s, o.method);
-    s->work.mg = &mg_step_ensure(s, s->A_ctor);
-  }
-  specest_prepare(s, s->A_ctor, o);
-  // solve_system!(s) with the constructor's A and b (diffusion.jl:275)
+// One solve of the constructor's system Â z = b̂ (A_ctor, s->b) and the state it leaves, for do_initial, solver_solve_again and
+// solver_first_solve_from_state.  from_state: start from a state and one product with it (the caller knows which methods that
+// serves), else from zero.  first: the solver's first solve -- the start state is s->x, scaled here (later solves start from the
+// z they left), and the time loop's bookkeeping begins.  mg: the hierarchy for a multigrid precond (mg_prepare), or null.
+void solve_ctor_system(pg_solver* s, const pg_krylov_opts& o, SolveStats& st, bool from_state, bool first, MgHierarchy* mg) {
   const i64 n = s->nb.n_own;
-  if (s->moving && o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && n > 0) {
-    // a slab of the moving solver: start from the previous state on this slab's active set (s->x, written by k_rhs_first;
-    // fresh cells start from the 0 their eliminated unknown held) -- a time step, as pg_solver_step's warm start
+  KrylovCall call;
+  call.mg = mg;
+  if (from_state) {
     hipStream_t stream = ctx().stream;
-    hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, s->A_ctor.ds.p, s->x.p, s->z.p, 1);
+    if (first) hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, s->A_ctor.ds.p, s->x.p, s->z.p, 1);
     spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);
     PG_HIP(hipGetLastError());
-    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
-  } else {
-    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
+    call.x0 = s->z.p; call.Ax0 = s->y.p;
   }
+  krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, call);
   std::swap(s->z.p, s->ysol.p);   // the scaled solution becomes the state (same-size buffers trade roles)
   s->z_matrix = &s->A_ctor;
   s->x_valid = false;
+  if (!first) return;
   s->initial_done = true;
   s->diag_ctor.snapped_version = s->diag_run.snapped_version = -1;   // z was replaced behind the compact path's back
   s->hist_cnt = 0;
   s->spec_y_valid = false;
+}
+
+void do_initial(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st) {
+  const pg_krylov_opts o = opts ? *opts : default_opts();
+  MgHierarchy* mg = mg_prepare(s, o);
+  if (mg_is_step(o.precond)) {
+    mg_step_conditions(s, o.method);
+    mg = &mg_step_ensure(s, s->A_ctor);
+  }
+  specest_prepare(s, s->A_ctor, o);
+  // solve_system!(s) with the constructor's A and b (diffusion.jl:275).  A slab of the moving solver starts from the previous
+  // state on this slab's active set (s->x, written by k_rhs_first; fresh cells start from the 0 their eliminated unknown held)
+  // -- a time step, as pg_solver_step's warm start
+  const bool from_state = s->moving && o.warm_start != 0 && o.method == PG_METHOD_BICGSTAB && s->nb.n_own > 0;
+  solve_ctor_system(s, o, st, from_state, true, mg);
 }
 
 // ---- host side of the extrapolated start (GuessArgs), shared by the compact and the plain warm path ---------------------
@@ -2035,6 +2046,204 @@ void guess_commit(pg_solver* s, const GuessPlan& gp, const void* owner) {
   s->hist_de = owner;
 }
 
+// the block rows of a diphasic CN right-hand side, matrix-free from the scaled state z (see k_rhs_block_mf)
+void launch_rhs_block_mf(pg_solver* s, int scheme, const CsrMatrix& A, hipStream_t stream) {
+  hipLaunchKernelGGL(k_rhs_block_mf, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, make_params(s, scheme), make_segs(s->nb),
+                     s->Mloc, A.n_blk, A.blk_rows.p, A.blk_idx.p, A.blk_coef.p, s->nb.row_cell.p, s->nb.red.p, A.ds.p,
+                     (const double*)s->z.p, s->mass.p, s->bconst.p, s->fixed.p, s->b.p);
+}
+
+// The compact warm step: the right-hand-side kernel solves the rows alone on their diagonal, BiCGStab with the polynomial runs on
+// the compact image DE.A of A (pg_reduce.hip, DiagElim).  used_de tells do_step's QuietGuard that this path's bookkeeping stands.
+void step_compact(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMatrix& A, DiagElim& DE, const DiagElim*& used_de,
+                  SolveStats& st) {
+  hipStream_t stream = ctx().stream;
+  const i64 n = s->nb.n_own;
+  KrylovWork& w = s->work;
+  // r = r̂ = p of the remaining rows go straight to the compact vectors; the other rows are solved in the same pass
+  const int stamp = (int)((s->steps_done % 2000000000) + 1);   // marks E.flag when a diagonal row moved in THIS step
+  // quiet: the previous step ran this path with the same constant data, so every diagonal row already holds its solution
+  // and none can move (beyond rounding) -- the coupling / renorm launches are not queued and the solver's start phase is
+  // folded into the right-hand-side kernel (3 launches less)
+  // Several ranks: the host-side knowledge "same constant data as the step before" is the same on every rank, so the
+  // coupling / renorm launches (and the exchange of the deltas they need there) are skipped collectively; only the folded
+  // start is a one-rank thing (the scalar phase of several ranks goes through an all-reduce).
+  const bool single = ctx().nranks == 1 && !ctx().comm;
+  const bool same_data = DE.snapped_version == s->bconst_version;
+  const bool quiet = same_data && single;
+  // extrapolated start (GuessArgs): steps with unchanged data only -- the rows alone on their diagonal rest, so the
+  // differences of the kept states are differences of the loop's rows alone and the products ŷ^{n-o} combine linearly.
+  // Several ranks: "unchanged data" is the same verdict everywhere, the fit's sums go through an all-reduce and every rank
+  // takes the same decision.
+  guess_policy(DE.guess_on, DE.last_products, DE.bytes_per_rank);
+  GuessPlan gp = guess_prepare(s, &DE, same_data && DE.guess_on, DE.last_products, stream);
+  const int KH = gp.KH;
+  // the extrapolated state itself is formed by the solve's first update of x (KrylovCall::xguess): the older states are
+  // then read there through the compact system's index map, once, and this kernel neither reads them nor writes the state
+  const Config& cfg = config();
+  // (not after a solve that met the tolerance at its start: the next one probably will too, no update of x runs then, and
+  //  writing the state from the first s kernel's early exit costs more than writing it here -- 64^3 BE near steady state)
+  const bool defer = KH > 0 && cfg.guess_defer && DE.last_products > 0.0;
+  gp.ga.defer = defer ? 1 : 0;
+  const GuessArgs& ga = gp.ga;
+  const double* zprev = s->z.p;      // z^n (the buffers trade places below)
+#define PG_RHS_INIT_C(KHV)                                                                                                        \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p,   \
+                     s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, DE.cmap.p, s->b.p, (const double*)DE.gdiag.p, DE.delta.p,     \
+                     DE.flag.p, stamp, w.rhat.p, w.partials.p, quiet ? w.ticket.p : nullptr, w.sc.p, o.reltol * o.reltol,          \
+                     o.abstol * o.abstol, same_data ? 0 : 1, ga)
+  switch (KH) {
+    case 1: PG_RHS_INIT_C(1); break;
+    case 2: PG_RHS_INIT_C(2); break;
+    case 3: PG_RHS_INIT_C(3); break;
+    case 4: PG_RHS_INIT_C(4); break;
+    default: PG_RHS_INIT_C(0); break;
+  }
+#undef PG_RHS_INIT_C
+  PG_HIP(hipGetLastError());
+  guess_after_rhs(s, gp, n, (const int*)DE.cmap.p, (const double*)A.ds.p, (const double*)w.rhat.p, single, w, stream);
+  if (!same_data) diag_fix(DE, s->nb, s->slab, stamp, !single, w.rhat.p, w.partials.p, w.grid, stream);
+  KrylovCall call;
+  call.preinit = call.p_in_rhat = true;
+  call.start_folded = quiet;
+  call.scatter = DE.rlist.p;
+  // several ranks, unchanged data: nobody looks at the rows alone on their diagonal (no diag_fix), so the flag k_rhs_init_c
+  // raised goes through the start phase's all-reduce and comes back as S_MOVED, the same on every rank
+  if (same_data && !single) { call.moved_flag = DE.flag.p; call.moved_stamp = stamp; }
+  DE.snapped_version = s->bconst_version;
+  used_de = &DE;
+  s->spec_pending = false;
+  if (quiet && s->hint_more_steps && config().speculate_product)
+    call.after_first_batch = [s, &A, stream]() {     // the next step's ŷ = Â z, behind this solve's (expected) last update of z
+      spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
+      s->spec_pending = true;
+      s->spec_matrix = &A;
+    };
+  if (defer) {
+    call.xguess.zbase = zprev;
+    for (int j = 0; j < 8; ++j) call.xguess.zr[j] = ga.zr[j];
+    call.xguess.coef = s->guess_coef.p + GUESS_USED;
+  }
+  krylov_solve(DE.A, DE.nb, s->slab, nullptr, s->z.p, w, o, st, call);
+  // the speculative product stands when the solve ended inside its first batch (nothing has touched z since)
+  s->spec_y_valid = s->spec_pending && st.polls == 1 && st.converged && st.poly_degree >= 0;
+  s->spec_pending = false;
+  const bool solved = st.poly_degree >= 0;   // -1: the polynomial stagnated on the compact system -> the full system below
+  DE.last_products = (double)st.products;
+
+  // A step with unchanged data rests on "no row alone on its diagonal moves while the data are unchanged"; k_rhs_init_c
+  // checks it anyway and the start phase reports it (S_MOVED): the residual the iteration started from then lacked the
+  // coupling term, and the step is finished on the full system from the state reached.  Several ranks read the verdict
+  // out of the start phase's all-reduce: a row that moved on one rank sends all of them this way, or none.
+  const bool moved_unseen = solved && same_data && w.h_sc[S_MOVED] != 0.0;
+  if (!solved || moved_unseen) {
+    s->spec_y_valid = false;
+    // z has moved (the rows left out hold their solution, the x-space iteration has updated the rest): the right-hand
+    // side b̂ of this step -- written for every row by k_rhs_init_c -- stands, the iteration continues on the full
+    // system from the state reached, r = b̂ - Âz
+    if (!solved) {
+      DE.active = false;
+      // the compact matrix is made of the full one's rows: the verdict on the polynomial holds for both, and the solve
+      // below goes plain at once instead of stagnating a second time
+      poly_record_stagnation(A);
+    }
+    used_de = nullptr;
+    const SolveStats first = st;
+    st = SolveStats();
+    spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
+    KrylovCall full;
+    full.x0 = s->z.p; full.Ax0 = s->y.p;
+    krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, w, o, st, full);
+    std::swap(s->z.p, s->ysol.p);
+    st.iters += first.iters;
+    st.products += first.products;
+  }
+  else guess_commit(s, gp, &DE);
+  s->x_valid = false;
+}
+
+// The plain warm step: the iteration starts from the previous state on the full system, or on Â_ωω where the γ elimination runs.
+void step_warm(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMatrix& A, bool mgs, SolveStats& st) {
+  hipStream_t stream = ctx().stream;
+  const i64 n = s->nb.n_own;
+  KrylovWork& w = s->work;
+  // Dirichlet interface: the γ rows are rows of the identity -- solved here, the iteration runs on Â_ωω (pg_reduce.hip)
+  GammaElim& E = (&A == &s->A_ctor) ? s->elim_ctor : s->elim_run;
+  if (!mgs && !E.tried) build_gamma_elim(A, s->nb, E);
+  const bool e_active = !mgs && E.active;
+  // The plain warm path (no row left out: diphasic systems, interfaces with Robin / Neumann conditions and no border rows)
+  // takes the extrapolated start as well, on one rank: the kept products are products of whole states whatever the data do,
+  // so steps with changing data qualify too.
+  const bool single = ctx().nranks == 1 && !ctx().comm;
+  const int which = (&A == &s->A_ctor) ? 0 : 1;
+  if (single && !e_active) guess_policy(s->plain_guess_on[which], s->plain_last_products[which], (double)A.spmv_bytes);
+  const GuessPlan gp = guess_prepare(s, &A, single && !e_active && s->plain_guess_on[which], s->plain_last_products[which], stream);
+#define PG_RHS_INIT(KHV)                                                                                                          \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, s->nb.n_vec(), scheme, s->z.p,     \
+                     s->y.p, A.ds.p, s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, s->b.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, \
+                     gp.ga)
+  switch (gp.KH) {
+    case 1: PG_RHS_INIT(1); break;
+    case 2: PG_RHS_INIT(2); break;
+    case 3: PG_RHS_INIT(3); break;
+    case 4: PG_RHS_INIT(4); break;
+    default: PG_RHS_INIT(0); break;
+  }
+#undef PG_RHS_INIT
+  PG_HIP(hipGetLastError());
+  guess_after_rhs(s, gp, n, nullptr, (const double*)A.ds.p, (const double*)w.rhat.p, true, w, stream);
+  KrylovCall call;
+  call.preinit = true;
+  if (e_active) {
+    gamma_fix(E, s->z.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, w.grid, stream);
+    // the sub-matrix carries Gershgorin's verdict on Â but no spectral estimate: PG_PRECOND_POLY_EST is precond = 0 here (the
+    // polynomial where Gershgorin admits, the plain loop where it refuses -- DESIGN.md section 16)
+    pg_krylov_opts oe = o;
+    if (oe.precond == PG_PRECOND_POLY_EST) oe.precond = 0;
+    krylov_solve(E.A, E.nb, s->slab, s->b.p, s->z.p, w, oe, st, call);
+  } else {
+    // y0 = z (in place), r0 = b̂ - ŷ: same solution as a zero start, fewer iterations
+    if (mgs) call.mg = &mg_step_ensure(s, A);
+    krylov_solve(A, s->nb, s->slab, s->b.p, s->z.p, w, o, st, call);
+    s->plain_last_products[which] = (double)st.products;
+    guess_commit(s, gp, &A);
+  }
+  s->x_valid = false;
+}
+
+// The cold step (and IDR(s)'s warm one): the right-hand side from the unscaled state, the solve from zero or from x0 / Ax0.
+void step_cold(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMatrix& A, bool mgs, SolveStats& st) {
+  hipStream_t stream = ctx().stream;
+  const i64 n = s->nb.n_own;
+  // cold start / CG: the reference's zero initial guess, on the unscaled state
+  s->hist_cnt = 0;
+  materialize_x(s);
+  // IDR(s) starts from the previous state here too (krylov_solve's x0 / Ax0): the scaled state and one product, which CN takes anyway
+  const bool idr_warm = o.warm_start != 0 && o.method == PG_METHOD_IDRS && n > 0;
+  if (n > 0) {
+    if (scheme == PG_SCHEME_CN || idr_warm) {
+      hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, A.ds.p, s->x.p, s->z.p, 1);
+      spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
+    }
+    hipLaunchKernelGGL(k_rhs, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, scheme, s->x.p, s->y.p, A.ds.p, s->mass.p,
+                       s->bconst.p, s->fixed.p, s->b.p);
+    if (A.n_blk > 0 && s->nphase == 2 && scheme == PG_SCHEME_CN)
+      launch_rhs_block_mf(s, scheme, A, stream);
+    else if (A.n_blk > 0)
+      hipLaunchKernelGGL(k_rhs_block, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_rows.p,
+                         A.blk_idx.p, A.blk_coef.p, A.blk_cn.p, s->x.p, (const double*)nullptr, s->y.p, s->mass.p,
+                         s->bconst.p, s->fixed.p, s->b.p);
+    PG_HIP(hipGetLastError());
+  }
+  KrylovCall call;
+  if (mgs) call.mg = &mg_step_ensure(s, A);
+  if (idr_warm) { call.x0 = s->z.p; call.Ax0 = s->y.p; }
+  krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, call);
+  std::swap(s->z.p, s->ysol.p);
+  s->z_matrix = &A;
+  s->x_valid = false;
+}
+
 void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& st) {
   PG_REQUIRE(s->scheme_ctor != PG_SCHEME_STEADY, "a steady solver has no time loop");
   PG_REQUIRE(!s->moving, "a moving-body solver is one space-time step: create the next one from the next time slab");
@@ -2087,11 +2296,8 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     s->spec_y_valid = false;
     if (!have_y) spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
     const bool blk_mf = s->nphase == 2 && scheme == PG_SCHEME_CN;   // (see k_rhs_block_mf)
-    if (A.n_blk > 0 && blk_mf) {
-      hipLaunchKernelGGL(k_rhs_block_mf, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, make_params(s, scheme), make_segs(s->nb),
-                         s->Mloc, A.n_blk, A.blk_rows.p, A.blk_idx.p, A.blk_coef.p, s->nb.row_cell.p, s->nb.red.p, A.ds.p,
-                         (const double*)s->z.p, s->mass.p, s->bconst.p, s->fixed.p, s->b.p);
-    } else if (A.n_blk > 0) {
+    if (A.n_blk > 0 && blk_mf) launch_rhs_block_mf(s, scheme, A, stream);
+    else if (A.n_blk > 0) {
       if (s->blk_cache_matrix != &A || s->blk_cache_scheme != scheme || s->blk_cache_version != s->bconst_version) {
         if (s->blk_wz.n != A.n_blk * MAX_KINDS) s->blk_wz.alloc(A.n_blk * MAX_KINDS);   // (time-dependent data: rebuilt every step)
         if (s->blk_c0.n != A.n_blk) s->blk_c0.alloc(A.n_blk);
@@ -2103,196 +2309,13 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
                          A.blk_idx.p, (const double*)s->blk_wz.p, (const double*)s->blk_c0.p, A.blk_cn.p, (const double*)s->z.p,
                          (const double*)s->y.p, s->b.p);
     }
-    KrylovWork& w = s->work;
     // rows alone on their diagonal (interface AND border identity rows) left out, compact vectors (pg_reduce.hip, DiagElim)
     DiagElim& DE = (&A == &s->A_ctor) ? s->diag_ctor : s->diag_run;
     // (PG_PRECOND_MG_STEP iterates on the full system: neither the compact system nor the γ elimination starts)
     if (!mgs && !DE.tried) build_diag_elim(A, s->nb, s->slab, DE);
-    if (!mgs && DE.active && krylov_uses_polynomial(DE.A, o)) {
-      // r = r̂ = p of the remaining rows go straight to the compact vectors; the other rows are solved in the same pass
-      const int stamp = (int)((s->steps_done % 2000000000) + 1);   // marks E.flag when a diagonal row moved in THIS step
-      // quiet: the previous step ran this path with the same constant data, so every diagonal row already holds its solution
-      // and none can move (beyond rounding) -- the coupling / renorm launches are not queued and the solver's start phase is
-      // folded into the right-hand-side kernel (3 launches less)
-      // Several ranks: the host-side knowledge "same constant data as the step before" is the same on every rank, so the
-      // coupling / renorm launches (and the exchange of the deltas they need there) are skipped collectively; only the folded
-      // start is a one-rank thing (the scalar phase of several ranks goes through an all-reduce).
-      const bool single = ctx().nranks == 1 && !ctx().comm;
-      const bool same_data = DE.snapped_version == s->bconst_version;
-      const bool quiet = same_data && single;
-      // extrapolated start (GuessArgs): steps with unchanged data only -- the rows alone on their diagonal rest, so the
-      // differences of the kept states are differences of the loop's rows alone and the products ŷ^{n-o} combine linearly.
-      // Several ranks: "unchanged data" is the same verdict everywhere, the fit's sums go through an all-reduce and every rank
-      // takes the same decision.
-      guess_policy(DE.guess_on, DE.last_products, DE.bytes_per_rank);
-      GuessPlan gp = guess_prepare(s, &DE, same_data && DE.guess_on, DE.last_products, stream);
-      const int KH = gp.KH;
-      // the extrapolated state itself is formed by the solve's first update of x (KrylovWork::xguess): the older states are
-      // then read there through the compact system's index map, once, and this kernel neither reads them nor writes the state
-      const Config& cfg = config();
-      // (not after a solve that met the tolerance at its start: the next one probably will too, no update of x runs then, and
-      //  writing the state from the first s kernel's early exit costs more than writing it here -- 64^3 BE near steady state)
-      const bool defer = KH > 0 && cfg.guess_defer && DE.last_products > 0.0;
-      gp.ga.defer = defer ? 1 : 0;
-      const GuessArgs& ga = gp.ga;
-      const double* zprev = s->z.p;      // z^n (the buffers trade places below)
-#define PG_RHS_INIT_C(KHV)                                                                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p,   \
-                     s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, DE.cmap.p, s->b.p, (const double*)DE.gdiag.p, DE.delta.p,     \
-                     DE.flag.p, stamp, w.rhat.p, w.partials.p, quiet ? w.ticket.p : nullptr, w.sc.p, o.reltol * o.reltol,          \
-                     o.abstol * o.abstol, same_data ? 0 : 1, ga)
-      switch (KH) {
-        case 1: PG_RHS_INIT_C(1); break;
-        case 2: PG_RHS_INIT_C(2); break;
-        case 3: PG_RHS_INIT_C(3); break;
-        case 4: PG_RHS_INIT_C(4); break;
-        default: PG_RHS_INIT_C(0); break;
-      }
-#undef PG_RHS_INIT_C
-      PG_HIP(hipGetLastError());
-      guess_after_rhs(s, gp, n, (const int*)DE.cmap.p, (const double*)A.ds.p, (const double*)w.rhat.p, single, w, stream);
-      if (!same_data) diag_fix(DE, s->nb, s->slab, stamp, !single, w.rhat.p, w.partials.p, w.grid, stream);
-      w.start_folded = quiet;
-      // several ranks, unchanged data: nobody looks at the rows alone on their diagonal (no diag_fix), so the flag k_rhs_init_c
-      // raised goes through the start phase's all-reduce and comes back as S_MOVED, the same on every rank
-      if (same_data && !single) { w.moved_flag = DE.flag.p; w.moved_stamp = stamp; }
-      DE.snapped_version = s->bconst_version;
-      used_de = &DE;
-      w.scatter = DE.rlist.p;
-      w.p_in_rhat = true;
-      bool solved = false;
-      s->spec_pending = false;
-      if (quiet && s->hint_more_steps && config().speculate_product)
-        w.after_first_batch = [s, &A, stream]() {     // the next step's ŷ = Â z, behind this solve's (expected) last update of z
-          spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
-          s->spec_pending = true;
-          s->spec_matrix = &A;
-        };
-      XGuess xg;
-      if (defer) {
-        xg.zbase = zprev;
-        for (int j = 0; j < 8; ++j) xg.zr[j] = ga.zr[j];
-        xg.coef = s->guess_coef.p + GUESS_USED;
-        w.xguess = xg;
-      }
-      try {
-        krylov_solve(DE.A, DE.nb, s->slab, nullptr, s->z.p, w, o, st, nullptr, nullptr, true);
-      } catch (...) {
-        w.scatter = nullptr;
-        w.after_first_batch = nullptr;
-        w.moved_flag = nullptr;
-        throw;
-      }
-      w.scatter = nullptr;
-      w.after_first_batch = nullptr;
-      // the speculative product stands when the solve ended inside its first batch (nothing has touched z since)
-      s->spec_y_valid = s->spec_pending && st.polls == 1 && st.converged && st.poly_degree >= 0;
-      s->spec_pending = false;
-      solved = st.poly_degree >= 0;            // -1: the polynomial stagnated on the compact system -> the full system below
-      DE.last_products = (double)st.products;
-
-      // A step with unchanged data rests on "no row alone on its diagonal moves while the data are unchanged"; k_rhs_init_c
-      // checks it anyway and the start phase reports it (S_MOVED): the residual the iteration started from then lacked the
-      // coupling term, and the step is finished on the full system from the state reached.  Several ranks read the verdict
-      // out of the start phase's all-reduce: a row that moved on one rank sends all of them this way, or none.
-      const bool moved_unseen = solved && same_data && w.h_sc[S_MOVED] != 0.0;
-      if (!solved || moved_unseen) {
-        s->spec_y_valid = false;
-        // z has moved (the rows left out hold their solution, the x-space iteration has updated the rest): the right-hand
-        // side b̂ of this step -- written for every row by k_rhs_init_c -- stands, the iteration continues on the full
-        // system from the state reached, r = b̂ - Âz
-        if (!solved) {
-          DE.active = false;
-          // the compact matrix is made of the full one's rows: the verdict on the polynomial holds for both, and the solve
-          // below goes plain at once instead of stagnating a second time
-          const_cast<CsrMatrix&>(A).poly_ok = false;
-          const_cast<CsrMatrix&>(A).est.admitted = false;
-          const_cast<CsrMatrix&>(A).poly_gave_up = true;
-        }
-        used_de = nullptr;
-        const SolveStats first = st;
-        st = SolveStats();
-        spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
-        krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, w, o, st, s->z.p, s->y.p, false);
-        std::swap(s->z.p, s->ysol.p);
-        st.iters += first.iters;
-        st.products += first.products;
-      }
-      else guess_commit(s, gp, &DE);
-      s->x_valid = false;
-      s->steps_done += 1;
-      return;
-    }
-    // Dirichlet interface: the γ rows are rows of the identity -- solved here, the iteration runs on Â_ωω (pg_reduce.hip)
-    GammaElim& E = (&A == &s->A_ctor) ? s->elim_ctor : s->elim_run;
-    if (!mgs && !E.tried) build_gamma_elim(A, s->nb, E);
-    const bool e_active = !mgs && E.active;
-    // The plain warm path (no row left out: diphasic systems, interfaces with Robin / Neumann conditions and no border rows)
-    // takes the extrapolated start as well, on one rank: the kept products are products of whole states whatever the data do,
-    // so steps with changing data qualify too.
-    const bool single = ctx().nranks == 1 && !ctx().comm;
-    const int which = (&A == &s->A_ctor) ? 0 : 1;
-    if (single && !e_active) guess_policy(s->plain_guess_on[which], s->plain_last_products[which], (double)A.spmv_bytes);
-    const GuessPlan gp = guess_prepare(s, &A, single && !e_active && s->plain_guess_on[which], s->plain_last_products[which], stream);
-#define PG_RHS_INIT(KHV)                                                                                                          \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, s->nb.n_vec(), scheme, s->z.p,     \
-                     s->y.p, A.ds.p, s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, s->b.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, \
-                     gp.ga)
-    switch (gp.KH) {
-      case 1: PG_RHS_INIT(1); break;
-      case 2: PG_RHS_INIT(2); break;
-      case 3: PG_RHS_INIT(3); break;
-      case 4: PG_RHS_INIT(4); break;
-      default: PG_RHS_INIT(0); break;
-    }
-#undef PG_RHS_INIT
-    PG_HIP(hipGetLastError());
-    guess_after_rhs(s, gp, n, nullptr, (const double*)A.ds.p, (const double*)w.rhat.p, true, w, stream);
-    if (e_active) {
-      gamma_fix(E, s->z.p, w.r.p, w.rhat.p, w.p.p, w.partials.p, w.grid, stream);
-      // the sub-matrix carries Gershgorin's verdict on Â but no spectral estimate: PG_PRECOND_POLY_EST is precond = 0 here (the
-      // polynomial where Gershgorin admits, the plain loop where it refuses -- DESIGN.md section 16)
-      pg_krylov_opts oe = o;
-      if (oe.precond == PG_PRECOND_POLY_EST) oe.precond = 0;
-      krylov_solve(E.A, E.nb, s->slab, s->b.p, s->z.p, w, oe, st, nullptr, nullptr, true);
-    } else {
-      // y0 = z (in place), r0 = b̂ - ŷ: same solution as a zero start, fewer iterations
-      if (mgs) w.mg = &mg_step_ensure(s, A);
-      krylov_solve(A, s->nb, s->slab, s->b.p, s->z.p, w, o, st, nullptr, nullptr, true);
-      s->plain_last_products[which] = (double)st.products;
-      guess_commit(s, gp, &A);
-    }
-    s->x_valid = false;
-  } else {
-    // cold start / CG: the reference's zero initial guess, on the unscaled state
-    s->hist_cnt = 0;
-    materialize_x(s);
-    // IDR(s) starts from the previous state here too (krylov_solve's x0 / Ax0): the scaled state and one product, which CN takes anyway
-    const bool idr_warm = o.warm_start != 0 && o.method == PG_METHOD_IDRS && n > 0;
-    if (n > 0) {
-      if (scheme == PG_SCHEME_CN || idr_warm) {
-        hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, A.ds.p, s->x.p, s->z.p, 1);
-        spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
-      }
-      hipLaunchKernelGGL(k_rhs, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, scheme, s->x.p, s->y.p, A.ds.p, s->mass.p,
-                         s->bconst.p, s->fixed.p, s->b.p);
-      if (A.n_blk > 0 && s->nphase == 2 && scheme == PG_SCHEME_CN)
-        hipLaunchKernelGGL(k_rhs_block_mf, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, make_params(s, scheme), make_segs(s->nb),
-                           s->Mloc, A.n_blk, A.blk_rows.p, A.blk_idx.p, A.blk_coef.p, s->nb.row_cell.p, s->nb.red.p, A.ds.p,
-                           (const double*)s->z.p, s->mass.p, s->bconst.p, s->fixed.p, s->b.p);
-      else if (A.n_blk > 0)
-        hipLaunchKernelGGL(k_rhs_block, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_rows.p,
-                           A.blk_idx.p, A.blk_coef.p, A.blk_cn.p, s->x.p, (const double*)nullptr, s->y.p, s->mass.p,
-                           s->bconst.p, s->fixed.p, s->b.p);
-      PG_HIP(hipGetLastError());
-    }
-    if (mgs) s->work.mg = &mg_step_ensure(s, A);
-    if (idr_warm) krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
-    else krylov_solve(A, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
-    std::swap(s->z.p, s->ysol.p);
-    s->z_matrix = &A;
-    s->x_valid = false;
-  }
+    if (!mgs && DE.active && krylov_uses_polynomial(DE.A, o)) step_compact(s, scheme, o, A, DE, used_de, st);
+    else step_warm(s, scheme, o, A, mgs, st);
+  } else step_cold(s, scheme, o, A, mgs, st);
   s->steps_done += 1;
 }
 
@@ -3908,23 +3931,15 @@ void solver_solve_again(pg_solver* s, const pg_krylov_opts* opts, SolveStats& st
     return;
   }
   const pg_krylov_opts o = opts ? *opts : default_opts();
-  mg_prepare(s, o);
+  MgHierarchy* const mg = mg_prepare(s, o);
   if (mg_is_step(o.precond)) mg_step_conditions(s, o.method);   // (refuses: a steady system)
   specest_prepare(s, s->A_ctor, o);
-  hipStream_t stream = ctx().stream;
   const i64 n = s->nb.n_own;
   ensure_bconst(s, PG_SCHEME_STEADY);
-  if (n > 0) apply_left(s->A_ctor, s->bconst.p, s->b.p, stream);      // b̂ = B⁻¹ S b
-  if (o.warm_start != 0 && (o.method == PG_METHOD_BICGSTAB || o.method == PG_METHOD_IDRS) && n > 0) {
-    spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);       // z: the previous solution, scaled by this matrix's S
-    PG_HIP(hipGetLastError());
-    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
-  } else {
-    krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st);
-  }
-  std::swap(s->z.p, s->ysol.p);
-  s->z_matrix = &s->A_ctor;
-  s->x_valid = false;
+  if (n > 0) apply_left(s->A_ctor, s->bconst.p, s->b.p, ctx().stream);      // b̂ = B⁻¹ S b
+  // z: the previous solution, scaled by this matrix's S
+  const bool from_state = o.warm_start != 0 && (o.method == PG_METHOD_BICGSTAB || o.method == PG_METHOD_IDRS) && n > 0;
+  solve_ctor_system(s, o, st, from_state, false, mg);
 }
 
 // One step of iterative refinement: r̂ = b̂ - Â z from a product (every row to the accuracy of its OWN entries), Â d = r̂ from zero
@@ -3981,17 +3996,7 @@ void solver_first_solve_from_state(pg_solver* s, const pg_krylov_opts* opts, Sol
     refine_once(s, o, st);
     return;
   }
-  hipStream_t stream = ctx().stream;
-  hipLaunchKernelGGL(k_scale_state, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, stream, n, s->A_ctor.ds.p, s->x.p, s->z.p, 1);
-  spmv_halo(s->A_ctor, s->nb, s->slab, s->z.p, s->y.p, stream);
-  PG_HIP(hipGetLastError());
-  krylov_solve(s->A_ctor, s->nb, s->slab, s->b.p, s->ysol.p, s->work, o, st, s->z.p, s->y.p, false);
-  std::swap(s->z.p, s->ysol.p);
-  s->z_matrix = &s->A_ctor;
-  s->x_valid = false;
-  s->initial_done = true;
-  s->hist_cnt = 0;
-  s->spec_y_valid = false;
+  solve_ctor_system(s, o, st, true, true, nullptr);
   refine_once(s, o, st);
 }
 

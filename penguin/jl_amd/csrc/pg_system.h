@@ -120,6 +120,14 @@ struct CsrMatrix {
   DevBuf<double> blk_coef, blk_cn, blk_fw;
   DevBuf<unsigned char> isblk;   // n: 1 for the rows listed in blk_rows
 };
+// The polynomial stagnated on A (CsrMatrix::poly_gave_up).  What a matrix has been found to be is not part of its value: the
+// solves that find it out hold the matrix const, so the verdict is written through that here, in one place.
+inline void poly_record_stagnation(const CsrMatrix& A) {
+  CsrMatrix& M = const_cast<CsrMatrix&>(A);
+  M.poly_ok = false;
+  M.est.admitted = false;
+  M.poly_gave_up = true;
+}
 constexpr int SPMV_CHUNK_ENTRIES = 508;   // + alignment shift (<= 3) fits the 512-slot LDS slice of a wave
 void build_spmv_chunks(CsrMatrix& A);   // pg_spmv.hip
 
