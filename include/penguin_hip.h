@@ -619,7 +619,33 @@ int32_t pg_capacity_polygon_ms_parts(const pg_capacity* c, double* ms /* 6 */);
 int32_t pg_capacity_create_spacetime_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */,
                                              const pg_program* dphidt, int32_t flags, double t0, double t1, int32_t nq,
                                              const double* tau_w /* nq x 2 */, pg_capacity** out);
-/* measurement, off by default: while on, pg_capacity_create_spacetime_program brackets each of its six kernels with events */
+/* Capacity(front_n, front_np1, SpaceTimeMesh(mesh, [t0, t1])) of a MOVING marker polygon -- the reference's
+   compute_spacetime_capacities(mesh, front_n, front_np1, dt) (src/front_tracking.jl:1472) with interpolate_front (:2289): xy0 and
+   xy1 are the M markers at t0 and at t1, the same count and order; inside the slab every marker moves on a straight line at
+   constant speed, vertex i at tau is xy0_i + s (xy1_i - xy0_i) with s = (tau - t0) / (t1 - t0), and the two time faces read xy0
+   and xy1 themselves.  A closing duplicate is dropped where both arrays close; the orientation is normalised to
+   counter-clockwise by the signed area at t0, the same reversal applied to both.  Fluid is the interior, PG_FLAG_COMPLEMENT: the
+   exterior.  The space-time kernels of pg_capacity_create_spacetime run with "the body at time node k" = that polygon measured
+   by the primitives of pg_capacity_create_polygon, with the conventions of pg_capacity_create_spacetime_program (time integrals
+   by the composite rule, V_t0 / V_t1 the spatial volumes at the faces -- a FULL face takes the full cells' measure, so V_t1 of
+   one slab and V_t0 of the next are the same bits --, FULL / EMPTY only if so at every node and both faces), except Gamma: it is
+   sum_k w_k sum_pieces len_p sqrt(1 + v_n,p^2) over the pieces the cell owns at tau_k, v_n,p the normal speed of the edge at the
+   piece's midpoint -- one speed per piece, exact for a rigid translation -- and C_gamma the mean with the same weights; a cell
+   that is never CUT may own a piece (an edge along its lower or left face) and then has Gamma > 0.  One edge lookup of the SWEPT
+   edges (the bounding box of an edge's two ends at t0 and t1) is built on the device per slab and serves every node and both
+   faces; a cell whose swept list is empty is finished by the cheap pass with the parity of its centre at t0.  Bitwise
+   repeatable.  Limits: straight marker paths within a slab; 2-D; closed fronts; one rank.  Refused before anything is allocated,
+   each with its own message: a NULL mesh, out, xy0, xy1 or tau_w (each named); M < 3; a non-finite coordinate; a mesh that is
+   not 2-D; nq outside 1 .. 4096; t1 <= t0; a node outside (t0, t1); weights that do not add up to t1 - t0 within
+   1e-12 (t1 - t0); more than one rank or a communicator; a zero-length edge, zero signed area or a self-intersection
+   (pg_capacity_create_polygon's rules) at t0, at t1 or at mid time -- NOT at the times in between --; an orientation that
+   differs between t0 and t1.  *out is NULL after a refusal.  pg_debug_capacity_spacetime_ms_parts gives the six kernel times
+   (with the timing below on) and entry 5 of pg_capacity_polygon_ms_parts the time of the edge lookup. */
+int32_t pg_capacity_create_spacetime_polygon(pg_mesh* m, const double* xy0 /* 2 M */, const double* xy1 /* 2 M */, int64_t M,
+                                             int32_t flags, double t0, double t1, int32_t nq, const double* tau_w /* nq x 2 */,
+                                             pg_capacity** out);
+/* measurement, off by default: while on, pg_capacity_create_spacetime_program and pg_capacity_create_spacetime_polygon bracket
+   each of their six kernels with events */
 int32_t pg_debug_spacetime_kernel_timing(int32_t on);
 /* capacities of pg_capacity_create_spacetime_program: the number of cells the cheap pass left to the list and, when built with
    the timing on, ms of k_st_classify, k_st_cells, k_st_sections, k_st_sections_cut, k_st_stagger, k_st_stagger_cut (0: not

@@ -1481,6 +1481,47 @@ function Capacity(body::DeviceFunction, mesh::SpaceTimeMesh; method::String="VOF
                          mesh, reported_body)
 end
 Capacity(b::MovingComplement, mesh::SpaceTimeMesh; kwargs...) = Capacity(b.body, mesh; complement=true, reported_body=b, kwargs...)
+
+# A marker polygon that moves: Capacity(front_n, front_np1, stmesh), the reference's compute_spacetime_capacities(mesh, front_n,
+# front_np1, dt) (src/front_tracking.jl:1472).  The two fronts hold the markers at the slab's two times, the same count and order;
+# inside the slab every marker moves on a straight line at constant speed (interpolate_front, :2289) and
+# pg_capacity_create_spacetime_polygon measures the polygon at every time node.  Fluid is the interior, complement=true: the
+# exterior.  2-D, closed fronts, one rank.  cap.body is front_n.
+function Capacity(front_n::FrontTracker, front_np1::FrontTracker, mesh::SpaceTimeMesh; method::String="VOFI",
+                  compute_centroids::Bool=true, time_panels::Int=16, time_order::Int=4, complement::Bool=false)
+    (front_n.is_closed && front_np1.is_closed) || error("PenguinHIP.Capacity(front_n, front_np1, SpaceTimeMesh): is_closed=false is not supported")
+    sp = mesh.space
+    N = length(sp.dims)
+    N == 2 || error("PenguinHIP.Capacity(front_n, front_np1, SpaceTimeMesh): a moving marker polygon is a 2-D body, the mesh is $(N)-D")
+    p0, p1 = front_n.markers, front_np1.markers
+    length(p0) == length(p1) || error("PenguinHIP.Capacity(front_n, front_np1, SpaceTimeMesh): the fronts have $(length(p0)) and " *
+                                      "$(length(p1)) markers; both need the same count and order")
+    init()
+    t0, t1 = mesh.nodes[end][1], mesh.nodes[end][2]
+    gx, gw = _gauss(time_order)
+    edges = range(t0, t1; length=time_panels + 1)
+    nq = time_panels * time_order
+    tau_w = zeros(2, nq)                               # column k = {tau, w}: the C layout nq x 2
+    k = 0
+    for p in 1:time_panels, i in 1:time_order
+        k += 1
+        a, b = edges[p], edges[p + 1]
+        tau_w[1, k], tau_w[2, k] = (a + b) / 2 + (b - a) / 2 * gx[i], (b - a) / 2 * gw[i]
+    end
+    tau_w[2, :] .*= (t1 - t0) / sum(tau_w[2, :])
+    xy0 = Float64[p[c] for p in p0 for c in 1:2]       # x0 y0 x1 y1 ...; a closing duplicate is dropped by the entry
+    xy1 = Float64[p[c] for p in p1 for c in 1:2]
+    flags = Int32((complement ? 1 : 0) | (compute_centroids ? 0 : 2))
+    hnd = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:pg_capacity_create_spacetime_polygon, libpg), Int32,
+                (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Int64, Int32, Float64, Float64, Int32, Ptr{Float64}, Ptr{Ptr{Cvoid}}),
+                sp.handle, xy0, xy1, length(p0), flags, t0, t1, Int32(nq), tau_w, hnd))
+    layer = _wrap_capacity(hnd[], sp, front_n, compute_centroids)
+    M = prod(sp.dims .+ 1)
+    SpaceTimeCapacity{N}(layer, _field(hnd[], PG_CAP_ST_V0, 0, M), _field(hnd[], PG_CAP_ST_V1, 0, M),
+                         _field(hnd[], PG_CAP_ST_CT_OMEGA, 0, M), compute_centroids ? _field(hnd[], PG_CAP_ST_CT_GAMMA, 0, M) : Float64[],
+                         mesh, front_n)
+end
 DiffusionOps(cap::SpaceTimeCapacity) = DiffusionOps(cap.layer)
 
 # ConvectionOps(capacity, uₒ, uᵧ) of a space-time capacity (2-D+t), as the moving advection-diffusion blocks slice it

@@ -19,7 +19,7 @@ from .api import (  # noqa: F401
     DeviceFunction, dev,
 )
 from .front import (  # noqa: F401,E402
-    FrontTracker, add_marker_b, create_circle_b, create_crystal_b, create_ellipse_b, create_rectangle_b, get_markers,
+    FrontTracker, MovingFront, add_marker_b, create_circle_b, create_crystal_b, create_ellipse_b, create_rectangle_b, get_markers,
     is_point_inside, sdf, set_markers_b,
 )
 from .utils import (  # noqa: F401,E402

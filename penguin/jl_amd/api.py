@@ -227,8 +227,8 @@ Ellipse = Ellipsoid
 def check_front_body(front: FrontTracker, mesh) -> None:
     """what Capacity(front, mesh) refuses before it touches the device"""
     if not hasattr(mesh, "_h"):
-        raise PenguinHipError("Capacity(FrontTracker, SpaceTimeMesh): space-time capacities of a moving front "
-                              "(compute_spacetime_capacities) are not supported; pass the spatial Mesh")
+        raise PenguinHipError("Capacity(FrontTracker, SpaceTimeMesh): one front has no motion; pass a MovingFront or the pair "
+                              "(front_n, front_np1) for the space-time capacities of a moving front, or the spatial Mesh")
     if not front.is_closed:
         raise PenguinHipError("Capacity(FrontTracker): is_closed=False is not supported (the reference substitutes the convex hull "
                               "of the markers for an open front; close the front or pass the hull's markers)")

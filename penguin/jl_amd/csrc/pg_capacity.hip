@@ -125,12 +125,15 @@ __device__ __forceinline__ const PolyBody& kernel_body(const PolyArg& a) { retur
 // bins (poly_edge_bins: at most 2 (n0 + n1) + 3 n0 + n1 visits, whatever the markers are; an edge outside the mesh visits none);
 // the integer atomics fix only WHERE in its bin an edge lands, and k_poly_order then puts every bin in ascending edge order,
 // so the lists, and every sum taken along them, are the same in every run.
-__global__ void k_poly_count(PolyBody b, int* __restrict__ count) {
+// (templates over PolyBody and MovingPoly: a moving polygon lists its swept edges, pg_geom_polygon.h)
+template <class P>
+__global__ void k_poly_count(P b, int* __restrict__ count) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= b.M) return;
   poly_edge_bins(b, k, [&](int bin) { atomicAdd(&count[bin], 1); });
 }
-__global__ void k_poly_fill(PolyBody b, const int* __restrict__ ptr, int* __restrict__ cursor, int* __restrict__ tmp_edge,
+template <class P>
+__global__ void k_poly_fill(P b, const int* __restrict__ ptr, int* __restrict__ cursor, int* __restrict__ tmp_edge,
                             int* __restrict__ tmp_bin) {
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= b.M) return;
@@ -457,6 +460,7 @@ struct MotionView {
 // only read the cell types, never touch the body and serve both.)
 struct StBall {
   static constexpr int MAX_BLOCK = 1024;        // (HIP's default: the closed-form instantiations compile as they always did)
+  static constexpr bool LISTS_TOUCHING = false;
 };
 struct StBallBase {};
 __device__ __forceinline__ StBallBase st_base(const StBall&) { return StBallBase(); }
@@ -467,6 +471,20 @@ __device__ __forceinline__ ProgBody<DevEval> st_base(const StProg& a) { return k
 __device__ __forceinline__ const BallSet& st_body(const StBallBase&, const MotionView& mv, int k) { return mv.bodies[k]; }
 __device__ __forceinline__ ProgBody<DevEval> st_body(ProgBody<DevEval> b, const MotionView& mv, int k) {
   b.t = k < mv.nq ? mv.q[k].tau : k == mv.nq ? mv.t0 : mv.t1;
+  return b;
+}
+
+// A moving marker polygon (MovingPoly of pg_geom_polygon.h: the markers at t0 and t1 and the lookup of the swept edges, all in
+// device memory).  The polygon at slot k is a view that interpolates a vertex when it is read: nothing is stored per node.  The
+// host puts s_k = (tau_k - t0) / (t1 - t0) into MotionNode::c[0]; the faces are taken by slot, never by s.
+struct StPoly : MovingPoly {
+  static constexpr int MAX_BLOCK = 256;
+  static constexpr bool LISTS_TOUCHING = true;  // a cell that is never CUT may own a piece of the front (an edge along its face)
+};
+__device__ __forceinline__ const MovingPoly& st_base(const StPoly& a) { return a; }
+__device__ __forceinline__ MovingPoly st_body(MovingPoly b, const MotionView& mv, int k) {
+  b.face = k < mv.nq ? 0 : k == mv.nq ? 1 : 2;
+  b.s = k < mv.nq ? mv.q[k].c[0] : 0.0;
   return b;
 }
 
@@ -488,12 +506,27 @@ __device__ inline int st_far(const ProgBody<DevEval>& b, const GeoView&, const M
   return prog_st_far(b, lo, hi, mv.t0, mv.t1);
 }
 
+// a polygon: no swept edge in the cell's list -- no edge comes into the closed cell at any time of the slab, so the cell is
+// what its centre is at t0 (parity, from its row's bucket)
+__device__ inline int st_far(const MovingPoly& b, const GeoView&, const MotionView&, const double* lo, const double* hi) {
+  const double cx = 0.5 * (lo[0] + hi[0]), cy = 0.5 * (lo[1] + hi[1]);
+  const int bin = poly_cell_bin(b, poly_locate(b, 0, cx), poly_locate(b, 1, cy));
+  if (b.ptr[bin + 1] > b.ptr[bin]) return 0;
+  MovingPoly f = b;
+  f.face = 1;
+  return poly_fluid_at(f, cx, cy) ? 1 : -1;
+}
+
 // the spatial volume at a time face.  Program bodies: a face that is FULL gets the measure the full cells get (from h, see
 // full_measure), so that V(t1) of one slab and V(t0) of the next are the same bits whichever of the two slabs cuts the cell;
 // the closed-form kinds keep the box's own product of node differences, as they always had
 __device__ __forceinline__ double st_face_volume(const StBallBase&, const GeoView&, const BoxMeasure& m) { return m.vol; }
 __device__ __forceinline__ double st_face_volume(const ProgBody<DevEval>&, const GeoView& g, const BoxMeasure& m) {
   return m.type == PG_FULL ? full_measure(g, -1) : m.vol;
+}
+
+__device__ __forceinline__ double st_face_volume(const MovingPoly&, const GeoView& g, const BoxMeasure& m) {
+  return m.type == PG_FULL ? full_measure(g, -1) : m.vol;     // (as the program bodies: Vn and the next slab's Vn_1 are the same bits)
 }
 
 // the normal speed of the interface at the spatial interface centroid cg of time node q
@@ -514,6 +547,11 @@ __device__ inline double st_normal_speed(const BallSet&, const MotionView& mv, c
 // - d_t phi / |grad phi| at (cg, tau) -- the body carries tau
 __device__ inline double st_normal_speed(const ProgBody<DevEval>& b, const MotionView&, const MotionNode&, const double* cg, int N) {
   return b.normal_speed(cg[0], N > 1 ? cg[1] : 0.0);
+}
+
+// a polygon takes one speed per PIECE of the front, inside box_measure: its gamma already carries sqrt(1 + v_n^2)
+__device__ __forceinline__ double st_normal_speed(const MovingPoly&, const MotionView&, const MotionNode&, const double*, int) {
+  return 0.0;
 }
 
 // Work is split as in the static kernels: a cheap pass over all cells finishes the ones that need no quadrature and
@@ -614,6 +652,14 @@ __global__ __launch_bounds__(St::MAX_BLOCK) void k_st_cells(GeoView g, MotionVie
   if (lane != 0) return;
   if (all_full || all_empty) {
     st_store_plain(g, mv, o, lc, lo, hi, true, all_full);
+    if constexpr (St::LISTS_TOUCHING) {
+      if (gam > 0.0) {                  // never CUT, but it owns a piece of the front: its type, volume and centroid stand
+        o.G[lc] = gam;
+        o.Ctg[lc] = gmt / gam;
+        for (int d = 0; d < g.N; ++d)
+          if (o.Cg[d]) o.Cg[d][lc] = gm[d] / gam;
+      }
+    }
     return;
   }
   double cw[3], cg[3] = {0.0, 0.0, 0.0}, tw = 0.5 * (mv.t0 + mv.t1), tg = 0.0;
@@ -832,6 +878,45 @@ void ensure_gl() {
   g_gl_uploaded = true;
 }
 
+// The edge lookup of `body` (PolyBody: the edges; MovingPoly: the swept edges) on the device: count, scan, fill, order.  The
+// lists stay alive in `t`; ms: the time of the four steps.
+struct PolyBins {
+  DevBuf<int> ptr, idx;
+  double ms = 0.0;
+};
+template <class P>
+void build_poly_bins(const P& body, pg_mesh* m, const char* who, hipStream_t st, PolyBins& t) {
+  const i64 nbins = m->n[0] + m->n[1] + m->n[0] * m->n[1], M = body.M;
+  DevBuf<int> count(nbins + 1), cursor(nbins), d_total(1);
+  t.ptr.alloc(nbins + 1);
+  count.zero();
+  cursor.zero();
+  EventPair bin_ev;
+  PG_HIP(hipEventRecord(bin_ev.e0, st));
+  const dim3 per_edge((unsigned)((M + 255) / 256));
+  hipLaunchKernelGGL(k_poly_count<P>, per_edge, dim3(256), 0, st, body, count.p);
+  PG_HIP(hipGetLastError());
+  scan_exclusive<int>(count.p, t.ptr.p, nbins + 1, d_total.p, st);          // ptr[nbins] = the total
+  int total = 0;
+  d_total.download(&total, 1);
+  PG_REQUIRE(total >= 0, std::string(who) + ": the edge lookup exceeds 2^31 entries");
+  DevBuf<int> tmp_edge(total > 0 ? total : 1), tmp_bin(total > 0 ? total : 1);
+  t.idx.alloc(total > 0 ? total : 1);
+  t.idx.zero();
+  if (total > 0) {                               // (a polygon wholly outside the mesh: no list, nothing to launch)
+    hipLaunchKernelGGL(k_poly_fill<P>, per_edge, dim3(256), 0, st, body, t.ptr.p, cursor.p, tmp_edge.p, tmp_bin.p);
+    PG_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_poly_order, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, st, t.ptr.p, tmp_edge.p, tmp_bin.p, total,
+                       t.idx.p);
+    PG_HIP(hipGetLastError());
+  }
+  PG_HIP(hipEventRecord(bin_ev.e1, st));
+  PG_HIP(hipEventSynchronize(bin_ev.e1));        // (tmp_edge / tmp_bin are freed on return)
+  float ms = 0.f;
+  PG_HIP(hipEventElapsedTime(&ms, bin_ev.e0, bin_ev.e1));
+  t.ms = ms;
+}
+
 // K1 .. K5 on the stored slab of c for the body in `ba`; LANES lanes share a cut box.  An empty work list launches nothing.
 template <int LANES, class BodyArg>
 void run_static_kernels(pg_capacity* c, pg_mesh* m, const BodyArg& ba, hipStream_t st) {
@@ -986,7 +1071,7 @@ void run_spacetime_kernels(pg_capacity* c, pg_mesh* m, const MotionView& mv, con
 
 // c_prog is one table per process: two host threads building program capacities at once take turns
 std::mutex g_prog_mutex;
-// measurement only (pg_debug_spacetime_kernel_timing): each of the six kernels of a program body between its own events
+// measurement only (pg_debug_spacetime_kernel_timing): each of the six kernels of a program or polygon body between its own events
 bool g_st_timing = false;
 
 }  // namespace
@@ -1194,35 +1279,12 @@ int32_t pg_capacity_create_polygon(pg_mesh* m, const double* xy, int64_t M, int3
   for (int d = 0; d < 2; ++d) { pa.n[d] = (int)m->n[d]; pa.nodes[d] = g.nodes[d]; }
   pa.ptr = nullptr;
   pa.idx = nullptr;
-  // ---- the edge lookup: count, scan, fill, order
-  const i64 nbins = m->n[0] + m->n[1] + m->n[0] * m->n[1];
-  DevBuf<int> count(nbins + 1), ptr(nbins + 1), cursor(nbins), d_total(1);
-  count.zero();
-  cursor.zero();
-  EventPair bin_ev;
-  PG_HIP(hipEventRecord(bin_ev.e0, st));
-  const dim3 per_edge((unsigned)((M + 255) / 256));
-  hipLaunchKernelGGL(k_poly_count, per_edge, dim3(256), 0, st, static_cast<const PolyBody&>(pa), count.p);
-  PG_HIP(hipGetLastError());
-  scan_exclusive<int>(count.p, ptr.p, nbins + 1, d_total.p, st);          // ptr[nbins] = the total
-  int total = 0;
-  d_total.download(&total, 1);
-  PG_REQUIRE(total >= 0, "pg_capacity_create_polygon: the edge lookup exceeds 2^31 entries");
-  DevBuf<int> tmp_edge(total > 0 ? total : 1), tmp_bin(total > 0 ? total : 1), idx(total > 0 ? total : 1);
-  idx.zero();
-  if (total > 0) {                               // (a polygon wholly outside the mesh: no list, nothing to launch)
-    hipLaunchKernelGGL(k_poly_fill, per_edge, dim3(256), 0, st, static_cast<const PolyBody&>(pa), ptr.p, cursor.p, tmp_edge.p, tmp_bin.p);
-    PG_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_poly_order, dim3(grid_for(total, 256, 256 * 16)), dim3(256), 0, st, ptr.p, tmp_edge.p, tmp_bin.p, total, idx.p);
-    PG_HIP(hipGetLastError());
-  }
-  PG_HIP(hipEventRecord(bin_ev.e1, st));
-  pa.ptr = ptr.p;
-  pa.idx = idx.p;
+  PolyBins bins;                                 // the edge lookup: count, scan, fill, order
+  build_poly_bins(static_cast<const PolyBody&>(pa), m, "pg_capacity_create_polygon", st, bins);
+  pa.ptr = bins.ptr.p;
+  pa.idx = bins.idx.p;
   run_static_kernels<CUT_LANES>(c, m, pa, st);   // (waits for its last kernel: the lists above outlive every launch)
-  float ms = 0.f;
-  PG_HIP(hipEventElapsedTime(&ms, bin_ev.e0, bin_ev.e1));
-  c->poly_bin_ms = ms;
+  c->poly_bin_ms = bins.ms;
   *out = guard.release();
   PG_API_END
 }
@@ -1417,6 +1479,83 @@ int32_t pg_capacity_create_spacetime_program(pg_mesh* m, const pg_program* phi, 
   sp.N = N;
   sp.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
   run_spacetime_kernels(c, m, mv, sp, ctx().stream, g_st_timing ? c->st_ms_parts : nullptr);
+  *out = guard.release();
+  PG_API_END
+}
+
+// compute_spacetime_capacities(mesh, front_n, front_np1, dt) -- src/front_tracking.jl:1472
+int32_t pg_capacity_create_spacetime_polygon(pg_mesh* m, const double* xy0, const double* xy1, int64_t M, int32_t flags, double t0,
+                                             double t1, int32_t nq, const double* tau_w, pg_capacity** out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(m, "pg_capacity_create_spacetime_polygon: NULL mesh");
+  PG_REQUIRE(out, "pg_capacity_create_spacetime_polygon: NULL output pointer");
+  *out = nullptr;                                // (missing markers or a missing rule are named by spacetime_polygon_check below)
+  PG_REQUIRE(ctx().nranks == 1 && !ctx().comm,
+             "pg_capacity_create_spacetime_polygon: single rank only (polygon bodies on slabs are not supported yet)");
+  M = moving_polygon_open_count(xy0, xy1, M);
+  {
+    std::string why;
+    PG_REQUIRE(spacetime_polygon_check(m->N, xy0, xy1, M, t0, t1, nq, tau_w, &why), "pg_capacity_create_spacetime_polygon refused: " + why);
+  }
+  PG_REQUIRE(m->n[0] < (i64)1 << 30 && m->n[1] < (i64)1 << 30 && m->n[0] + m->n[1] + m->n[0] * m->n[1] < (i64)2147483647 - 1,
+             "pg_capacity_create_spacetime_polygon: the edge lookup exceeds 2^31 bins");
+  const std::vector<double> ccw0 = polygon_normalise_as(xy0, xy0, M), ccw1 = polygon_normalise_as(xy1, xy0, M);
+  AsyncAllocScope pool;   // one capacity per time slab: the stream-ordered allocator (pg_common.h)
+  hipStream_t st = ctx().stream;
+  MotionView mv;
+  std::memset(&mv, 0, sizeof(mv));
+  mv.kind = BODY_BALLS;          // (not read: the body is the polygon; the phase lives in its flip)
+  mv.sgn = 1.0;
+  mv.nq = nq;
+  mv.t0 = t0;
+  mv.t1 = t1;
+  std::vector<MotionNode> hq(nq);
+  for (int k = 0; k < nq; ++k) {
+    std::memset(&hq[k], 0, sizeof(MotionNode));
+    hq[k].tau = tau_w[2 * k];
+    hq[k].w = tau_w[2 * k + 1];
+    hq[k].c[0] = (hq[k].tau - t0) / (t1 - t0);   // s_k of the interpolating view
+  }
+  DevBuf<MotionNode> dq(nq);
+  dq.upload(hq.data(), nq);
+  mv.q = dq.p;
+
+  auto* c = new pg_capacity();
+  std::unique_ptr<pg_capacity> guard(c);
+  c->mesh = m;
+  c->N = 2;
+  c->from_body = false;
+  c->has_cg = !(flags & PG_FLAG_NO_CENTROIDS);
+  std::memset(&c->body, 0, sizeof(c->body));     // (not a BallSet: nothing reads it)
+  c->spacetime = true;
+  c->t0 = t0;
+  c->t1 = t1;
+  c->slab = m->base_slab();
+  ensure_gl();
+  const GeoView g = geo_view(m, c->slab);
+  DevBuf<double> dxy0(2 * M), dxy1(2 * M);
+  dxy0.upload(ccw0.data(), 2 * M);
+  dxy1.upload(ccw1.data(), 2 * M);
+  StPoly sp;
+  sp.N = 2;
+  sp.complement = 0;
+  sp.flip = (flags & PG_FLAG_COMPLEMENT) ? 1 : 0;
+  sp.M = (int)M;
+  sp.xy = dxy0.p;
+  sp.xy1 = dxy1.p;
+  for (int d = 0; d < 2; ++d) { sp.n[d] = (int)m->n[d]; sp.nodes[d] = g.nodes[d]; }
+  sp.ptr = nullptr;
+  sp.idx = nullptr;
+  sp.s = 0.0;
+  sp.dt = t1 - t0;
+  sp.face = 1;
+  PolyBins bins;                                 // of the swept edges: one table for every node and both faces
+  build_poly_bins(static_cast<const MovingPoly&>(sp), m, "pg_capacity_create_spacetime_polygon", st, bins);
+  sp.ptr = bins.ptr.p;
+  sp.idx = bins.idx.p;
+  run_spacetime_kernels(c, m, mv, sp, st, g_st_timing ? c->st_ms_parts : nullptr);   // (waits for its last kernel)
+  c->poly_bin_ms = bins.ms;
   *out = guard.release();
   PG_API_END
 }

@@ -52,14 +52,47 @@ struct PolyBody {
   const int* idx;               // edge ids, ascending in every bin
 };
 
+// A MOVING polygon inside one time slab [t0, t1] (the reference's interpolate_front, src/front_tracking.jl:2289-2307): two marker
+// arrays of the same length and order, every marker on a straight line at constant speed.  The view is the polygon at ONE time:
+// vertex i is xy[i] + s (xy1[i] - xy[i]) in this order of operations, s = (tau - t0) / (t1 - t0), interpolated when it is read --
+// nothing is stored per time.  The two time faces are taken by slot, not by s: face 1 reads xy, face 2 reads xy1, exactly.
+// Its edge lookup lists the SWEPT edge (poly_edge_bins below), so one table serves every time of the slab.  Its front measure
+// carries the space-time factor: Gamma is the sum over the owned pieces of len sqrt(1 + v_n^2), v_n the normal speed at the
+// piece's midpoint, and C_gamma the mean of the midpoints with the same weights (box_measure below).
+struct MovingPoly : PolyBody {
+  const double* xy1;            // 2 M: the markers at t1 (xy: at t0), the same normalisation applied to both
+  double s;                     // (tau - t0) / (t1 - t0) of this view; not read at a face
+  double dt;                    // t1 - t0
+  int face;                     // 0: a time inside the slab, 1: the face t0, 2: the face t1
+};
+
+PG_HD void poly_vertex(const PolyBody& b, int k, double& x, double& y) {
+  x = b.xy[2 * k];
+  y = b.xy[2 * k + 1];
+}
+PG_HD void poly_vertex(const MovingPoly& b, int k, double& x, double& y) {
+  if (b.face == 2) { x = b.xy1[2 * k]; y = b.xy1[2 * k + 1]; return; }
+  x = b.xy[2 * k];
+  y = b.xy[2 * k + 1];
+  if (b.face == 1) return;
+  x = x + b.s * (b.xy1[2 * k] - x);
+  y = y + b.s * (b.xy1[2 * k + 1] - y);
+}
+// the velocity of marker k: (p1 - p0) / (t1 - t0)
+PG_HD void poly_velocity(const MovingPoly& b, int k, double& ux, double& uy) {
+  ux = (b.xy1[2 * k] - b.xy[2 * k]) / b.dt;
+  uy = (b.xy1[2 * k + 1] - b.xy[2 * k + 1]) / b.dt;
+}
+
 PG_HD int poly_col_bin(const PolyBody&, int i) { return i; }
 PG_HD int poly_row_bin(const PolyBody& b, int j) { return b.n[0] + j; }
 PG_HD int poly_cell_bin(const PolyBody& b, int i, int j) { return b.n[0] + b.n[1] + j * b.n[0] + i; }
 
-PG_HD void poly_edge(const PolyBody& b, int k, double& px, double& py, double& qx, double& qy) {
+template <class P>
+PG_HD void poly_edge(const P& b, int k, double& px, double& py, double& qx, double& qy) {
   const int k1 = k + 1 < b.M ? k + 1 : 0;
-  px = b.xy[2 * k]; py = b.xy[2 * k + 1];
-  qx = b.xy[2 * k1]; qy = b.xy[2 * k1 + 1];
+  poly_vertex(b, k, px, py);
+  poly_vertex(b, k1, qx, qy);
 }
 
 // the cell of axis d that holds s: the largest i in [0, n_d - 1] with nodes_d[i] <= s, 0 if there is none
@@ -116,6 +149,30 @@ PG_HD void poly_edge_bins(const PolyBody& b, int k, Visit visit) {
   }
 }
 
+// The bins of the SWEPT edge k of a moving polygon: the bounding box of p0_k, q0_k, p1_k, q1_k.  Both ends move on straight
+// lines, so by convexity every position of the edge during the slab lies inside that box, and the interpolated coordinates
+// leave it by rounding only: the box is widened by 2^-50 of its largest coordinate.  Its columns, its rows and every cell of
+// both; listing an edge where it does not reach is harmless, so the one table serves every time node and both faces.
+template <class Visit>
+PG_HD void poly_edge_bins(const MovingPoly& b, int k, Visit visit) {
+  const int k1 = k + 1 < b.M ? k + 1 : 0;
+  const double x[4] = {b.xy[2 * k], b.xy[2 * k1], b.xy1[2 * k], b.xy1[2 * k1]};
+  const double y[4] = {b.xy[2 * k + 1], b.xy[2 * k1 + 1], b.xy1[2 * k + 1], b.xy1[2 * k1 + 1]};
+  double xa = dmin(dmin(x[0], x[1]), dmin(x[2], x[3])), xz = dmax(dmax(x[0], x[1]), dmax(x[2], x[3]));
+  double ya = dmin(dmin(y[0], y[1]), dmin(y[2], y[3])), yz = dmax(dmax(y[0], y[1]), dmax(y[2], y[3]));
+  const double ex = 0x1p-50 * dmax(fabs(xa), fabs(xz)), ey = 0x1p-50 * dmax(fabs(ya), fabs(yz));
+  xa -= ex; xz += ex; ya -= ey; yz += ey;
+  int c0 = 0, c1 = -1, r0 = 0, r1 = -1;
+  const bool hc = poly_range(b, 0, xa, xz, c0, c1), hr = poly_range(b, 1, ya, yz, r0, r1);
+  if (hc)
+    for (int i = c0; i <= c1; ++i) visit(poly_col_bin(b, i));
+  if (hr)
+    for (int j = r0; j <= r1; ++j) visit(poly_row_bin(b, j));
+  if (!(hc && hr)) return;
+  for (int j = r0; j <= r1; ++j)
+    for (int i = c0; i <= c1; ++i) visit(poly_cell_bin(b, i, j));
+}
+
 // does the edge cross the line x_d = s, and where on the other axis
 PG_HD bool poly_cross(double pd, double po, double qd, double qo, double s, double& c) {
   if ((pd <= s) == (qd <= s)) return false;
@@ -125,7 +182,8 @@ PG_HD bool poly_cross(double pd, double po, double qd, double qo, double s, doub
   return true;
 }
 
-PG_HD bool poly_cross_edge(const PolyBody& b, int k, int d, double s, double& c) {
+template <class P>
+PG_HD bool poly_cross_edge(const P& b, int k, int d, double s, double& c) {
   double px, py, qx, qy;
   poly_edge(b, k, px, py, qx, qy);
   return d == 0 ? poly_cross(px, py, qx, qy, s, c) : poly_cross(py, px, qy, qx, s, c);
@@ -137,7 +195,8 @@ PG_HD int poly_line_bin(const PolyBody& b, int d, double s) {
 }
 
 // is the point fluid
-PG_HD bool poly_fluid_at(const PolyBody& b, double x, double y) {
+template <class P>
+PG_HD bool poly_fluid_at(const P& b, double x, double y) {
   const int bin = poly_line_bin(b, 1, y);
   int below = 0;
   for (int e = b.ptr[bin]; e < b.ptr[bin + 1]; ++e) {
@@ -148,7 +207,8 @@ PG_HD bool poly_fluid_at(const PolyBody& b, double x, double y) {
 }
 
 // fluid length of {x_d = s} and [a, z] on the other axis, z > a; `full`: what a wholly fluid section returns
-PG_HD double poly_section(const PolyBody& b, int d, double s, double a, double z, double full) {
+template <class P>
+PG_HD double poly_section(const P& b, int d, double s, double a, double z, double full) {
   const int bin = poly_line_bin(b, d, s);
   const int e0 = b.ptr[bin], e1 = b.ptr[bin + 1];
   int below = 0, inside = 0;
@@ -179,9 +239,10 @@ PG_HD double poly_section(const PolyBody& b, int d, double s, double a, double z
   return len < z - a ? len : z - a;
 }
 
-// Liang-Barsky: the piece of p -> q inside the closed box, in the edge's direction; false: none of positive length
+// Liang-Barsky: the piece of p -> q inside the closed box, in the edge's direction; false: none of positive length.  lambda: the
+// parameter of the piece's midpoint on the edge, m = p + lambda (q - p)
 PG_HD bool poly_clip(double px, double py, double qx, double qy, double lo0, double lo1, double hi0, double hi1, double& ax,
-                     double& ay, double& bx, double& by) {
+                     double& ay, double& bx, double& by, double& lambda) {
   double t0 = 0.0, t1 = 1.0;
   const double dx = qx - px, dy = qy - py;
   auto side = [&](double p, double q) {          // p t <= q
@@ -198,6 +259,7 @@ PG_HD bool poly_clip(double px, double py, double qx, double qy, double lo0, dou
   };
   if (!side(-dx, px - lo0) || !side(dx, hi0 - px) || !side(-dy, py - lo1) || !side(dy, hi1 - py)) return false;
   if (!(t1 > t0)) return false;
+  lambda = 0.5 * (t0 + t1);
   ax = t0 == 0.0 ? px : px + t0 * dx;
   ay = t0 == 0.0 ? py : py + t0 * dy;
   bx = t1 == 1.0 ? qx : px + t1 * dx;
@@ -205,6 +267,26 @@ PG_HD bool poly_clip(double px, double py, double qx, double qy, double lo0, dou
   ax = dmin(dmax(ax, lo0), hi0); bx = dmin(dmax(bx, lo0), hi0);
   ay = dmin(dmax(ay, lo1), hi1); by = dmin(dmax(by, lo1), hi1);
   return true;
+}
+PG_HD bool poly_clip(double px, double py, double qx, double qy, double lo0, double lo1, double hi0, double hi1, double& ax,
+                     double& ay, double& bx, double& by) {
+  double lambda;
+  return poly_clip(px, py, qx, qy, lo0, lo1, hi0, hi1, ax, ay, bx, by, lambda);
+}
+
+// what a piece of the front weighs: its length -- and for a moving polygon len sqrt(1 + v_n^2), the space-time measure of the
+// strip it sweeps per unit time: v_n = u(m) . n, u(m) = u_p + lambda (u_q - u_p) the velocity of the edge's point at the piece's
+// midpoint (u_i = (p1_i - p0_i) / (t1 - t0)) and n = (dy, -dx) / len the edge's unit normal at this time.  One speed per PIECE:
+// a corner inside a cell has two normals.  Exact for a rigid translation.
+PG_HD double poly_piece_weight(const PolyBody&, int, double, double, double, double len) { return len; }
+PG_HD double poly_piece_weight(const MovingPoly& b, int k, double lambda, double dx, double dy, double len) {
+  const int k1 = k + 1 < b.M ? k + 1 : 0;
+  double upx, upy, uqx, uqy;
+  poly_velocity(b, k, upx, upy);
+  poly_velocity(b, k1, uqx, uqy);
+  const double ux = upx + lambda * (uqx - upx), uy = upy + lambda * (uqy - upy);
+  const double vn = (ux * dy - uy * dx) / len;
+  return len * sqrt(1.0 + vn * vn);
 }
 
 // the cells a box of positive extent overlaps, from the nodes
@@ -227,7 +309,8 @@ PG_HD void poly_part(const PolyBody& b, const double* lo, const double* hi, int 
 }
 
 // type of a box, and (the return value) whether it owns a piece of the front
-PG_HD int pick_ball(const PolyBody& b, const double* lo, const double* hi, int& type) {
+template <class P>
+PG_HD int poly_pick(const P& b, const double* lo, const double* hi, int& type) {
   bool cut = false, own = false;
   if (hi[0] - lo[0] > 0.0 && hi[1] - lo[1] > 0.0) {
     int i0, i1, j0, j1;
@@ -252,12 +335,14 @@ PG_HD int pick_ball(const PolyBody& b, const double* lo, const double* hi, int& 
   return own ? 1 : 0;
 }
 
+PG_HD int pick_ball(const PolyBody& b, const double* lo, const double* hi, int& type) { return poly_pick(b, lo, hi, type); }
+PG_HD int pick_ball(const MovingPoly& b, const double* lo, const double* hi, int& type) { return poly_pick(b, lo, hi, type); }
+
 // qlane / qstride: as ball_box_moments -- this caller takes the edges qlane, qlane + qstride, ... of every cell's list and `group`
 // adds the partial sums up; lane 0 adds the box's own right and top edges.  Mom::m[2], unused in 2-D, counts the pieces that
 // make the box CUT, so that the group's sum carries the type.
-template <class Group = NoGroup>
-PG_HD BoxMeasure box_measure(const PolyBody& b, const double* lo, const double* hi, bool want_surface, const GLTable&, int qlane = 0,
-                             int qstride = 1, Group group = Group()) {
+template <class P, class Group>
+PG_HD BoxMeasure poly_box(const P& b, const double* lo, const double* hi, bool want_surface, int qlane, int qstride, Group group) {
   BoxMeasure o;
   o.vol = 0.0; o.gamma = 0.0;
   for (int d = 0; d < 3; ++d) { o.cen[d] = 0.0; o.cg[d] = 0.0; }
@@ -279,9 +364,9 @@ PG_HD BoxMeasure box_measure(const PolyBody& b, const double* lo, const double* 
         const int bin = poly_cell_bin(b, i, j);
         double sv = 0.0, sm0 = 0.0, sm1 = 0.0;                  // about the part's own lower corner
         for (int e = b.ptr[bin] + qlane; e < b.ptr[bin + 1]; e += qstride) {
-          double px, py, qx, qy, ax, ay, bx, by;
+          double px, py, qx, qy, ax, ay, bx, by, lambda;
           poly_edge(b, b.idx[e], px, py, qx, qy);
-          if (!poly_clip(px, py, qx, qy, s0, s1, z0, z1, ax, ay, bx, by)) continue;
+          if (!poly_clip(px, py, qx, qy, s0, s1, z0, z1, ax, ay, bx, by, lambda)) continue;
           const double mx = 0.5 * (ax + bx), my = 0.5 * (ay + by);
           if (mx > lo[0] && mx < hi[0] && my > lo[1] && my < hi[1]) m.m[2] += 1.0;
           const double ua = ax - s0, ub = bx - s0, va = ay - s1, vb = by - s1, dx = bx - ax, dy = by - ay;
@@ -289,7 +374,7 @@ PG_HD BoxMeasure box_measure(const PolyBody& b, const double* lo, const double* 
           sm0 += (ua * ua + ua * ub + ub * ub) / 6.0 * dy;
           sm1 -= (va * va + va * vb + vb * vb) / 6.0 * dx;
           if (want_surface && mx >= s0 && mx < z0 && my >= s1 && my < z1) {
-            const double len = sqrt(dx * dx + dy * dy);
+            const double len = poly_piece_weight(b, b.idx[e], lambda, dx, dy, sqrt(dx * dx + dy * dy));
             m.gamma += len;
             m.gm[0] += len * (mx - lo[0]);
             m.gm[1] += len * (my - lo[1]);
@@ -336,11 +421,29 @@ PG_HD BoxMeasure box_measure(const PolyBody& b, const double* lo, const double* 
   return o;
 }
 
+template <class Group = NoGroup>
+PG_HD BoxMeasure box_measure(const PolyBody& b, const double* lo, const double* hi, bool want_surface, const GLTable&, int qlane = 0,
+                             int qstride = 1, Group group = Group()) {
+  return poly_box(b, lo, hi, want_surface, qlane, qstride, group);
+}
+template <class Group = NoGroup>
+PG_HD BoxMeasure box_measure(const MovingPoly& b, const double* lo, const double* hi, bool want_surface, const GLTable&,
+                             int qlane = 0, int qstride = 1, Group group = Group()) {
+  return poly_box(b, lo, hi, want_surface, qlane, qstride, group);
+}
+
 // fluid measure of {x_d = s} and the box.  With no crossing strictly inside: the caller's full measure, or 0
-PG_HD double section_measure(const PolyBody& b, int d, double s, const double* lo, const double* hi, double full_measure = -1.0) {
+template <class P>
+PG_HD double poly_section_measure(const P& b, int d, double s, const double* lo, const double* hi, double full_measure) {
   const double a = d == 0 ? lo[1] : lo[0], z = d == 0 ? hi[1] : hi[0];
   if (!(z - a > 0.0)) return 0.0;
   return poly_section(b, d, s, a, z, full_measure >= 0.0 ? full_measure : z - a);
+}
+PG_HD double section_measure(const PolyBody& b, int d, double s, const double* lo, const double* hi, double full_measure = -1.0) {
+  return poly_section_measure(b, d, s, lo, hi, full_measure);
+}
+PG_HD double section_measure(const MovingPoly& b, int d, double s, const double* lo, const double* hi, double full_measure = -1.0) {
+  return poly_section_measure(b, d, s, lo, hi, full_measure);
 }
 
 // ---- host only -----------------------------------------------------------------------------------------------------------------
@@ -422,11 +525,68 @@ inline std::vector<double> polygon_normalise(const double* xy, int64_t M) {
   return out;
 }
 
+// the markers the kernels see of a moving polygon: the reversal is decided by the signed area at t0 and applied to both arrays
+inline std::vector<double> polygon_normalise_as(const double* xy, const double* like, int64_t M) {
+  std::vector<double> out(xy, xy + 2 * M);
+  if (polygon_area2(like, M) < 0.0)
+    for (int64_t k = 1; k < M; ++k) {
+      out[2 * k] = xy[2 * (M - k)];
+      out[2 * k + 1] = xy[2 * (M - k) + 1];
+    }
+  return out;
+}
+
+// markers of a moving polygon without the closing duplicate: it is dropped where BOTH arrays close (one that closes alone keeps
+// it, and is refused for its zero-length edge)
+inline int64_t moving_polygon_open_count(const double* xy0, const double* xy1, int64_t M) {
+  return (xy0 && xy1 && polygon_open_count(xy0, M) == M - 1 && polygon_open_count(xy1, M) == M - 1) ? M - 1 : M;
+}
+
+// Host only: what pg_capacity_create_spacetime_polygon refuses before it allocates anything, each with its own message (the
+// mesh, the output pointer and the ranks are the caller's to check).  M: without the closing duplicate.  The polygon must be
+// simple (polygon_body_check's rules) at t0, at t1 and at mid time -- NOT at every time in between -- and keep its orientation.
+inline bool spacetime_polygon_check(int N, const double* xy0, const double* xy1, int64_t M, double t0, double t1, int nq,
+                                    const double* tau_w /* nq x 2 */, std::string* why) {
+  auto fail = [&](const std::string& m) {
+    if (why) *why = m;
+    return false;
+  };
+  if (!xy0) return fail("xy0 == NULL: the markers at t0 are needed");
+  if (!xy1) return fail("xy1 == NULL: the markers at t1 are needed");
+  if (!tau_w) return fail("tau_w == NULL: the time nodes and weights are needed");
+  if (N != 2) return fail("a moving marker polygon is a 2-D body, the mesh is " + std::to_string(N) + "-D");
+  if (M < 3) return fail("a polygon needs at least 3 markers (got " + std::to_string((long long)(M < 0 ? 0 : M)) + ")");
+  if (M > 100000000) return fail("more than 1e8 markers");
+  for (int e = 0; e < 2; ++e)
+    for (int64_t k = 0; k < 2 * M; ++k)
+      if (!std::isfinite((e ? xy1 : xy0)[k]))
+        return fail("marker " + std::to_string((long long)(k / 2)) + " has a non-finite coordinate at " + (e ? "t1" : "t0"));
+  if (nq < 1 || nq > 4096) return fail("1 .. 4096 time nodes");
+  if (!(t1 > t0)) return fail("empty time slab");
+  double wsum = 0.0;
+  for (int k = 0; k < nq; ++k) {
+    if (!(tau_w[2 * k] > t0 && tau_w[2 * k] < t1)) return fail("time nodes must lie inside (t0, t1)");
+    wsum += tau_w[2 * k + 1];
+  }
+  if (!(fabs(wsum - (t1 - t0)) <= 1e-12 * (t1 - t0))) return fail("time weights must add up to t1 - t0");
+  std::vector<double> mid((size_t)(2 * M));
+  for (int64_t k = 0; k < 2 * M; ++k) mid[(size_t)k] = xy0[k] + 0.5 * (xy1[k] - xy0[k]);
+  for (int e = 0; e < 3; ++e) {
+    std::string w;
+    if (!polygon_body_check(e == 0 ? xy0 : e == 1 ? xy1 : mid.data(), M, &w))
+      return fail(std::string(e == 0 ? "at t0: " : e == 1 ? "at t1: " : "at mid time: ") + w);
+  }
+  if ((polygon_area2(xy0, M) > 0.0) != (polygon_area2(xy1, M) > 0.0) || (polygon_area2(xy0, M) > 0.0) != (polygon_area2(mid.data(), M) > 0.0))
+    return fail("the orientation of the polygon differs between t0 and t1 (the front turns inside out during the slab)");
+  return true;
+}
+
 // the edge lookup, built on the host (the CPU tests; the product builds it on the device with the same poly_edge_bins)
 struct PolyBinsHost {
   std::vector<int> ptr, idx;
 };
-inline PolyBinsHost polygon_bins_host(PolyBody b) {
+template <class P>
+inline PolyBinsHost polygon_bins_host(P b) {
   const int nb = b.n[0] + b.n[1] + b.n[0] * b.n[1];
   PolyBinsHost t;
   t.ptr.assign((size_t)nb + 1, 0);

@@ -2,7 +2,8 @@
 interior is the fluid.  `Capacity(front, mesh)` sends the markers to pg_capacity_create_polygon, where the capacity kernels
 measure the polygon itself (penguin/jl_amd/csrc/pg_geom_polygon.h).  Everything in this file runs on the host in numpy: the
 marker generators with the reference's formulas, `is_point_inside` and `sdf` -- the object is callable as front(x, y) and returns
-the signed distance, negative inside, so that cap.body behaves like the other bodies.  The `_b` suffix stands for `!`."""
+the signed distance, negative inside, so that cap.body behaves like the other bodies.  The `_b` suffix stands for `!`.
+MovingFront is a front that moves: a callable t -> markers, for Capacity(mf, SpaceTimeMesh(...)) and the moving solvers."""
 from __future__ import annotations
 
 import math
@@ -158,3 +159,77 @@ def sdf(ft: FrontTracker, x, y):
     dist = np.min(np.hypot(X - (p[:, 0] + t * ex), Y - (p[:, 1] + t * ey)), axis=-1)
     out = np.where(is_point_inside(ft, x, y), -dist, dist)
     return out if x.shape else float(out)
+
+
+class MovingFront:
+    """MovingFront(markers_of_t, complement=False): a marker polygon that moves.  `markers_of_t(t)` returns the (M, 2) markers at
+    time t, the same count and order at every t.  `Capacity(mf, SpaceTimeMesh(mesh, [t, t + Δt]))` evaluates it at the slab's two
+    times only and moves every marker on a straight line at constant speed in between -- the reference's interpolate_front
+    (src/front_tracking.jl:2289-2307) inside compute_spacetime_capacities (:1472); the prescribed-motion drivers take it as
+    `body`, and `MovingFront(..., complement=True)` (fluid outside) as `body_c`.  Callable as mf(x, y, t): the signed distance to
+    the polygon of `markers_of_t(t)`, negative in the fluid."""
+
+    def __init__(self, markers_of_t, complement: bool = False):
+        if not callable(markers_of_t):
+            raise TypeError("MovingFront: markers_of_t must be callable, t -> (M, 2) markers (two fronts: MovingFront.from_fronts)")
+        self.markers_of_t, self.complement = markers_of_t, bool(complement)
+        self._count = None
+
+    def markers(self, t: float) -> np.ndarray:
+        """the (M, 2) markers at t, as float64; the count must not change between calls"""
+        p = np.ascontiguousarray(np.asarray(self.markers_of_t(float(t)), dtype=np.float64))
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"MovingFront: markers_of_t(t) must return an (M, 2) array, got shape {p.shape}")
+        if self._count is None:
+            self._count = len(p)
+        elif len(p) != self._count:
+            raise ValueError(f"MovingFront: {len(p)} markers at t = {t}, {self._count} before: the count and order must not change")
+        return p
+
+    def at(self, t: float) -> FrontTracker:
+        return FrontTracker([tuple(r) for r in self.markers(t)])
+
+    def __call__(self, x, y, t, *_):
+        d = sdf(self.at(t), x, y)
+        return -d if self.complement else d
+
+    def __repr__(self):
+        return f"MovingFront({self._count if self._count is not None else '?'} markers, complement={self.complement})"
+
+    @classmethod
+    def rigid(cls, front, shift=None, angle=None, about=(0.0, 0.0), complement: bool = False) -> "MovingFront":
+        """the markers of `front` (a FrontTracker or an (M, 2) array) turned by angle(t) about `about`, then moved by shift(t)"""
+        base = front.polygon() if isinstance(front, FrontTracker) else np.asarray(front, dtype=np.float64).reshape(-1, 2)
+        c = np.asarray(about, dtype=np.float64)
+
+        def markers_of_t(t):
+            a = float(angle(t)) if angle is not None else 0.0
+            d = np.asarray(shift(t), dtype=np.float64) if shift is not None else np.zeros(2)
+            ca, sa = math.cos(a), math.sin(a)
+            r = base - c
+            return np.column_stack([c[0] + ca * r[:, 0] - sa * r[:, 1] + d[0], c[1] + sa * r[:, 0] + ca * r[:, 1] + d[1]])
+        return cls(markers_of_t, complement)
+
+    @classmethod
+    def from_fronts(cls, fronts, times, complement: bool = False) -> "MovingFront":
+        """piecewise linear in time through the given fronts (FrontTrackers or (M, 2) arrays) at the ascending `times`; exactly
+        fronts[i] at times[i]"""
+        P = [f.polygon() if isinstance(f, FrontTracker) else np.asarray(f, dtype=np.float64).reshape(-1, 2) for f in fronts]
+        T = [float(t) for t in times]
+        if len(P) != len(T) or len(P) < 2:
+            raise ValueError("MovingFront.from_fronts: as many times as fronts, at least two")
+        if any(b <= a for a, b in zip(T[:-1], T[1:])):
+            raise ValueError("MovingFront.from_fronts: the times must ascend")
+        if any(p.shape != P[0].shape for p in P):
+            raise ValueError("MovingFront.from_fronts: every front needs the same number of markers")
+
+        def markers_of_t(t):
+            if not T[0] <= t <= T[-1]:
+                raise ValueError(f"MovingFront.from_fronts: t = {t} outside [{T[0]}, {T[-1]}]")
+            for i, ti in enumerate(T):
+                if t == ti:
+                    return P[i].copy()
+            i = int(np.searchsorted(T, t)) - 1
+            s = (t - T[i]) / (T[i + 1] - T[i])
+            return P[i] + s * (P[i + 1] - P[i])
+        return cls(markers_of_t, complement)

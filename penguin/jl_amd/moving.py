@@ -13,7 +13,10 @@ there (pg_solver_create_moving_mono) and solves; the host only evaluates the mot
 user's closures.  The level set of the reference is an arbitrary `body(x..., t)`; here it is a tagged moving body, as for
 static capacities, or any closure wrapped in DeviceFunction: `Capacity(DeviceFunction(lambda x, y, t: ...), STmesh)` traces it
 once and evaluates phi, its gradient and d phi / dt inside the space-time kernels (pg_capacity_create_spacetime_program,
-DESIGN.md section 24); the drivers take it as `body`, and `DeviceFunction(fn, complement=True)` as `body_c`.  A plain callable
+DESIGN.md section 24); the drivers take it as `body`, and `DeviceFunction(fn, complement=True)` as `body_c`.  A marker polygon
+that moves is a MovingFront (front.py): `Capacity(mf, STmesh)`, or `Capacity((front_n, front_np1), STmesh)` as the reference's
+compute_spacetime_capacities is called, sends the markers at the slab's two times to pg_capacity_create_spacetime_polygon
+(DESIGN.md section 26); the drivers take `mf` as `body` and `MovingFront(..., complement=True)` as `body_c`.  A plain callable
 is refused (integrate it yourself and use SpaceTimeCapacity.from_arrays).
 1-D and 2-D in space: the reference's 3-D+t selection `[1:end÷2]` drops the z direction."""
 from __future__ import annotations
@@ -27,6 +30,7 @@ from . import _lib as L
 from . import api
 from ._lib import PenguinHipError
 from .devfn import DeviceFunction, pg_program
+from .front import MovingFront
 
 
 class SpaceTimeMesh:
@@ -131,6 +135,10 @@ class SpaceTimeCapacity(api.Capacity):
                  time_panels: int = 16, time_order: int = 4, complement: bool = False):
         if isinstance(body, api.FrontTracker):
             api.check_front_body(body, mesh)
+        if isinstance(body, MovingFront) or (isinstance(body, (tuple, list)) and len(body) == 2
+                                             and all(isinstance(f, api.FrontTracker) for f in body)):
+            self._init_front(body, mesh, compute_centroids, time_panels, time_order, complement)
+            return
         if complement:
             if not isinstance(body, DeviceFunction):
                 raise PenguinHipError("Capacity(complement=True) is for DeviceFunction bodies; tagged bodies take complement=True themselves")
@@ -190,9 +198,44 @@ class SpaceTimeCapacity(api.Capacity):
                                                              C.c_double(t0), C.c_double(t1), C.c_int32(len(tau)),
                                                              L.dptr(self._nodes), C.byref(self._h)))
 
+    def _init_front(self, body, mesh: SpaceTimeMesh, compute_centroids: bool, time_panels: int, time_order: int, complement: bool):
+        """Capacity(mf, STmesh) with a MovingFront, or Capacity((front_n, front_np1), STmesh) -- the reference's
+        compute_spacetime_capacities(mesh, front_n, front_np1, dt) (src/front_tracking.jl:1472): the markers at the slab's two
+        times go to pg_capacity_create_spacetime_polygon, which moves every marker on a straight line in between.  cap.body is a
+        MovingFront either way."""
+        t0, t1 = mesh.time
+        if isinstance(body, MovingFront):
+            if complement:
+                raise PenguinHipError("Capacity(MovingFront, complement=True): the MovingFront carries its own flag, "
+                                      "MovingFront(..., complement=True)")
+            p0, p1 = body.markers(t0), body.markers(t1)
+        else:
+            for f in body:
+                if not f.is_closed:
+                    raise PenguinHipError("Capacity((front_n, front_np1), SpaceTimeMesh): is_closed=False is not supported")
+            p0, p1 = body[0].polygon(), body[1].polygon()
+            if len(p0) != len(p1):
+                raise PenguinHipError(f"Capacity((front_n, front_np1), SpaceTimeMesh): the fronts have {len(p0)} and {len(p1)} "
+                                      "markers; both need the same count and order")
+            body = MovingFront.from_fronts([p0, p1], [t0, t1], complement=complement)
+        L.init()
+        self.stmesh, self.mesh, self.body, self.compute_centroids = mesh, mesh.space, body, compute_centroids
+        self.complement = body.complement
+        tau, wt = time_rule(t0, t1, time_panels, time_order)
+        self._nodes = np.ascontiguousarray(np.column_stack([tau, wt]))
+        self._xy0 = np.ascontiguousarray(p0.reshape(-1), dtype=np.float64)
+        self._xy1 = np.ascontiguousarray(p1.reshape(-1), dtype=np.float64)
+        self._h = C.c_void_p()
+        self._cache = {}
+        flags = (L.PG_FLAG_COMPLEMENT if body.complement else 0) | (0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
+        L.check(L.lib().pg_capacity_create_spacetime_polygon(self.mesh._h, L.dptr(self._xy0), L.dptr(self._xy1),
+                                                             C.c_int64(len(self._xy0) // 2), C.c_int32(flags), C.c_double(t0),
+                                                             C.c_double(t1), C.c_int32(len(tau)), L.dptr(self._nodes),
+                                                             C.byref(self._h)))
+
     @property
     def spacetime_kernel_ms(self):
-        """measurement, program bodies: ({kernel: ms}, cells the cheap pass left to the list).  The times are those of this slab's
+        """measurement, program and polygon bodies: ({kernel: ms}, cells the cheap pass left to the list).  The times are those of this slab's
         six kernels when the capacity was built under `spacetime_kernel_timing(True)`, 0 otherwise and for a kernel not launched."""
         ms, n = (C.c_double * 6)(), C.c_int64(0)
         L.check(L.lib().pg_debug_capacity_spacetime_ms_parts(self._h, ms, C.byref(n)))
