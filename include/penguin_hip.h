@@ -587,6 +587,21 @@ int32_t pg_debug_program_eval(const pg_program* prog, int64_t npts, const double
    host threads are serialised by a mutex inside, each holding it until its last kernel has run. */
 int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_program* grad /* N programs */, int32_t flags,
                                    pg_capacity** out);
+/* Capacity(body::Function, mesh) of the reference (src/capacity.jl:51-123) for an ARBITRARY level set in 3-D: phi(x, y, z) as a
+   program and the 3 programs of d phi / dx, d phi / dy, d phi / dz; fluid where phi <= 0, flags as pg_capacity_create_program.
+   The same five kernels with the 3-D rule of csrc/pg_geom_program3.h: a cell is classified on 9 samples
+   of each of its 12 edges, its 6 face centres and its centre; a cut box is integrated by one wave, heights along the axis with
+   the largest |d phi / d x_d| at the box centre, the 2-D rule of pg_capacity_create_program in the plane of every outer
+   Gauss-Legendre node, outer breakpoints at the roots of phi on the 4 box edges along the outer axis; a face is the 2-D rule on
+   the slice x_d = const, 16 lanes per face.  Cells in which the trace of the interface on a face turns back along the outer
+   axis, or the derivative along the height axis vanishes (around the "poles" of a closed body), are integrated across a
+   square-root singularity: about 1e-3 of a cell there, rounding elsewhere.  Results are bitwise repeatable.  Refused before
+   anything is allocated, each with its own message: a missing or invalid program; a program that reads t; a mesh that is not
+   3-D; grad == NULL; more than one rank or a communicator; a gradient that disagrees with central differences of phi
+   (pg_capacity_create_program's rule and tolerance).  *out is NULL after a refusal.  The __constant__ table and its mutex are
+   pg_capacity_create_program's, which keeps refusing a 3-D mesh. */
+int32_t pg_capacity_create_program3(pg_mesh* m, const pg_program* phi, const pg_program* grad /* 3 programs */, int32_t flags,
+                                    pg_capacity** out);
 /* Capacity(front::FrontTracker, mesh) (PG_BODY_POLYGON): a simple closed polygon of M >= 3 markers in 2-D, xy = x0 y0 x1 y1 ...;
    fluid is the interior (the reference's get_fluid_polygon), PG_FLAG_COMPLEMENT: the exterior, PG_FLAG_NO_CENTROIDS as for the
    other kinds.  A closing duplicate of the first marker is dropped and the orientation is normalised to counter-clockwise.  The

@@ -720,15 +720,28 @@ function gradient_programs(df::DeviceFunction, N::Integer)
     end
     out
 end
-function Capacity(body::DeviceFunction, mesh::Mesh{N}; method::String="VOFI", compute_centroids::Bool=true, complement::Bool=false) where N
-    N == 3 && error("PenguinHIP.Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D)")
+# quadrature="height": the 3-D rule of a traced level set (csrc/pg_geom_program3.h, pg_capacity_create_program3), opt-in under its
+# own name; without it a 3-D mesh keeps its refusal, and with it a 1-D or 2-D mesh is refused (they need no keyword)
+function Capacity(body::DeviceFunction, mesh::Mesh{N}; method::String="VOFI", compute_centroids::Bool=true, complement::Bool=false,
+                  quadrature::Union{Nothing, String}=nothing) where N
+    if quadrature !== nothing
+        quadrature == "height" || error("PenguinHIP.Capacity(quadrature=$(repr(quadrature))): the only rule to choose is \"height\", for a DeviceFunction body on a 3-D mesh")
+        N == 3 || error("PenguinHIP.Capacity(quadrature=\"height\") is the rule of a 3-D mesh; this mesh is $N-D and needs no keyword")
+    end
+    N == 3 && quadrature === nothing &&
+        error("PenguinHIP.Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D) without quadrature=\"height\", the keyword that chooses the 3-D rule")
     init()
     phi = body_program(body, N)
     grad = reduce(vcat, gradient_programs(body, N))          # N programs, contiguous as the C array
     flags = Int32((complement ? 1 : 0) | (compute_centroids ? 0 : 2))
     h = Ref{Ptr{Cvoid}}(C_NULL)
-    check(ccall((:pg_capacity_create_program, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
-                mesh.handle, phi, grad, flags, h))
+    if N == 3
+        check(ccall((:pg_capacity_create_program3, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                    mesh.handle, phi, grad, flags, h))
+    else
+        check(ccall((:pg_capacity_create_program, libpg), Int32, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Ptr{Cvoid}}),
+                    mesh.handle, phi, grad, flags, h))
+    end
     _wrap_capacity(h[], mesh, body, compute_centroids)
 end
 # ---- FrontTracker (src/front_tracking.jl:5-266): a closed polyline of markers whose interior is the fluid.  Capacity(front, mesh)

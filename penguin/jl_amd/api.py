@@ -243,16 +243,27 @@ class Capacity:
 
     Fields A, B, W (N-tuples), V, Γ are the DIAGONALS of the reference's diagonal matrices (length
     M = prod(n_d+1)); C_ω, C_γ are (M,N) arrays; cell_types is the Float64 vector.  They are fetched
-    from the GPU on first access.  `body` is a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace / Plane) or, in 1-D
-    and 2-D, any level set wrapped in DeviceFunction: `Capacity(DeviceFunction(lambda x, y: ...), mesh)` traces the closure and
+    from the GPU on first access.  `body` is a tagged body (Sphere / MultiSphere / Ellipsoid / HalfSpace / Plane) or any level set
+    wrapped in DeviceFunction; in 3-D under the keyword `quadrature="height"`, the rule of csrc/pg_geom_program3.h:
+    `Capacity(DeviceFunction(lambda x, y, z: ...), mesh, quadrature="height")` (without it a 3-D mesh is refused).  In 1-D
+    and 2-D: `Capacity(DeviceFunction(lambda x, y: ...), mesh)` traces the closure and
     its derivatives and evaluates them inside the capacity kernels (fluid where it is <= 0; `complement=True`: where it is
     >= 0, the other phase; `cap.body` stays callable as the closure, negated for the complement).  A plain callable needs DeviceFunction or precomputed arrays: Capacity.from_arrays(...).
     `Capacity(front, mesh)` with a FrontTracker (2-D): the closed polygon of its markers, interior fluid, measured by the same
     kernels (src/capacity.jl:472-598); `complement=True`: the exterior."""
 
-    def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True, complement: bool = False):
+    def __init__(self, body, mesh: Mesh, method: str = "VOFI", compute_centroids: bool = True, complement: bool = False,
+                 quadrature: Optional[str] = None):
         if method not in ("VOFI", "ImplicitIntegration"):
             raise ValueError('method must be "VOFI" or "ImplicitIntegration"')
+        if quadrature is not None:
+            # the 3-D rule of a traced level set is opt-in under its own name (csrc/pg_geom_program3.h)
+            if quadrature != "height":
+                raise PenguinHipError(f'Capacity(quadrature={quadrature!r}): the only rule to choose is "height", for a DeviceFunction body on a 3-D mesh')
+            if not isinstance(body, DeviceFunction):
+                raise PenguinHipError('Capacity(quadrature="height") is for DeviceFunction bodies: ' + type(body).__name__ + " bodies have their own rule")
+            if mesh.N != 3:
+                raise PenguinHipError(f'Capacity(quadrature="height") is the rule of a 3-D mesh; this mesh is {mesh.N}-D and needs no keyword')
         if isinstance(body, FrontTracker):
             self._init_front(body, mesh, compute_centroids, complement)
             return
@@ -267,8 +278,9 @@ class Capacity:
                 "Capacity: arbitrary level-set callables cannot be evaluated on the GPU; pass a tagged body "
                 "(Sphere, MultiSphere, Ellipsoid, HalfSpace, Plane), wrap the closure in DeviceFunction (1-D and 2-D: it is "
                 "traced and evaluated in the kernels) or use Capacity.from_arrays with precomputed capacities")
-        if program_body and mesh.N == 3:
-            raise PenguinHipError("Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D)")
+        if program_body and mesh.N == 3 and quadrature is None:
+            raise PenguinHipError("Capacity(DeviceFunction): 3-D program bodies are not supported yet (1-D and 2-D) without "
+                                  'quadrature="height", the keyword that chooses the 3-D rule')
         L.init()
         self.mesh = mesh
         self.body = body
@@ -278,10 +290,11 @@ class Capacity:
             phi = body.body_program(mesh.N)
             grad = (pg_program * mesh.N)(*body.gradient_programs(mesh.N))
             self._h = C.c_void_p()
-            L.check(L.lib().pg_capacity_create_program(mesh._h, C.byref(phi), grad,
-                                                       C.c_int32((0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
-                                                                 | (L.PG_FLAG_COMPLEMENT if body.complement else 0)),
-                                                       C.byref(self._h)))
+            create = L.lib().pg_capacity_create_program3 if mesh.N == 3 else L.lib().pg_capacity_create_program
+            L.check(create(mesh._h, C.byref(phi), grad,
+                           C.c_int32((0 if compute_centroids else L.PG_FLAG_NO_CENTROIDS)
+                                     | (L.PG_FLAG_COMPLEMENT if body.complement else 0)),
+                           C.byref(self._h)))
             self._cache = {}
             return
         kind, params, flags = body._abi(mesh.N)

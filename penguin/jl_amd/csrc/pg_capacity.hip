@@ -13,6 +13,7 @@
 // cell.  Compiled with -ffp-contract=off: classification must match the oracle bit for bit.
 #include "pg_capacity.h"
 #include "pg_geom_program.h"
+#include "pg_geom_program3.h"
 #include "pg_geom_polygon.h"
 #include "pg_scan.h"
 
@@ -20,14 +21,16 @@
 #include <cmath>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 
 using namespace pg;
 using namespace pggeom;
 
 __constant__ GLTable c_gl;
-// the programs of the traced level set under construction: phi, d phi / dx, d phi / dy, d phi / dt (moving bodies).  (Not in
-// the unnamed namespace: a variable with internal linkage that no device code writes is folded to its zero initialiser.)
-__constant__ pg_program c_prog[4];
+// the programs of the traced level set under construction: phi, d phi / dx, d phi / dy, d phi / dt (moving bodies), d phi / dz
+// (3-D bodies).  (Not in the unnamed namespace: a variable with internal linkage that no device code writes is folded to its
+// zero initialiser.)
+__constant__ pg_program c_prog[5];
 
 namespace {
 
@@ -99,7 +102,7 @@ struct ProgStack {
   __device__ void set(int d, double x) { col[d * PROG_BLOCK] = x; }
 };
 
-__device__ __noinline__ double prog_value(int which, double* col, double x, double y, double t) {
+__device__ __noinline__ __attribute__((flatten)) double prog_value(int which, double* col, double x, double y, double t) {
   ProgStack S{col};
   return pgprog::prog_eval(c_prog[__builtin_amdgcn_readfirstlane(which)], x, y, 0.0, t, S);
 }
@@ -112,6 +115,32 @@ struct DevEval {
 __device__ __forceinline__ ProgBody<DevEval> kernel_body(const ProgArg& a) {
   __shared__ double stack[PG_PROG_MAX_STACK * PROG_BLOCK];
   return ProgBody<DevEval>{a.N, 0, a.sgn, DevEval{stack + threadIdx.x}};
+}
+
+// A traced level set in 3-D (pg_geom_program3.h): the same table, slot 4 holding d phi / dz, an evaluator of its own that passes
+// z on, and the same LDS columns.  One WAVE shares a cut box (lane l: outer node l & 15, inner nodes l >> 4, (l >> 4) + 4, ...);
+// the faces the cell types do not finish go to a work list, 16 lanes per item (SECTION_LIST).
+struct Prog3Arg {
+  static constexpr int MAX_BLOCK = PROG_BLOCK;
+  static constexpr bool LISTS_TOUCHING = false;
+  double sgn;
+};
+
+// (flatten, here and on prog_value: prog_eval is part of each evaluator whatever the number of its callers -- left to the
+// inliner, a second caller put it out of line and gave every ProgArg kernel a call level and 56 bytes of scratch)
+__device__ __noinline__ __attribute__((flatten)) double prog_value3(int which, double* col, double x, double y, double z, double t) {
+  ProgStack S{col};
+  return pgprog::prog_eval(c_prog[__builtin_amdgcn_readfirstlane(which)], x, y, z, t, S);
+}
+
+struct DevEval3 {
+  double* col;
+  __device__ double value(int which, double x, double y, double z) const { return prog_value3(which, col, x, y, z, 0.0); }
+};
+
+__device__ __forceinline__ Prog3Body<DevEval3> kernel_body(const Prog3Arg& a) {
+  __shared__ double stack[PG_PROG_MAX_STACK * PROG_BLOCK];
+  return Prog3Body<DevEval3>{3, 0, a.sgn, DevEval3{stack + threadIdx.x}};
 }
 
 // A marker polygon: the body is the struct itself (markers, mesh nodes and the edge lookup, all in device memory).
@@ -311,6 +340,73 @@ __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_sections(GeoView g, Body
   }
 }
 
+// K2 + K4 of a 3-D traced level set.  A section there is a 2-D quadrature: k_sections_list finishes the faces of FULL and EMPTY
+// cells as k_sections does and lists the others as (cell, 2 d + (0: A, 1: B)); k_sections_cut measures every item with a group of
+// SEC_LANES lanes that share the Gauss-Legendre nodes of the 2-D rule.
+constexpr int SEC_LANES = 16;   // = NGL
+
+__global__ void k_sections_list(GeoView g, i64 Mloc, const double* ct, double* A0, double* A1, double* A2, double* B0, double* B1,
+                                double* B2, int* list, int* count, int cap) {
+  double* A[3] = {A0, A1, A2};
+  double* B[3] = {B0, B1, B2};
+  for (i64 lc = blockIdx.x * (i64)blockDim.x + threadIdx.x; lc < Mloc; lc += (i64)gridDim.x * blockDim.x) {
+    i64 idx[3];
+    decode_cell(g.N, g.ext, g.plane, g.s0, lc, idx);
+    const bool real = is_real_cell(g, idx);
+    for (int d = 0; d < g.N; ++d) {
+      bool others_real = true;
+      for (int k = 0; k < g.N; ++k)
+        if (k != d && idx[k] >= g.n[k]) others_real = false;
+      double a = 0.0, b = 0.0;
+      if (others_real) {
+        double t = (double)PG_CUT;
+        if (real) t = ct[lc];
+        else if (idx[d] >= g.n[d] && lc - g.stride[d] >= 0) t = ct[lc - g.stride[d]];
+        if (t == (double)PG_FULL) {
+          a = full_measure(g, d);
+          b = real ? a : 0.0;
+        } else if (t != (double)PG_EMPTY) {
+          const int want = real ? 2 : 1;
+          const int slot = atomicAdd(count, want);
+          for (int q = 0; q < want; ++q)
+            if (slot + q < cap) { list[2 * (slot + q)] = (int)lc; list[2 * (slot + q) + 1] = 2 * d + q; }
+        }
+      }
+      A[d][lc] = a;
+      B[d][lc] = b;
+    }
+  }
+}
+
+template <class BodyArg>
+__global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_sections_cut(GeoView g, BodyArg ba, const int* __restrict__ list, int nlist,
+                                                                     const double* Cw0, const double* Cw1, const double* Cw2,
+                                                                     double* A0, double* A1, double* A2, double* B0, double* B1,
+                                                                     double* B2) {
+  const auto& bs = kernel_body(ba);
+  const i64 gt = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+  const int ql = (int)(gt % SEC_LANES);
+  i64 k = gt / SEC_LANES;
+  const bool live = k < nlist;
+  if (!live) k = nlist - 1;         // whole groups stay in the shuffles
+  const i64 lc = list[2 * k];
+  const int d = list[2 * k + 1] >> 1, which = list[2 * k + 1] & 1;
+  i64 idx[3];
+  decode_cell(g.N, g.ext, g.plane, g.s0, lc, idx);
+  double lo[3], hi[3];
+  for (int q = 0; q < 3; ++q) {
+    const i64 iq = idx[q] < g.n[q] ? idx[q] : g.n[q] - 1;
+    lo[q] = g.nodes[q][iq];
+    hi[q] = g.nodes[q][iq + 1];
+  }
+  // (d picks by selects, never by an index into a private array)
+  const double* cw = d == 0 ? Cw0 : d == 1 ? Cw1 : Cw2;
+  double* dst = which ? (d == 0 ? B0 : d == 1 ? B1 : B2) : (d == 0 ? A0 : d == 1 ? A1 : A2);
+  const double s = which ? cw[lc] : g.nodes[d][d == 0 ? idx[0] : d == 1 ? idx[1] : idx[2]];
+  const double m = section_measure(bs, d, s, lo, hi, full_measure(g, d), c_gl, ql, SEC_LANES, LaneGroup<SEC_LANES>());
+  if (live && ql == 0) dst[lc] = m;
+}
+
 // K3 (cheap part): W_d between the centroids of i-e_d and i; cut boxes go to the work list.
 template <class BodyArg>
 __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_stagger(GeoView g, BodyArg ba, i64 Mloc, const double* ct, const double* Cw0,
@@ -390,13 +486,24 @@ __global__ __launch_bounds__(BodyArg::MAX_BLOCK) void k_stagger_cut(GeoView g, B
   const i64 lp = lc + (ip - idx[d]) * g.stride[d];
   const i64 ln = lc + (in - idx[d]) * g.stride[d];
   double lo[3], hi[3];
-  for (int q = 0; q < g.N; ++q) {
-    if (q == d) continue;
-    lo[q] = g.nodes[q][idx[q]];
-    hi[q] = g.nodes[q][idx[q] + 1];
+  if constexpr (std::is_same<BodyArg, Prog3Arg>::value) {
+    // the same box, every entry written at a literal index: lo and hi stay in registers (the other kinds keep their code)
+    const double cp = Cw[d][lp], cn = Cw[d][ln];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      const i64 iq = q == d ? 0 : idx[q];        // (along d the nodes are not read: always an index inside the array)
+      lo[q] = q == d ? cp : g.nodes[q][iq];
+      hi[q] = q == d ? cn : g.nodes[q][iq + 1];
+    }
+  } else {
+    for (int q = 0; q < g.N; ++q) {
+      if (q == d) continue;
+      lo[q] = g.nodes[q][idx[q]];
+      hi[q] = g.nodes[q][idx[q] + 1];
+    }
+    lo[d] = Cw[d][lp];
+    hi[d] = Cw[d][ln];
   }
-  lo[d] = Cw[d][lp];
-  hi[d] = Cw[d][ln];
   const double w = box_measure(bs, lo, hi, false, c_gl, ql, LANES, LaneGroup<LANES>()).vol;
   if (live && ql == 0) W[d][lc] = w;
 }
@@ -950,10 +1057,30 @@ void run_static_kernels(pg_capacity* c, pg_mesh* m, const BodyArg& ba, hipStream
     PG_HIP(hipEventRecord(part[1].e1, st));
   }
   PG_HIP(hipEventRecord(part[2].e0, st));
-  hipLaunchKernelGGL(k_sections<BodyArg>, dim3(gr), dim3(256), 0, st, g, ba, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
-                     c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
-  PG_HIP(hipGetLastError());
-  PG_HIP(hipEventRecord(part[2].e1, st));
+  if constexpr (std::is_same<BodyArg, Prog3Arg>::value) {
+    // at most 6 sections per cut cell and 3 padding faces next to one
+    const i64 scap = std::min<i64>((i64)2 * N * Ml, (i64)9 * (i64)ncut + 1024);
+    DevBuf<int> slist(2 * scap), scount(1);
+    scount.zero();
+    hipLaunchKernelGGL(k_sections_list, dim3(gr), dim3(256), 0, st, g, Ml, c->ct.p, c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p,
+                       c->B[1].p, c->B[2].p, slist.p, scount.p, (int)scap);
+    PG_HIP(hipGetLastError());
+    int ns = 0;
+    scount.download(&ns, 1);
+    PG_REQUIRE(ns <= scap, "internal: section work list overflow");
+    if (ns > 0) {
+      hipLaunchKernelGGL(k_sections_cut<BodyArg>, dim3((unsigned)(((i64)ns * SEC_LANES + 255) / 256)), dim3(256), 0, st, g, ba, slist.p,
+                         ns, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p, c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
+      PG_HIP(hipGetLastError());
+    }
+    PG_HIP(hipEventRecord(part[2].e1, st));
+    PG_HIP(hipEventSynchronize(part[2].e1));    // (the list is freed at the end of this block)
+  } else {
+    hipLaunchKernelGGL(k_sections<BodyArg>, dim3(gr), dim3(256), 0, st, g, ba, Ml, c->ct.p, c->Cw[0].p, c->Cw[1].p, c->Cw[2].p,
+                       c->A[0].p, c->A[1].p, c->A[2].p, c->B[0].p, c->B[1].p, c->B[2].p);
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipEventRecord(part[2].e1, st));
+  }
   // W work list: at most N entries per cut-adjacent cell; bound by 2*N*ncut + slack
   const i64 wcap = std::min<i64>((i64)N * Ml, (i64)4 * N * (i64)ncut + 1024);
   wlist.alloc(2 * wcap);
@@ -1215,7 +1342,8 @@ int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_p
     const double* nodes[3];
     for (int d = 0; d < N; ++d) { n[d] = m->n[d]; nodes[d] = m->nodes[d].data(); }
     std::string why;
-    PG_REQUIRE(program_body_check(N, n, nodes, phi, grad, &why), "pg_capacity_create_program refused: " + why);
+    PG_REQUIRE(program_body_check(N, n, nodes, phi, grad, &why),
+               "pg_capacity_create_program refused: " + why + (N == 3 && grad ? ": pg_capacity_create_program3 takes a 3-D mesh" : ""));
   }
   auto* c = new pg_capacity();
   std::unique_ptr<pg_capacity> guard(c);
@@ -1237,6 +1365,45 @@ int32_t pg_capacity_create_program(pg_mesh* m, const pg_program* phi, const pg_p
   pa.N = N;
   pa.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
   run_static_kernels<CUT_LANES>(c, m, pa, cx.stream);
+  *out = guard.release();
+  PG_API_END
+}
+
+int32_t pg_capacity_create_program3(pg_mesh* m, const pg_program* phi, const pg_program* grad, int32_t flags, pg_capacity** out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(m && out, "pg_capacity_create_program3: NULL argument");
+  *out = nullptr;                                // (a missing program is named by program3_body_check below)
+  Context& cx = ctx();
+  {
+    i64 n[3] = {1, 1, 1};
+    const double* nodes[3] = {nullptr, nullptr, nullptr};
+    for (int d = 0; d < m->N; ++d) { n[d] = m->n[d]; nodes[d] = m->nodes[d].data(); }
+    std::string why;
+    PG_REQUIRE(program3_body_check(m->N, n, nodes, phi, grad, cx.nranks == 1 && !cx.comm, &why),
+               "pg_capacity_create_program3 refused: " + why);
+  }
+  auto* c = new pg_capacity();
+  std::unique_ptr<pg_capacity> guard(c);
+  c->mesh = m;
+  c->N = 3;
+  c->from_body = true;
+  c->has_cg = !(flags & PG_FLAG_NO_CENTROIDS);
+  std::memset(&c->body, 0, sizeof(c->body));     // (not a BallSet: nothing reads it)
+  c->slab = m->base_slab();
+  ensure_gl();
+  pg_program progs[5];
+  std::memset(progs, 0, sizeof(progs));
+  progs[0] = *phi;
+  progs[P3_DX] = grad[0];
+  progs[P3_DY] = grad[1];
+  progs[P3_DZ] = grad[2];
+  std::lock_guard<std::mutex> table(g_prog_mutex);   // held until the last kernel of this capacity has run
+  PG_HIP(hipStreamSynchronize(cx.stream));       // (no earlier launch may still read the table)
+  PG_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_prog), progs, sizeof(progs)));
+  Prog3Arg pa;
+  pa.sgn = (flags & PG_FLAG_COMPLEMENT) ? -1.0 : 1.0;
+  run_static_kernels<64>(c, m, pa, cx.stream);   // one wave per cut box
   *out = guard.release();
   PG_API_END
 }

@@ -132,7 +132,10 @@ class SpaceTimeCapacity(api.Capacity):
     time_panels x time_order: the composite Gauss-Legendre rule in time (space is exact)."""
 
     def __init__(self, body, mesh: SpaceTimeMesh, method: str = "VOFI", compute_centroids: bool = True,
-                 time_panels: int = 16, time_order: int = 4, complement: bool = False):
+                 time_panels: int = 16, time_order: int = 4, complement: bool = False, quadrature: Optional[str] = None):
+        if quadrature is not None:
+            raise PenguinHipError(f"Capacity(quadrature={quadrature!r}) on a SpaceTimeMesh: the keyword chooses the rule of a static "
+                                  "3-D level set; space-time capacities are 1-D+t and 2-D+t and take no such keyword")
         if isinstance(body, api.FrontTracker):
             api.check_front_body(body, mesh)
         if isinstance(body, MovingFront) or (isinstance(body, (tuple, list)) and len(body) == 2
