@@ -107,6 +107,8 @@ struct Config {
   double guess_pass_cost = 0.34;  // PG_GUESS_PASS_COST: one more vector read of k_rhs_init_c, in products of the loop
   double guess_gain = 0.8;        // PG_GUESS_GAIN: products saved per product the fit predicts (what is left after the
                                   // extrapolation sits where the polynomial is weakest)
+  bool step_fuse = true;          // PG_STEP_FUSE: one rank, compact loop: the fit rides in the right-hand-side launch (0: k_guess_fit as a
+                                  // launch of its own -- A/B runs and the parity tests)
   bool speculate_product = true;  // PG_SPECULATE: pg_solver_run queues the next step's first product behind a solve's first batch
   int mg_tail_rows = 2048;        // PG_MG_TAIL_ROWS: multigrid levels of at most this many rows run in the fused one-workgroup tail, as far
                                   // as their vectors fit its LDS (pg_multigrid.hip; DESIGN.md "Multigrid")

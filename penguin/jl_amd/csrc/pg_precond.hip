@@ -378,7 +378,9 @@ void assemble_csr_preconditioned(const SysParams& P, const Slab& s, const Number
                      A.ds.p, (int*)nullptr, (unsigned char*)nullptr, (unsigned long long*)nullptr, (const int*)A.rowptr.p, A.col.p, A.val.p);
   PG_HIP(hipGetLastError());
   // compact table of the rows whose cell has B != I (right-hand sides need B⁻¹S applied too)
-  DevBuf<int> pos(n), total(1);
+  A.blk_pos.alloc(n);
+  DevBuf<int>& pos = A.blk_pos;
+  DevBuf<int> total(1);
   scan_exclusive<unsigned char>(isblk.p, pos.p, n, total.p, st);
   int nblk = 0;
   total.download(&nblk, 1);
@@ -477,7 +479,9 @@ void assemble_csr_like(const SysParams& P, const Slab& s, const Numbering& nb, c
   A.blk_cn.alloc((i64)MAX_KINDS * nb1);
   A.blk_fw.alloc((i64)MAX_KINDS * nb1);
   if (nblk > 0) {
-    DevBuf<int> pos(n), total(1);
+    A.blk_pos.alloc(n);
+    DevBuf<int>& pos = A.blk_pos;
+    DevBuf<int> total(1);
     scan_exclusive<unsigned char>(A.isblk.p, pos.p, n, total.p, st);
     hipLaunchKernelGGL(k_blk_table, dim3(gr), dim3(256), 0, st, P, seg, nb.Mloc, n, nb.row_cell.p, nb.red.p, A.ds.p, A.isblk.p,
                        pos.p, A.blk_rows.p, A.blk_idx.p, A.blk_coef.p, A.blk_cn.p, A.blk_fw.p);

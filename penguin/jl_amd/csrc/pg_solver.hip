@@ -116,6 +116,8 @@ struct pg_solver {
   // the extrapolated start of a quiet step (GuessArgs).  hist_cnt of them are valid, all for the matrix of hist_de.
   DevBuf<double> zh[8], yh[8], guess_coef, guess_partials;
   DevBuf<unsigned> guess_ticket;
+  int guess_buf = 0;                // which of guess_coef's two coefficient blocks stands (GUESS_USED; 1 only where the fit rides
+                                    // in the right-hand-side launch: it reads one block and writes the other)
   int hist_cnt = 0, hist_k = 0;     // (hist_k: the ring's depth the count refers to)
   bool plain_guess_on[2] = {false, false};          // the plain warm path's switch and last solve's products, per matrix
   double plain_last_products[2] = {0.0, 0.0};       // (ctor / run; the compact path keeps its own in DiagElim)
@@ -323,24 +325,36 @@ __global__ void k_blk_cache(i64 nblk, int scheme, const int* __restrict__ blk_id
   }
 }
 
-__global__ void k_rhs_block_c(i64 nblk, int scheme, const int* __restrict__ blk_rows, const int* __restrict__ blk_idx,
-                              const double* __restrict__ wz, const double* __restrict__ c0, const double* __restrict__ blk_cn,
-                              const double* __restrict__ z, const double* __restrict__ yhat, double* __restrict__ b) {
-  for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < nblk; q += (i64)gridDim.x * blockDim.x) {
-    int j[MAX_KINDS];
-    double zz[MAX_KINDS], yy[MAX_KINDS];
+// the tables of the block rows as the warm loop's kernels take them
+struct BlkTables {
+  const int* idx;        // blk_idx
+  const double* wz;      // k_blk_cache
+  const double* c0;
+  const double* cn;      // blk_cn
+  const int* pos;        // row -> block-table index (CsrMatrix::blk_pos): how the fit's blocks of k_rhs_init_c find a sampled block row
+};
+
+// block row q of the table: the one expression of k_rhs_block_c and of the fit's blocks of k_rhs_init_c (guess_fit_part)
+__device__ inline double rhs_block_row(i64 q, int scheme, const BlkTables& t, const double* z, const double* yhat) {
+  int j[MAX_KINDS];
+  double zz[MAX_KINDS], yy[MAX_KINDS];
 #pragma unroll
-    for (int a = 0; a < MAX_KINDS; ++a) j[a] = blk_idx[q * MAX_KINDS + a];
+  for (int a = 0; a < MAX_KINDS; ++a) j[a] = t.idx[q * MAX_KINDS + a];
 #pragma unroll
-    for (int a = 0; a < MAX_KINDS; ++a) {   // every gather in flight before the first FMA
-      zz[a] = j[a] >= 0 ? z[j[a]] : 0.0;
-      yy[a] = (j[a] >= 0 && scheme == PG_SCHEME_CN) ? yhat[j[a]] : 0.0;
-    }
-    double v = c0[q];
-#pragma unroll
-    for (int a = 0; a < MAX_KINDS; ++a) v += wz[q * MAX_KINDS + a] * zz[a] - (scheme == PG_SCHEME_CN ? blk_cn[q * MAX_KINDS + a] * yy[a] : 0.0);
-    b[blk_rows[q]] = v;
+  for (int a = 0; a < MAX_KINDS; ++a) {   // every gather in flight before the first FMA
+    zz[a] = j[a] >= 0 ? z[j[a]] : 0.0;
+    yy[a] = (j[a] >= 0 && scheme == PG_SCHEME_CN) ? yhat[j[a]] : 0.0;
   }
+  double v = t.c0[q];
+#pragma unroll
+  for (int a = 0; a < MAX_KINDS; ++a) v += t.wz[q * MAX_KINDS + a] * zz[a] - (scheme == PG_SCHEME_CN ? t.cn[q * MAX_KINDS + a] * yy[a] : 0.0);
+  return v;
+}
+
+__global__ void k_rhs_block_c(i64 nblk, int scheme, const int* __restrict__ blk_rows, BlkTables t, const double* __restrict__ z,
+                              const double* __restrict__ yhat, double* __restrict__ b) {
+  for (i64 q = blockIdx.x * (i64)blockDim.x + threadIdx.x; q < nblk; q += (i64)gridDim.x * blockDim.x)
+    b[blk_rows[q]] = rhs_block_row(q, scheme, t, z, yhat);
 }
 
 // The same rows of a DIPHASIC system under Crank-Nicolson, matrix-free: b̂_r = Σ_a (B⁻¹S)[r,a] (c_a - M_a (A x)_a), with
@@ -393,12 +407,17 @@ struct GuessArgs {
   const double* zr[8];      // z^{n-1} .. z^{n-R}   (the last one is also znew: a lane reads its element before writing it)
   const double* yr[8];      // ŷ^{n-1} ..
   double* znew;             // z^{n+1}'s buffer: z_g for the rows of the loop, the solved value for a row alone on its diagonal
-  double* coef;             // [0..3] c_j, [4] how many, [5..8] their ring indices o_j - 1   (k_guess_fit); [13] += the number of
-                            // older states this launch read (a running total for the bench's byte count)
-  int defer;                // 1: z_g is NOT formed here -- the older states are not read for it and znew gets the rows alone on
+  const double* coef;       // [0..3] c_j, [4] how many, [5..8] their ring indices o_j - 1   (the fit of the step before)
+  double* count;            // += the number of older states this launch read (a running total for the bench's byte count)
+  int defer;                // (k_rhs_init_c takes it at compile time, its DEFER)  1: z_g is NOT formed here -- the older states are not read for it and znew gets the rows alone on
                             // their diagonal only; the solve's first update of x writes z_g + α M⁻¹p (KrylovCall::xguess) from
-                            // the copy of [0..8] this launch leaves at coef[GUESS_USED ..] (the fit rewrites [0..8] meanwhile)
+                            // the coefficients this launch read: `coef` itself where the fit rides in this launch (it writes the
+                            // other one of two coefficient blocks), else the copy of [0..8] this launch leaves at `used`
+  double* used;             // NULL: no copy
 };
+// The solver's coefficient buffer: block 0 at [0..11] ([9..11]: the fit's diagnostics), [13] the running count, [16..] the
+// fit's sums of several ranks, [GUESS_USED..]: the copy of [0..8] for the deferred start, or -- where the fit rides in the
+// right-hand-side launch -- coefficient block 1, which trades roles with block 0 at every fit (pg_solver::guess_buf)
 constexpr int GUESS_USED = 64;
 
 __device__ inline const double* ring_pick(const double* const (&r)[8], int i) {
@@ -406,307 +425,6 @@ __device__ inline const double* ring_pick(const double* const (&r)[8], int i) {
 #pragma unroll
   for (int q = 1; q < 8; ++q) p = i == q ? r[q] : p;   // (uniform: scalar selects, no private-memory copy of the argument)
   return p;
-}
-
-// K8 + the BiCGStab start in one pass (loop form, warm start): from the scaled state z and ŷ = Âz
-//   b̂ = S(2 mass∘(S z) + bconst) - ŷ  (CN) | S(mass∘(S z) + bconst) (BE) | S bconst (fixed rows) | as written by k_rhs_block
-//   r = r̂ = p = b̂ - ŷ,  x = z (in place),  partial sums of (r,r) and (b̂,b̂) in slots 0 / 1   (k_rhs_init_c: r̂ only)
-// replaces k_rhs + k_bicg_init: 9.3 instead of 14.1 vector passes, and no separate scaling kernels per step
-typedef double rd2_t __attribute__((ext_vector_type(2)));
-typedef unsigned char ruc2_t __attribute__((ext_vector_type(2)));
-
-// one element of k_rhs_init
-__device__ inline void rhs_init_one(int scheme, double z, double yh, double d, double ms, double bc, bool fx, bool blk, double bold,
-                                    double& bi, double& ri) {
-  if (blk) bi = bold;
-  else if (fx) bi = d * bc;
-  else if (scheme == PG_SCHEME_CN) bi = d * (2.0 * (ms * (d * z)) + bc) - yh;
-  else bi = d * (ms * (d * z) + bc);
-  ri = bi - yh;
-}
-
-// TWO elements per lane (16-byte accesses: half the vector-memory instructions of the 11 streams; the two flag bytes of
-// a pair come with one 2-byte load each); the odd last element and the ghost tail are handled by the same lanes
-// KH > 0: the start extrapolated from older states (GuessArgs; every row takes part: no row is left out on this path), the
-// state written out of place
-template <int KH>
-__global__ __launch_bounds__(BLOCK) void k_rhs_init(i64 n, i64 nvec, int scheme, const double* __restrict__ z,
-                                                    const double* __restrict__ yhat, const double* __restrict__ ds,
-                                                    const double* __restrict__ mass, const double* __restrict__ bconst,
-                                                    const unsigned char* __restrict__ fixed,
-                                                    const unsigned char* __restrict__ isblk, double* __restrict__ b,
-                                                    double* __restrict__ r, double* __restrict__ rhat,
-                                                    double* __restrict__ p, double* __restrict__ partials, GuessArgs g) {
-  __shared__ double s_red[BLOCK / 64];
-  double acc = 0.0, accb = 0.0, accw = 0.0;   // (r,r), (b,b)_W, (r,r)_W: slots 0, 1, 2 as k_bicg_init (weights ds²)
-  double cj[KH > 0 ? KH : 1];
-  const double* zo[KH > 0 ? KH : 1];
-  const double* yo[KH > 0 ? KH : 1];
-  int ku = 0;
-  if (KH > 0) {
-    ku = min(KH, (int)g.coef[4]);
-#pragma unroll
-    for (int j = 0; j < KH; ++j) {
-      const int sel = j < ku ? (int)g.coef[5 + j] : 0;
-      cj[j] = j < ku ? g.coef[j] : 0.0;
-      zo[j] = ring_pick(g.zr, sel);
-      yo[j] = ring_pick(g.yr, sel);
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) g.coef[13] += (double)ku;
-  }
-  const i64 npair = (nvec + 1) / 2;
-  for (i64 q = blockIdx.x * (i64)BLOCK + threadIdx.x; q < npair; q += (i64)gridDim.x * BLOCK) {
-    const i64 i = 2 * q;
-    if (i + 1 < n) {
-      // (stream hints: the per-row data is read once per step and b̂ is only kept for inspection -- neither should
-      //  displace the SpMV's matrix data from the Infinity Cache)
-      const rd2_t yh = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(yhat + i));
-      const rd2_t d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
-      const rd2_t bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
-      const rd2_t ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
-      const rd2_t zz = *reinterpret_cast<const rd2_t*>(z + i);
-      const ruc2_t fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
-      const ruc2_t bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
-      rd2_t bold;
-      bold.x = 0.0; bold.y = 0.0;
-      if (bk.x | bk.y) bold = *reinterpret_cast<const rd2_t*>(b + i);
-      double b0, r0, b1, r1;
-      rhs_init_one(scheme, zz.x, yh.x, d.x, ms.x, bc.x, fx.x != 0, bk.x != 0, bold.x, b0, r0);
-      rhs_init_one(scheme, zz.y, yh.y, d.y, ms.y, bc.y, fx.y != 0, bk.y != 0, bold.y, b1, r1);
-      if (KH > 0) {
-        rd2_t zg = zz;
-#pragma unroll
-        for (int j = 0; j < KH; ++j) {
-          if (j < ku) {
-            const rd2_t a = *reinterpret_cast<const rd2_t*>(zo[j] + i);
-            const rd2_t y2 = *reinterpret_cast<const rd2_t*>(yo[j] + i);
-            r0 -= cj[j] * (y2.x - yh.x); r1 -= cj[j] * (y2.y - yh.y);
-            zg.x += cj[j] * (a.x - zz.x); zg.y += cj[j] * (a.y - zz.y);
-          }
-        }
-        *reinterpret_cast<rd2_t*>(g.znew + i) = zg;
-      }
-      rd2_t bi, ri;
-      bi.x = b0; bi.y = b1; ri.x = r0; ri.y = r1;
-      __builtin_nontemporal_store(bi, reinterpret_cast<rd2_t*>(b + i));
-      *reinterpret_cast<rd2_t*>(r + i) = ri;
-      *reinterpret_cast<rd2_t*>(rhat + i) = ri;
-      *reinterpret_cast<rd2_t*>(p + i) = ri;
-      acc += ri.x * ri.x + ri.y * ri.y;
-      accb += (d.x * bi.x) * (d.x * bi.x) + (d.y * bi.y) * (d.y * bi.y);
-      accw += (d.x * ri.x) * (d.x * ri.x) + (d.y * ri.y) * (d.y * ri.y);
-    } else {
-      for (i64 k = i; k < i + 2 && k < nvec; ++k) {
-        if (k < n) {
-          double bi, ri;
-          rhs_init_one(scheme, z[k], yhat[k], ds[k], mass[k], bconst[k], fixed[k] != 0, isblk[k] != 0, isblk[k] ? b[k] : 0.0, bi, ri);
-          if (KH > 0) {
-            double zg = z[k];
-#pragma unroll
-            for (int j = 0; j < KH; ++j)
-              if (j < ku) { ri -= cj[j] * (yo[j][k] - yhat[k]); zg += cj[j] * (zo[j][k] - z[k]); }
-            g.znew[k] = zg;
-          }
-          b[k] = bi;
-          r[k] = ri; rhat[k] = ri; p[k] = ri;
-          acc += ri * ri;
-          accb += (ds[k] * bi) * (ds[k] * bi);
-          accw += (ds[k] * ri) * (ds[k] * ri);
-        } else {
-          p[k] = 0.0;
-        }
-      }
-    }
-  }
-  const double t = block_sum(acc, s_red);
-  if (threadIdx.x == 0) partials[blockIdx.x] = t;
-  const double tb = block_sum(accb, s_red);
-  if (threadIdx.x == 0) partials[gridDim.x + blockIdx.x] = tb;
-  const double tw = block_sum(accw, s_red);
-  if (threadIdx.x == 0) partials[2 * (size_t)gridDim.x + blockIdx.x] = tw;
-}
-
-// k_rhs_init for a COMPACT loop system (pg_reduce.hip, DiagElim): cmap[i] >= 0: the row stays, r = r̂ = p go to that index of
-// the compact vectors and count in the start sums; cmap[i] = -1 - e: the row is alone on its diagonal (entry e of gdiag /
-// delta): solved on the spot, left out of the sums.  b̂ is written for every row, (b̂,b̂)_W sums over all of them.
-// KH > 0: the extrapolated start above (out of place: the state written is g.znew), up to KH older states.
-template <int KH>
-__global__ __launch_bounds__(BLOCK) void k_rhs_init_c(i64 n, int scheme, const double* z,
-                                                      const double* __restrict__ yhat, const double* __restrict__ ds,
-                                                      const double* __restrict__ mass, const double* __restrict__ bconst,
-                                                      const unsigned char* __restrict__ fixed,
-                                                      const unsigned char* __restrict__ isblk, const int* __restrict__ cmap,
-                                                      double* __restrict__ b, const double* __restrict__ gdiag,
-                                                      double* __restrict__ delta, int* __restrict__ flag, int stamp,
-                                                      double* __restrict__ rhat, double* __restrict__ partials,
-                                                      unsigned* __restrict__ ticket, double* __restrict__ sc, double reltol2,
-                                                      double abstol2, int coupled, GuessArgs g) {
-  // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovCall::p_in_rhat)
-  // coupled != 0: diag_fix follows (the data changed): every δ != 0 moves its row, raises the flag and is coupled into the
-  // residual of the rows that reference it.  coupled == 0: no coupling launch follows (unchanged data); only a δ beyond the
-  // noise threshold raises the flag, and the step is then finished on the full system.  Several ranks with unchanged data
-  // take this branch WITHOUT a ticket (their start phase goes through an all-reduce): there a δ within the threshold still
-  // moves its row with neither coupling nor S_HELD, and the residual reported can miss the state's by up to ||S Â_RE δ|| --
-  // the one-rank remedy below needs the held sum in that all-reduce and is not carried over yet.
-  // ticket != NULL: the solver's start phase (scalar reset, start sums, PH_INIT) by the last block of this launch -- the
-  // caller knows that nothing will touch the start sums afterwards (diag_fix is not launched).  A row alone on its diagonal
-  // whose δ is within the noise threshold then STAYS where it is: moving it would leave the start residual of the rows coupled
-  // to it -- formed from ŷ = Âz with the row at its old place -- short of Â_RE δ, and with it every residual the solve reports
-  // afterwards.  (With a Dirichlet interface and CN such a row reads x_new = 2 g - x_old: what the first solve left on it, a
-  // fraction of its tolerance, changes sign every step and never dies out.)  What the rows that stay lack is their own
-  // residual, constant through the solve and on rows of their own: its weighted square goes to S_HELD, the tolerance of the
-  // iteration is lowered by it and the residual reported has it added (pg_krylov.hip) -- the solve is accepted on, and
-  // reports, the residual of the whole state.  Where that square is half the tolerance's or more the step is finished on the
-  // full system, as if a row had moved.
-  __shared__ double s_red[BLOCK / 64];
-  double acc = 0.0, accb = 0.0, accw = 0.0, acch = 0.0;
-  const bool hold = ticket != nullptr;
-  double cj[KH > 0 ? KH : 1];
-  const double* zo[KH > 0 ? KH : 1];
-  const double* yo[KH > 0 ? KH : 1];
-  int ku = 0;
-  const bool defer = KH > 0 && g.defer != 0;
-  if (KH > 0) {
-    ku = min(KH, (int)g.coef[4]);
-#pragma unroll
-    for (int j = 0; j < KH; ++j) {
-      const int sel = j < ku ? (int)g.coef[5 + j] : 0;
-      cj[j] = j < ku ? g.coef[j] : 0.0;
-      zo[j] = ring_pick(g.zr, sel);
-      yo[j] = ring_pick(g.yr, sel);
-    }
-    if (defer && blockIdx.x == 0 && threadIdx.x < 9) g.coef[GUESS_USED + threadIdx.x] = g.coef[threadIdx.x];
-  }
-  int moved = 0;
-  double* zw = KH > 0 ? g.znew : const_cast<double*>(z);   // (in place: a lane writes only elements it has read itself)
-  // zh / yv: the row's entries of the chosen older states and products
-  auto one = [&](i64 i, double zi, double yh, double d, double ms, double bc, bool fx, bool blk, double bold, int c, double& bi,
-                 const double* zh, const double* yv) {
-    double ri;
-    rhs_init_one(scheme, zi, yh, d, ms, bc, fx, blk, bold, bi, ri);
-    accb += (d * bi) * (d * bi);
-    if (c >= 0) {
-      if (KH > 0) {
-        double zg = zi, corr = 0.0;
-#pragma unroll
-        for (int j = 0; j < KH; ++j) {
-          corr += cj[j] * (yv[j] - yh);      // (cj = 0, yv = yh, zh = zi beyond ku)
-          zg += cj[j] * (zh[j] - zi);
-        }
-        ri -= corr;
-        if (!defer) zw[i] = zg;
-      }
-      rhat[c] = ri;
-      acc += ri * ri;
-      accw += (d * ri) * (d * ri);
-    } else {
-      // a row alone on its diagonal: solved here, x += δ = r / a_ii (δ = 0 once the row's datum has stopped changing, up to
-      // the rows that stay on a folded start); δ is what the rows coupled to it need (diag_fix), the flag says whether any row moved
-      const int e = -1 - c;
-      double dl = ri / gdiag[e];
-      const bool beyond = fabs(dl) > 1e-12 * fabs(zi);
-      if (hold && !beyond) {
-        acch += (d * ri) * (d * ri);
-        dl = 0.0;
-      }
-      delta[e] = dl;
-      if (KH > 0 || dl != 0.0) zw[i] = zi + dl;
-      if (coupled ? dl != 0.0 : beyond) moved = 1;
-    }
-  };
-  // two rows per lane, 16-byte loads of the seven input streams (as k_rhs_init); the compact stores are 8-byte
-  const i64 npair = (n + 1) / 2;
-  for (i64 q = blockIdx.x * (i64)BLOCK + threadIdx.x; q < npair; q += (i64)gridDim.x * BLOCK) {
-    const i64 i = 2 * q;
-    double zh0[KH > 0 ? KH : 1], zh1[KH > 0 ? KH : 1], yv0[KH > 0 ? KH : 1], yv1[KH > 0 ? KH : 1];
-    if (i + 1 < n) {
-      const rd2_t yh = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(yhat + i));
-      const rd2_t d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
-      const rd2_t bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
-      const rd2_t ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
-      const rd2_t zz = *reinterpret_cast<const rd2_t*>(z + i);
-      const ruc2_t fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
-      const ruc2_t bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
-      const int c0 = cmap[i], c1 = cmap[i + 1];
-      if (KH > 0) {
-#pragma unroll
-        for (int j = 0; j < KH; ++j) {
-          rd2_t a = zz, y2 = yh;
-          if (j < ku && (c0 >= 0 || c1 >= 0)) {     // (rows alone on their diagonal take nothing from the older states)
-            if (!defer) a = *reinterpret_cast<const rd2_t*>(zo[j] + i);
-            y2 = *reinterpret_cast<const rd2_t*>(yo[j] + i);
-          }
-          zh0[j] = a.x; zh1[j] = a.y; yv0[j] = y2.x; yv1[j] = y2.y;
-        }
-      }
-      rd2_t bold;
-      bold.x = 0.0; bold.y = 0.0;
-      if (bk.x | bk.y) bold = *reinterpret_cast<const rd2_t*>(b + i);
-      rd2_t bi;
-      double b0, b1;
-      one(i, zz.x, yh.x, d.x, ms.x, bc.x, fx.x != 0, bk.x != 0, bold.x, c0, b0, zh0, yv0);
-      one(i + 1, zz.y, yh.y, d.y, ms.y, bc.y, fx.y != 0, bk.y != 0, bold.y, c1, b1, zh1, yv1);
-      bi.x = b0; bi.y = b1;
-      __builtin_nontemporal_store(bi, reinterpret_cast<rd2_t*>(b + i));
-    } else if (i < n) {
-      const double zi = z[i], yh = yhat[i];
-      if (KH > 0) {
-#pragma unroll
-        for (int j = 0; j < KH; ++j) {
-          zh0[j] = (j < ku && !defer) ? zo[j][i] : zi;
-          yv0[j] = j < ku ? yo[j][i] : yh;
-        }
-      }
-      double b0;
-      one(i, zi, yh, ds[i], mass[i], bconst[i], fixed[i] != 0, isblk[i] != 0, isblk[i] ? b[i] : 0.0, cmap[i], b0, zh0, yv0);
-      b[i] = b0;
-    }
-  }
-  if (__any(moved) && (threadIdx.x & 63) == 0) atomicMax(flag, stamp);
-  const double t = block_sum(acc, s_red);
-  const double tb = block_sum(accb, s_red);
-  const double tw = block_sum(accw, s_red);
-  if (!ticket) {
-    if (threadIdx.x == 0) {
-      partials[blockIdx.x] = t;
-      partials[gridDim.x + blockIdx.x] = tb;
-      partials[2 * (size_t)gridDim.x + blockIdx.x] = tw;
-      if (KH > 0 && blockIdx.x == 0) g.coef[13] += (double)ku;
-    }
-    return;
-  }
-  if (threadIdx.x == 0) {
-    pg::store_partial(partials + blockIdx.x, t);
-    pg::store_partial(partials + gridDim.x + blockIdx.x, tb);
-    pg::store_partial(partials + 2 * (size_t)gridDim.x + blockIdx.x, tw);
-  }
-  const double th = block_sum(acch, s_red);
-  if (threadIdx.x == 0) pg::store_partial(partials + 3 * (size_t)gridDim.x + blockIdx.x, th);
-  if (!pg::last_block_arrives(ticket, gridDim.x, s_red)) return;
-  // (k_start's work, in its order of summation)
-  if (threadIdx.x < pg::S_COUNT) sc[threadIdx.x] = threadIdx.x == pg::S_RELTOL2 ? reltol2 : (threadIdx.x == pg::S_ABSTOL2 ? abstol2 : 0.0);
-  __syncthreads();
-  for (int sl = 0; sl < 4; ++sl) {      // (slot 3: the rows that stayed)
-    double a = 0.0;
-    for (int i = threadIdx.x; i < (int)gridDim.x; i += BLOCK) a += pg::load_partial(partials + (size_t)sl * gridDim.x + i);
-    const double sum = block_sum(a, s_red);
-    if (threadIdx.x == 0) sc[pg::S_RED0 + sl] = sum;
-  }
-  if (threadIdx.x == 0) {
-    pg::derive(pg::PH_INIT, sc);
-    // (every block's atomicMax on the flag was drained before it drew its ticket)
-    sc[pg::S_MOVED] = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == stamp ? 1.0 : 0.0;
-    const double held = sc[pg::S_RED0 + 3];
-    if (held > 0.0) {
-      if (2.0 * held >= sc[pg::S_TOL2]) sc[pg::S_MOVED] = 1.0;
-      else {
-        sc[pg::S_HELD] = held;
-        sc[pg::S_TOL2] -= held;
-        sc[pg::S_DONE] = sc[pg::S_RR] <= sc[pg::S_TOL2] ? 1.0 : 0.0;
-      }
-    }
-    if (KH > 0) g.coef[13] += (double)ku;
-  }
 }
 
 // The fit behind the extrapolated start (GuessArgs): over every `stride`-th chunk of BLOCK rows (a few hundred blocks share
@@ -726,6 +444,7 @@ struct GuessFit {
   int stride, avail, kmax;
   double rate2, pass_cost, gain;
   double* sums;           // several ranks: where the GUESS_NS local sums go (NULL: one rank, the launch decides itself)
+  int nblocks;            // blocks the partial sums are kept for (k_guess_fit: its grid)
 };
 
 __device__ inline int guess_tri(int j, int l) { return j * GUESS_RM - j * (j - 1) / 2 + (l - j); }   // l >= j
@@ -822,6 +541,488 @@ __device__ inline void guess_decide(const double* s_g, const GuessFit& f) {
   }
 }
 
+// K8 + the BiCGStab start in one pass (loop form, warm start): from the scaled state z and ŷ = Âz
+//   b̂ = S(2 mass∘(S z) + bconst) - ŷ  (CN) | S(mass∘(S z) + bconst) (BE) | S bconst (fixed rows) | as written by k_rhs_block
+//   r = r̂ = p = b̂ - ŷ,  x = z (in place),  partial sums of (r,r) and (b̂,b̂) in slots 0 / 1   (k_rhs_init_c: r̂ only)
+// replaces k_rhs + k_bicg_init: 9.3 instead of 14.1 vector passes, and no separate scaling kernels per step
+typedef double rd2_t __attribute__((ext_vector_type(2)));
+typedef unsigned char ruc2_t __attribute__((ext_vector_type(2)));
+
+// one element of k_rhs_init
+__device__ inline void rhs_init_one(int scheme, double z, double yh, double d, double ms, double bc, bool fx, bool blk, double bold,
+                                    double& bi, double& ri) {
+  if (blk) bi = bold;
+  else if (fx) bi = d * bc;
+  else if (scheme == PG_SCHEME_CN) bi = d * (2.0 * (ms * (d * z)) + bc) - yh;
+  else bi = d * (ms * (d * z) + bc);
+  ri = bi - yh;
+}
+
+// TWO elements per lane (16-byte accesses: half the vector-memory instructions of the 11 streams; the two flag bytes of
+// a pair come with one 2-byte load each); the odd last element and the ghost tail are handled by the same lanes
+// KH > 0: the start extrapolated from older states (GuessArgs; every row takes part: no row is left out on this path), the
+// state written out of place
+template <int KH>
+__global__ __launch_bounds__(BLOCK) void k_rhs_init(i64 n, i64 nvec, int scheme, const double* __restrict__ z,
+                                                    const double* __restrict__ yhat, const double* __restrict__ ds,
+                                                    const double* __restrict__ mass, const double* __restrict__ bconst,
+                                                    const unsigned char* __restrict__ fixed,
+                                                    const unsigned char* __restrict__ isblk, double* __restrict__ b,
+                                                    double* __restrict__ r, double* __restrict__ rhat,
+                                                    double* __restrict__ p, double* __restrict__ partials, GuessArgs g) {
+  __shared__ double s_red[BLOCK / 64];
+  double acc = 0.0, accb = 0.0, accw = 0.0;   // (r,r), (b,b)_W, (r,r)_W: slots 0, 1, 2 as k_bicg_init (weights ds²)
+  double cj[KH > 0 ? KH : 1];
+  const double* zo[KH > 0 ? KH : 1];
+  const double* yo[KH > 0 ? KH : 1];
+  int ku = 0;
+  if (KH > 0) {
+    ku = min(KH, (int)g.coef[4]);
+#pragma unroll
+    for (int j = 0; j < KH; ++j) {
+      const int sel = j < ku ? (int)g.coef[5 + j] : 0;
+      cj[j] = j < ku ? g.coef[j] : 0.0;
+      zo[j] = ring_pick(g.zr, sel);
+      yo[j] = ring_pick(g.yr, sel);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *g.count += (double)ku;
+  }
+  const i64 npair = (nvec + 1) / 2;
+  for (i64 q = blockIdx.x * (i64)BLOCK + threadIdx.x; q < npair; q += (i64)gridDim.x * BLOCK) {
+    const i64 i = 2 * q;
+    if (i + 1 < n) {
+      // (stream hints: the per-row data is read once per step and b̂ is only kept for inspection -- neither should
+      //  displace the SpMV's matrix data from the Infinity Cache)
+      const rd2_t yh = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(yhat + i));
+      const rd2_t d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
+      const rd2_t bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
+      const rd2_t ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
+      const rd2_t zz = *reinterpret_cast<const rd2_t*>(z + i);
+      const ruc2_t fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
+      const ruc2_t bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
+      rd2_t bold;
+      bold.x = 0.0; bold.y = 0.0;
+      if (bk.x | bk.y) bold = *reinterpret_cast<const rd2_t*>(b + i);
+      double b0, r0, b1, r1;
+      rhs_init_one(scheme, zz.x, yh.x, d.x, ms.x, bc.x, fx.x != 0, bk.x != 0, bold.x, b0, r0);
+      rhs_init_one(scheme, zz.y, yh.y, d.y, ms.y, bc.y, fx.y != 0, bk.y != 0, bold.y, b1, r1);
+      if (KH > 0) {
+        rd2_t zg = zz;
+#pragma unroll
+        for (int j = 0; j < KH; ++j) {
+          if (j < ku) {
+            const rd2_t a = *reinterpret_cast<const rd2_t*>(zo[j] + i);
+            const rd2_t y2 = *reinterpret_cast<const rd2_t*>(yo[j] + i);
+            r0 -= cj[j] * (y2.x - yh.x); r1 -= cj[j] * (y2.y - yh.y);
+            zg.x += cj[j] * (a.x - zz.x); zg.y += cj[j] * (a.y - zz.y);
+          }
+        }
+        *reinterpret_cast<rd2_t*>(g.znew + i) = zg;
+      }
+      rd2_t bi, ri;
+      bi.x = b0; bi.y = b1; ri.x = r0; ri.y = r1;
+      __builtin_nontemporal_store(bi, reinterpret_cast<rd2_t*>(b + i));
+      *reinterpret_cast<rd2_t*>(r + i) = ri;
+      *reinterpret_cast<rd2_t*>(rhat + i) = ri;
+      *reinterpret_cast<rd2_t*>(p + i) = ri;
+      acc += ri.x * ri.x + ri.y * ri.y;
+      accb += (d.x * bi.x) * (d.x * bi.x) + (d.y * bi.y) * (d.y * bi.y);
+      accw += (d.x * ri.x) * (d.x * ri.x) + (d.y * ri.y) * (d.y * ri.y);
+    } else {
+      for (i64 k = i; k < i + 2 && k < nvec; ++k) {
+        if (k < n) {
+          double bi, ri;
+          rhs_init_one(scheme, z[k], yhat[k], ds[k], mass[k], bconst[k], fixed[k] != 0, isblk[k] != 0, isblk[k] ? b[k] : 0.0, bi, ri);
+          if (KH > 0) {
+            double zg = z[k];
+#pragma unroll
+            for (int j = 0; j < KH; ++j)
+              if (j < ku) { ri -= cj[j] * (yo[j][k] - yhat[k]); zg += cj[j] * (zo[j][k] - z[k]); }
+            g.znew[k] = zg;
+          }
+          b[k] = bi;
+          r[k] = ri; rhat[k] = ri; p[k] = ri;
+          acc += ri * ri;
+          accb += (ds[k] * bi) * (ds[k] * bi);
+          accw += (ds[k] * ri) * (ds[k] * ri);
+        } else {
+          p[k] = 0.0;
+        }
+      }
+    }
+  }
+  const double t = block_sum(acc, s_red);
+  if (threadIdx.x == 0) partials[blockIdx.x] = t;
+  const double tb = block_sum(accb, s_red);
+  if (threadIdx.x == 0) partials[gridDim.x + blockIdx.x] = tb;
+  const double tw = block_sum(accw, s_red);
+  if (threadIdx.x == 0) partials[2 * (size_t)gridDim.x + blockIdx.x] = tw;
+}
+
+// the last block of a fit, every block's partial sums standing: the sums in a fixed order -- a wave per sum, a lane per block
+// (at most 128 blocks), shuffle tree; every load of a wave in flight before the first is used, the trees level by level --
+// and the decision (one rank) or the hand-over to the all-reduce (several)
+__device__ inline void guess_fit_last(const GuessFit& f, int G, double* s_g) {
+  constexpr int NS = GUESS_NS;
+  {
+    constexpr int PW = (NS + BLOCK / 64 - 1) / (BLOCK / 64);   // sums per wave
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double a0[PW], a1[PW];
+#pragma unroll
+    for (int k = 0; k < PW; ++k) {
+      const int sl = wave + k * (BLOCK / 64);
+      a0[k] = (sl < NS && lane < G) ? pg::load_partial(f.partials + (size_t)sl * G + lane) : 0.0;
+      a1[k] = (sl < NS && lane + 64 < G) ? pg::load_partial(f.partials + (size_t)sl * G + lane + 64) : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < PW; ++k) a0[k] += a1[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+      for (int k = 0; k < PW; ++k) a0[k] += __shfl_down(a0[k], off, 64);
+    if (lane == 0) {
+#pragma unroll
+      for (int k = 0; k < PW; ++k) {
+        const int sl = wave + k * (BLOCK / 64);
+        if (sl < NS) s_g[sl] = a0[k];
+      }
+    }
+  }
+  __syncthreads();
+  if (f.sums) {                     // several ranks: the sums go through an all-reduce, k_guess_decide follows
+    if (threadIdx.x < NS) f.sums[threadIdx.x] = s_g[threadIdx.x];
+    return;
+  }
+  guess_decide(s_g, f);
+}
+
+// the correction of the start residual by the chosen older products (cj = 0, yv = yh beyond the ones in use)
+template <int KH>
+__device__ inline double guess_corr(const double* cj, const double* yv, double yh) {
+  double corr = 0.0;
+#pragma unroll
+  for (int j = 0; j < KH; ++j) corr += cj[j] * (yv[j] - yh);
+  return corr;
+}
+
+// Which instantiations of k_rhs_init_c take the fit inside: KH (the older states the launch is built for) from 2 on, the
+// extrapolated state left to the solve's first update of x (DEFER, the default: the launch then reads no older state, and
+// its main path has the registers to spare).  Those ask, by their launch bounds, for 5 waves per SIMD -- KH = 4 had 4: the
+// fifth is the slot in which the fit's blocks run beside the 4 main blocks per CU, from the launch's start -- and must
+// reach them without scratch; every other instantiation is compiled as it was and keeps k_guess_fit as a launch.
+// profiles/step_head_resource_usage_{parent,this}.txt have the compiler's report.
+constexpr bool rhs_fuses(int KH, bool DEFER) { return KH >= 2 && DEFER; }
+// The 37 sums of the fit are shared out among FIT_PARTS blocks per sampled set of chunks, FIT_PER sums each: the
+// accumulators of one group and the row in flight fit the registers of the main path (all 37 in one block: 158 VGPRs)
+constexpr int FIT_PARTS = 5, FIT_PER = (GUESS_NS + FIT_PARTS - 1) / FIT_PARTS;
+
+// The fit as blocks of the right-hand-side launch itself (k_rhs_init_c: the blocks past its main ones).  bid / G: the
+// number of the k_guess_fit block whose chunks this block takes, and their count; part: its group of sums.  What k_guess_fit
+// reads from b̂ and r̂ is being written by the main blocks of the same launch, so a fit block evaluates both for its sampled
+// rows from the launch's inputs, by the main blocks' own functions (rhs_init_one, guess_corr; a sampled block row by
+// rhs_block_row, the function of k_rhs_block_c): the same bits.  Every sum is k_guess_fit's -- a lane adds its chunks in
+// their order, then the shuffle tree, the waves, the blocks.  The FIT_PARTS blocks of a bid read the same rows, about 5 MB
+// in all at 512^3; what they buy is a chain of dependent memory round trips per block -- 2 to 3 us each beside the main
+// blocks' streams -- that is a fraction of the launch: one block taking the groups one after another outlasted the main blocks.
+template <int KH, int PART>
+__device__ inline void guess_fit_part(i64 n, int scheme, const double* z, const double* yhat, const double* ds, const double* mass,
+                                      const double* bconst, const unsigned char* fixed, const unsigned char* isblk, const int* cmap,
+                                      const BlkTables& bt, const GuessArgs& g, const GuessFit& f, int bid, int G, const double (&cj)[KH],
+                                      const int (&sel)[KH], int ku, int nld, double (*s_w)[GUESS_NS]) {
+  constexpr int RM = GUESS_RM, NS = GUESS_NS, PER = FIT_PER, T0 = PART * PER, T1 = T0 + PER < NS ? T0 + PER : NS;
+  constexpr bool NEED_RU = T1 > RM * (RM + 1) / 2, NEED_RA = T1 == NS;
+  double gs[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) gs[k] = 0.0;
+  const i64 nchunk = (n + BLOCK - 1) / BLOCK;
+  for (i64 ch = (i64)bid * f.stride; ch < nchunk; ch += (i64)G * f.stride) {
+    const i64 i = ch * BLOCK + threadIdx.x;
+    if (i >= n) continue;
+    // (every stream at once: the rows left out of the loop are read too and dropped below)
+    // (a group made of Gram entries alone needs neither residual, NEED_RU, nor the residual taken, NEED_RA)
+    const int c = cmap[i];
+    const double d = ds[i], y0 = yhat[i];
+    double zi = 0.0, ms = 0.0, bc = 0.0;
+    bool fx = false, bk = false;
+    if (NEED_RU) { zi = z[i]; ms = mass[i]; bc = bconst[i]; fx = fixed[i] != 0; bk = isblk[i] != 0; }
+    double yr[RM];
+#pragma unroll
+    for (int j = 0; j < RM; ++j) yr[j] = j < nld ? g.yr[j][i] : 0.0;      // (g.yr: the pointers of f.yr)
+    if (c < 0) continue;
+    const double w = d * d;
+    double bi, ru = 0.0, ra = 0.0;
+    if (NEED_RU) rhs_init_one(scheme, zi, y0, d, ms, bc, fx, bk, bk ? rhs_block_row(bt.pos[i], scheme, bt, z, yhat) : 0.0, bi, ru);
+    if (NEED_RA) {
+      double yv[KH];
+#pragma unroll
+      for (int j = 0; j < KH; ++j) {
+        double v = yr[0];
+#pragma unroll
+        for (int q = 1; q < RM; ++q) v = sel[j] == q ? yr[q] : v;
+        yv[j] = j < ku ? v : y0;
+      }
+      ra = ru - guess_corr<KH>(cj, yv, y0);
+    }
+    double q[RM];
+#pragma unroll
+    for (int j = 0; j < RM; ++j) q[j] = j < f.avail ? yr[j] - y0 : 0.0;
+    int t = 0;                      // (k_guess_fit's sums in its numbering; this block keeps [T0, T1) of them)
+#pragma unroll
+    for (int j = 0; j < RM; ++j)
+#pragma unroll
+      for (int l = j; l < RM; ++l, ++t)
+        if (t >= T0 && t < T1) gs[t - T0] += w * q[j] * q[l];
+#pragma unroll
+    for (int j = 0; j < RM; ++j, ++t)
+      if (t >= T0 && t < T1) gs[t - T0] += w * q[j] * ru;
+    if (t >= T0 && t < T1) gs[t - T0] += w * ru * ru;
+    ++t;
+    if (t >= T0 && t < T1) gs[t - T0] += w * ra * ra;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int k = 0; k < PER; ++k) gs[k] += __shfl_down(gs[k], off, 64);
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (T0 + k < T1) s_w[threadIdx.x >> 6][T0 + k] = gs[k];
+  }
+}
+
+template <int KH>
+__device__ inline void guess_fit_rows(i64 n, int scheme, const double* z, const double* yhat, const double* ds, const double* mass,
+                                      const double* bconst, const unsigned char* fixed, const unsigned char* isblk, const int* cmap,
+                                      const BlkTables& bt, const GuessArgs& g, const GuessFit& f, int bid, int part, int G,
+                                      double* s_red) {
+  constexpr int NS = GUESS_NS, RM = GUESS_RM;
+  __shared__ double s_g[NS];
+  __shared__ double s_w[BLOCK / 64][NS];
+  // the coefficients the main blocks of this launch take
+  double cj[KH];
+  int sel[KH];
+  const int ku = min(KH, (int)g.coef[4]);
+  int nld = f.avail;                // products read per row: the fit's, and the ones the start takes
+#pragma unroll
+  for (int j = 0; j < KH; ++j) {
+    sel[j] = j < ku ? (int)g.coef[5 + j] : 0;
+    cj[j] = j < ku ? g.coef[j] : 0.0;
+    if (j < ku) nld = max(nld, sel[j] + 1);
+  }
+  nld = min(nld, RM);
+#define PG_FIT_PART(P) guess_fit_part<KH, P>(n, scheme, z, yhat, ds, mass, bconst, fixed, isblk, cmap, bt, g, f, bid, G, cj, sel, ku, nld, s_w)
+  static_assert(FIT_PARTS == 5, "guess_fit_rows: one case per group of sums");
+  switch (part) {                   // (uniform per block)
+    case 0: PG_FIT_PART(0); break;
+    case 1: PG_FIT_PART(1); break;
+    case 2: PG_FIT_PART(2); break;
+    case 3: PG_FIT_PART(3); break;
+    default: PG_FIT_PART(4); break;
+  }
+#undef PG_FIT_PART
+  __syncthreads();
+  const int t0 = part * FIT_PER;
+  if ((int)threadIdx.x >= t0 && (int)threadIdx.x < min(t0 + FIT_PER, NS)) {
+    double a = 0.0;
+#pragma unroll
+    for (int q = 0; q < BLOCK / 64; ++q) a += s_w[q][threadIdx.x];
+    pg::store_partial(f.partials + (size_t)threadIdx.x * G + bid, a);
+  }
+  if (!pg::last_block_arrives(f.ticket, (unsigned)(FIT_PARTS * G), s_red)) return;
+  guess_fit_last(f, G, s_g);
+}
+
+// k_rhs_init for a COMPACT loop system (pg_reduce.hip, DiagElim): cmap[i] >= 0: the row stays, r = r̂ = p go to that index of
+// the compact vectors and count in the start sums; cmap[i] = -1 - e: the row is alone on its diagonal (entry e of gdiag /
+// delta): solved on the spot, left out of the sums.  b̂ is written for every row, (b̂,b̂)_W sums over all of them.
+// KH > 0: the extrapolated start above (out of place: the state written is g.znew), up to KH older states.
+// DEFER: GuessArgs::defer at compile time (the older states' registers are not taken where they are not read).
+template <int KH, bool DEFER>
+__global__ __launch_bounds__(BLOCK, (rhs_fuses(KH, DEFER) ? 5 : 1)) void k_rhs_init_c(i64 n, int scheme, const double* z,
+                                                      const double* __restrict__ yhat, const double* __restrict__ ds,
+                                                      const double* __restrict__ mass, const double* __restrict__ bconst,
+                                                      const unsigned char* __restrict__ fixed,
+                                                      const unsigned char* __restrict__ isblk, const int* __restrict__ cmap,
+                                                      double* __restrict__ b, const double* __restrict__ gdiag,
+                                                      double* __restrict__ delta, int* __restrict__ flag, int stamp,
+                                                      double* __restrict__ rhat, double* __restrict__ partials,
+                                                      unsigned* __restrict__ ticket, double* __restrict__ sc, double reltol2,
+                                                      double abstol2, int coupled, GuessArgs g, BlkTables bt, GuessFit gf,
+                                                      int main_grid) {
+  // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovCall::p_in_rhat)
+  // coupled != 0: diag_fix follows (the data changed): every δ != 0 moves its row, raises the flag and is coupled into the
+  // residual of the rows that reference it.  coupled == 0: no coupling launch follows (unchanged data); only a δ beyond the
+  // noise threshold raises the flag, and the step is then finished on the full system.  Several ranks with unchanged data
+  // take this branch WITHOUT a ticket (their start phase goes through an all-reduce): there a δ within the threshold still
+  // moves its row with neither coupling nor S_HELD, and the residual reported can miss the state's by up to ||S Â_RE δ|| --
+  // the one-rank remedy below needs the held sum in that all-reduce and is not carried over yet.
+  // ticket != NULL: the solver's start phase (scalar reset, start sums, PH_INIT) by the last block of this launch -- the
+  // caller knows that nothing will touch the start sums afterwards (diag_fix is not launched).  A row alone on its diagonal
+  // whose δ is within the noise threshold then STAYS where it is: moving it would leave the start residual of the rows coupled
+  // to it -- formed from ŷ = Âz with the row at its old place -- short of Â_RE δ, and with it every residual the solve reports
+  // afterwards.  (With a Dirichlet interface and CN such a row reads x_new = 2 g - x_old: what the first solve left on it, a
+  // fraction of its tolerance, changes sign every step and never dies out.)  What the rows that stay lack is their own
+  // residual, constant through the solve and on rows of their own: its weighted square goes to S_HELD, the tolerance of the
+  // iteration is lowered by it and the residual reported has it added (pg_krylov.hip) -- the solve is accepted on, and
+  // reports, the residual of the whole state.  Where that square is half the tolerance's or more the step is finished on the
+  // full system, as if a row had moved.
+  __shared__ double s_red[BLOCK / 64];
+  // main_grid > 0: the blocks past the first main_grid are the fit's (guess_fit_rows); the main blocks stride, count and sum
+  // over main_grid, and the fit's blocks draw the fit's ticket and write the fit's partials only
+  const unsigned G0 = main_grid > 0 ? (unsigned)main_grid : gridDim.x;
+  if (KH > 0 && blockIdx.x >= G0) {      // (uniform per block)
+    if constexpr (rhs_fuses(KH, DEFER))
+      guess_fit_rows<KH>(n, scheme, z, yhat, ds, mass, bconst, fixed, isblk, cmap, bt, g, gf, (int)((blockIdx.x - G0) % gf.nblocks),
+                         (int)((blockIdx.x - G0) / gf.nblocks), gf.nblocks, s_red);
+    return;
+  }
+  double acc = 0.0, accb = 0.0, accw = 0.0, acch = 0.0;
+  const bool hold = ticket != nullptr;
+  double cj[KH > 0 ? KH : 1];
+  const double* zo[KH > 0 ? KH : 1];
+  const double* yo[KH > 0 ? KH : 1];
+  int ku = 0;
+  constexpr bool defer = KH > 0 && DEFER;
+  if (KH > 0) {
+    ku = min(KH, (int)g.coef[4]);
+#pragma unroll
+    for (int j = 0; j < KH; ++j) {
+      const int sel = j < ku ? (int)g.coef[5 + j] : 0;
+      cj[j] = j < ku ? g.coef[j] : 0.0;
+      zo[j] = ring_pick(g.zr, sel);
+      yo[j] = ring_pick(g.yr, sel);
+    }
+    if (defer && g.used && blockIdx.x == 0 && threadIdx.x < 9) g.used[threadIdx.x] = g.coef[threadIdx.x];
+  }
+  int moved = 0;
+  double* zw = KH > 0 ? g.znew : const_cast<double*>(z);   // (in place: a lane writes only elements it has read itself)
+  // zh / yv: the row's entries of the chosen older states and products
+  auto one = [&](i64 i, double zi, double yh, double d, double ms, double bc, bool fx, bool blk, double bold, int c, double& bi,
+                 const double* zh, const double* yv) {
+    double ri;
+    rhs_init_one(scheme, zi, yh, d, ms, bc, fx, blk, bold, bi, ri);
+    accb += (d * bi) * (d * bi);
+    if (c >= 0) {
+      if (KH > 0) {
+        double zg = zi;
+#pragma unroll
+        for (int j = 0; j < KH; ++j) zg += cj[j] * (zh[j] - zi);      // (cj = 0, yv = yh, zh = zi beyond ku)
+        ri -= guess_corr<KH>(cj, yv, yh);
+        if (!defer) zw[i] = zg;
+      }
+      rhat[c] = ri;
+      acc += ri * ri;
+      accw += (d * ri) * (d * ri);
+    } else {
+      // a row alone on its diagonal: solved here, x += δ = r / a_ii (δ = 0 once the row's datum has stopped changing, up to
+      // the rows that stay on a folded start); δ is what the rows coupled to it need (diag_fix), the flag says whether any row moved
+      const int e = -1 - c;
+      double dl = ri / gdiag[e];
+      const bool beyond = fabs(dl) > 1e-12 * fabs(zi);
+      if (hold && !beyond) {
+        acch += (d * ri) * (d * ri);
+        dl = 0.0;
+      }
+      delta[e] = dl;
+      if (KH > 0 || dl != 0.0) zw[i] = zi + dl;
+      if (coupled ? dl != 0.0 : beyond) moved = 1;
+    }
+  };
+  // two rows per lane, 16-byte loads of the seven input streams (as k_rhs_init); the compact stores are 8-byte
+  const i64 npair = (n + 1) / 2;
+  for (i64 q = blockIdx.x * (i64)BLOCK + threadIdx.x; q < npair; q += (i64)G0 * BLOCK) {
+    const i64 i = 2 * q;
+    double zh0[KH > 0 ? KH : 1], zh1[KH > 0 ? KH : 1], yv0[KH > 0 ? KH : 1], yv1[KH > 0 ? KH : 1];
+    if (i + 1 < n) {
+      const rd2_t yh = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(yhat + i));
+      const rd2_t d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
+      const rd2_t bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
+      const rd2_t ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
+      const rd2_t zz = *reinterpret_cast<const rd2_t*>(z + i);
+      const ruc2_t fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
+      const ruc2_t bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
+      const int c0 = cmap[i], c1 = cmap[i + 1];
+      rd2_t bold;
+      bold.x = 0.0; bold.y = 0.0;
+      if (bk.x | bk.y) bold = *reinterpret_cast<const rd2_t*>(b + i);
+      if (KH > 0) {
+#pragma unroll
+        for (int j = 0; j < KH; ++j) {
+          rd2_t a = zz, y2 = yh;
+          if (j < ku && (c0 >= 0 || c1 >= 0)) {     // (rows alone on their diagonal take nothing from the older states)
+            if (!defer) a = *reinterpret_cast<const rd2_t*>(zo[j] + i);
+            y2 = *reinterpret_cast<const rd2_t*>(yo[j] + i);
+          }
+          zh0[j] = a.x; zh1[j] = a.y; yv0[j] = y2.x; yv1[j] = y2.y;
+        }
+      }
+      rd2_t bi;
+      double b0, b1;
+      one(i, zz.x, yh.x, d.x, ms.x, bc.x, fx.x != 0, bk.x != 0, bold.x, c0, b0, zh0, yv0);
+      one(i + 1, zz.y, yh.y, d.y, ms.y, bc.y, fx.y != 0, bk.y != 0, bold.y, c1, b1, zh1, yv1);
+      bi.x = b0; bi.y = b1;
+      __builtin_nontemporal_store(bi, reinterpret_cast<rd2_t*>(b + i));
+    } else if (i < n) {
+      const double zi = z[i], yh = yhat[i];
+      if (KH > 0) {
+#pragma unroll
+        for (int j = 0; j < KH; ++j) {
+          zh0[j] = (j < ku && !defer) ? zo[j][i] : zi;
+          yv0[j] = j < ku ? yo[j][i] : yh;
+        }
+      }
+      double b0;
+      one(i, zi, yh, ds[i], mass[i], bconst[i], fixed[i] != 0, isblk[i] != 0, isblk[i] ? b[i] : 0.0, cmap[i], b0, zh0, yv0);
+      b[i] = b0;
+    }
+  }
+  if (__any(moved) && (threadIdx.x & 63) == 0) atomicMax(flag, stamp);
+  const double t = block_sum(acc, s_red);
+  const double tb = block_sum(accb, s_red);
+  const double tw = block_sum(accw, s_red);
+  if (!ticket) {
+    if (threadIdx.x == 0) {
+      partials[blockIdx.x] = t;
+      partials[G0 + blockIdx.x] = tb;
+      partials[2 * (size_t)G0 + blockIdx.x] = tw;
+      if (KH > 0 && blockIdx.x == 0) *g.count += (double)ku;
+    }
+    return;
+  }
+  if (threadIdx.x == 0) {
+    pg::store_partial(partials + blockIdx.x, t);
+    pg::store_partial(partials + G0 + blockIdx.x, tb);
+    pg::store_partial(partials + 2 * (size_t)G0 + blockIdx.x, tw);
+  }
+  const double th = block_sum(acch, s_red);
+  if (threadIdx.x == 0) pg::store_partial(partials + 3 * (size_t)G0 + blockIdx.x, th);
+  if (!pg::last_block_arrives(ticket, G0, s_red)) return;
+  // (k_start's work, in its order of summation)
+  if (threadIdx.x < pg::S_COUNT) sc[threadIdx.x] = threadIdx.x == pg::S_RELTOL2 ? reltol2 : (threadIdx.x == pg::S_ABSTOL2 ? abstol2 : 0.0);
+  __syncthreads();
+  for (int sl = 0; sl < 4; ++sl) {      // (slot 3: the rows that stayed)
+    double a = 0.0;
+    for (int i = threadIdx.x; i < (int)G0; i += BLOCK) a += pg::load_partial(partials + (size_t)sl * G0 + i);
+    const double sum = block_sum(a, s_red);
+    if (threadIdx.x == 0) sc[pg::S_RED0 + sl] = sum;
+  }
+  if (threadIdx.x == 0) {
+    pg::derive(pg::PH_INIT, sc);
+    // (every block's atomicMax on the flag was drained before it drew its ticket)
+    sc[pg::S_MOVED] = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == stamp ? 1.0 : 0.0;
+    const double held = sc[pg::S_RED0 + 3];
+    if (held > 0.0) {
+      if (2.0 * held >= sc[pg::S_TOL2]) sc[pg::S_MOVED] = 1.0;
+      else {
+        sc[pg::S_HELD] = held;
+        sc[pg::S_TOL2] -= held;
+        sc[pg::S_DONE] = sc[pg::S_RR] <= sc[pg::S_TOL2] ? 1.0 : 0.0;
+      }
+    }
+    if (KH > 0) *g.count += (double)ku;
+  }
+}
+
 __global__ __launch_bounds__(BLOCK) void k_guess_fit(i64 n, const int* __restrict__ cmap, const double* __restrict__ ds,
                                                      const double* __restrict__ b, const double* __restrict__ yn,
                                                      const double* __restrict__ rhat, GuessFit f) {
@@ -871,38 +1072,7 @@ __global__ __launch_bounds__(BLOCK) void k_guess_fit(i64 n, const int* __restric
     }
   }
   if (!pg::last_block_arrives(f.ticket, gridDim.x, s_red)) return;
-  // the blocks' partial sums, in a fixed order: a wave per sum, a lane per block (at most 128 blocks), shuffle tree -- every
-  // load of a wave in flight before the first is used, the trees level by level
-  {
-    constexpr int PW = (NS + BLOCK / 64 - 1) / (BLOCK / 64);   // sums per wave
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, G = (int)gridDim.x;
-    double a0[PW], a1[PW];
-#pragma unroll
-    for (int k = 0; k < PW; ++k) {
-      const int sl = wave + k * (BLOCK / 64);
-      a0[k] = (sl < NS && lane < G) ? pg::load_partial(f.partials + (size_t)sl * G + lane) : 0.0;
-      a1[k] = (sl < NS && lane + 64 < G) ? pg::load_partial(f.partials + (size_t)sl * G + lane + 64) : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < PW; ++k) a0[k] += a1[k];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-      for (int k = 0; k < PW; ++k) a0[k] += __shfl_down(a0[k], off, 64);
-    if (lane == 0) {
-#pragma unroll
-      for (int k = 0; k < PW; ++k) {
-        const int sl = wave + k * (BLOCK / 64);
-        if (sl < NS) s_g[sl] = a0[k];
-      }
-    }
-  }
-  __syncthreads();
-  if (f.sums) {                     // several ranks: the sums go through an all-reduce, k_guess_decide follows
-    if (threadIdx.x < NS) f.sums[threadIdx.x] = s_g[threadIdx.x];
-    return;
-  }
-  guess_decide(s_g, f);
+  guess_fit_last(f, (int)gridDim.x, s_g);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_guess_decide(GuessFit f) {
@@ -1959,11 +2129,17 @@ struct GuessPlan {
   int KH = 0, R = 0, hist_had = 0;
   bool refit = true;      // false: this step keeps the coefficients it has (see guess_prepare)
   GuessArgs ga{};
+  bool fit_due() const { return KH > 0 && hist_had > 0 && refit; }
 };
+
+inline double* guess_block(pg_solver* s) { return s->guess_coef.p + (s->guess_buf ? GUESS_USED : 0); }
 
 // before the step's first kernel: the ring buffers and the kernel's arguments; the count of valid older states is taken
 // and reset (guess_commit restores it once the step has gone its way to the end)
-GuessPlan guess_prepare(pg_solver* s, const void* owner, bool allowed, double last_products, hipStream_t stream) {
+// two_blocks: the caller's fit rides in its right-hand-side launch and alternates between the two coefficient blocks; every
+// other caller reads and rewrites block 0 (a solver that changes from the one to the other starts its history afresh)
+GuessPlan guess_prepare(pg_solver* s, const void* owner, bool allowed, double last_products, hipStream_t stream,
+                        bool two_blocks = false) {
   const Config& cfg = config();
   GuessPlan gp;
   // a loop that is down to the smallest polynomial (or meets the tolerance at the start) has nothing left to save: the fit
@@ -1974,6 +2150,7 @@ GuessPlan guess_prepare(pg_solver* s, const void* owner, bool allowed, double la
   gp.hist_had = (s->hist_de == owner && s->hist_k == gp.R) ? s->hist_cnt : 0;
   s->hist_cnt = 0;
   if (gp.KH == 0) return gp;
+  if (!two_blocks && s->guess_buf != 0) gp.hist_had = 0;
   const int R = gp.R;
   const i64 nva = s->z.n;
   if (s->guess_coef.n == 0) { s->guess_coef.alloc(GUESS_USED + 16); s->guess_coef.zero(); s->guess_ticket.alloc(1); s->guess_ticket.zero(); }
@@ -1981,37 +2158,53 @@ GuessPlan guess_prepare(pg_solver* s, const void* owner, bool allowed, double la
     if (j < R && s->zh[j].n != nva) { s->zh[j].alloc(nva); s->zh[j].zero(); }   //  product while the fit still reads the others)
     if (s->yh[j].n != nva) { s->yh[j].alloc(nva); s->yh[j].zero(); }
   }
-  if (gp.hist_had == 0) PG_HIP(hipMemsetAsync(s->guess_coef.p, 0, 12 * sizeof(double), stream));   // (the counters stay)
+  if (gp.hist_had == 0) {
+    PG_HIP(hipMemsetAsync(s->guess_coef.p, 0, 12 * sizeof(double), stream));   // (the counters stay)
+    PG_HIP(hipMemsetAsync(s->guess_coef.p + GUESS_USED, 0, 12 * sizeof(double), stream));
+    s->guess_buf = 0;
+  }
   for (int j = 0; j < 8; ++j) { gp.ga.zr[j] = s->zh[std::min(j, R - 1)].p; gp.ga.yr[j] = s->yh[std::min(j, R - 1)].p; }
   gp.ga.znew = s->zh[R - 1].p;
-  gp.ga.coef = s->guess_coef.p;
+  gp.ga.coef = guess_block(s);
+  gp.ga.count = s->guess_coef.p + 13;
+  gp.ga.used = nullptr;
   return gp;
 }
 
 // after the step's first kernel: the fit for the next step (k_guess_fit; cmap == NULL: every row is in the loop), then the
 // buffers trade places
-void guess_after_rhs(pg_solver* s, const GuessPlan& gp, i64 n, const int* cmap, const double* ds, const double* rhat, bool single,
-                     KrylovWork& w, hipStream_t stream) {
-  if (gp.KH == 0) return;
+// the fit's arguments and its number of blocks (gp.fit_due() holds); the coefficients go to the block that stands
+GuessFit guess_fit_args(pg_solver* s, const GuessPlan& gp, i64 n, bool single, const KrylovWork& w, int& gfit) {
   const Config& cfg = config();
   const int R = gp.R;
-  if (gp.hist_had > 0 && gp.refit) {
-    GuessFit gf{};
-    for (int j = 0; j < 8; ++j) gf.yr[j] = s->yh[std::min(j, R - 1)].p;
-    const i64 nchunk = (n + BLOCK - 1) / BLOCK;
-    gf.stride = (int)std::max<i64>(1, std::min<i64>(cfg.guess_monitor, nchunk / 128));   // (small systems: every chunk)
-    const int gfit = (int)std::min<i64>(128, (nchunk + gf.stride - 1) / gf.stride);
-    if (s->guess_partials.n != (i64)GUESS_NS * std::max(gfit, 1)) s->guess_partials.alloc((i64)GUESS_NS * std::max(gfit, 1));
-    gf.partials = s->guess_partials.p;
-    gf.ticket = s->guess_ticket.p;
-    gf.coef = s->guess_coef.p;
-    gf.avail = std::min(gp.hist_had, GUESS_RM);
-    gf.kmax = gp.KH;
-    gf.rate2 = w.last_rate2;
-    gf.pass_cost = cfg.guess_pass_cost;
-    gf.gain = cfg.guess_gain;
-    gf.sums = single ? nullptr : s->guess_coef.p + 16;
-    hipLaunchKernelGGL(k_guess_fit, dim3(std::max(gfit, 1)), dim3(BLOCK), 0, stream, n, cmap, ds, (const double*)s->b.p,
+  GuessFit gf{};
+  for (int j = 0; j < 8; ++j) gf.yr[j] = s->yh[std::min(j, R - 1)].p;
+  const i64 nchunk = (n + BLOCK - 1) / BLOCK;
+  gf.stride = (int)std::max<i64>(1, std::min<i64>(cfg.guess_monitor, nchunk / 128));   // (small systems: every chunk)
+  gfit = std::max((int)std::min<i64>(128, (nchunk + gf.stride - 1) / gf.stride), 1);
+  if (s->guess_partials.n != (i64)GUESS_NS * gfit) s->guess_partials.alloc((i64)GUESS_NS * gfit);
+  gf.partials = s->guess_partials.p;
+  gf.ticket = s->guess_ticket.p;
+  gf.coef = guess_block(s);
+  gf.avail = std::min(gp.hist_had, GUESS_RM);
+  gf.kmax = gp.KH;
+  gf.rate2 = w.last_rate2;
+  gf.pass_cost = cfg.guess_pass_cost;
+  gf.gain = cfg.guess_gain;
+  gf.sums = single ? nullptr : s->guess_coef.p + 16;
+  gf.nblocks = gfit;
+  return gf;
+}
+
+// fit_done: the fit has run inside the step's first kernel (step_compact)
+void guess_after_rhs(pg_solver* s, const GuessPlan& gp, i64 n, const int* cmap, const double* ds, const double* rhat, bool single,
+                     KrylovWork& w, hipStream_t stream, bool fit_done = false) {
+  if (gp.KH == 0) return;
+  const int R = gp.R;
+  if (gp.fit_due() && !fit_done) {
+    int gfit = 0;
+    const GuessFit gf = guess_fit_args(s, gp, n, single, w, gfit);
+    hipLaunchKernelGGL(k_guess_fit, dim3(gfit), dim3(BLOCK), 0, stream, n, cmap, ds, (const double*)s->b.p,
                        (const double*)s->y.p, rhat, gf);
     if (!single) {
       comm_allreduce_sum_f64(gf.sums, GUESS_NS, stream);
@@ -2035,7 +2228,7 @@ void guess_commit(pg_solver* s, const GuessPlan& gp, const void* owner) {
   if (gp.KH == 0) return;
   if (config().debug) {
     double hc[16];
-    s->guess_coef.download(hc, 16);
+    s->guess_coef.download(hc, 16, s->guess_buf ? GUESS_USED : 0);
     fprintf(stderr, "[pg_solver] extrapolated start: %d older states kept; sampled (r,r)_W plain %.3e, taken %.3e; next step: %d states",
             gp.hist_had, hc[9], hc[10], (int)hc[4]);
     for (int j = 0; j < (int)hc[4]; ++j) fprintf(stderr, " z(n-%d)*%.4f", (int)hc[5 + j] + 1, hc[j]);
@@ -2051,6 +2244,32 @@ void launch_rhs_block_mf(pg_solver* s, int scheme, const CsrMatrix& A, hipStream
   hipLaunchKernelGGL(k_rhs_block_mf, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, make_params(s, scheme), make_segs(s->nb),
                      s->Mloc, A.n_blk, A.blk_rows.p, A.blk_idx.p, A.blk_coef.p, s->nb.row_cell.p, s->nb.red.p, A.ds.p,
                      (const double*)s->z.p, s->mass.p, s->bconst.p, s->fixed.p, s->b.p);
+}
+
+// The block rows of the warm loop's right-hand side.  rhs_block_cached: they come from the tables of k_blk_cache, which are
+// brought up to date here (false: there are none, or the diphasic CN form evaluates them matrix-free); launch_rhs_block: the
+// launch that writes them to b̂, whichever form it is.
+bool rhs_block_cached(pg_solver* s, int scheme, const CsrMatrix& A) {
+  hipStream_t stream = ctx().stream;
+  const bool blk_mf = s->nphase == 2 && scheme == PG_SCHEME_CN;   // (see k_rhs_block_mf)
+  if (A.n_blk <= 0 || blk_mf) return false;
+  if (s->blk_cache_matrix != &A || s->blk_cache_scheme != scheme || s->blk_cache_version != s->bconst_version) {
+    if (s->blk_wz.n != A.n_blk * MAX_KINDS) s->blk_wz.alloc(A.n_blk * MAX_KINDS);   // (time-dependent data: rebuilt every step)
+    if (s->blk_c0.n != A.n_blk) s->blk_c0.alloc(A.n_blk);
+    hipLaunchKernelGGL(k_blk_cache, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_idx.p,
+                       A.blk_coef.p, A.ds.p, s->mass.p, s->bconst.p, s->fixed.p, s->blk_wz.p, s->blk_c0.p);
+    s->blk_cache_matrix = &A; s->blk_cache_scheme = scheme; s->blk_cache_version = s->bconst_version;
+  }
+  return true;
+}
+
+void launch_rhs_block(pg_solver* s, int scheme, const CsrMatrix& A, hipStream_t stream) {
+  if (A.n_blk <= 0) return;
+  if (rhs_block_cached(s, scheme, A))
+    hipLaunchKernelGGL(k_rhs_block_c, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_rows.p,
+                       BlkTables{A.blk_idx.p, s->blk_wz.p, s->blk_c0.p, A.blk_cn.p, nullptr}, (const double*)s->z.p,
+                       (const double*)s->y.p, s->b.p);
+  else launch_rhs_block_mf(s, scheme, A, stream);
 }
 
 // The compact warm step: the right-hand-side kernel solves the rows alone on their diagonal, BiCGStab with the polynomial runs on
@@ -2076,32 +2295,49 @@ void step_compact(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMa
   // Several ranks: "unchanged data" is the same verdict everywhere, the fit's sums go through an all-reduce and every rank
   // takes the same decision.
   guess_policy(DE.guess_on, DE.last_products, DE.bytes_per_rank);
-  GuessPlan gp = guess_prepare(s, &DE, same_data && DE.guess_on, DE.last_products, stream);
+  const Config& cfg = config();
+  // PG_STEP_FUSE, one rank: the fit for the next step rides in the right-hand-side launch -- blocks of the same launch, past its
+  // w.grid main ones, writing the coefficient block this launch does not read.  Not where the block rows are evaluated
+  // matrix-free (k_rhs_block_mf): the fit's blocks evaluate the block rows they sample from the tables of k_blk_cache (do_step
+  // has brought them up to date), and read no b̂.
+  const bool fuse_mode = cfg.step_fuse && single && !(A.n_blk > 0 && s->nphase == 2 && scheme == PG_SCHEME_CN);
+  GuessPlan gp = guess_prepare(s, &DE, same_data && DE.guess_on, DE.last_products, stream, fuse_mode);
   const int KH = gp.KH;
   // the extrapolated state itself is formed by the solve's first update of x (KrylovCall::xguess): the older states are
   // then read there through the compact system's index map, once, and this kernel neither reads them nor writes the state
-  const Config& cfg = config();
   // (not after a solve that met the tolerance at its start: the next one probably will too, no update of x runs then, and
   //  writing the state from the first s kernel's early exit costs more than writing it here -- 64^3 BE near steady state)
   const bool defer = KH > 0 && cfg.guess_defer && DE.last_products > 0.0;
   gp.ga.defer = defer ? 1 : 0;
+  const bool fit_rides = fuse_mode && rhs_fuses(KH, defer);      // (whenever a fit is due)
+  const bool fit_fused = fit_rides && gp.fit_due();
+  const BlkTables bt{A.blk_idx.p, s->blk_wz.p, s->blk_c0.p, A.blk_cn.p, A.n_blk > 0 ? A.blk_pos.p : nullptr};
+  int gfit = 0;
+  GuessFit gf{};
+  if (fit_fused) {
+    gf = guess_fit_args(s, gp, n, true, w, gfit);
+    s->guess_buf ^= 1;
+    gf.coef = guess_block(s);
+  }
+  // (the fit rides: nothing rewrites the block this launch reads before the step is over -- the first update of x reads it there too)
+  gp.ga.used = (defer && !fit_rides) ? s->guess_coef.p + GUESS_USED : nullptr;
   const GuessArgs& ga = gp.ga;
   const double* zprev = s->z.p;      // z^n (the buffers trade places below)
-#define PG_RHS_INIT_C(KHV)                                                                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV>), dim3(w.grid), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p,   \
+#define PG_RHS_INIT_C(KHV, DF)                                                                                                    \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV, DF>), dim3(w.grid + gfit * FIT_PARTS), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p, \
                      s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, DE.cmap.p, s->b.p, (const double*)DE.gdiag.p, DE.delta.p,     \
                      DE.flag.p, stamp, w.rhat.p, w.partials.p, quiet ? w.ticket.p : nullptr, w.sc.p, o.reltol * o.reltol,          \
-                     o.abstol * o.abstol, same_data ? 0 : 1, ga)
+                     o.abstol * o.abstol, same_data ? 0 : 1, ga, bt, gf, w.grid)
   switch (KH) {
-    case 1: PG_RHS_INIT_C(1); break;
-    case 2: PG_RHS_INIT_C(2); break;
-    case 3: PG_RHS_INIT_C(3); break;
-    case 4: PG_RHS_INIT_C(4); break;
-    default: PG_RHS_INIT_C(0); break;
+    case 1: if (defer) PG_RHS_INIT_C(1, true); else PG_RHS_INIT_C(1, false); break;
+    case 2: if (defer) PG_RHS_INIT_C(2, true); else PG_RHS_INIT_C(2, false); break;
+    case 3: if (defer) PG_RHS_INIT_C(3, true); else PG_RHS_INIT_C(3, false); break;
+    case 4: if (defer) PG_RHS_INIT_C(4, true); else PG_RHS_INIT_C(4, false); break;
+    default: PG_RHS_INIT_C(0, false); break;
   }
 #undef PG_RHS_INIT_C
   PG_HIP(hipGetLastError());
-  guess_after_rhs(s, gp, n, (const int*)DE.cmap.p, (const double*)A.ds.p, (const double*)w.rhat.p, single, w, stream);
+  guess_after_rhs(s, gp, n, (const int*)DE.cmap.p, (const double*)A.ds.p, (const double*)w.rhat.p, single, w, stream, fit_fused);
   if (!same_data) diag_fix(DE, s->nb, s->slab, stamp, !single, w.rhat.p, w.partials.p, w.grid, stream);
   KrylovCall call;
   call.preinit = call.p_in_rhat = true;
@@ -2122,7 +2358,7 @@ void step_compact(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMa
   if (defer) {
     call.xguess.zbase = zprev;
     for (int j = 0; j < 8; ++j) call.xguess.zr[j] = ga.zr[j];
-    call.xguess.coef = s->guess_coef.p + GUESS_USED;
+    call.xguess.coef = ga.used ? ga.used : ga.coef;
   }
   krylov_solve(DE.A, DE.nb, s->slab, nullptr, s->z.p, w, o, st, call);
   // the speculative product stands when the solve ended inside its first batch (nothing has touched z since)
@@ -2295,20 +2531,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     const bool have_y = s->spec_y_valid && s->spec_matrix == &A;
     s->spec_y_valid = false;
     if (!have_y) spmv_halo(A, s->nb, s->slab, s->z.p, s->y.p, stream);
-    const bool blk_mf = s->nphase == 2 && scheme == PG_SCHEME_CN;   // (see k_rhs_block_mf)
-    if (A.n_blk > 0 && blk_mf) launch_rhs_block_mf(s, scheme, A, stream);
-    else if (A.n_blk > 0) {
-      if (s->blk_cache_matrix != &A || s->blk_cache_scheme != scheme || s->blk_cache_version != s->bconst_version) {
-        if (s->blk_wz.n != A.n_blk * MAX_KINDS) s->blk_wz.alloc(A.n_blk * MAX_KINDS);   // (time-dependent data: rebuilt every step)
-        if (s->blk_c0.n != A.n_blk) s->blk_c0.alloc(A.n_blk);
-        hipLaunchKernelGGL(k_blk_cache, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_idx.p,
-                           A.blk_coef.p, A.ds.p, s->mass.p, s->bconst.p, s->fixed.p, s->blk_wz.p, s->blk_c0.p);
-        s->blk_cache_matrix = &A; s->blk_cache_scheme = scheme; s->blk_cache_version = s->bconst_version;
-      }
-      hipLaunchKernelGGL(k_rhs_block_c, dim3(grid_for(A.n_blk, BLOCK)), dim3(BLOCK), 0, stream, A.n_blk, scheme, A.blk_rows.p,
-                         A.blk_idx.p, (const double*)s->blk_wz.p, (const double*)s->blk_c0.p, A.blk_cn.p, (const double*)s->z.p,
-                         (const double*)s->y.p, s->b.p);
-    }
+    launch_rhs_block(s, scheme, A, stream);
     // rows alone on their diagonal (interface AND border identity rows) left out, compact vectors (pg_reduce.hip, DiagElim)
     DiagElim& DE = (&A == &s->A_ctor) ? s->diag_ctor : s->diag_run;
     // (PG_PRECOND_MG_STEP iterates on the full system: neither the compact system nor the γ elimination starts)
@@ -3824,7 +4047,7 @@ int32_t pg_solver_guess_info(pg_solver* s, int32_t* kept, int32_t* nstates, int3
   for (int j = 0; j < 4; ++j) { offsets[j] = 0; coef[j] = 0.0; }
   if (s->guess_coef.n >= 16 && s->hist_cnt > 0) {
     double hc[16];
-    s->guess_coef.download(hc, 16);
+    s->guess_coef.download(hc, 16, s->guess_buf ? GUESS_USED : 0);
     *nstates = (int32_t)hc[4];
     for (int j = 0; j < *nstates && j < 4; ++j) { offsets[j] = (int32_t)hc[5 + j] + 1; coef[j] = hc[j]; }
     *rr_plain = hc[9];

@@ -119,6 +119,7 @@ struct CsrMatrix {
   DevBuf<int> blk_rows, blk_idx;
   DevBuf<double> blk_coef, blk_cn, blk_fw;
   DevBuf<unsigned char> isblk;   // n: 1 for the rows listed in blk_rows
+  DevBuf<int> blk_pos;           // n: row -> its index in blk_rows (the scan of isblk: meaningful where isblk is set only)
 };
 // The polynomial stagnated on A (CsrMatrix::poly_gave_up).  What a matrix has been found to be is not part of its value: the
 // solves that find it out hold the matrix const, so the verdict is written through that here, in one place.
