@@ -883,6 +883,18 @@ int32_t pg_debug_specest_hessenberg(pg_solver* s, int32_t which, int32_t* steps,
 int32_t pg_solver_guess_info(pg_solver* s, int32_t* kept, int32_t* nstates, int32_t* offsets /* [4] */, double* coef /* [4] */,
                              double* rr_plain, double* rr_taken);
 
+/* Rows whose per-row constants are one value (PG_ROW_CONST, default 1; no reference counterpart): the compact loop's kernels
+   take the equilibration weight, the mass, the constant part of the right-hand side and the index maps of such rows from
+   their arguments instead of streaming them, in groups of 16 consecutive rows.  out[0], out[1]: groups and qualifying groups
+   of the full system's table; out[2], out[3]: of the loop system's -- for the compact system the last step ran on (zeros:
+   the last step did not take the compact loop, or PG_ROW_CONST=0). */
+int32_t pg_solver_row_const_info(pg_solver* s, int64_t* out /* [4] */);
+/* (tests) The mark that says where the constant part of the right-hand side is one value as well, for the same system.  It is
+   data, not matrix: valid for one version of that vector, built at the second step in a row that finds the same version (later
+   where marks were dropped sooner than they waited).  out[0]: 1 if the last step's launch took a mark; out[1]: groups it marks;
+   out[2]: marks built so far on this system; out[3]: launches that took the standing mark. */
+int32_t pg_debug_row_const_bconst(pg_solver* s, int64_t* out /* [4] */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1101,6 +1101,20 @@ class Solver:
         return {"kept": kept.value, "offsets": list(off[: ns.value]), "coef": list(cf[: ns.value]), "rr_plain": ru.value,
                 "rr_taken": rw.value}
 
+    def row_const_info(self) -> dict:
+        """Groups of 16 rows whose per-row constants are one value (pg_solver_row_const_info, PG_ROW_CONST): groups and
+        qualifying groups of the full system's and of the loop system's table, for the compact loop the last step took."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().pg_solver_row_const_info(self._h, out))
+        return {"full_groups": int(out[0]), "full_const": int(out[1]), "loop_groups": int(out[2]), "loop_const": int(out[3])}
+
+    def row_const_bconst_info(self) -> dict:
+        """(tests) The bconst mark of row_const_info's full table (pg_debug_row_const_bconst): whether the last step's launch took
+        one, the groups it marks, marks built so far and launches that took the standing one."""
+        out = (C.c_int64 * 4)()
+        L.check(L.lib().pg_debug_row_const_bconst(self._h, out))
+        return {"valid": int(out[0]), "const": int(out[1]), "builds": int(out[2]), "uses": int(out[3])}
+
     def mg_info(self, precond="mg") -> dict:
         """The multigrid hierarchy of the constructor system (pg_solver_mg_info): levels (0 before the first solve with
         that `precond`), tail_level, rows and nnz per level, setup_ms, bytes.  precond: "mg" or "mg-cell" -- a solver holds

@@ -109,6 +109,8 @@ struct Config {
                                   // extrapolation sits where the polynomial is weakest)
   bool step_fuse = true;          // PG_STEP_FUSE: one rank, compact loop: the fit rides in the right-hand-side launch (0: k_guess_fit as a
                                   // launch of its own -- A/B runs and the parity tests)
+  bool row_const = true;          // PG_ROW_CONST: compact loop: groups of 16 rows whose per-row constants are one value take them from the
+                                  // launch's arguments, not from memory (pg_reduce.h, RowConst; 0: every row streams them)
   bool speculate_product = true;  // PG_SPECULATE: pg_solver_run queues the next step's first product behind a solve's first batch
   int mg_tail_rows = 2048;        // PG_MG_TAIL_ROWS: multigrid levels of at most this many rows run in the fused one-workgroup tail, as far
                                   // as their vectors fit its LDS (pg_multigrid.hip; DESIGN.md "Multigrid")

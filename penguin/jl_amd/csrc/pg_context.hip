@@ -72,6 +72,7 @@ const Config& config() {
     k.guess_defer = geti("PG_GUESS_DEFER", 1) != 0;
     k.guess_gain = getd("PG_GUESS_GAIN", 0.8);
     k.step_fuse = geti("PG_STEP_FUSE", 1) != 0;
+    k.row_const = geti("PG_ROW_CONST", 1) != 0;
     k.unit_order = (int)geti("PG_SPMV_UNIT_ORDER", 0);
     return k;
   }();
@@ -402,11 +403,11 @@ int32_t pg_config_string(char* buf, size_t n) {
            "spmv_variant=%d spmv_xcd=%d spmv_strip=%d spmv_unit_order=%d spmv_march=%d spmv_edges=%d spmv_march_k=%d spmv_minrun=%d spmv_tile_units=%d "
            "spmv_blocks_per_cu=%d halo_overlap=%d speculate=%d poly=%d poly_degree=%d poly_adapt=%d "
            "poly_margin=%g poly_slack=%g poly_hist=%d poly_trend=%d poly_maxdeg=%d poly_f32=%d poly_f32_tail=%d gamma_elim=%d diag_elim=%d "
-           "guess_states=%d guess_depth=%d guess_defer=%d step_fuse=%d async_alloc=%d cache_limit_mb=%lld alloc_poison=%d alloc_guard=%d profile_sample=%d debug=%d",
+           "guess_states=%d guess_depth=%d guess_defer=%d step_fuse=%d row_const=%d async_alloc=%d cache_limit_mb=%lld alloc_poison=%d alloc_guard=%d profile_sample=%d debug=%d",
            k.spmv_variant, k.spmv_xcd, k.spmv_strip, k.unit_order, (int)k.spmv_march, (int)k.spmv_edges, k.spmv_march_k, k.spmv_minrun, k.spmv_tile_units,
            k.spmv_blocks_per_cu, (int)k.halo_overlap, (int)k.speculate_product, (int)k.poly, k.poly_degree, (int)k.poly_adapt,
            k.poly_margin, k.poly_slack, k.poly_hist, (int)k.poly_trend, k.poly_maxdeg, (int)k.poly_f32, k.poly_f32_tail,
-           (int)k.gamma_elim, (int)k.diag_elim, k.guess_n, k.guess_depth, (int)k.guess_defer, (int)k.step_fuse, k.async_alloc, k.pool_limit_mb, k.alloc_poison, k.alloc_guard, k.profile_sample, (int)k.debug);
+           (int)k.gamma_elim, (int)k.diag_elim, k.guess_n, k.guess_depth, (int)k.guess_defer, (int)k.step_fuse, (int)k.row_const, k.async_alloc, k.pool_limit_mb, k.alloc_poison, k.alloc_guard, k.profile_sample, (int)k.debug);
   if (buf && n > 0) {
     std::strncpy(buf, tmp, n - 1);
     buf[n - 1] = 0;

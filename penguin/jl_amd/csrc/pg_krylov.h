@@ -85,6 +85,9 @@ struct KrylovCall {
   // the system is a compact image of the caller's (pg_reduce.hip, DiagElim) and x is the caller's FULL vector -- the updates
   // x += α M⁻¹p, x += ω M⁻¹s land at x[scatter[i]].  Needs the polynomial path.
   const int* scatter = nullptr;
+  // with scatter: the table of the compact system's rows whose ds is one value and whose scatter indices are consecutive
+  // (pg_system.h, RowConst; tab == nullptr: none) -- k_bicg_s_x then loads neither on those rows (k_bicg_xrp streams: it measured slower with the table).
+  RowConst row_const;
   // with opts.precond = PG_PRECOND_MG and its kin: the multigrid hierarchy of THIS matrix (the caller has checked that the
   // system admits it, pg_solver.hip mg_prepare); refused without such a precond.
   MgHierarchy* mg = nullptr;

@@ -140,7 +140,8 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_s_x(i64 n, double* __restrict__ 
                                                     const double* __restrict__ rhat, double* __restrict__ r,
                                                     double* __restrict__ partials, const double* __restrict__ ds,
                                                     unsigned* __restrict__ ticket, int r_in_rhat, const double* __restrict__ phat,
-                                                    double* x, const int* __restrict__ map, XGuess xg, int first_launch) {
+                                                    double* x, const int* __restrict__ map, XGuess xg, int first_launch,
+                                                    RowConst rc) {
   __shared__ double s_red[BLOCK / 64];
   const bool done = sc[S_DONE] != 0.0;
   if (done && !(xg.zbase != nullptr && first_launch != 0)) return;
@@ -189,14 +190,19 @@ __global__ __launch_bounds__(BLOCK) void k_bicg_s_x(i64 n, double* __restrict__ 
     const dd2 rh = *reinterpret_cast<const dd2*>(rhat + i);
     const dd2 rr = rrhat ? rh : *reinterpret_cast<const dd2*>(rsrc + i);
     const dd2 vv = __builtin_nontemporal_load(reinterpret_cast<const dd2*>(v + i));
-    const dd2 dw = *reinterpret_cast<const dd2*>(ds + i);
+    // (RowConst: a group of 16 rows -- 8 lanes -- whose ds is rc.d and whose map advances by one loads neither; e: map of its first row)
+    const int e = rc.tab ? rc.tab[i >> RC_SHIFT] : -1;
+    dd2 dw;
+    dw.x = rc.d; dw.y = rc.d;
+    if (e < 0) dw = *reinterpret_cast<const dd2*>(ds + i);
     const dd2 ph = __builtin_nontemporal_load(reinterpret_cast<const dd2*>(phat + i));
     dd2 si;
     si.x = rr.x - alpha * vv.x;
     si.y = rr.y - alpha * vv.y;
     *reinterpret_cast<dd2*>(r + i) = si;
     if (map) {
-      const int j0 = map[i], j1 = map[i + 1];
+      int j0 = e + (int)(i & (RC_GROUP - 1)), j1 = j0 + 1;
+      if (e < 0) { j0 = map[i]; j1 = map[i + 1]; }
       if (fresh) {
         const double g0 = base_of(j0), g1 = base_of(j1);
         x[j0] = g0 + alpha * ph.x;
@@ -735,6 +741,8 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
   const bool p_in_rhat = call.p_in_rhat, start_folded = call.start_folded;
   const XGuess& xg = call.xguess;      // (first update of x out of place: see KrylovCall::xguess)
   const int* const scatter = call.scatter;
+  PG_REQUIRE(scatter || !call.row_const.tab, "krylov_solve: row_const describes scatter and is refused without it");
+  const RowConst rc = call.row_const;
   const bool fused_start = !start_folded && preinit && opts.method == PG_METHOD_BICGSTAB && cx.nranks == 1 && !cx.comm;   // k_start below
   if (!fused_start && !start_folded)
     hipLaunchKernelGGL(k_sc_reset, dim3(1), dim3(S_COUNT), 0, st, w.sc.p, opts.reltol * opts.reltol, opts.abstol * opts.abstol);
@@ -952,7 +960,7 @@ void krylov_solve(const CsrMatrix& A, const Numbering& nb, const Slab& slab, con
     // iteration the sums of slot 4 are simply not looked at
     if (pre)
       hipLaunchKernelGGL(k_bicg_s_x, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.v.p, w.rhat.p, w.r.p, w.partials.p, (const double*)A.ds.p, tk,
-                         p_in_rhat ? 1 : 0, (const double*)w.ya.p, x, scatter, xg, itn == 0 ? 1 : 0);
+                         p_in_rhat ? 1 : 0, (const double*)w.ya.p, x, scatter, xg, itn == 0 ? 1 : 0, rc);
     else
       hipLaunchKernelGGL(k_bicg_s, dim3(G), dim3(BLOCK), 0, st, n, w.sc.p, w.v.p, w.rhat.p, w.r.p, w.partials.p, (const double*)A.ds.p, tk,
                          p_in_rhat ? 1 : 0);

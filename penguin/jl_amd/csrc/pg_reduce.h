@@ -43,9 +43,31 @@ struct DiagElim {
   // for the fit's launch to pay (bytes_per_rank: a product's streamed bytes, averaged over the ranks -- the same everywhere)
   double bytes_per_rank = 0.0, last_products = 0.0;
   bool guess_on = false;
+  // RowConst tables of this system (build_row_const): rc_full over the n full rows (ds, mass, fixed, isblk, cmap), rc_loop over
+  // the n_c compact rows (A.ds, rlist); they describe cmap / rlist / ds and live and die with them.  rc_bmark follows the
+  // caller's bconst, which is data, not matrix: valid for the version rc_bmark_version alone (row_const_bconst).
+  bool rc_tried = false;
+  DevBuf<int> rc_full, rc_loop;
+  DevBuf<unsigned char> rc_bmark;
+  double rc_full_d = 0.0, rc_full_ms = 0.0, rc_loop_d = 0.0, rc_bc = 0.0;
+  long long rc_bmark_version = -1, rc_seen_version = -1;   // the version the mark stands for (-1: none) / seen at the last step
+  int rc_same = 0, rc_need = 2;                            // steps in a row with rc_seen_version / ... that a mark waits for
+  i64 rc_bmark_uses = 0, rc_bmark_builds = 0, rc_bmark_const = 0;   // launches that took this mark, marks built, groups this one marks
+  i64 rc_groups[2] = {0, 0}, rc_const[2] = {0, 0};   // groups / qualifying groups: full, loop
+  RowConst rc_view_full() const { return RowConst{rc_full.p, nullptr, rc_full_d, rc_full_ms, 0.0}; }
+  RowConst rc_view_loop() const { return RowConst{rc_loop.p, nullptr, rc_loop_d, 0.0, 0.0}; }
 };
 // Collective when several ranks run (every rank calls it at the same point: all-reduced activation test, one halo exchange).
 void build_diag_elim(const CsrMatrix& A, const Numbering& nb, const Slab& slab, DiagElim& E);
+// The RowConst tables of an active E (not collective: every rank describes its own rows).  mass / fixed: the caller's per-row
+// vectors over the full rows, constant for the life of E.  D* and M* are the pair that qualifies the most groups among the
+// pairs found at 32 evenly spaced groups -- a poor pick only qualifies fewer groups.
+void build_row_const(const CsrMatrix& A, const double* mass, const unsigned char* fixed, DiagElim& E);
+// The bconst mark of rc_full for the caller's bconst of `version`.  A version seen for the first time streams (data that change
+// every step would pay a pass over bconst per step for a mark used once); the rc_need-th step in a row with the same version
+// builds the mark (2, doubling up to 64 while marks are dropped sooner than they waited), every later one finds it.  Returns
+// the view the right-hand-side launch of THIS step takes: never a mark of another version.
+RowConst row_const_bconst(DiagElim& E, const double* bconst, long long version);
 // r_full: the start residuals of the rows that are left out (k_rhs_init_c; entries of the other rows are not read), r / r̂ / p:
 // the compact start residual.  x_E += r_E / d; the change goes through the coupling block into r, r̂, p; the start sums (slots
 // 0 and 2 of partials) are recomputed when the change is more than rounding noise.

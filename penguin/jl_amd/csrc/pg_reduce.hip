@@ -263,7 +263,211 @@ __global__ void k_c_couple(i64 n_wg, const int* __restrict__ wg_rows, const int*
   }
 }
 
+// ---- RowConst tables (pg_system.h): a thread per group of RC_GROUP rows, built once per system ----
+constexpr int RC_SAMPLES = 32;
+
+__device__ inline bool same_bits(double a, double b) { return __double_as_longlong(a) == __double_as_longlong(b); }
+
+// pre[g] = map[first row] where the group's rows have ONE value of v1 (and of v2, fixed = isblk = 0, where given) and mapped
+// indices that are >= 0 and consecutive; -1 elsewhere.  g1 / g2: the group's values.  Groups [ng_full, ng) are partial: -1.
+__global__ void k_rc_scan(i64 ng, i64 ng_full, const double* __restrict__ v1, const double* __restrict__ v2,
+                          const unsigned char* __restrict__ fixed, const unsigned char* __restrict__ isblk,
+                          const int* __restrict__ map, int* __restrict__ pre, double* __restrict__ g1, double* __restrict__ g2) {
+  for (i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x; g < ng; g += (i64)gridDim.x * blockDim.x) {
+    const i64 i0 = g * RC_GROUP;
+    bool ok = g < ng_full;
+    double a = 0.0, b = 0.0;
+    int m0 = -1;
+    if (ok) {
+      a = v1[i0];
+      b = v2 ? v2[i0] : 0.0;
+      m0 = map[i0];
+      ok = m0 >= 0;
+      for (int k = 0; k < RC_GROUP && ok; ++k) {
+        const i64 i = i0 + k;
+        ok = same_bits(v1[i], a) && map[i] == m0 + k;
+        if (ok && v2) ok = same_bits(v2[i], b);
+        if (ok && fixed) ok = fixed[i] == 0;
+        if (ok && isblk) ok = isblk[i] == 0;
+      }
+    }
+    pre[g] = ok ? m0 : -1;
+    g1[g] = a; g2[g] = b;
+  }
+}
+
+// the bconst variant: groups that qualify in tab and hold one value of bconst
+__global__ void k_rc_scan_b(i64 ng, const int* __restrict__ tab, const double* __restrict__ bconst, int* __restrict__ pre,
+                            double* __restrict__ g1) {
+  for (i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x; g < ng; g += (i64)gridDim.x * blockDim.x) {
+    bool ok = tab[g] >= 0;
+    double a = 0.0;
+    if (ok) {
+      const i64 i0 = g * RC_GROUP;
+      a = bconst[i0];
+      for (int k = 1; k < RC_GROUP && ok; ++k) ok = same_bits(bconst[i0 + k], a);
+    }
+    pre[g] = ok ? 0 : -1;
+    g1[g] = a;
+  }
+}
+
+// the candidates: the values of RC_SAMPLES evenly spaced groups
+__global__ void k_rc_sample(i64 ng, const int* __restrict__ pre, const double* __restrict__ g1, const double* __restrict__ g2,
+                            int* __restrict__ ok, double* __restrict__ c1, double* __restrict__ c2) {
+  const int k = threadIdx.x;
+  if (k >= RC_SAMPLES) return;
+  const i64 g = ((2 * (i64)k + 1) * ng) / (2 * RC_SAMPLES);
+  ok[k] = pre[g] >= 0 ? 1 : 0;
+  c1[k] = g1[g];
+  c2[k] = g2 ? g2[g] : 0.0;
+}
+
+// how many groups each candidate qualifies (integer counts: the same in every run)
+__global__ void k_rc_count(i64 ng, const int* __restrict__ pre, const double* __restrict__ g1, const double* __restrict__ g2, int nc,
+                           const double* __restrict__ c1, const double* __restrict__ c2, unsigned long long* __restrict__ counts) {
+  const i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+  const bool in = g < ng && pre[g] >= 0;
+  const double a = in ? g1[g] : 0.0, b = (in && g2) ? g2[g] : 0.0;
+  for (int k = 0; k < nc; ++k) {
+    const unsigned long long hit = __ballot(in && same_bits(a, c1[k]) && same_bits(b, c2[k]));
+    if ((threadIdx.x & 63) == 0 && hit) atomicAdd(counts + k, (unsigned long long)__popcll(hit));
+  }
+}
+
+// the table: pre where the group's values are the chosen ones, -1 elsewhere (tab, in place over pre) or the mark (0 / 1)
+__global__ void k_rc_final(i64 ng, int* __restrict__ pre, const double* __restrict__ g1, const double* __restrict__ g2, double a, double b,
+                           unsigned char* __restrict__ mark) {
+  for (i64 g = blockIdx.x * (i64)blockDim.x + threadIdx.x; g < ng; g += (i64)gridDim.x * blockDim.x) {
+    const bool ok = pre[g] >= 0 && same_bits(g1[g], a) && (!g2 || same_bits(g2[g], b));
+    if (mark) mark[g] = ok ? 1 : 0;
+    else if (!ok) pre[g] = -1;
+  }
+}
+
 }  // namespace
+
+namespace {
+// among the pairs of values at the sampled groups, the one that the most groups have (the first of equals); returns that
+// count, 0 where no sampled group qualifies
+i64 rc_pick(i64 ng, const int* pre, const double* g1, const double* g2, double& a, double& b, hipStream_t st) {
+  a = b = 0.0;
+  if (ng <= 0) return 0;
+  DevBuf<int> d_ok(RC_SAMPLES);
+  DevBuf<double> d_c(2 * RC_SAMPLES);
+  hipLaunchKernelGGL(k_rc_sample, dim3(1), dim3(64), 0, st, ng, pre, g1, g2, d_ok.p, d_c.p, d_c.p + RC_SAMPLES);
+  PG_HIP(hipGetLastError());
+  int ok[RC_SAMPLES];
+  double c[2 * RC_SAMPLES];
+  d_ok.download(ok, RC_SAMPLES);
+  d_c.download(c, 2 * RC_SAMPLES);
+  double h1[RC_SAMPLES], h2[RC_SAMPLES];
+  int nc = 0;
+  auto bits = [](double v) { long long q; std::memcpy(&q, &v, sizeof q); return q; };
+  for (int k = 0; k < RC_SAMPLES; ++k) {
+    if (!ok[k]) continue;
+    bool seen = false;
+    for (int j = 0; j < nc; ++j) seen = seen || (bits(h1[j]) == bits(c[k]) && bits(h2[j]) == bits(c[RC_SAMPLES + k]));
+    if (!seen) { h1[nc] = c[k]; h2[nc] = c[RC_SAMPLES + k]; ++nc; }
+  }
+  if (nc == 0) return 0;
+  DevBuf<unsigned long long> d_cnt(RC_SAMPLES);
+  d_cnt.zero();
+  std::memcpy(c, h1, sizeof(double) * nc);
+  std::memcpy(c + RC_SAMPLES, h2, sizeof(double) * nc);
+  d_c.upload(c, 2 * RC_SAMPLES);
+  hipLaunchKernelGGL(k_rc_count, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, st, ng, pre, g1, g2, nc, (const double*)d_c.p,
+                     (const double*)(d_c.p + RC_SAMPLES), d_cnt.p);
+  PG_HIP(hipGetLastError());
+  unsigned long long cnt[RC_SAMPLES];
+  d_cnt.download(cnt, RC_SAMPLES);
+  int best = 0;
+  for (int j = 1; j < nc; ++j)
+    if (cnt[j] > cnt[best]) best = j;
+  a = h1[best]; b = h2[best];
+  return (i64)cnt[best];
+}
+
+// one table: the rows [0, n) of v1 (v2, fixed, isblk where given) and map
+i64 rc_table(i64 n, const double* v1, const double* v2, const unsigned char* fixed, const unsigned char* isblk, const int* map,
+             DevBuf<int>& tab, double& a, double& b, hipStream_t st) {
+  const i64 ng = (n + RC_GROUP - 1) / RC_GROUP, ng_full = n / RC_GROUP;
+  tab.alloc(ng > 0 ? ng : 1);
+  a = b = 0.0;
+  if (ng <= 0) return 0;
+  DevBuf<double> g1(ng), g2(ng);
+  hipLaunchKernelGGL(k_rc_scan, dim3(grid_for(ng, 256)), dim3(256), 0, st, ng, ng_full, v1, v2, fixed, isblk, map, tab.p, g1.p, g2.p);
+  PG_HIP(hipGetLastError());
+  const i64 cnt = rc_pick(ng, tab.p, g1.p, g2.p, a, b, st);
+  if (cnt > 0)
+    hipLaunchKernelGGL(k_rc_final, dim3(grid_for(ng, 256)), dim3(256), 0, st, ng, tab.p, (const double*)g1.p, (const double*)g2.p, a, b,
+                       (unsigned char*)nullptr);
+  else PG_HIP(hipMemsetAsync(tab.p, 0xff, sizeof(int) * (size_t)ng, st));   // (no sampled group qualifies: every entry -1)
+  PG_HIP(hipGetLastError());
+  PG_HIP(hipStreamSynchronize(st));   // (g1 / g2 are freed on return)
+  return cnt;
+}
+}  // namespace
+
+void build_row_const(const CsrMatrix& A, const double* mass, const unsigned char* fixed, DiagElim& E) {
+  E.rc_tried = true;
+  E.rc_full.release(); E.rc_loop.release(); E.rc_bmark.release();
+  E.rc_bmark_version = E.rc_seen_version = -1;
+  E.rc_same = 0; E.rc_need = 2; E.rc_bmark_uses = E.rc_bmark_builds = E.rc_bmark_const = 0;
+  for (int k = 0; k < 2; ++k) E.rc_groups[k] = E.rc_const[k] = 0;
+  if (!config().row_const || !E.active || E.n <= 0 || E.n_c <= 0) return;
+  hipStream_t st = ctx().stream;
+  E.rc_groups[0] = (E.n + RC_GROUP - 1) / RC_GROUP;
+  E.rc_const[0] = rc_table(E.n, A.ds.p, mass, fixed, A.isblk.p, E.cmap.p, E.rc_full, E.rc_full_d, E.rc_full_ms, st);
+  double unused = 0.0;
+  E.rc_groups[1] = (E.n_c + RC_GROUP - 1) / RC_GROUP;
+  E.rc_const[1] = rc_table(E.n_c, E.A.ds.p, nullptr, nullptr, nullptr, E.rlist.p, E.rc_loop, E.rc_loop_d, unused, st);
+  if (config().debug)
+    fprintf(stderr, "[pg_reduce] rank %d: rows with one value of their constants: %lld of %lld groups of %d full rows, %lld of %lld of the loop's\n",
+            ctx().rank, (long long)E.rc_const[0], (long long)E.rc_groups[0], RC_GROUP, (long long)E.rc_const[1], (long long)E.rc_groups[1]);
+}
+
+RowConst row_const_bconst(DiagElim& E, const double* bconst, long long version) {
+  RowConst rc = E.rc_view_full();
+  if (!rc.tab || E.rc_const[0] <= 0) return rc;
+  if (E.rc_bmark_version != version) {
+    if (E.rc_seen_version != version) {
+      // another bconst.  Building a mark costs a pass over bconst, two small allocations and three waits for the device; a
+      // mark that was dropped after fewer launches than it waited for doubles the wait of the next one (data that change
+      // every k-th step: at most 64 steps), a mark that served 8 times as long resets it
+      if (E.rc_bmark_version >= 0) {
+        if (E.rc_bmark_uses < E.rc_need) E.rc_need = std::min(2 * E.rc_need, 64);
+        else if (E.rc_bmark_uses >= 8 * E.rc_need) E.rc_need = 2;
+      }
+      E.rc_bmark_version = -1;
+      E.rc_seen_version = version;
+      E.rc_same = 0;
+    }
+    if (++E.rc_same < E.rc_need) return rc;          // (bconst streams in this step)
+    hipStream_t st = ctx().stream;
+    const i64 ng = E.rc_groups[0];
+    if (E.rc_bmark.n != ng) E.rc_bmark.alloc(ng);
+    DevBuf<int> pre(ng);
+    DevBuf<double> g1(ng);
+    hipLaunchKernelGGL(k_rc_scan_b, dim3(grid_for(ng, 256)), dim3(256), 0, st, ng, (const int*)E.rc_full.p, bconst, pre.p, g1.p);
+    PG_HIP(hipGetLastError());
+    double unused = 0.0;
+    E.rc_bmark_const = rc_pick(ng, pre.p, g1.p, nullptr, E.rc_bc, unused, st);
+    if (E.rc_bmark_const > 0)
+      hipLaunchKernelGGL(k_rc_final, dim3(grid_for(ng, 256)), dim3(256), 0, st, ng, pre.p, (const double*)g1.p, (const double*)nullptr,
+                         E.rc_bc, 0.0, E.rc_bmark.p);
+    else E.rc_bmark.zero();
+    PG_HIP(hipGetLastError());
+    PG_HIP(hipStreamSynchronize(st));
+    E.rc_bmark_version = version;
+    E.rc_bmark_uses = 0;
+    ++E.rc_bmark_builds;
+  }
+  ++E.rc_bmark_uses;
+  rc.bmark = E.rc_bmark.p;
+  rc.bc = E.rc_bc;
+  return rc;
+}
 
 void build_gamma_elim(const CsrMatrix& A, const Numbering& nb, GammaElim& E) {
   E.tried = true;

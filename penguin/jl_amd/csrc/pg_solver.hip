@@ -94,6 +94,7 @@ struct pg_solver {
   const CsrMatrix* blk_cache_matrix = nullptr;
   int blk_cache_scheme = -1;
   long long blk_cache_version = -1;
+  const DiagElim* rc_last = nullptr;   // the compact system the last step ran on, if it took one (pg_solver_row_const_info)
   // vectors
   DevBuf<double> x, b, y;     // n_vec: unscaled state, scaled right-hand side, Â z
   DevBuf<double> z, ysol;     // n_vec: scaled state S⁻¹x (SpMV input), Krylov solution y (x = S y)
@@ -848,7 +849,7 @@ __global__ __launch_bounds__(BLOCK, (rhs_fuses(KH, DEFER) ? 5 : 1)) void k_rhs_i
                                                       double* __restrict__ rhat, double* __restrict__ partials,
                                                       unsigned* __restrict__ ticket, double* __restrict__ sc, double reltol2,
                                                       double abstol2, int coupled, GuessArgs g, BlkTables bt, GuessFit gf,
-                                                      int main_grid) {
+                                                      int main_grid, RowConst rc) {
   // (p = r = r̂ are NOT written: the first iteration reads r̂ for them, KrylovCall::p_in_rhat)
   // coupled != 0: diag_fix follows (the data changed): every δ != 0 moves its row, raises the flag and is coupled into the
   // residual of the rows that reference it.  coupled == 0: no coupling launch follows (unchanged data); only a δ beyond the
@@ -934,14 +935,25 @@ __global__ __launch_bounds__(BLOCK, (rhs_fuses(KH, DEFER) ? 5 : 1)) void k_rhs_i
     const i64 i = 2 * q;
     double zh0[KH > 0 ? KH : 1], zh1[KH > 0 ? KH : 1], yv0[KH > 0 ? KH : 1], yv1[KH > 0 ? KH : 1];
     if (i + 1 < n) {
+      // RowConst (pg_system.h): a group of 16 rows -- 8 lanes -- whose ds, mass (and bconst, where its mark stands) are one value
+      // each, no row fixed or a block row, cmap advancing by one from e: those lanes request none of the six lines
+      const int e = rc.tab ? rc.tab[i >> RC_SHIFT] : -1;
+      const bool bc_one = e >= 0 && rc.bmark && rc.bmark[i >> RC_SHIFT] != 0;
       const rd2_t yh = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(yhat + i));
-      const rd2_t d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
-      const rd2_t bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
-      const rd2_t ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
       const rd2_t zz = *reinterpret_cast<const rd2_t*>(z + i);
-      const ruc2_t fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
-      const ruc2_t bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
-      const int c0 = cmap[i], c1 = cmap[i + 1];
+      rd2_t d, bc, ms;
+      ruc2_t fx, bk;
+      int c0 = e + (int)(i & (RC_GROUP - 1)), c1 = c0 + 1;
+      d.x = rc.d; d.y = rc.d; ms.x = rc.ms; ms.y = rc.ms; bc.x = rc.bc; bc.y = rc.bc;
+      fx.x = 0; fx.y = 0; bk.x = 0; bk.y = 0;
+      if (e < 0) {
+        d = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(ds + i));
+        ms = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(mass + i));
+        fx = *reinterpret_cast<const ruc2_t*>(fixed + i);
+        bk = *reinterpret_cast<const ruc2_t*>(isblk + i);
+        c0 = cmap[i]; c1 = cmap[i + 1];
+      }
+      if (!bc_one) bc = __builtin_nontemporal_load(reinterpret_cast<const rd2_t*>(bconst + i));
       rd2_t bold;
       bold.x = 0.0; bold.y = 0.0;
       if (bk.x | bk.y) bold = *reinterpret_cast<const rd2_t*>(b + i);
@@ -1847,6 +1859,7 @@ void ensure_run_matrix(pg_solver* s, int scheme) {
   s->spec_y_valid = false;          // (a product queued ahead with the matrix that is about to be replaced)
   s->elim_run = GammaElim();        // (belongs to the matrix that is about to be replaced)
   s->diag_run = DiagElim();
+  if (s->rc_last == &s->diag_run) s->rc_last = nullptr;
   if (!s->mg_step[1].lev.empty()) s->mg_step[1] = MgHierarchy();
   if (s->blk_cache_matrix == &s->A_run) s->blk_cache_matrix = nullptr;
   assemble_csr_like(P, s->slab, s->nb, s->A_ctor, s->A_run);
@@ -2323,11 +2336,15 @@ void step_compact(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMa
   gp.ga.used = (defer && !fit_rides) ? s->guess_coef.p + GUESS_USED : nullptr;
   const GuessArgs& ga = gp.ga;
   const double* zprev = s->z.p;      // z^n (the buffers trade places below)
+  // the rows whose constants are one value (PG_ROW_CONST; pg_reduce.h): mass and fixed are written once, by setup_common, so
+  // the tables stand as long as DE does; bconst's mark is looked up for this step's version
+  if (!DE.rc_tried) build_row_const(A, s->mass.p, s->fixed.p, DE);
+  const RowConst rc_full = row_const_bconst(DE, s->bconst.p, s->bconst_version);
 #define PG_RHS_INIT_C(KHV, DF)                                                                                                    \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rhs_init_c<KHV, DF>), dim3(w.grid + gfit * FIT_PARTS), dim3(BLOCK), 0, stream, n, scheme, s->z.p, s->y.p, A.ds.p, \
                      s->mass.p, s->bconst.p, s->fixed.p, A.isblk.p, DE.cmap.p, s->b.p, (const double*)DE.gdiag.p, DE.delta.p,     \
                      DE.flag.p, stamp, w.rhat.p, w.partials.p, quiet ? w.ticket.p : nullptr, w.sc.p, o.reltol * o.reltol,          \
-                     o.abstol * o.abstol, same_data ? 0 : 1, ga, bt, gf, w.grid)
+                     o.abstol * o.abstol, same_data ? 0 : 1, ga, bt, gf, w.grid, rc_full)
   switch (KH) {
     case 1: if (defer) PG_RHS_INIT_C(1, true); else PG_RHS_INIT_C(1, false); break;
     case 2: if (defer) PG_RHS_INIT_C(2, true); else PG_RHS_INIT_C(2, false); break;
@@ -2343,6 +2360,8 @@ void step_compact(pg_solver* s, int scheme, const pg_krylov_opts& o, const CsrMa
   call.preinit = call.p_in_rhat = true;
   call.start_folded = quiet;
   call.scatter = DE.rlist.p;
+  call.row_const = DE.rc_view_loop();
+  s->rc_last = &DE;
   // several ranks, unchanged data: nobody looks at the rows alone on their diagonal (no diag_fix), so the flag k_rhs_init_c
   // raised goes through the start phase's all-reduce and comes back as S_MOVED, the same on every rank
   if (same_data && !single) { call.moved_flag = DE.flag.p; call.moved_stamp = stamp; }
@@ -2520,6 +2539,7 @@ void do_step(pg_solver* s, int scheme, const pg_krylov_opts* opts, SolveStats& s
     }
   } quiet_guard{s, used_de};
   s->t += s->dt;                     // diffusion.jl:287
+  s->rc_last = nullptr;
   ensure_bconst(s, scheme);
   if (warm) {
     // loop form on the scaled state: z is the previous Krylov solution itself
@@ -4052,6 +4072,32 @@ int32_t pg_solver_guess_info(pg_solver* s, int32_t* kept, int32_t* nstates, int3
     for (int j = 0; j < *nstates && j < 4; ++j) { offsets[j] = (int32_t)hc[5 + j] + 1; coef[j] = hc[j]; }
     *rr_plain = hc[9];
     *rr_taken = hc[10];
+  }
+  PG_API_END
+}
+
+int32_t pg_solver_row_const_info(pg_solver* s, int64_t* out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && out, "pg_solver_row_const_info: NULL argument");
+  for (int k = 0; k < 4; ++k) out[k] = 0;
+  if (const DiagElim* E = s->rc_last) {
+    out[0] = E->rc_groups[0]; out[1] = E->rc_const[0];
+    out[2] = E->rc_groups[1]; out[3] = E->rc_const[1];
+  }
+  PG_API_END
+}
+
+int32_t pg_debug_row_const_bconst(pg_solver* s, int64_t* out) {
+  PG_API_BEGIN
+  require_init();
+  PG_REQUIRE(s && out, "pg_debug_row_const_bconst: NULL argument");
+  for (int k = 0; k < 4; ++k) out[k] = 0;
+  if (const DiagElim* E = s->rc_last) {
+    out[0] = E->rc_bmark_version >= 0 && E->rc_bmark_version == s->bconst_version ? 1 : 0;
+    out[1] = out[0] ? E->rc_bmark_const : 0;
+    out[2] = E->rc_bmark_builds;
+    out[3] = out[0] ? E->rc_bmark_uses : 0;
   }
   PG_API_END
 }

@@ -129,6 +129,21 @@ inline void poly_record_stagnation(const CsrMatrix& A) {
   M.est.admitted = false;
   M.poly_gave_up = true;
 }
+// Rows whose per-row constants are one value (PG_ROW_CONST).  Away from the interface a uniform mesh has full cells only: the
+// equilibration weight ds, the mass and the constant part of the right-hand side are the same bits row after row, no row is
+// fixed or a block row, and the index maps advance by one.  The kernels that stream those vectors per row (k_rhs_init_c,
+// k_bicg_s_x) take them from their arguments instead: tab has one entry per group of RC_GROUP consecutive rows
+// (one 128-byte line of a double stream) -- the mapped index of the group's first row where EVERY row of the group has the
+// values below and consecutive mapped indices, -1 elsewhere (a partial last group always) -- and the loads of the other
+// groups sit under their lanes' predicate, so a line that holds nothing but the constant is not requested.  The same values
+// enter the same expressions: the results are the streamed ones bit for bit.
+constexpr int RC_SHIFT = 4, RC_GROUP = 1 << RC_SHIFT;
+struct RowConst {                  // (a kernel argument; tab == nullptr: every row streams)
+  const int* tab = nullptr;
+  const unsigned char* bmark = nullptr;   // full system only: != 0 where bconst is `bc` on every row of a qualifying group (nullptr: bconst streams)
+  double d = 0.0, ms = 0.0, bc = 0.0;     // ds; full system only: mass, bconst
+};
+
 constexpr int SPMV_CHUNK_ENTRIES = 508;   // + alignment shift (<= 3) fits the 512-slot LDS slice of a wave
 void build_spmv_chunks(CsrMatrix& A);   // pg_spmv.hip
 
